@@ -2,7 +2,7 @@
 """bench.py — headline benchmark of the MI355X ALP path (BASELINE.json): fused ALP decode (falp + patch) GB/s of
 decoded doubles per GPU and fraction of the HBM roofline, with encode GB/s and the reference's CPU path next to it.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--full] [--dump-outputs DIR]
     python bench.py --gpus N --steps K --warmup W [--column-gb 100]      (starts its own N local ranks when no launcher did)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--column-gb 100]
@@ -12,9 +12,10 @@ N = 1 (BASELINE.json configs[1]): 1 Mi vectors (1024 doubles each, 8 GiB decoded
 ALP-encoded, bit widths sweeping 1..53 across rowgroups (rowgroup r has bw = 1 + r mod 53), per-vector
 base = splitmix64(42, v) mod 2^bw, (f, e) = (min(12, floor((62-bw) log10 2)), f+2), no exceptions; packed words are
 uniform random bits (every bit pattern is a valid FFOR stream of uniform digits).  All inputs are resident in HBM
-before the timed region.  A "step" = one alpgpu_decode_f64 over the whole column.  Extras: the per-bit-width sweep,
-exceptions, fused consumers, the encode legs (configs[2], configs[3]), the float path, and the reference's CPU encode
-and decode timed on the box's host cores.
+before the timed region.  A "step" = one alpgpu_decode_f64 over the whole column.  A plain run sets up, warms up, times
+the steps and prints the headline.  --full adds the extras: the per-bit-width sweep, exceptions, fused consumers, the
+encode legs (configs[2], configs[3]), the float path, and the reference's CPU encode and decode timed on the host cores.
+--dump-outputs DIR writes a seeded sample of the last timed step's decoded doubles (dump_outputs) at any N.
 
 N > 1, or --column-gb G at any N (BASELINE.json configs[4]): ONE column of G GB (default 100) of doubles, sharded by
 whole rowgroups over the ranks (alp_amd/sharding.py; no collective on the data path).  Two legs under the same
@@ -118,6 +119,30 @@ def build_decode_column(n_vectors: int, device: int, seed: int, bw_of_rowgroup=N
     # algorithmic bytes per launch: read 128*bw + (8 + 2)*exc + 13, write 8192, per vector (float: 6 bytes per exception, 4096 written)
     alg_bytes = int((128 * bw + eb1 * cnt + 13 + 1024 * value_bytes).sum())
     return col, vec, alg_bytes
+
+
+DUMP_VECTORS = 4096  # decoded vectors written by --dump-outputs: 4096 x 8 KiB = 32 MiB (the budget is 64 MB)
+DUMP_SEED = 20240601
+
+
+def dump_sample_vectors(n_vectors: int, budget: int = DUMP_VECTORS) -> np.ndarray:
+    """the vectors --dump-outputs writes: a fixed, seeded, sorted sample of [0, n_vectors) that always holds the first and the last vector"""
+    if n_vectors <= budget:
+        return np.arange(n_vectors, dtype=np.int64)
+    pick = np.random.default_rng(DUMP_SEED).choice(np.arange(1, n_vectors - 1), budget - 2, replace=False)
+    return np.sort(np.concatenate([[0, n_vectors - 1], pick])).astype(np.int64)
+
+
+def dump_outputs(args, out: torch.Tensor, n_vectors: int, name: str = "decoded_f64") -> None:
+    """--dump-outputs DIR: what the timed decode returned in its last step (the caller's output buffer), as DIR/<name>.npy — the sampled
+    vectors of dump_sample_vectors(), float64, shape (vectors, 1024).  The inputs are seeded, so two builds can be compared value for value."""
+    if not args.dump_outputs:
+        return
+    idx = dump_sample_vectors(n_vectors, max(2, DUMP_VECTORS // max(1, int(os.environ.get("WORLD_SIZE", "1")))))
+    torch.cuda.synchronize()
+    sample = out.view(-1, VEC)[torch.from_numpy(idx).to(out.device)].cpu().numpy().astype(np.float64, copy=False)
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, name + ".npy"), sample)
 
 
 def time_launches(fn, iters: int, warmup: int):
@@ -553,7 +578,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=10, help="untimed steps first (the first ~10 launches after an idle gap run 3-30 %% slower: tools/launch_trend.py)")
     ap.add_argument("--vectors", type=int, default=1 << 20, help="N = 1 headline: vectors of the configs[1] column (default 1 Mi = 8 GiB decoded)")
     ap.add_argument("--column-gb", type=float, default=None, help="configs[4]: size of the ONE column that is sharded over the ranks (default 100 when N > 1)")
-    ap.add_argument("--no-extras", action="store_true", help="N = 1: skip the per-bit-width sweep, the encode legs and the CPU baselines")
+    ap.add_argument("--full", action="store_true", help="N = 1: after the headline, also run the extras (per-bit-width sweeps, tuning, consumers, the encode "
+                                                         "legs, real-data-shaped columns, ceilings, the float path) and the reference's CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="N = 1: skip the extras even with --full (a plain run never runs them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write a fixed, seeded sample of the timed decode's output of the last step "
+                                                                         "as DIR/*.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
     ensure_launcher(args)
 
@@ -675,6 +704,7 @@ def sharded_column_bench(args, ctx, clock, world, rank, local_rank, dev):
     col, vec, alg_bytes = build_decode_column(n, local_rank, seed=42, first_vector=first)
     out = torch.empty(n * VEC, dtype=torch.float64, device=dev)
     elapsed, kern_ms = clock.run(lambda: ctx.decode(col, out), args.steps, args.warmup)
+    dump_outputs(args, out, n, "decoded_f64" if world == 1 else f"decoded_f64_rank{rank}")
     shape = ctx.decode_vectors_per_wg(col)
     total_decoded = clock.total(n * 8192)
     value = total_decoded * args.steps / elapsed / 1e9
@@ -760,9 +790,10 @@ def single_gpu_bench(args, ctx, clock, local_rank, dev):
                       "BASELINE.json configs[1]: falp fused decode, synthetic decimal doubles, 1024-value vectors, bit widths 1-53 by rowgroup, no exceptions",
                       "weak", {"vectors_per_gpu": n, "decoded_bytes_per_gpu": n * 8192, "decode_vectors_per_wg": shape,
                                "parallelism": "1 shard; --gpus N shards ONE 100 GB column over N ranks (configs[4]); this value is that curve's N = 1 point (the rate does not depend on the shard's length)"})
+    dump_outputs(args, out, n)
     traffic_from_profile(result, n)
     result["lib_sha16"] = lib_sha16()
-    if args.no_extras:
+    if not args.full or args.no_extras:
         return result
 
     def frac(bytes_, ms):

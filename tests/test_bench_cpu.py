@@ -99,3 +99,20 @@ def test_gpus_4_dry_run_returns_four_rank_records():
     firsts = [x["first_vector"] for x in r["ranks"]]
     assert firsts == sorted(firsts) and firsts[0] == 0 and all(f % 100 == 0 for f in firsts), "contiguous whole-rowgroup shards in rank order"
     assert all("device" in x for x in r["ranks"])
+
+
+# ---- --dump-outputs: a fixed sample of the timed decode's output, small enough to keep next to every run ------------------------------------
+def test_dump_sample_is_fixed_sorted_and_within_the_budget(bench):
+    import numpy as np
+    n = 1 << 20
+    a, b = bench.dump_sample_vectors(n), bench.dump_sample_vectors(n)
+    assert np.array_equal(a, b), "the same vectors on every run"
+    assert a.size == bench.DUMP_VECTORS and a[0] == 0 and a[-1] == n - 1 and (np.diff(a) > 0).all()
+    assert a.size * bench.VEC * 8 <= 64e6, "float64 sample within 64 MB"
+    assert np.array_equal(bench.dump_sample_vectors(1000), np.arange(1000)), "a small column is written whole"
+    assert bench.dump_sample_vectors(n, 512).size == 512
+
+
+def test_full_and_dump_outputs_are_options():
+    p = _run_bench(["--help"], {}, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout

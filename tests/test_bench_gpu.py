@@ -56,3 +56,25 @@ def test_gpus_2_without_a_launcher_starts_its_own_ranks():
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], capture_output=True, text=True, timeout=300,
                          env=dict(env, WORLD_SIZE="4", RANK="0"), cwd=ROOT)
     assert bad.returncode != 0 and "WORLD_SIZE=4" in bad.stderr
+
+
+def test_plain_run_times_the_headline_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (small column): exactly K timed steps, the headline keys, none of the --full
+    extras, and DIR/decoded_f64.npy — the seeded sample of the last step's decoded doubles — bit for bit the same on a second run"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--vectors", "20000", "--dump-outputs", str(d)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+        r = json.loads(p.stdout.rstrip().splitlines()[-1])
+        assert r["steps"] == 4 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0
+        assert r["unit"] == "GB/s" and r["higher_is_better"] is True and r["dtype"] == "f64" and r["metric"].startswith("ALP fused decode")
+        assert "extras" not in r and "cpu_baseline" not in r and "summaries" not in r
+        assert sorted(os.listdir(d)) == ["decoded_f64.npy"]
+        a = np.load(d / "decoded_f64.npy")
+        assert a.dtype == np.float64 and a.shape == (4096, 1024) and np.isfinite(a).all()
+        dumps.append(a)
+    assert np.array_equal(dumps[0].view(np.uint64), dumps[1].view(np.uint64))

@@ -152,31 +152,3 @@ def test_late_kernel_arguments_are_where_the_kernels_read_them():
             seen += 1
     assert seen >= 3, f"k_encode_lean<false>, <true> and k_encode_fused_f32<single pass> expected, saw {seen}: {[k for k in kernels if 'encode' in k]}"
 
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/include"), reason="the reference tree exists in the build container only")
-def test_the_references_own_callers_compile_against_this_repos_headers():
-    """the drop-in claim, pinned against header drift: the reference's unmodified test/test_alp_sample.cpp and
-    publication/source_code/bench_compression_ratio/alp.cpp pass the compiler's front end with THIS repo's include/ in place of the reference's
-    (gtest and the reference's data headers are outside the path: a stub gtest for syntax only, the data headers from where they lie)"""
-    import subprocess
-    import tempfile
-    cxx = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx) and shutil.which(cxx) is None:
-        pytest.skip("no clang++")
-    with tempfile.TemporaryDirectory() as tmp:
-        os.makedirs(os.path.join(tmp, "gtest"))
-        open(os.path.join(tmp, "gtest", "gtest.h"), "w").write(
-            "#pragma once\n#include <iostream>\nnamespace testing { struct Test { virtual ~Test() = default; virtual void SetUp() {} virtual void TearDown() {} }; }\n"
-            "struct gtest_sink_ { template <class T> gtest_sink_& operator<<(const T&) { return *this; } };\n"
-            "#define TEST_F(a, b) struct a##_##b : a { void body(); }; void a##_##b::body()\n"
-            "#define ASSERT_EQ(a, b) if ((a) == (b)) {} else gtest_sink_()\n#define EXPECT_EQ(a, b) if ((a) == (b)) {} else gtest_sink_()\n"
-            "#define ASSERT_TRUE(a) if (a) {} else gtest_sink_()\n#define EXPECT_TRUE(a) if (a) {} else gtest_sink_()\n#define SUCCEED() gtest_sink_()\n"
-            "#define ASSERT_NE(a, b) if ((a) != (b)) {} else gtest_sink_()\n#define ASSERT_LE(a, b) if ((a) <= (b)) {} else gtest_sink_()\n")
-        for src, extra in (("/root/reference/test/test_alp_sample.cpp", ["-I/root/reference/data/include", "-I/root/reference/test/include"]),
-                           ("/root/reference/publication/source_code/bench_compression_ratio/alp.cpp", ["-I/root/reference/data/include", "-I/root/reference/publication/source_code/include"])):
-            if not os.path.exists(src):
-                pytest.skip(f"{src} is not in this copy of the reference")
-            cmd = [cxx, "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), "-I" + tmp, *extra,
-                   "-DCMAKE_SOURCE_DIR=\"/root/reference\"", "-DALP_CMAKE_SOURCE_DIR=\"/root/reference\"", "-DPAPER_ROOT=\"/root/reference/publication\"", src]
-            p = subprocess.run(cmd, capture_output=True, text=True)
-            assert p.returncode == 0, " ".join(cmd) + "\n" + p.stderr[-3000:]

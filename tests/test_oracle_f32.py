@@ -111,16 +111,14 @@ def test_whole_column_matches_reference(of32, rf32, name):
 
 def test_reference_float_test_columns(of32, rf32):
     """data/float/test_{0..3}.csv and data/edge_case/avx512dq.csv with the values the reference's unit test asserts
-    (data/include/float/test.hpp:10-14: bit widths 4, 10, 17, 0; float/edge_case.hpp:10: 192 exceptions, bw 0)"""
-    import os
-    root = "/root/reference/data"
-    if not os.path.isdir(root):
-        pytest.skip("reference data absent")
+    (data/include/float/test.hpp:10-14: bit widths 4, 10, 17, 0; float/edge_case.hpp:10: 192 exceptions, bw 0).  The columns come from
+    tests/golden/float_vectors.npz, where tools/make_golden.py stored them (padded with 0.0 to 1024 values)."""
+    stored = {name: col for name, col, _, _ in golden_io.float_vectors()}
     expect = {"float/test_0.csv": (4, None), "float/test_1.csv": (10, None), "float/test_2.csv": (17, None),
               "float/test_3.csv": (0, None), "edge_case/avx512dq.csv": (0, 192)}
     for rel, (bw, exc) in expect.items():
-        vals = [np.float32(l.strip().rstrip(",")) for l in open(os.path.join(root, rel)) if l.strip()]
-        col = np.array(vals + [0.0] * (1024 - len(vals)), np.float32)
+        col = stored[rel.replace("/", "_").replace(".csv", "")]
+        assert col.dtype == np.float32 and col.size == 1024, rel
         a, b = of32.encode_column(col), rf32.encode_column(col)
         golden_io.assert_same_encoding(a, b, rel, word=np.uint32)
         assert a["scheme"][0] == 2 and int(a["bw"][0]) == bw, rel

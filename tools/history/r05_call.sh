@@ -133,7 +133,7 @@ case $step in
 	grep -v "^==\|amdgpu.ids" "$out/f32.txt"
 	;;
 11) # the bench line as the driver runs it (does it fit the 8 KB tail? every key there?), then with a 2-rank shared-GPU run of the N > 1 path
-	run 900 bench.txt python bench.py --steps 20 --warmup 5
+	run 900 bench.txt python bench.py --full --steps 20 --warmup 5
 	grep "^{" "$out/bench.txt" | tail -1 > "$out/bench.json"
 	wc -c "$out/bench.json"
 	cat "$out/bench.json"
@@ -300,7 +300,7 @@ case $step in
 	tail -3 "$out/pytest.txt"
 	run 300 short.txt python tools/r05_read_ahead_short.py
 	grep -v "amdgpu.ids\|^==" "$out/short.txt"
-	run 400 bench.json python bench.py --steps 20 --warmup 5
+	run 400 bench.json python bench.py --full --steps 20 --warmup 5
 	tail -c 6000 "$out/bench.json"
 	;;
 33) # by column length, cold (2 GiB read between launches)
@@ -413,7 +413,7 @@ case $step in
 50) # the rule extended to 11 bits (9 with exceptions), leads 12 + 6.5 us per bit up to 60: decode tests, then the bench line
 	run 300 pytest.txt python -m pytest tests/test_decode_gpu.py -x -q
 	tail -2 "$out/pytest.txt"
-	run 400 bench.json python bench.py --steps 20 --warmup 5
+	run 400 bench.json python bench.py --full --steps 20 --warmup 5
 	python - <<'PY'
 import json
 d = json.loads([l for l in open("gpurun_out/r05/50/bench.json") if l.startswith("{")][-1])
@@ -444,7 +444,7 @@ final) # the closing run on the library as committed: whole GPU suite, smoke, th
 	tail -4 "$out/pytest.txt"
 	run 120 smoke.txt python __graft_entry__.py smoke
 	tail -1 "$out/smoke.txt"
-	run 900 bench.txt python bench.py --steps 20 --warmup 5
+	run 900 bench.txt python bench.py --full --steps 20 --warmup 5
 	grep "^{" "$out/bench.txt" | tail -1 > "$out/bench.json"; wc -c "$out/bench.json"
 	run 900 bench_configs4.txt python bench.py --gpus 1 --column-gb 100 --steps 10 --warmup 3
 	grep "^{" "$out/bench_configs4.txt" | tail -1 > "$out/bench_configs4_n1.json"; wc -c "$out/bench_configs4_n1.json"

@@ -17,7 +17,7 @@ case $step in
   run 200 unhinted.txt python tools/time_unhinted.py
   ALPGPU_READ_AHEAD_ADAPT=0 run 120 adapt_off.txt python tools/time_read_ahead.py
   ALPGPU_READ_AHEAD_ADAPT=1 run 120 adapt_on.txt python tools/time_read_ahead.py
-  run 300 bench.txt python bench.py
+  run 300 bench.txt python bench.py --full
   ;;
 2) # the whole GPU suite again; the tiles' search items (experiment: vectors alone with / without them); the decode of encoder output in a grid of shapes
   run 600 tests.txt python -m pytest tests -m gpu -x -q
@@ -47,7 +47,7 @@ case $step in
   ALPGPU_LIB=build/variants/libalpgpu_r06_exc256.so PADS=0,6 run 200 decode_encoded_exc256.txt python tools/time_decode_encoded.py
   ALPGPU_LIB=build/variants/libalpgpu_r06_exc256.so run 300 tests_exc256.txt python -m pytest tests/test_decode_gpu.py tests/test_decode_sum_gpu.py tests/test_fuzz_gpu.py -m gpu -x -q
   run 600 tests.txt python -m pytest tests -m gpu -x -q
-  run 400 bench.txt python bench.py
+  run 400 bench.txt python bench.py --full
   ;;
 7) # the 256-entry exception stage as an INSTANCE of its own, launched for exception-heavy columns only: parity, then the decode grid
   run 300 tests.txt python -m pytest tests/test_decode_gpu.py tests/test_decode_sum_gpu.py tests/test_fuzz_gpu.py tests/test_unhinted_gpu.py -m gpu -x -q
@@ -136,7 +136,7 @@ case $step in
   ;;
 29) # the whole GPU suite and the bench line on the tree as it is
   run 900 tests.txt python -m pytest tests -m gpu -x -q
-  run 600 bench.txt python bench.py
+  run 600 bench.txt python bench.py --full
   ;;
 32) # narrow double columns under the read-ahead: two vectors per workgroup, five workgroups per CU — the suite, the rule against the old shape
   run 900 tests.txt python -m pytest tests -m gpu -x -q
@@ -157,7 +157,7 @@ case $step in
 41) # soak: the whole GPU suite three times, smoke, the default bench line
   for i in 1 2 3; do run 600 tests_$i.txt python -m pytest tests -m gpu -x -q -p no:cacheprovider; done
   run 300 smoke.txt python -c "import __graft_entry__ as g; g.smoke()"
-  timeout 600 python bench.py > $out/bench.json 2> $out/bench.err
+  timeout 600 python bench.py --full > $out/bench.json 2> $out/bench.err
   ;;
 42) # the whole-column entry points captured into a hipGraph and replayed
   run 800 graph.txt python -m pytest tests/test_graph_gpu.py -m gpu -q -s -p no:cacheprovider
@@ -199,7 +199,7 @@ case $step in
 final) # the closing run: whole GPU suite, smoke, the bench line, configs[4] at N = 1 (tools/profile_round.sh r06 is a call of its own)
   run 900 tests.txt python -m pytest tests -m gpu -x -q
   run 300 smoke.txt python -c "import __graft_entry__ as g; g.smoke()"
-  timeout 900 python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
+  timeout 900 python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
   timeout 900 python bench.py --gpus 1 --column-gb 100 --steps 10 --warmup 3 > $out/bench_configs4_n1.json 2> $out/bench_configs4.err; echo "configs4 rc=$?"
   ;;
 *) echo "unknown step $step";;
