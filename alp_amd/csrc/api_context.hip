@@ -78,9 +78,7 @@ int alpgpu_ctx_create(int device, alpgpu_ctx** out_ctx) {
 	{
 		int least = 0, greatest = 0;
 		(void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-		const char* pr = std::getenv("ALPGPU_INIT_STREAM_PRIO"); // experiments: "low" / "normal"; default: highest
-		const int   prio = pr && pr[0] == 'l' ? least : (pr && pr[0] == 'n' ? 0 : greatest);
-		if (hipStreamCreateWithPriority(&ctx->init_stream, hipStreamNonBlocking, prio) != hipSuccess ||
+		if (hipStreamCreateWithPriority(&ctx->init_stream, hipStreamNonBlocking, greatest) != hipSuccess ||
 		    hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess ||
 		    hipEventCreateWithFlags(&ctx->ev_head, hipEventDisableTiming) != hipSuccess) {
 			(void)hipStreamDestroy(ctx->own_stream);
@@ -88,38 +86,23 @@ int alpgpu_ctx_create(int device, alpgpu_ctx** out_ctx) {
 			return fail(ALPGPU_ERR_HIP, "hipStreamCreate / hipEventCreate failed");
 		}
 	}
-	ctx->async_init     = std::getenv("ALPGPU_ENCODE_SYNC_INIT") ? 0 : 1;
-	ctx->async_init_wg_per_cu = std::getenv("ALPGPU_ASYNC_INIT_WG_PER_CU") ? std::atoi(std::getenv("ALPGPU_ASYNC_INIT_WG_PER_CU")) : 1;
-	if (ctx->async_init_wg_per_cu < 1) { ctx->async_init_wg_per_cu = 1; }
-	ctx->async_init_adaptive = std::getenv("ALPGPU_ASYNC_INIT_ADAPTIVE") ? std::atoi(std::getenv("ALPGPU_ASYNC_INIT_ADAPTIVE")) : 1;
+	ctx->async_init     = 1;
 	ctx->n_cus          = prop.multiProcessorCount;
 	ctx->hbm_bytes      = prop.totalGlobalMem;
 	ctx->decode_variant  = 1; // bit 0: one vector per decode workgroup, bit 1: plain stores
 	ctx->decode_auto     = 1;
 	ctx->decode_vpw      = 0;
-	ctx->decode_four_bits     = std::getenv("ALPGPU_DECODE_FOUR_BITS") ? std::atof(std::getenv("ALPGPU_DECODE_FOUR_BITS")) : 0.0;     // (tuning runs; defaults set from the sweep)
-	ctx->decode_four_bits_exc = std::getenv("ALPGPU_DECODE_FOUR_BITS_EXC") ? std::atof(std::getenv("ALPGPU_DECODE_FOUR_BITS_EXC")) : 0.0;
-	ctx->encode_two_pass = std::getenv("ALPGPU_ENCODE_TWO_PASS") ? 1 : 0;
+	ctx->encode_two_pass = 0;
 	ctx->force_stall     = 0;
 	ctx->pipelined_consumer = 0;
-	// (round 5: 0.  With the per-vector loops k_decode_column<2> is 10-20 % ahead of k_decode_pairs on narrow vectors with exceptions: profiles/r05_decode_exceptions.txt)
-	ctx->decode_pairs_auto = std::getenv("ALPGPU_DECODE_PAIRS_AUTO") ? std::atoi(std::getenv("ALPGPU_DECODE_PAIRS_AUTO")) : 0;
-	ctx->decode_pad_kib     = std::getenv("ALPGPU_DECODE_PAD_LDS_KIB") ? std::atoi(std::getenv("ALPGPU_DECODE_PAD_LDS_KIB")) & 0xFF : -1;
-	// the patch arm exists in -DALPGPU_DECODE_PATCH_MODE=1 / 2 builds of decode_kernels.hip only (measured slower than the mask route: profiles/r05_decode_exceptions.txt);
-	// the default build ignores the limit, and the launch rule must not count on an arm that is not there: 0 unless asked for
-	ctx->decode_patch_max   = (std::getenv("ALPGPU_DECODE_PATCH_AFTER") && alpgpu::decode_patch_arm_compiled()) ? std::atoi(std::getenv("ALPGPU_DECODE_PATCH_AFTER")) : 0; // (A/B runs)
-	if (ctx->decode_patch_max < 0 || ctx->decode_patch_max > 64) { ctx->decode_patch_max = 64; }
-	ctx->decode_patch_shape = std::getenv("ALPGPU_DECODE_PATCH_SHAPE") ? std::atoi(std::getenv("ALPGPU_DECODE_PATCH_SHAPE")) : 1;
-	ctx->decode_pairing  = std::getenv("ALPGPU_DECODE_PAIRING") ? (std::atoi(std::getenv("ALPGPU_DECODE_PAIRING")) & 3) : 0; // (A/B runs)
-	ctx->encode_kernel   = std::getenv("ALPGPU_ENCODE_KERNEL") ? std::atoi(std::getenv("ALPGPU_ENCODE_KERNEL")) : ALPGPU_ENCODE_KERNEL_LEAN; // (A/B runs)
-	ctx->encode_unordered = std::getenv("ALPGPU_ENCODE_UNORDERED") ? std::atoi(std::getenv("ALPGPU_ENCODE_UNORDERED")) : 0; // (A/B runs)
-	ctx->read_ahead      = std::getenv("ALPGPU_DECODE_READ_AHEAD") ? std::atoi(std::getenv("ALPGPU_DECODE_READ_AHEAD")) : -1; // -1: by the column (read_ahead_for)
-	ctx->read_ahead_us   = std::getenv("ALPGPU_READ_AHEAD_US") ? std::atoi(std::getenv("ALPGPU_READ_AHEAD_US")) : 0; // 0: by the vectors' width (alpgpu_decode_f64)
-	ctx->read_ahead_grid = std::getenv("ALPGPU_READ_AHEAD_GRID") ? std::atoi(std::getenv("ALPGPU_READ_AHEAD_GRID")) : 64;
-	ctx->decode_segments = std::getenv("ALPGPU_DECODE_SEGMENTS") ? std::atoi(std::getenv("ALPGPU_DECODE_SEGMENTS")) : 1;
+	ctx->decode_pad_kib  = -1;
+	ctx->encode_unordered = 0;
+	ctx->read_ahead      = -1; // -1: by the column (read_ahead_for)
+	ctx->read_ahead_us   = 0;  // 0: by the vectors' width (alpgpu_decode_f64)
+	ctx->decode_segments = 1;
 	for (auto& t : ctx->seg_tables) { t.key = nullptr; }
 	ctx->seg_next        = 0;
-	ctx->decode_unhinted = std::getenv("ALPGPU_DECODE_UNHINTED") ? std::atoi(std::getenv("ALPGPU_DECODE_UNHINTED")) : 1;
+	ctx->decode_unhinted = 1;
 	for (auto& l : ctx->learn) { l.state = 0, l.key = nullptr, l.ev = nullptr; }
 	ctx->learn_next      = 0;
 	ctx->h_learn         = nullptr;
@@ -131,7 +114,6 @@ int alpgpu_ctx_create(int device, alpgpu_ctx** out_ctx) {
 		const char* q   = std::getenv("GPU_MAX_HW_QUEUES");
 		ctx->streams_serialize = ((ser && std::atoi(ser) != 0) || (blk && std::atoi(blk) != 0) || (q && std::atoi(q) == 1)) ? 1 : 0;
 	}
-	ctx->read_ahead_bits = std::getenv("ALPGPU_READ_AHEAD_BITS") ? std::atoi(std::getenv("ALPGPU_READ_AHEAD_BITS")) : 128;
 	ctx->d_progress      = nullptr;
 	ctx->progress_gen    = 0;
 	{
@@ -173,10 +155,6 @@ int alpgpu_ctx_create(int device, alpgpu_ctx** out_ctx) {
 				break;
 			}
 		}
-	}
-	if (const char* v = std::getenv("ALPGPU_DECODE_VARIANT")) { // A/B runs
-		ctx->decode_variant = std::atoi(v);
-		ctx->decode_auto    = 0;
 	}
 	std::snprintf(ctx->name, sizeof(ctx->name), "%s (%s)", prop.name, prop.gcnArchName);
 	*out_ctx = ctx;
@@ -229,7 +207,7 @@ int alpgpu_set_option(alpgpu_ctx* ctx, int option, int64_t value) {
 		}
 		ctx->decode_auto    = value == 0;
 		ctx->decode_vpw     = static_cast<int>(value);
-		ctx->decode_variant = (ctx->decode_variant & ~5) | ((value == 2 || value == 4) ? 0 : 1) | (value == 4 ? 4 : 0); // (4: four vectors over the narrow stage; 8: float columns only, double columns take 1)
+		ctx->decode_variant = (ctx->decode_variant & ~1) | ((value == 2 || value == 4) ? 0 : 1); // (double columns run 4 as 2; 8 and up: float columns only, double columns take 1)
 		return ALPGPU_OK;
 	case ALPGPU_OPT_ENCODE_TWO_PASS:
 		ctx->encode_two_pass = value ? 1 : 0;
@@ -244,13 +222,11 @@ int alpgpu_set_option(alpgpu_ctx* ctx, int option, int64_t value) {
 		if (value < 0 || value > 2) { return fail(ALPGPU_ERR_INVALID, "async init: 0 (off), 1 (double columns: default) or 2 (float columns too)"); }
 		ctx->async_init = static_cast<int>(value);
 		return ALPGPU_OK;
-	case ALPGPU_OPT_DECODE_PAIRING:
+	case ALPGPU_OPT_DECODE_PAIRING: // retired: accepted, no effect
 		if (value < 0 || value > 3) { return fail(ALPGPU_ERR_INVALID, "decode pairing: 0 (off) .. 3"); }
-		ctx->decode_pairing = static_cast<int>(value);
 		return ALPGPU_OK;
-	case ALPGPU_OPT_ENCODE_KERNEL:
+	case ALPGPU_OPT_ENCODE_KERNEL: // retired: accepted, no effect (the lean kernel always runs)
 		if (value != ALPGPU_ENCODE_KERNEL_LEAN && value != ALPGPU_ENCODE_KERNEL_CLASSIC) { return fail(ALPGPU_ERR_INVALID, "encode kernel: 0 (lean) or 1 (classic)"); }
-		ctx->encode_kernel = static_cast<int>(value);
 		return ALPGPU_OK;
 	case ALPGPU_OPT_DECODE_RESIDENCY_PAD:
 		if (value < -1 || value > 150) { return fail(ALPGPU_ERR_INVALID, "decode residency pad: -1 (by the library's rule) or 0..150 KiB"); }
@@ -263,12 +239,8 @@ int alpgpu_set_option(alpgpu_ctx* ctx, int option, int64_t value) {
 		if (value < 0 || value > 2) { return fail(ALPGPU_ERR_INVALID, "unhinted decode: 0 (as before round 6), 1 (sizes summed on the stream, read-ahead planned on the device, learned for the next decode) or 2 (1 + every candidate shape launched, gated)"); }
 		ctx->decode_unhinted = static_cast<int>(value);
 		return ALPGPU_OK;
-	case ALPGPU_OPT_DECODE_PATCH_AFTER:
+	case ALPGPU_OPT_DECODE_PATCH_AFTER: // retired: accepted, no effect
 		if (value < 0 || value > 64) { return fail(ALPGPU_ERR_INVALID, "decode patch-after: 0 (never) .. 64 exceptions per vector"); }
-		// the arm exists in -DALPGPU_DECODE_PATCH_MODE=1 / 2 builds only: a build without it accepts the option and IGNORES it — the launch rule (shape, residency pad,
-		// read-ahead limit, segment kinds: column_decodes_with_exceptions) must not count on an arm that is not there
-		if (!alpgpu::decode_patch_arm_compiled()) { value = 0; }
-		ctx->decode_patch_max = static_cast<int>(value);
 		return ALPGPU_OK;
 	case ALPGPU_OPT_DECODE_READ_AHEAD:
 		if (value < -1 || value > 1) { return fail(ALPGPU_ERR_INVALID, "decode read-ahead: -1 (columns of narrow vectors: the default), 0 (off) or 1 (on)"); }

@@ -7,17 +7,14 @@ using alpgpu::kReadAheadBits;
 using alpgpu::kReadAheadBitsExc;
 using alpgpu::kReadAheadVectors;
 
+constexpr int      kReadAheadGrid    = 64;  // the read-ahead's eight-wavefront workgroups
+constexpr uint32_t kReadAheadMaxBits = 128; // ... read the records of vectors of at most this many packed bits per value (the descriptors of all)
+
 extern "C" {
 
-// "the column's vectors carry exceptions" as far as the decode's launch shape is concerned: about two or more per vector — unless they are
-// patched in after the stores (ALPGPU_OPT_DECODE_PATCH_AFTER: an average of at most half the arm's limit, 10 bytes of record each), which
-// costs a wavefront a handful of instructions: such a column behaves like one without exceptions
-static bool column_decodes_with_exceptions(const alpgpu_ctx* ctx, const alpgpu_column* col) {
-	const double n = static_cast<double>(col->n_vectors);
-	const double e = static_cast<double>(col->exc_bytes_hint);
-	if (e < 16.0 * n) { return false; }
-	if (ctx->decode_patch_shape && ctx->decode_patch_max > 0 && e <= 5.0 * static_cast<double>(ctx->decode_patch_max) * n) { return false; } // (builds with a patch arm only: decode_patch_max is 0 otherwise)
-	return true;
+// "the column's vectors carry exceptions" as far as the decode's launch shape is concerned: about two or more per vector
+static bool column_decodes_with_exceptions(const alpgpu_ctx*, const alpgpu_column* col) {
+	return static_cast<double>(col->exc_bytes_hint) >= 16.0 * static_cast<double>(col->n_vectors);
 }
 
 // The store decode of this column runs with the read-ahead (read_ahead_kernels.hip).  Asked for (1): any column long enough to be worth a second launch whose
@@ -43,41 +40,29 @@ static int decode_variant_for(const alpgpu_ctx* ctx, const alpgpu_column* col) {
 		// More vectors per workgroup = more bytes in flight per CU, which is what narrow vectors lack (two dependent round trips for 8 KiB of
 		// output) and what wide ones pay for.  Crossovers measured at 1-bit resolution on 1 Mi-vector columns (tools/sweep_vpw_fine.py,
 		// profiles/r04_decode_floor.txt): without exceptions one vector per workgroup wins from 17 bits on (16 itself — whole KiB per vector —
-		// still prefers more), with ~2 or more exceptions per vector from 21 bits on; every ALP_RD column is far beyond either.  Up to
-		// kNarrowAutoBits bits FOUR vectors share a workgroup over the narrow stage (round 4).
+		// still prefers more), with ~2 or more exceptions per vector from 21 bits on; every ALP_RD column is far beyond either.
 		const bool   with_exc = column_decodes_with_exceptions(ctx, col);
 		const double bits     = static_cast<double>(col->packed_bytes_hint) / (128.0 * (n > 0 ? n : 1.0));
 		const bool   narrow   = bits <= (with_exc ? alpgpu::kTwoVectorsBitsExc : alpgpu::kTwoVectorsBits); // (17.5: with the residency caps below two vectors per workgroup win through 17 bits; with exceptions through 22: round 5)
-		const double four_max = with_exc ? ctx->decode_four_bits_exc : ctx->decode_four_bits; // (0 = never: the four-vector shape lost at every width, it is chosen by tuning runs only)
-		const bool   four     = four_max > 0.0 && bits <= four_max;
-		variant               = (variant & ~5) | ((hinted && narrow) ? 0 : 1) | ((hinted && four) ? 4 : 0);
+		variant               = (variant & ~1) | ((hinted && narrow) ? 0 : 1);
 		// narrow vectors under the read-ahead: their reads hit the Infinity Cache, and ONE vector per workgroup — the shape that suffers most from the two round
 		// trips (0.53 at 2-6 bits) — becomes the best one (0.75-0.80); with exceptions two per workgroup stay ahead (0.68-0.74 against 0.64-0.68)
-		if (ctx->read_ahead < 0 && read_ahead_for(ctx, col) && !with_exc) { variant = (variant & ~5) | 1; }
+		if (ctx->read_ahead < 0 && read_ahead_for(ctx, col) && !with_exc) { variant |= 1; }
 		// (almost) nothing but 0-bit vectors — a pure stream of stores, e.g. the gov26 shape: one vector per workgroup (and six workgroups per CU, below): 0.71 -> 0.82 (call 2)
-		if (hinted && bits <= alpgpu::kEmptyVectorsBits) { variant = (variant & ~5) | 1; }
-	}
-	// Narrow vectors WITH exceptions: the pair kernel (k_decode_pairs, both vectors' loads in flight together when both are narrow, one after the
-	// other otherwise) is 1-4 % ahead of k_decode_column<2> up to 18 bits (tools/sweep_pairing.py, profiles/r04_decode_floor.txt section 4); without
-	// exceptions it is not.  ALPGPU_OPT_DECODE_PAIRING overrides.
-	int pairing = ctx->decode_pairing;
-	if (ctx->decode_auto && pairing == 0 && ctx->decode_pairs_auto && col->packed_bytes_hint != 0) {
-		const double n = static_cast<double>(col->n_vectors);
-		if (column_decodes_with_exceptions(ctx, col) && static_cast<double>(col->packed_bytes_hint) <= 18.0 * 128.0 * n) { pairing = 1; }
+		if (hinted && bits <= alpgpu::kEmptyVectorsBits) { variant |= 1; }
 	}
 	// Residency by width (decode_kernels.hip: launch_decode_column; unused dynamic LDS): what a CU wants is a certain amount of bytes in flight, not a
 	// certain number of workgroups.  One vector per workgroup: eight workgroups per CU up to 33 bits, seven up to 35, six beyond; seven for ALP_RD
-	// columns.  Two vectors per workgroup: eight / seven / six workgroups by width.  ALPGPU_DECODE_PAD_LDS_KIB overrides (A/B runs; 0 = never cap).
-	const int pad_env = ctx->decode_pad_kib; // ALPGPU_OPT_DECODE_RESIDENCY_PAD / ALPGPU_DECODE_PAD_LDS_KIB: -1 = by the rule below
-	int pad_kib = pad_env >= 0 ? pad_env : 0;
-	if (pad_env < 0 && ctx->decode_auto && pairing == 0 && col->packed_bytes_hint != 0 && col->n_vectors != 0 && !(ctx->read_ahead < 0 && read_ahead_for(ctx, col))) { // (under the read-ahead no cap helps)
+	// columns.  Two vectors per workgroup: eight / seven / six workgroups by width.  ALPGPU_OPT_DECODE_RESIDENCY_PAD overrides (0 = never cap).
+	int pad_kib = ctx->decode_pad_kib >= 0 ? ctx->decode_pad_kib : 0; // -1: by the rule below
+	if (ctx->decode_pad_kib < 0 && ctx->decode_auto && col->packed_bytes_hint != 0 && col->n_vectors != 0 && !(ctx->read_ahead < 0 && read_ahead_for(ctx, col))) { // (under the read-ahead no cap helps)
 		const double n        = static_cast<double>(col->n_vectors);
 		const double bits     = static_cast<double>(col->packed_bytes_hint) / (128.0 * n);
 		const bool   with_exc = column_decodes_with_exceptions(ctx, col);
 		const bool   mostly_rd = col->alp_rd_rowgroups_hint != 0 && 2.0 * static_cast<double>(col->alp_rd_rowgroups_hint - 1) * 100.0 > n;
 		// (re-measured in round 5 with the per-vector decode loops — a workgroup's stores no longer wait for one another, workgroups live shorter and a CU
 		//  wants somewhat fewer of them: tools/r05_decode_resid.py, profiles/r05_decode_exceptions.txt)
-		if ((variant & 5) == 1) {
+		if (variant & 1) {
 			// one vector per workgroup: up to ~30 bits a 6 KiB pad (ten workgroups' worth of LDS for eight: 0.77-0.80 -> 0.79-0.81, with exceptions
 			// 0.75-0.79 -> 0.78-0.82 up to 38 bits); 30-38 bits without exceptions none; from 38 bits on seven, then six workgroups per CU
 			// (+5-7 %); ALP_RD columns — more arithmetic per value — seven
@@ -90,7 +75,7 @@ static int decode_variant_for(const alpgpu_ctx* ctx, const alpgpu_column* col) {
 			} else {
 				pad_kib = bits >= 38.0 ? 14 : (bits >= 30.0 ? 0 : 6);
 			}
-		} else if ((variant & 5) == 0 && !with_exc) {
+		} else if (!with_exc) {
 			// two vectors per workgroup, no exceptions: sixteen vectors in flight per CU up to 8 bits, fourteen (seven workgroups) beyond.  With
 			// exceptions the caps lose.
 			pad_kib = bits > 8.5 ? 3 : 0;
@@ -99,16 +84,16 @@ static int decode_variant_for(const alpgpu_ctx* ctx, const alpgpu_column* col) {
 	// exception-heavy columns (more exceptions per vector than the 128-entry stage holds, on average): the instance with the 256-entry stage (decode_kernels.hip:
 	// DecodeLdsManyExc; one vector per workgroup, non-temporal stores): 0.72 -> 0.77 on bench.py's 10 %-exceptions column (call 6)
 	int many_exc = 0;
-	if (ctx->decode_auto && pairing == 0 && (variant & 7) == 1 && col->n_vectors != 0 && static_cast<double>(col->exc_bytes_hint) >= 10.0 * 128.0 * static_cast<double>(col->n_vectors) &&
+	if (ctx->decode_auto && (variant & 3) == 1 && col->n_vectors != 0 && static_cast<double>(col->exc_bytes_hint) >= 10.0 * 128.0 * static_cast<double>(col->n_vectors) &&
 	    !(col->alp_rd_rowgroups_hint != 0 && 2.0 * static_cast<double>(col->alp_rd_rowgroups_hint - 1) * 100.0 > static_cast<double>(col->n_vectors))) {
 		many_exc = 64;
 	}
-	return (variant & 7) | (pairing << 3) | many_exc | (pad_kib << 8);
+	return (variant & 3) | many_exc | (pad_kib << 8);
 }
 
 // Float columns (round 6): vectors per workgroup — 2 (the bytes in flight of one double vector), FOUR for columns of narrow vectors whose sizes are known, what
 // ALPGPU_OPT_DECODE_VECTORS_PER_WG says otherwise — and the residency pad (ALPGPU_OPT_DECODE_RESIDENCY_PAD, else none).  tools/sweep_f32_decode.py,
-// profiles/r06_float_decode.txt.  Returns vectors per workgroup | pad KiB << 8 (pad 0xFF: the kernel's environment knob, for experiments).
+// profiles/r06_float_decode.txt.  Returns vectors per workgroup | pad KiB << 8 (pad 0xFF: none).
 static int decode_shape_f32(const alpgpu_ctx* ctx, const alpgpu_column* col) {
 	int vpw = ctx->decode_vpw ? ctx->decode_vpw : 2;
 	if (ctx->decode_vpw == 0 && ctx->decode_auto && col->packed_bytes_hint != 0 && col->n_vectors != 0) {
@@ -201,7 +186,7 @@ static int stretch_kind(const alpgpu_ctx* ctx, uint64_t n, uint64_t packed, uint
 
 // runs[0 .. return) cover the column; 0 = no plan (decode the column whole)
 static int plan_decode_runs(alpgpu_ctx* ctx, const alpgpu_column* col, DecodeRun* runs, int value_bytes = 8) {
-	if (!ctx->decode_segments || !ctx->decode_auto || ctx->decode_pad_kib >= 0 || ctx->decode_pairing != 0) { return 0; } // (a forced shape is a forced shape)
+	if (!ctx->decode_segments || !ctx->decode_auto || ctx->decode_pad_kib >= 0) { return 0; } // (a forced shape is a forced shape)
 	if (value_bytes == 4 && ctx->decode_vpw != 0) { return 0; }
 	const SegmentTable* t = segment_table_of(ctx, col);
 	if (!t || t->n_seg < 2) { return 0; }
@@ -239,9 +224,7 @@ static alpgpu_column run_view(const alpgpu_column* col, const DecodeRun& r) {
 int alpgpu_decode_vectors_per_wg(alpgpu_ctx* ctx, const alpgpu_column* col, int is_f32) {
 	if (!ctx || !col) { return fail(ALPGPU_ERR_INVALID, "null context or column"); }
 	if (is_f32) { return decode_shape_f32(ctx, col) & 0xFF; }
-	const int variant = decode_variant_for(ctx, col);
-	if ((variant >> 3) & 3) { return 2; } // (the pair kernel: two vectors per workgroup, run together or one after the other)
-	return (variant & 4) ? 4 : ((variant & 1) ? 1 : 2);
+	return (decode_variant_for(ctx, col) & 1) ? 1 : 2;
 }
 
 // ... and whether it would start the read-ahead beside the decode kernel (ALPGPU_OPT_DECODE_READ_AHEAD): 1 / 0; negative on bad arguments
@@ -350,11 +333,7 @@ static int decode_one(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_out) {
 	// The read-ahead (read_ahead_kernels.hip): a few persistent workgroups on the context's second stream pull the column's streams into the Infinity
 	// Cache a bounded distance ahead of the decode kernel, which tells them where it is.  Started first so that it is ahead from the first workgroup on.
 	// (a float column streamed by persistent workgroups prefetches for itself; the read-ahead beside it changed nothing: call 14)
-#ifdef ALPGPU_STREAM_WITH_READ_AHEAD // measurement build: the read-ahead beside the streamed float decode too
-	const bool ahead = read_ahead_for(ctx, col, VB);
-#else
 	const bool ahead = read_ahead_for(ctx, col, VB) && !(VB == 4 && (decode_shape_f32(ctx, col) & 0xFF) >= 16);
-#endif
 	uint64_t   tag   = 0;
 	if (ahead) {
 		tag = next_progress_tag(ctx);
@@ -365,7 +344,7 @@ static int decode_one(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_out) {
 	// that is not even enqueued leaves, and that decode then runs without one).  The side stream has the higher priority: its few workgroups are placed at once.
 	int rc;
 	if constexpr (VB == 8) {
-		rc = alpgpu::launch_decode_column(ctx->stream, col, static_cast<double*>(d_out), decode_variant_for(ctx, col), ctx->n_cus, static_cast<uint32_t>(ctx->decode_patch_max), ahead ? ctx->d_progress : nullptr, tag);
+		rc = alpgpu::launch_decode_column(ctx->stream, col, static_cast<double*>(d_out), decode_variant_for(ctx, col), ctx->n_cus, ahead ? ctx->d_progress : nullptr, tag);
 	} else {
 		const int shape = decode_shape_f32(ctx, col);
 		if ((shape & 0xFF) >= 16) { // the column streamed by persistent workgroups (decode_stream_f32_kernels.hip): no read-ahead beside it, nothing to report
@@ -378,7 +357,7 @@ static int decode_one(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_out) {
 		const alpgpu::ReadAheadPace pace = alpgpu::policy_read_ahead_pace(static_cast<double>(col->n_vectors), static_cast<double>(col->packed_bytes_hint),
 		                                                                  static_cast<double>(col->exc_bytes_hint), VB, ctx->read_ahead_us); // (decode_policy.hpp: the lead is a time)
 		ALPGPU_HIP(hipStreamWaitEvent(ctx->init_stream, ctx->ev_fork, 0));
-		if (alpgpu::launch_read_ahead(ctx->init_stream, col, VB, ctx->d_progress, tag, pace.lead_min, pace.lead_max, pace.ps_per_vector, ctx->wall_tick_ps, static_cast<uint32_t>(ctx->read_ahead_bits), ctx->read_ahead_grid) != ALPGPU_OK) {
+		if (alpgpu::launch_read_ahead(ctx->init_stream, col, VB, ctx->d_progress, tag, pace.lead_min, pace.lead_max, pace.ps_per_vector, ctx->wall_tick_ps, kReadAheadMaxBits, kReadAheadGrid) != ALPGPU_OK) {
 			return fail(ALPGPU_ERR_HIP, "read-ahead launch failed", hipGetLastError());
 		}
 		ALPGPU_HIP(hipEventRecord(ctx->ev_join, ctx->init_stream));
@@ -437,7 +416,7 @@ static int decode_unhinted(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_ou
 	const uint64_t seg_vectors = segment_vectors_for(col->n_vectors);
 	const uint32_t n_seg       = static_cast<uint32_t>((col->n_vectors + seg_vectors - 1) / seg_vectors);
 	if (alpgpu::launch_segment_sums(ctx->stream, col, seg_vectors, n_seg, words + alpgpu::kCtxWordSegments) != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "segment sums launch failed", hipGetLastError()); }
-	if (alpgpu::launch_unhinted_plan(ctx->stream, words, n_seg, col->n_vectors, VB, (ctx->read_ahead < 0 && ctx->streams_serialize) ? 0 : ctx->read_ahead, ctx->read_ahead_us, static_cast<uint32_t>(ctx->read_ahead_bits)) != ALPGPU_OK) {
+	if (alpgpu::launch_unhinted_plan(ctx->stream, words, n_seg, col->n_vectors, VB, (ctx->read_ahead < 0 && ctx->streams_serialize) ? 0 : ctx->read_ahead, ctx->read_ahead_us, kReadAheadMaxBits) != ALPGPU_OK) {
 		return fail(ALPGPU_ERR_HIP, "plan launch failed", hipGetLastError());
 	}
 	const uint64_t tag        = next_progress_tag(ctx);
@@ -453,17 +432,17 @@ static int decode_unhinted(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_ou
 		if (ctx->decode_unhinted == 2) {
 			const int variants[alpgpu::kUnhintedShapesF64] = {1 | (6 << 8), 0, 1 | (11 << 8)};
 			for (int c = 0; c < alpgpu::kUnhintedShapesF64 && rc == ALPGPU_OK; ++c) {
-				rc = alpgpu::launch_decode_column(ctx->stream, col, static_cast<double*>(d_out), variants[c] | (plain ? 2 : 0), ctx->n_cus, 0u, words, tag, static_cast<uint32_t>(c + 1));
+				rc = alpgpu::launch_decode_column(ctx->stream, col, static_cast<double*>(d_out), variants[c] | (plain ? 2 : 0), ctx->n_cus, words, tag, static_cast<uint32_t>(c + 1));
 			}
 		} else {
-			rc = alpgpu::launch_decode_column(ctx->stream, col, static_cast<double*>(d_out), 1 | (6 << 8) | (plain ? 2 : 0), ctx->n_cus, 0u, words, tag, 0u);
+			rc = alpgpu::launch_decode_column(ctx->stream, col, static_cast<double*>(d_out), 1 | (6 << 8) | (plain ? 2 : 0), ctx->n_cus, words, tag, 0u);
 		}
 	} else {
 		rc = alpgpu::launch_decode_column_f32(ctx->stream, col, static_cast<float*>(d_out), 2, plain, 0, words, tag, 0u);
 	}
 	if (with_ahead) { // behind the decode's launch (decode_one says why); the kernel leaves at once when the plan says "no read-ahead for this column"
 		ALPGPU_HIP(hipStreamWaitEvent(ctx->init_stream, ctx->ev_fork, 0));
-		if (alpgpu::launch_read_ahead(ctx->init_stream, col, VB, words, tag, 0, 0, 0, ctx->wall_tick_ps, 0, ctx->read_ahead_grid, true) != ALPGPU_OK) {
+		if (alpgpu::launch_read_ahead(ctx->init_stream, col, VB, words, tag, 0, 0, 0, ctx->wall_tick_ps, 0, kReadAheadGrid, true) != ALPGPU_OK) {
 			return fail(ALPGPU_ERR_HIP, "read-ahead launch failed", hipGetLastError());
 		}
 		ALPGPU_HIP(hipEventRecord(ctx->ev_join, ctx->init_stream));
@@ -504,7 +483,7 @@ static int decode_column(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_out)
 	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
 	alpgpu_column hinted;
 	const bool    unhinted = col->packed_bytes_hint == 0 && col->exc_bytes_hint == 0;
-	const bool    free_shape = ctx->decode_auto && ctx->decode_pairing == 0 && ctx->decode_pad_kib < 0 && (VB == 8 || ctx->decode_vpw == 0);
+	const bool    free_shape = ctx->decode_auto && ctx->decode_pad_kib < 0 && (VB == 8 || ctx->decode_vpw == 0);
 	if (unhinted && ctx->decode_unhinted && free_shape && ctx->d_progress != nullptr && col->n_vectors >= kUnhintedMinVectors) {
 		if (learned_hints(ctx, col, VB, &hinted)) {
 			col = &hinted; // an earlier decode of this column took its sizes: planned on the host from here on

@@ -58,8 +58,7 @@ static int encode_vectors_f64(alpgpu_ctx* ctx, const double* d_in, uint64_t n_ve
 	if (ctx->encode_two_pass) {
 		rc = alpgpu::launch_encode_vectors(ctx->stream, d_in, n_vectors, col, ws, ctx->n_cus);
 	} else {
-		const int kernel = ctx->encode_kernel | ((ctx->encode_unordered && ctx->encode_kernel == ALPGPU_ENCODE_KERNEL_LEAN) ? alpgpu::kEncodeUnorderedFlag : 0);
-		rc = alpgpu::launch_encode_fused(ctx->stream, d_in, n_vectors, col, ws, ctx->force_stall != 0, async_states, ctx->ev_join, ctx->ev_head, kernel); // (waits for / joins the search's stream)
+		rc = alpgpu::launch_encode_fused(ctx->stream, d_in, n_vectors, col, ws, ctx->force_stall != 0, async_states, ctx->ev_join, ctx->ev_head, ctx->encode_unordered != 0); // (waits for / joins the search's stream)
 		if (rc == ALPGPU_OK) { rc = alpgpu::launch_encode_vectors(ctx->stream, d_in, n_vectors, col, ws, ctx->n_cus, col->d_totals + 6); }
 	}
 	if (rc != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "encode launch failed", hipGetLastError()); }
@@ -91,11 +90,10 @@ static int encode_with_side_search(alpgpu_ctx* ctx, const T* d_in, uint64_t n_ve
 	ALPGPU_CHECK_CTX(ctx);
 	if (!d_in) { return fail(ALPGPU_ERR_INVALID, "null input"); }
 	if (int rc = check_column(col, n_vectors)) { return rc; }
-	static const bool serial = std::getenv("ALPGPU_ASYNC_SERIAL") != nullptr; // experiment: the publishing search IN FRONT of the polling encode, one stream
-	hipStream_t       side   = serial ? ctx->stream : ctx->init_stream;
+	hipStream_t side = ctx->init_stream;
 	ALPGPU_HIP(hipMemsetAsync(col->d_rowgroups, alpgpu::kStateUnpublished, 32ull * n_rg, ctx->stream)); // "unpublished": no tag, every word all-ones (alp_device.hpp)
 	ALPGPU_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-	if (!serial) { ALPGPU_HIP(hipStreamWaitEvent(ctx->init_stream, ctx->ev_fork, 0)); }
+	ALPGPU_HIP(hipStreamWaitEvent(ctx->init_stream, ctx->ev_fork, 0));
 	// the head of the search and, behind it, the persistent rest: both on the side stream; the context's stream meanwhile clears its
 	// totals and status words and then waits for the head only
 	auto search = [&](uint64_t first, uint64_t count, int grid, uint32_t adaptive_base = 0) {
@@ -103,16 +101,16 @@ static int encode_with_side_search(alpgpu_ctx* ctx, const T* d_in, uint64_t n_ve
 			return alpgpu::launch_rowgroup_init_async_f32(side, d_in, n_vectors, col->d_rowgroups, col->d_rd_order, first, count, grid);
 		} else {
 			return alpgpu::launch_rowgroup_init_async(side, d_in, n_vectors, col->d_rowgroups, col->d_rd_order, first, count, grid,
-			                                          ctx->encode_kernel == ALPGPU_ENCODE_KERNEL_LEAN && count > static_cast<uint64_t>(grid), adaptive_base);
+			                                          count > static_cast<uint64_t>(grid), adaptive_base);
 		}
 	};
 	if (search(0, kAsyncHeadRowgroups, static_cast<int>(kAsyncHeadRowgroups)) != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "rowgroup init launch failed", hipGetLastError()); }
 	ALPGPU_HIP(hipEventRecord(ctx->ev_head, side));
 	// double columns beside the lean kernel: three search workgroups per CU are launched, two of them leave at once unless the column's head is
 	// mostly ALP_RD (whose latency-bound search the encode would wait for anyway; k_rowgroup_init: `walkers`)
-	const bool adaptive = !f32 && ctx->async_init_adaptive && ctx->encode_kernel == ALPGPU_ENCODE_KERNEL_LEAN && ctx->async_init_wg_per_cu < 3;
-	const int  wg_per_cu = adaptive ? 3 : ctx->async_init_wg_per_cu;
-	if (search(kAsyncHeadRowgroups, n_rg - kAsyncHeadRowgroups, ctx->n_cus * wg_per_cu, adaptive ? static_cast<uint32_t>(ctx->n_cus * ctx->async_init_wg_per_cu) : 0u) != ALPGPU_OK) {
+	// (float columns: one search workgroup per CU)
+	const int wg_per_cu = f32 ? 1 : 3;
+	if (search(kAsyncHeadRowgroups, n_rg - kAsyncHeadRowgroups, ctx->n_cus * wg_per_cu, f32 ? 0u : static_cast<uint32_t>(ctx->n_cus)) != ALPGPU_OK) {
 		return fail(ALPGPU_ERR_HIP, "rowgroup init launch failed", hipGetLastError());
 	}
 	ALPGPU_HIP(hipEventRecord(ctx->ev_join, side));
@@ -224,15 +222,12 @@ int alpgpu_debug_traffic_probe_with_search(alpgpu_ctx* ctx, const double* d_in, 
 	ALPGPU_HIP(hipMemsetAsync(scratch->d_rowgroups, alpgpu::kStateUnpublished, 32ull * n_rg, ctx->stream));
 	ALPGPU_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
 	ALPGPU_HIP(hipStreamWaitEvent(ctx->init_stream, ctx->ev_fork, 0));
-	const bool lean = ctx->encode_kernel == ALPGPU_ENCODE_KERNEL_LEAN;
 	if (alpgpu::launch_rowgroup_init_async(ctx->init_stream, d_in, n_vectors, scratch->d_rowgroups, scratch->d_rd_order, 0, kAsyncHeadRowgroups, static_cast<int>(kAsyncHeadRowgroups), false, 0) != ALPGPU_OK) {
 		return fail(ALPGPU_ERR_HIP, "rowgroup init launch failed", hipGetLastError());
 	}
 	ALPGPU_HIP(hipEventRecord(ctx->ev_head, ctx->init_stream));
-	const bool adaptive  = ctx->async_init_adaptive && lean && ctx->async_init_wg_per_cu < 3;
-	const int  wg_per_cu = adaptive ? 3 : ctx->async_init_wg_per_cu;
-	if (alpgpu::launch_rowgroup_init_async(ctx->init_stream, d_in, n_vectors, scratch->d_rowgroups, scratch->d_rd_order, kAsyncHeadRowgroups, n_rg - kAsyncHeadRowgroups, ctx->n_cus * wg_per_cu,
-	                                       lean, adaptive ? static_cast<uint32_t>(ctx->n_cus * ctx->async_init_wg_per_cu) : 0u) != ALPGPU_OK) {
+	if (alpgpu::launch_rowgroup_init_async(ctx->init_stream, d_in, n_vectors, scratch->d_rowgroups, scratch->d_rd_order, kAsyncHeadRowgroups, n_rg - kAsyncHeadRowgroups, ctx->n_cus * 3,
+	                                       true, static_cast<uint32_t>(ctx->n_cus)) != ALPGPU_OK) {
 		return fail(ALPGPU_ERR_HIP, "rowgroup init launch failed", hipGetLastError());
 	}
 	ALPGPU_HIP(hipEventRecord(ctx->ev_join, ctx->init_stream));

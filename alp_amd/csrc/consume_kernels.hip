@@ -26,28 +26,17 @@
 
 namespace alpgpu {
 
-#ifndef ALPGPU_CONS_WAVES
-#define ALPGPU_CONS_WAVES 8
-#endif
-#ifndef ALPGPU_CONS_RING
-#define ALPGPU_CONS_RING 8
-#endif
-#ifndef ALPGPU_CONS_PREFETCH
-#define ALPGPU_CONS_PREFETCH 4
-#endif
-#ifndef ALPGPU_CONS_WG_PER_CU
-#define ALPGPU_CONS_WG_PER_CU 2
-#endif
-constexpr int      kConsWaves     = ALPGPU_CONS_WAVES;    // wavefronts per workgroup (no cooperation between them: LDS bookkeeping only)
-constexpr int      kRingPieces    = ALPGPU_CONS_RING;     // 1-KiB pieces per wavefront ring (a power of two).  A vector whose packed words + exception
+constexpr int kConsWgPerCu = 2;
+constexpr int      kConsWaves     = 8;    // wavefronts per workgroup (no cooperation between them: LDS bookkeeping only)
+constexpr int      kRingPieces    = 8;     // 1-KiB pieces per wavefront ring (a power of two).  A vector whose packed words + exception
                                                           // record need more pieces than the ring has (8: ALP wider than 56 bits with exceptions, a few
                                                           // ALP_RD shapes) is unpacked straight from HBM, without the ring — rare, correct, not fast
 constexpr uint32_t kRingBytes     = 1024u * kRingPieces;
-constexpr int      kPrefetchMax   = ALPGPU_CONS_PREFETCH; // vectors in flight behind the one being unpacked (ring space permitting)
+constexpr int      kPrefetchMax   = 4; // vectors in flight behind the one being unpacked (ring space permitting)
 constexpr uint32_t kExcStageBytes = 1024; // of a vector's exception record that travels with its packed words (ALP: the values of <= 128
                                           // exceptions, the whole record up to 102; ALP_RD: whole records up to 256 exceptions)
 static_assert((kRingPieces & (kRingPieces - 1)) == 0 && kRingPieces >= 4, "ring = power of two");
-constexpr int kConsWavesPerSimd = kConsWaves * ALPGPU_CONS_WG_PER_CU / 4; // the occupancy the register budget is sized for
+constexpr int kConsWavesPerSimd = kConsWaves * kConsWgPerCu / 4; // the occupancy the register budget is sized for
 
 constexpr int kDescBatch = 8;  // descriptors requested together (one 32-byte LDS-DMA load each)
 constexpr int kDescSlots = 32; // descriptor ring: the batch in use, the two ahead of it, and the one being replaced
@@ -338,11 +327,7 @@ __global__ __launch_bounds__(64 * kConsWaves, kConsWavesPerSimd) void k_consume_
 			for (uint32_t j = 0; j < pk_pieces; ++j) { // wave-uniform trip count
 				const uint32_t c   = 64u * j + static_cast<uint32_t>(lane);
 				uint8_t*       dst = L.ring + (((head + j) & (kRingPieces - 1u)) << 10); // wave-uniform base; the hardware adds 16 * lane
-#ifdef ALPGPU_CONS_NO_DMA // experiment: through registers
-				if (c < n_units) { reinterpret_cast<ull2*>(dst)[lane] = g[c]; }
-#else
 				if (c < n_units) { __builtin_amdgcn_global_load_lds(g + c, reinterpret_cast<ull2*>(dst), 16, 0, 0); }
-#endif
 			}
 			if (exc_loads) {
 				const bool      is_alp = d_issue.scheme == ALPGPU_SCHEME_ALP;
@@ -352,11 +337,7 @@ __global__ __launch_bounds__(64 * kConsWaves, kConsWavesPerSimd) void k_consume_
 				uint8_t*        dst    = L.ring + (((head + pk_pieces) & (kRingPieces - 1u)) << 10);
 				for (uint32_t q = 0; q < exc_loads; ++q) {
 					const uint32_t c = 64u * q + static_cast<uint32_t>(lane);
-#ifdef ALPGPU_CONS_NO_DMA
-					if (c < dwords) { reinterpret_cast<uint32_t*>(dst + 256u * q)[lane] = ge[c]; }
-#else
 					if (c < dwords) { __builtin_amdgcn_global_load_lds(ge + c, reinterpret_cast<uint32_t*>(dst + 256u * q), 4, 0, 0); }
-#endif
 				}
 			}
 			issued += pk_pieces + exc_loads;
@@ -394,33 +375,6 @@ __global__ __launch_bounds__(64 * kConsWaves, kConsWavesPerSimd) void k_consume_
 		const uint32_t rec_l    = ring_lds + (((start_piece + pk_pieces) & (kRingPieces - 1u)) << 10);
 		if (cnt > 0 && lane < 32) { lds_write_b32(mask_lds + 4u * static_cast<uint32_t>(lane), 0u); }
 		wait_vmcnt_le(issued - end_count); // everything of vector k has landed in the ring
-#ifdef ALPGPU_CONS_DELAY // experiment
-		for (int zz = 0; zz < ALPGPU_CONS_DELAY; ++zz) { __builtin_amdgcn_s_sleep(127); }
-#endif
-#ifdef ALPGPU_CONS_VERIFY // experiment: is the ring what was asked for?  out[v] = mismatching 16-byte units + 1000 * (first bad unit + 1)
-		{
-			const uint32_t n_units_k = 8u * (static_cast<uint32_t>(d.bw) + (is_alp ? 0u : static_cast<uint32_t>(d.lbw)));
-			const ull2v_t* gk        = reinterpret_cast<const ull2v_t*>(packed + d.packed_off);
-			int            bad = 0, first = 1 << 20;
-			for (uint32_t c = lane; c < n_units_k; c += 64) {
-				const ull2v_t want = gk[c];
-				ull2v_t       have;
-				asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(have) : "v"(ring_lds + ((((start_piece & (kRingPieces - 1u)) << 10) + 16u * c) & (kRingBytes - 1u))) : "memory");
-				if (want.x != have.x || want.y != have.y) {
-					++bad;
-					first = first < static_cast<int>(c) ? first : static_cast<int>(c);
-				}
-			}
-			for (int dd = 32; dd >= 1; dd >>= 1) {
-				bad += __shfl_xor(bad, dd);
-				const int o = __shfl_xor(first, dd);
-				first       = o < first ? o : first;
-			}
-			if (lane == 0) { static_cast<double*>(out)[v] = bad == 0 ? 0.0 : static_cast<double>(bad + 1000 * (first + 1)); }
-			tail = start_piece + pk_pieces + (exc_loads ? 1u : 0u);
-			continue;
-		}
-#endif
 		ConsExcMask em {0u, 0};
 		if (cnt > 0) { // wave-uniform
 			if (whole) {
@@ -607,7 +561,7 @@ __global__ __launch_bounds__(256) void k_tree_sum(const double* __restrict__ in,
 }
 
 static unsigned consume_grid(int n_cus, uint64_t n_vectors) {
-	const uint64_t want = static_cast<uint64_t>(n_cus > 0 ? n_cus : 256) * ALPGPU_CONS_WG_PER_CU;
+	const uint64_t want = static_cast<uint64_t>(n_cus > 0 ? n_cus : 256) * kConsWgPerCu;
 	const uint64_t need = (n_vectors + kConsWaves - 1) / kConsWaves;
 	return static_cast<unsigned>(need < want ? need : want);
 }

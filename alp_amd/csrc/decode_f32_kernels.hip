@@ -22,10 +22,7 @@ namespace alpgpu {
 
 constexpr int kDecThreadsF  = 256;
 constexpr int kStageBytesF  = 4480; // >= 31*128 (RD right) + 3*128 (RD left) + 128 pad, and >= 32*128 + 128 (ALP bw 32)
-#ifndef ALPGPU_EXC_STAGE_F
-#define ALPGPU_EXC_STAGE_F 256 // (round 5, late: 128 -> 256.  bench.py's decimal float column carries 94 exceptions per vector on average, 39 % of its vectors more than 128: decode 0.72-0.73 -> 0.75-0.76; the others unchanged)
-#endif
-constexpr int kExcStageF    = ALPGPU_EXC_STAGE_F; // exception values (4 bytes; ALP_RD: twice as many 2-byte ones) staged in LDS per vector
+constexpr int kExcStageF    = 256; // exception values (4 bytes; ALP_RD: twice as many 2-byte ones) staged in LDS per vector (round 5, late: 128 -> 256.  bench.py's decimal float column carries 94 exceptions per vector on average, 39 % of its vectors more than 128: decode 0.72-0.73 -> 0.75-0.76; the others unchanged)
 
 struct __attribute__((aligned(16))) DecodeLdsF32 {
 	static constexpr bool kPrefixInLds = false; // exception lookup by ds_bpermute
@@ -77,9 +74,6 @@ __device__ __forceinline__ uint32_t fetch_exception_f32(const LDS& L, const uint
 			} else {
 				v = reinterpret_cast<const uint16_t*>(rec)[rank];
 			}
-#ifdef ALPGPU_F32_EXC_WAIT_IN_BRANCH // A/B (round 5): waited for HERE instead of at the join in front of the quad's store — measured 4 % SLOWER on columns whose vectors carry more exceptions than the stage holds (every such fetch then waits on its own)
-			asm volatile("" : "+v"(v));
-#endif
 		}
 	}
 	return v;
@@ -194,12 +188,6 @@ __device__ __forceinline__ void finish_quad_f32(const LDS& L, const QuadWords& w
 	u32x4          q;
 #pragma unroll
 	for (int c = 0; c < 4; ++c) { q[c] = __builtin_amdgcn_alignbit(w.w1[c], w.w0[c], s) & msk; }
-#if defined(ALPGPU_SINKF_STOP_AT) && ALPGPU_SINKF_STOP_AT == 4 // measurement builds (profiles/r05_float_sink.txt): the quad ends behind its unpack
-	if constexpr (SINK != kSinkStoreF) {
-		*acc += static_cast<double>(q[0] ^ q[1] ^ q[2] ^ q[3] ^ hits);
-		return;
-	}
-#endif
 	u32x4          out;
 	if (d.scheme == ALPGPU_SCHEME_ALP) {
 		const uint32_t base = static_cast<uint32_t>(d.base);
@@ -222,12 +210,6 @@ __device__ __forceinline__ void finish_quad_f32(const LDS& L, const QuadWords& w
 #pragma unroll
 			for (int c = 0; c < 4; ++c) { out[c] = __float_as_uint(decode_value_f32(static_cast<int32_t>(q[c] + base), fact, frac)); }
 		}
-#if defined(ALPGPU_SINKF_STOP_AT) && ALPGPU_SINKF_STOP_AT == 5 // ... behind the conversion
-		if constexpr (SINK != kSinkStoreF) {
-			*acc += static_cast<double>(out[0] ^ out[1] ^ out[2] ^ out[3] ^ hits);
-			return;
-		}
-#endif
 		if constexpr (kApart) {
 			// (the sinks: an exception position contributes +0.0f — (double)(+0.0f) added to a partial that is never -0.0 leaves it as it is — or, for COUNT, a NaN)
 #pragma unroll
@@ -258,11 +240,7 @@ __device__ __forceinline__ void finish_quad_f32(const LDS& L, const QuadWords& w
 			const uint32_t f0  = static_cast<uint32_t>(w.l0 >> (16 * c)) & 0xFFFFu;
 			const uint32_t f1  = static_cast<uint32_t>(w.l1 >> (16 * c)) & 0xFFFFu;
 			const uint32_t idx = ((f0 >> ls) | (f1 << (16 - ls))) & lmsk;
-#ifdef ALPGPU_F32_RD_DICT_IN_REGISTERS // A/B (round 6): the lookup as it was until round 5
-			uint32_t       l   = static_cast<uint32_t>((idx < 4 ? dlo >> (16 * idx) : dhi >> (16 * (idx & 3))) & 0xFFFFull);
-#else
 			uint32_t       l   = L.rdict[idx & 7u];
-#endif
 			if (hits & (1u << c)) {
 				l = fetch_exception_f32<2>(L, rec, rank, all_staged);
 				++rank;
@@ -270,12 +248,6 @@ __device__ __forceinline__ void finish_quad_f32(const LDS& L, const QuadWords& w
 			out[c] = (l << rbw) | q[c];
 		}
 	}
-#if defined(ALPGPU_SINKF_STOP_AT) && ALPGPU_SINKF_STOP_AT == 6 // ... behind the exceptions, in front of the widening adds
-	if constexpr (SINK != kSinkStoreF) {
-		*acc += static_cast<double>(out[0] ^ out[1] ^ out[2] ^ out[3]);
-		return;
-	}
-#endif
 	if constexpr (SINK == kSinkSumF) {
 #pragma unroll
 		for (int c = 0; c < 4; ++c) { *acc += static_cast<double>(__uint_as_float(out[c])); }
@@ -351,15 +323,6 @@ __global__ __launch_bounds__(kDecThreadsF) void k_decode_column_f32(const alpgpu
 		if (progress != nullptr && (blockIdx.x & 127u) == 0 && tid == 0) { __hip_atomic_store(progress, progress_tag | v0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 	}
 
-#if defined(ALPGPU_F32_DISSECT) && ALPGPU_F32_DISSECT == 3 // measurement builds (profiles/r06_float_decode.txt): the launch as a plain fill
-	if constexpr (SINK == kSinkStoreF) {
-#pragma unroll
-		for (int i = 0; i < V; ++i) {
-			if (v0 + i < n_vectors) { store_quad<NT_STORE>(out + (v0 + i) * kVec + 4 * tid, u32x4 {1u, 2u, 3u, 4u}); }
-		}
-		return;
-	}
-#endif
 	alpgpu_vector_desc d[V];
 	uint32_t           pos[V];
 #pragma unroll
@@ -370,16 +333,6 @@ __global__ __launch_bounds__(kDecThreadsF) void k_decode_column_f32(const alpgpu
 	RdDict dict[V];
 #pragma unroll
 	for (int i = 0; i < V; ++i) { dict[i] = load_vector_consts_f32(rgs, v0 + i < n_vectors ? v0 + i : v0, d[i]); }
-#if defined(ALPGPU_F32_DISSECT) && ALPGPU_F32_DISSECT == 2 // ... a fill behind the descriptors' round trip
-	if constexpr (SINK == kSinkStoreF) {
-#pragma unroll
-		for (int i = 0; i < V; ++i) {
-			const uint32_t x = static_cast<uint32_t>(d[i].base) + d[i].bw + static_cast<uint32_t>(dict[i].lo ^ dict[i].hi);
-			if (v0 + i < n_vectors) { store_quad<NT_STORE>(out + (v0 + i) * kVec + 4 * tid, u32x4 {x, x + tid, 3u, 4u}); }
-		}
-		return;
-	}
-#endif
 #pragma unroll
 	for (int i = 0; i < V; ++i) { pos[i] = issue_vector_loads_f32(L[i], d[i], packed, excs + d[i].exc_off, tid, wave); }
 	// ALP_RD vectors: the dictionary into the vector's LDS (lanes 0..3 of wavefront 0; visible behind the barrier below)
@@ -435,13 +388,6 @@ __global__ __launch_bounds__(kDecThreadsF) void k_decode_column_f32(const alpgpu
 		}
 		return;
 	}
-#if defined(ALPGPU_F32_DISSECT) && ALPGPU_F32_DISSECT == 1 // ... the staged words stored as they are (no unpack, no exceptions)
-#pragma unroll
-	for (int i = 0; i < V; ++i) {
-		if (v0 + i < n_vectors) { store_quad<NT_STORE>(out + (v0 + i) * kVec + 4 * tid, reinterpret_cast<const u32x4*>(L[i].stage)[tid & 31]); }
-	}
-	return;
-#endif
 #pragma unroll
 	for (int i = 0; i < V; ++i) {
 		if (v0 + i < n_vectors) {
@@ -455,9 +401,8 @@ static void launch_v(hipStream_t stream, const alpgpu_column* col, float* d_out,
 	const uint64_t n        = col->n_vectors;
 	const uint64_t n_wg     = (n + V - 1) / V;
 	const uint64_t kMaxGrid = 1ull << 30;
-	// unused dynamic LDS that caps the workgroups resident per CU, as the double decode does by width (pad_kib < 0: ALPGPU_DECODE_F32_PAD_LDS_KIB, for experiments, else none)
-	static const int env_pad = std::getenv("ALPGPU_DECODE_F32_PAD_LDS_KIB") ? std::atoi(std::getenv("ALPGPU_DECODE_F32_PAD_LDS_KIB")) : 0;
-	const unsigned   pad_lds = static_cast<unsigned>(pad_kib >= 0 ? pad_kib : env_pad) * 1024u;
+	// unused dynamic LDS that caps the workgroups resident per CU, as the double decode does by width (pad_kib < 0: none)
+	const unsigned pad_lds = static_cast<unsigned>(pad_kib >= 0 ? pad_kib : 0) * 1024u;
 	if (gate != 0 && progress == nullptr) { gate = 0; }
 	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
 		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(kDecThreadsF);
@@ -502,17 +447,11 @@ static int launch_sink_f32(hipStream_t stream, const alpgpu_column* col, void* d
 // ---- the float sinks with ONE wavefront per vector, packed words straight from HBM (decode_kernels.hip: k_sink_direct) ----------------
 // Lane L does what threads L, 64 + L, 128 + L, 192 + L of the staged kernel do: four quads, their partials kept apart (p[w][L]), all four
 // quads' words requested before the first is used; then (p0 + p1) + (p2 + p3) and the adjacent-lane tree: the same bits.
-#ifndef ALPGPU_SINK_STAGE_F32
-#define ALPGPU_SINK_STAGE_F32 3584 // bytes of packed words (bit widths <= 28) a wavefront of k_sink_direct_f32 stages in its LDS by LDS-DMA (0: none), as k_sink_direct does
-#endif
-#ifndef ALPGPU_SINK_STAGE_F32_MAX_EXC
-#define ALPGPU_SINK_STAGE_F32_MAX_EXC 1024 // ... only for vectors with at most this many exceptions (round 6: any — it was 48 while the exception values were looked up per quad; with them taken behind the quads the stage pays at every count: +1.5 %, call 26)
-#endif
+constexpr int kSinkStageF32 = 3584; // bytes of packed words (bit widths <= 28) a wavefront of k_sink_direct_f32 stages in its LDS by LDS-DMA (0: none), as k_sink_direct does
+constexpr int kSinkStageF32MaxExc = 1024; // ... only for vectors with at most this many exceptions (round 6: any — it was 48 while the exception values were looked up per quad; with them taken behind the quads the stage pays at every count: +1.5 %, call 26)
 struct __attribute__((aligned(16))) SinkWaveLdsF32 {
 	static constexpr bool kPrefixInLds = true;
-#if ALPGPU_SINK_STAGE_F32 > 0
-	uint8_t  stage[ALPGPU_SINK_STAGE_F32 + 128]; // + the unit row past the end that the unpack reads and masks off
-#endif
+	uint8_t  stage[kSinkStageF32 + 128]; // + the unit row past the end that the unpack reads and masks off
 	uint32_t mask[32];
 	uint8_t  excv[4 * kExcStageF];
 	uint32_t pref[32]; // exceptions in front of mask word i
@@ -540,21 +479,12 @@ __global__ __launch_bounds__(kDecThreadsF, 8) void k_sink_direct_f32(const alpgp
 	const bool               is_alp = d.scheme == ALPGPU_SCHEME_ALP;
 	const int                cnt    = d.exc_cnt;
 	ExcMaskF                 em {0u, 0};
-#if defined(ALPGPU_SINKF_STOP_AT) && ALPGPU_SINKF_STOP_AT == 1 // measurement builds: every wavefront ends behind stage n with one dependent store
-	if (lane == 0) { out[v] = static_cast<double>(d.bw + cnt) + static_cast<double>(dict.lo ^ dict.hi); }
-	return;
-#endif
-#if ALPGPU_SINK_STAGE_F32 > 0
 	// Round 4: a narrow ALP vector's words whole into the wavefront's LDS by LDS-DMA (1 KiB per instruction, no registers): ONE round trip for all
 	// of them instead of eight 16-byte buffer loads per lane — what took the double sink from 0.85 to 0.73 ms (profiles/r03_consumers.txt) and what
 	// the float one never had ("is the stage arm even taken for float?" — there was none).
 	// (late round 4: ALP_RD vectors too — right words, then left words, as they lie in the stream; -DALPGPU_SINK_STAGE_F32_ALP_ONLY: the first form)
-#ifdef ALPGPU_SINK_STAGE_F32_ALP_ONLY
-	const int  stage_words = is_alp ? static_cast<int>(d.bw) : 1000;
-#else
 	const int  stage_words = static_cast<int>(d.bw) + (is_alp ? 0 : static_cast<int>(d.lbw));
-#endif
-	const bool staged = 128 * stage_words <= ALPGPU_SINK_STAGE_F32 && cnt <= ALPGPU_SINK_STAGE_F32_MAX_EXC; // wave-uniform
+	const bool staged = 128 * stage_words <= kSinkStageF32 && cnt <= kSinkStageF32MaxExc; // wave-uniform
 	if (staged) {
 		typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
 		const ull2* g       = reinterpret_cast<const ull2*>(packed + d.packed_off);
@@ -563,7 +493,6 @@ __global__ __launch_bounds__(kDecThreadsF, 8) void k_sink_direct_f32(const alpgp
 			if (64 * j + lane < n_units) { __builtin_amdgcn_global_load_lds(g + 64 * j + lane, reinterpret_cast<ull2*>(L.stage) + 64 * j, 16, 0, 0); }
 		}
 	}
-#endif
 	if (cnt > 0) { // wave-uniform: values of the first kExcStageF exceptions by LDS-DMA, the mask from the positions
 		const uint32_t val_bytes = (is_alp ? 4u : 2u) * static_cast<uint32_t>(cnt);
 		const int      dwords    = static_cast<int>(((val_bytes < 4u * kExcStageF ? val_bytes : 4u * kExcStageF) + 3u) >> 2);
@@ -587,17 +516,11 @@ __global__ __launch_bounds__(kDecThreadsF, 8) void k_sink_direct_f32(const alpgp
 	constexpr int      kRsrcFlags = 0x00020000; // gfx9 raw buffer, 32-bit data format
 	const BufferWordsF words {__builtin_amdgcn_make_buffer_rsrc(first, 0, 128 * d.bw, kRsrcFlags),
 	                          __builtin_amdgcn_make_buffer_rsrc(first + 128u * d.bw, 0, is_alp ? 0 : 128 * d.lbw, kRsrcFlags)};
-#if defined(ALPGPU_SINKF_STOP_AT) && ALPGPU_SINKF_STOP_AT == 2 // ... behind the issue of the loads and the exception mask
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	if (lane == 0) { out[v] = static_cast<double>(em.excl + static_cast<int>(em.word)); }
-	return;
-#endif
 	if (!is_alp) { // wave-uniform: the dictionary into the wavefront's LDS, behind the issue of every load (its own scalar loads are waited for here, not in front of them)
 		if (lane < 4) { reinterpret_cast<uint32_t*>(L.rdict)[lane] = static_cast<uint32_t>((lane < 2 ? dict.lo : dict.hi) >> (32 * (lane & 1))); }
 		wave_lds_sync();
 	}
 	QuadWords w[4];
-#if ALPGPU_SINK_STAGE_F32 > 0
 	if (staged) {
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // LDS-DMA completion is not tracked through the LDS for the compiler
 		wave_lds_sync();
@@ -605,20 +528,10 @@ __global__ __launch_bounds__(kDecThreadsF, 8) void k_sink_direct_f32(const alpgp
 #pragma unroll
 		for (int q = 0; q < 4; ++q) { w[q] = request_quad_f32(sw, d, 64 * q + lane); }
 	} else
-#endif
 	{
 #pragma unroll
 		for (int q = 0; q < 4; ++q) { w[q] = request_quad_f32(words, d, 64 * q + lane); }
 	}
-#if defined(ALPGPU_SINKF_STOP_AT) && ALPGPU_SINKF_STOP_AT == 3 // ... behind the arrival of the quads' words
-	{
-		uint32_t x = 0;
-#pragma unroll
-		for (int q = 0; q < 4; ++q) { x ^= w[q].w0[0] ^ w[q].w0[1] ^ w[q].w0[2] ^ w[q].w0[3] ^ w[q].w1[0] ^ w[q].w1[1] ^ w[q].w1[2] ^ w[q].w1[3] ^ static_cast<uint32_t>(w[q].l0 ^ w[q].l1); }
-		out[v * 64 % n_vectors] = static_cast<double>(x);
-		return;
-	}
-#endif
 	if constexpr (SINK == kSinkStoreF) {
 		// Round 6: the same wavefront as a STORE decoder (ALPGPU_OPT_DECODE_VECTORS_PER_WG = 8 for float columns): lane L's four quads are the 16-byte units L, 64 + L,
 		// 128 + L, 192 + L of the vector — four store instructions of 1 KiB each, no barrier, one wave-uniform prologue per vector instead of four.

@@ -34,19 +34,11 @@
 
 namespace alpgpu {
 
-#ifndef ALPGPU_DEC_WAVES
-#define ALPGPU_DEC_WAVES 4
-#endif
-constexpr int kDecWaves     = ALPGPU_DEC_WAVES; // wavefronts cooperating on one vector
+constexpr int kDecWaves     = 4; // wavefronts cooperating on one vector
 constexpr int kStepsPerWave = 8 / kDecWaves;
-#ifndef ALPGPU_DECODE_BATCH
-#define ALPGPU_DECODE_BATCH 4 // steps whose words are requested together (decode_vector_quarters)
-#endif
+constexpr int kDecodeBatch  = 4; // steps whose words are requested together (decode_vector_quarters)
 constexpr int kStageBytes   = 8704; // >= 63*128 (RD right) + 3*128 (RD left) + 128 pad, and >= 64*128 + 128 (ALP bw 64)
-#ifndef ALPGPU_EXC_STAGE
-#define ALPGPU_EXC_STAGE 128 // (A/B builds: 256 — round 6, profiles/r06_decode_policy.txt)
-#endif
-constexpr int kExcStage     = ALPGPU_EXC_STAGE;  // 8-byte exception values staged in LDS per vector (four times as many 2-byte ALP_RD ones); the rest are read from HBM on use
+constexpr int kExcStage     = 128; // 8-byte exception values staged in LDS per vector (four times as many 2-byte ALP_RD ones); the rest are read from HBM on use
 constexpr uint32_t kExcStageBytes = 8u * kExcStage;
 
 template <int STAGE, int EXC = kExcStage>
@@ -65,13 +57,6 @@ using DecodeLds = DecodeLdsT<kStageBytes>;
 // of the HBM peak — and costs every OTHER column 2-6 % (1 KiB more LDS per vector: city_temperature 0.78 -> 0.74, nyc29 0.81 -> 0.78; call 6), so it is an instance
 // of its own, launched for columns whose hints say so (api_decode.hip: decode_variant_for, variant bit 6).
 using DecodeLdsManyExc = DecodeLdsT<kStageBytes, 2 * kExcStage>;
-// Round 4: FOUR narrow vectors per workgroup.  With two, a column of <= 16-bit vectors sits on a plateau of 0.69-0.73 of the HBM peak whatever its
-// width (profiles/r04_decode_floor.txt): what bounds it is the bytes in flight per CU — 16 vectors, each two dependent round trips — and the full
-// 8.5 KiB stage per vector is what caps a CU at two vectors x eight workgroups.  A stage of 2.25 KiB (17 bits + the unit row the unpack reads
-// past the end) lets a workgroup take four.  A vector that does not fit it (the launch shape follows the column's AVERAGE width) is not staged:
-// its lanes read their words straight from HBM through buffer loads, as the one-wavefront sinks do.
-constexpr int kNarrowStageBytes = 17 * 128 + 128;
-using DecodeLdsNarrow = DecodeLdsT<kNarrowStageBytes>;
 
 // The exception mask (32 words) as seen by one wavefront: lane l < 32 holds word l and the number of exceptions in the
 // words before it.  The prefix is a DPP row scan (register-to-register; a __shfl_up chain would be five dependent trips
@@ -255,13 +240,7 @@ struct WordPair {
 struct StagedWords {
 	const uint8_t* stage;
 	__device__ __forceinline__ WordPair pair(int i) const { // units i and i + 8: stream words k and k + 1 of a column pair
-#ifdef ALPGPU_STAGED_WORDS_FULL_WAIT
-		WordPair w {reinterpret_cast<const ulonglong2*>(stage)[i], reinterpret_cast<const ulonglong2*>(stage)[i + 8]};
-		asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(w.w0.x), "+v"(w.w0.y), "+v"(w.w1.x), "+v"(w.w1.y)::"memory");
-		return w;
-#else
 		return WordPair {reinterpret_cast<const ulonglong2*>(stage)[i], reinterpret_cast<const ulonglong2*>(stage)[i + 8]};
-#endif
 	}
 	__device__ __forceinline__ uint2 left_pair(int rbw, int i) const { // left words i and i + 32
 		return make_uint2(reinterpret_cast<const uint32_t*>(stage + 128 * rbw)[i], reinterpret_cast<const uint32_t*>(stage + 128 * rbw)[i + 32]);
@@ -285,94 +264,6 @@ struct BufferWords { // HBM through buffer loads: the resources are sized to the
 	}
 };
 
-// ---- exceptions patched AFTER the stores (round 5; the reference's own order: decode everything, then scatter, decoder.hpp:141-149) ---------------
-// An ALP vector with a few exceptions is decoded as if it had none — no mask, no prefix, no per-value lookup (the +60 % vector instructions of
-// profiles/r01_pmc_sq_decode_exceptions.txt) — and its exceptions are then written over the freshly stored values: exception j (positions ascend, so
-// j is also its rank) by lane j of the wavefront that OWNS the quarter the position lies in, i.e. the same wavefront that stored that quarter a few
-// instructions earlier.  A wavefront's vector stores reach memory in issue order (both go down the same L1 queue to the same L2 channel, same cache
-// policy), so the 8-byte patch lands on the 16-byte store it overlaps; no barrier, no fence, no LDS.  Position and value are loaded (2 + 8 bytes
-// per lane, straight from the record) together with the packed words and wait in two / three registers.  Vectors with more exceptions than
-// `patch_max` (a kernel argument, <= 64: one lane each; 0 switches the arm off) and ALP_RD vectors (their exceptions replace the LEFT part only:
-// the patched double needs the right part the lane no longer has) take the mask route below.  -DALPGPU_DECODE_PATCH_FENCE: s_waitcnt vmcnt(0)
-// between a wavefront's stores and its patches (the conservative form, for A/B runs).
-struct PatchRegs {
-	uint32_t pos;
-	uint64_t val;
-};
-__device__ __forceinline__ bool vector_patches_after(const alpgpu_vector_desc& d, uint32_t patch_max) { // wave-uniform
-	return d.scheme == ALPGPU_SCHEME_ALP && d.exc_cnt != 0 && static_cast<uint32_t>(d.exc_cnt) <= patch_max;
-}
-__device__ __forceinline__ PatchRegs issue_patch_loads(const alpgpu_vector_desc& d, const uint8_t* __restrict__ rec, int lane) {
-	PatchRegs   r {0u, 0ull};
-	const int   cnt = d.exc_cnt;
-	if (lane < cnt) {
-		r.val = reinterpret_cast<const uint64_t*>(rec)[lane];
-		r.pos = reinterpret_cast<const uint16_t*>(rec + 8u * static_cast<uint32_t>(cnt))[lane];
-	}
-	return r;
-}
-template <bool NT_STORE>
-__device__ __forceinline__ void apply_patches(const PatchRegs& r, int cnt, double* __restrict__ out_vec, int wave, int lane) {
-#ifdef ALPGPU_DECODE_PATCH_FENCE
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-	if (lane < cnt && static_cast<int>(r.pos >> 8) == wave) { // this wavefront stored values 256 wave .. 256 wave + 255 (steps 2 wave, 2 wave + 1)
-		const double x = __longlong_as_double(static_cast<long long>(r.val));
-#if defined(ALPGPU_DECODE_PATCH_NO_STORE) // timing experiment (wrong output): what the patch stores themselves cost
-		asm volatile("" ::"v"(x), "v"(out_vec + r.pos));
-#elif defined(ALPGPU_DECODE_PATCH_PLAIN) // A/B: the patch as an ordinary store whatever the vector's own stores are
-		out_vec[r.pos] = x;
-#else
-		if constexpr (NT_STORE) {
-			__builtin_nontemporal_store(x, out_vec + r.pos);
-		} else {
-			out_vec[r.pos] = x;
-		}
-#endif
-	}
-}
-__device__ __forceinline__ alpgpu_vector_desc without_exceptions(alpgpu_vector_desc d) {
-	d.exc_cnt = 0;
-	return d;
-}
-// ALPGPU_DECODE_PATCH_MODE 1: as described above (a second, 8-byte store per exception).  2: the exceptions are put in their places IN REGISTERS, in
-// front of the one store: each wavefront keeps a 256-byte slot table in LDS (its quarter of the vector's exception stage: byte i = 1 + the index of
-// the exception at position 256 wave + i, 0 = none; zeroed behind the issue of the loads, filled once position and value have arrived), a lane reads
-// the two bytes of its pair per step, and a hit fetches the value from the lane that holds it (exception j sits in lane j: ds_bpermute).  No
-// partial-line write reaches HBM; no rank, no prefix, no mask.
-// 0 (the default build since the measurement below): no patch arm is compiled in and `patch_max` is ignored.  Round 5's result (profiles/
-// r05_decode_exceptions.txt): once the stores of a wavefront no longer wait for one another (ExcMode below), the mask route itself is 5-10 % FASTER
-// than it was, mode 1 is slower than it at every width (its 8-byte stores reach HBM as read-modify-writes of lines the L2 has already let go:
-// +20-30 % time on narrow vectors), mode 2 equals it on wide vectors and loses 5-10 % on narrow ones — and the mere presence of either arm's
-// code and registers costs the two-vectors-per-workgroup kernel 8 % on exception-free columns of 3-6 bits.
-#ifndef ALPGPU_DECODE_PATCH_MODE
-#define ALPGPU_DECODE_PATCH_MODE 0
-#endif
-template <class LDS>
-__device__ __forceinline__ void patch_table_zero(LDS& L, int wave, int lane) {
-	reinterpret_cast<uint32_t*>(L.excv)[64 * wave + lane] = 0u;
-}
-template <class LDS>
-__device__ __forceinline__ void patch_table_fill(LDS& L, const PatchRegs& r, int cnt, int wave, int lane) { // (behind the barrier that follows the loads)
-	if (lane < cnt && static_cast<int>(r.pos >> 8) == wave) { L.excv[256 * wave + (r.pos & 255u)] = static_cast<uint8_t>(lane + 1); }
-	wave_lds_sync();
-}
-// the pair of step m of this wavefront's quarter: exceptions (if any) over the decoded values
-template <class LDS>
-__device__ __forceinline__ void patch_pair_from_table(const LDS& L, const PatchRegs& r, int m, int wave, int lane, double& ox, double& oy) {
-	const uint32_t t = reinterpret_cast<const uint16_t*>(L.excv)[128 * wave + 64 * (m & (kStepsPerWave - 1)) + lane];
-	if (ballot64(t != 0u) != 0) { // wave-uniform: some lane's pair of this step holds an exception
-		const int i0 = static_cast<int>(t & 255u) - 1, i1 = static_cast<int>(t >> 8) - 1;
-		const int lo = static_cast<int>(static_cast<uint32_t>(r.val)), hi = static_cast<int>(static_cast<uint32_t>(r.val >> 32));
-		const uint64_t v0 = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(4 * (i0 < 0 ? 0 : i0), hi))) << 32) |
-		                    static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(4 * (i0 < 0 ? 0 : i0), lo));
-		const uint64_t v1 = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(4 * (i1 < 0 ? 0 : i1), hi))) << 32) |
-		                    static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(4 * (i1 < 0 ? 0 : i1), lo));
-		ox = i0 >= 0 ? __longlong_as_double(static_cast<long long>(v0)) : ox;
-		oy = i1 >= 0 ? __longlong_as_double(static_cast<long long>(v1)) : oy;
-	}
-}
-
 template <int V>
 struct ExcMode {
 	static constexpr int value = V;
@@ -388,9 +279,7 @@ struct ArithShortcut {
 template <bool NT_STORE, int SINK, int N_Q, int ONLY = 0, class LDS, class WORDS>
 __device__ __forceinline__ void decode_vector_quarters(const LDS& L, const WORDS& units, const alpgpu_vector_desc& d, const VectorConsts& dict, const ExcMask& em,
                                                       const uint8_t* __restrict__ rec, double2* __restrict__ dst, int q0, int lane, double* acc,
-                                                       double range_lo, double range_hi, bool use_patch = false, PatchRegs patch = PatchRegs {0u, 0ull}) {
-	// use_patch (ALPGPU_DECODE_PATCH_MODE 2; ALP store decode, one quarter per wavefront: q0 = the wavefront): d is the vector without its
-	// exceptions, which are looked up in the wavefront's slot table instead (patch_pair_from_table)
+                                                       double range_lo, double range_hi) {
 	const int      bw       = d.bw;
 	const int      cnt      = d.exc_cnt;
 	const bool     all_staged = cnt <= static_cast<int>(LDS::kExcBytes) / (d.scheme == ALPGPU_SCHEME_ALP ? 8 : 2); // wave-uniform
@@ -400,7 +289,7 @@ __device__ __forceinline__ void decode_vector_quarters(const LDS& L, const WORDS
 	// batch of steps are requested before the first of them is used — with the words in HBM (k_sink_direct) every step is otherwise its own
 	// dependent round trip.
 	constexpr int kSteps = N_Q * kStepsPerWave;
-	constexpr int kBatch = kSteps < ALPGPU_DECODE_BATCH ? kSteps : ALPGPU_DECODE_BATCH;
+	constexpr int kBatch = kSteps < kDecodeBatch ? kSteps : kDecodeBatch;
 	constexpr int kBatchRd = ONLY == 2 ? 1 : (kSteps < 2 ? kSteps : 2); // ALP_RD keeps the left words and the dictionary selects in registers as well
 	auto request = [&](int width, int row) { return units.pair(8 * ((row * width) >> 6) + a); };
 	auto extract = [&](int width, uint64_t wmask, int row, const WordPair w) {
@@ -439,9 +328,6 @@ __device__ __forceinline__ void decode_vector_quarters(const LDS& L, const WORDS
 		// the loop per vector (wave-uniform); the sinks (register budgets tuned around the old form) stay on 2.
 		auto finish_pair = [&](auto exc_mode, int m, double ox, double oy, double* acc_q) {
 			constexpr int EXC = decltype(exc_mode)::value;
-			if constexpr (SINK == kSinkStore && N_Q == 1 && ALPGPU_DECODE_PATCH_MODE == 2) {
-				if (use_patch) { patch_pair_from_table(L, patch, m, q0, lane, ox, oy); } // (wave-uniform)
-			}
 			if (EXC == 1 || (EXC == 2 && cnt > 0)) {
 				const bool     staged = EXC == 1 ? true : all_staged;
 				int            rank;
@@ -456,9 +342,6 @@ __device__ __forceinline__ void decode_vector_quarters(const LDS& L, const WORDS
 			if constexpr (SINK != kSinkStore) {
 				consume_pair<SINK>(ox, oy, acc_q, range_lo, range_hi);
 			} else {
-#ifdef ALPGPU_DECODE_STORE_WAIT // A/B: every store waits for the one before it, as every build did until round 5 (see above)
-				asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
 				store_pair<NT_STORE>(dst + 64 * m + lane, ox, oy);
 			}
 		};
@@ -505,11 +388,7 @@ __device__ __forceinline__ void decode_vector_quarters(const LDS& L, const WORDS
 			}
 		};
 		constexpr bool kPerVectorLoops = SINK == kSinkStore && N_Q == 1;
-#ifdef ALPGPU_DECODE_NO_NARROW_ARITH // A/B: without the 32-bit form
-		const bool narrow32 = false;
-#else
 		const bool narrow32 = kPerVectorLoops && bw <= 32;
-#endif
 		if (shortcut) { // wave-uniform; ONE branch per vector, not one per step (scalar instructions are the scarce ones here)
 			if (kPerVectorLoops && cnt == 0) {
 				if (narrow32) {
@@ -524,14 +403,14 @@ __device__ __forceinline__ void decode_vector_quarters(const LDS& L, const WORDS
 					alp_steps(ExcMode<1> {}, ArithShortcut<1> {});
 				}
 			} else {
-#ifndef ALPGPU_SINK_NO_NARROW_ARITH // round 6, call 36: the SINKS' vectors of <= 32 bits through the 32-bit unpack too (7 vector instructions per value instead of 13; until
+				// round 6, call 36: the SINKS' vectors of <= 32 bits through the 32-bit unpack too (7 vector instructions per value instead of 13; until
 				// then the store decode's only): SUM of 2-24-bit columns 0.54-0.76 -> 0.45-0.69 ms per 1 Mi vectors (-9 to -15 %), with 20 exceptions per vector -8 to -13 %,
-				// the benchmark column -3 %; same bits.  -DALPGPU_SINK_NO_NARROW_ARITH: the A/B.
+				// the benchmark column -3 %; same bits.
 				if (!kPerVectorLoops && bw <= 32) {
 					alp_steps(ExcMode<2> {}, ArithShortcut<2> {});
-				} else
-#endif
-				alp_steps(ExcMode<2> {}, ArithShortcut<1> {});
+				} else {
+					alp_steps(ExcMode<2> {}, ArithShortcut<1> {});
+				}
 			}
 		} else {
 			alp_steps(ExcMode<2> {}, ArithShortcut<0> {});
@@ -568,13 +447,8 @@ __device__ __forceinline__ void decode_vector_quarters(const LDS& L, const WORDS
 					const uint32_t w0 = lw[i].x, w1 = lw[i].y;
 					const uint32_t i0  = (((w0 & 0xFFFFu) >> s) | ((w1 & 0xFFFFu) << (16 - s))) & lmsk;
 					const uint32_t i1  = (((w0 >> 16) >> s) | ((w1 >> 16) << (16 - s))) & lmsk;
-#ifdef ALPGPU_RD_DICT_IN_REGISTERS // A/B (round 6): the lookup as it was until round 5 — a 3-way select through a 64-bit shift per value
-					uint64_t       l0  = ((i0 < 4 ? dlo >> (16 * i0) : dhi >> (16 * (i0 & 3))) & 0xFFFFull);
-					uint64_t       l1  = ((i1 < 4 ? dlo >> (16 * i1) : dhi >> (16 * (i1 & 3))) & 0xFFFFull);
-#else
 					uint64_t       l0  = L.rdict[i0 & 7u];
 					uint64_t       l1  = L.rdict[i1 & 7u];
-#endif
 					if (EXC == 1 || (EXC == 2 && cnt > 0)) {
 						const bool     staged = EXC == 1 ? true : all_staged;
 						int            rank;
@@ -613,24 +487,24 @@ __device__ __forceinline__ void decode_vector_quarters(const LDS& L, const WORDS
 template <bool NT_STORE, int SINK = kSinkStore, class LDS = DecodeLds>
 __device__ __forceinline__ void decode_staged_vector(const LDS& L, const alpgpu_vector_desc& d, const VectorConsts& dict,
                                                      const uint8_t* __restrict__ rec, double2* __restrict__ dst, int wave, int lane, double* acc = nullptr,
-                                                     double range_lo = 0.0, double range_hi = 0.0, bool use_patch = false, PatchRegs patch = PatchRegs {0u, 0ull}) {
+                                                     double range_lo = 0.0, double range_hi = 0.0) {
 	ExcMask em {0u, 0};
 	if (d.exc_cnt > 0) { em = load_exception_mask(L, lane); }
-	decode_vector_quarters<NT_STORE, SINK, 1>(L, StagedWords {L.stage}, d, dict, em, rec, dst, wave, lane, acc, range_lo, range_hi, use_patch, patch);
+	decode_vector_quarters<NT_STORE, SINK, 1>(L, StagedWords {L.stage}, d, dict, em, rec, dst, wave, lane, acc, range_lo, range_hi);
 }
 
 // Issues every load of one vector: packed words and the values of its exceptions straight into LDS (global_load_lds, 16 resp. 4 bytes per
 // lane, no VGPR round trip), exception positions into registers.  (Until round 3 the values went through registers too, behind a branch on the
 // scheme for their width — and the compiler's wait-count pass put an s_waitcnt vmcnt(0) between the two arms, i.e. a whole HBM round trip in
 // front of the packed loads of every vector with exceptions of one of the two schemes.)
-// (a vector whose words do not fit the workgroup's stage — narrow stage only — is not staged: see vector_fits_stage)
+// (a vector whose words do not fit the workgroup's stage is not staged: see vector_fits_stage)
 template <class LDS>
 __device__ __forceinline__ bool vector_fits_stage(const alpgpu_vector_desc& d) {
 	return 128 * (static_cast<int>(d.bw) + (d.scheme == ALPGPU_SCHEME_ALP ? 0 : static_cast<int>(d.lbw))) + 128 <= LDS::kStage;
 }
 template <class LDS>
 __device__ __forceinline__ uint32_t issue_vector_loads(LDS& L, const alpgpu_vector_desc& d, const uint8_t* __restrict__ packed,
-                                                       const uint8_t* __restrict__ rec, int tid, int wave, bool record_elsewhere = false) {
+                                                       const uint8_t* __restrict__ rec, int tid, int wave) {
 	typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
 	constexpr int T       = 64 * kDecWaves;
 	const bool    is_alp  = d.scheme == ALPGPU_SCHEME_ALP;
@@ -645,7 +519,7 @@ __device__ __forceinline__ uint32_t issue_vector_loads(LDS& L, const alpgpu_vect
 		}
 	}
 	uint32_t  pos = 0u;
-	const int cnt = record_elsewhere ? 0 : d.exc_cnt; // (record_elsewhere: the vector's exceptions are patched in after its stores, issue_patch_loads)
+	const int cnt = d.exc_cnt;
 	if (cnt > 0) { // wave-uniform
 		const uint32_t val_bytes = (is_alp ? 8u : 2u) * static_cast<uint32_t>(cnt);
 		const int      dwords    = static_cast<int>(((val_bytes < LDS::kExcBytes ? val_bytes : LDS::kExcBytes) + 3u) >> 2); // (records are 8-byte multiples)
@@ -680,33 +554,19 @@ __global__ __launch_bounds__(64 * kDecWaves) void k_decode_column(const alpgpu_v
                                                                   const alpgpu_rowgroup_state* __restrict__ rgs,
                                                                   const uint8_t* __restrict__ packed,
                                                                   const uint8_t* __restrict__ excs, double* __restrict__ out,
-                                                                  uint64_t n_vectors, uint64_t wg_offset, double lo, double hi, uint32_t patch_max,
+                                                                  uint64_t n_vectors, uint64_t wg_offset, double lo, double hi, uint32_t gate_word,
                                                                   uint64_t* __restrict__ progress, uint64_t progress_tag) {
 	static_assert(LDS::kStage == kStageBytes || SINK == kSinkStore, "the sinks pass their lane partials through a full stage");
 	__shared__ LDS L[V];
 	const int      tid  = static_cast<int>(threadIdx.x);
 	const int      lane = tid & 63;
 	const int      wave = wave_in_wg();
-#ifdef ALPGPU_DEC_XCD_GROUP // experiment (round 6, call 40): consecutive workgroups go to consecutive XCDs; here each XCD takes ALPGPU_DEC_XCD_GROUP CONSECUTIVE workgroups' vectors of a span of 8 groups
-	uint64_t b_idx = blockIdx.x;
-	{
-		constexpr uint64_t kG = ALPGPU_DEC_XCD_GROUP, kSpan = 8 * kG;
-		const uint64_t     full = (static_cast<uint64_t>(gridDim.x) / kSpan) * kSpan;
-		if (b_idx < full) {
-			const uint64_t r = b_idx % kSpan;
-			b_idx            = b_idx - r + (r & 7u) * kG + (r >> 3);
-		}
-	}
-	const uint64_t v0 = (wg_offset + b_idx) * V;
-#else
 	const uint64_t v0   = (wg_offset + blockIdx.x) * V;
-#endif
 	if (v0 >= n_vectors) { return; }
-	// An unhinted decode (api_decode.hip) launches every candidate shape; the plan kernel in front of them has written which one runs (bits 8.. of patch_max
+	// An unhinted decode (api_decode.hip) launches every candidate shape; the plan kernel in front of them has written which one runs (bits 8.. of gate_word
 	// = this launch's number, 0 = not a candidate: the usual launch).  One scalar load, taken by candidates only; a closed candidate costs its dispatch.
-	if (SINK == kSinkStore && (patch_max >> 8) != 0u) { // (kernel argument: uniform)
-		if (progress[kCtxWordShape] != static_cast<uint64_t>(patch_max >> 8)) { return; }
-		patch_max &= 0xFFu;
+	if (SINK == kSinkStore && (gate_word >> 8) != 0u) { // (kernel argument: uniform)
+		if (progress[kCtxWordShape] != static_cast<uint64_t>(gate_word >> 8)) { return; }
 	}
 	// the read-ahead's pace (read_ahead_kernels.hip): workgroups are dispatched in ascending order, every 128th says where the launch is
 	if (SINK == kSinkStore && progress != nullptr && (blockIdx.x & 127u) == 0 && tid == 0) {
@@ -723,18 +583,13 @@ __global__ __launch_bounds__(64 * kDecWaves) void k_decode_column(const alpgpu_v
 	VectorConsts dict[V];
 #pragma unroll
 	for (int i = 0; i < V; ++i) { dict[i] = load_vector_consts(rgs, v0 + i < n_vectors ? v0 + i : v0, d[i]); }
-	// vectors whose (few) exceptions are written over their stored values afterwards (apply_patches): nothing of them goes through the mask
-	bool      patched[V];
-	PatchRegs pr[V];
+	// (no_mask[i] is always false and dd below is a plain copy: with the flags and the copy gone the compiler orders the V = 2 kernels' instructions
+	// differently.  They are left from the patch-after arm, removed with it, so that the shipped instruction stream stays the one measured.)
+	bool no_mask[V];
 #pragma unroll
 	for (int i = 0; i < V; ++i) {
-		patched[i] = ALPGPU_DECODE_PATCH_MODE != 0 && SINK == kSinkStore && vector_patches_after(d[i], patch_max); // workgroup-uniform
-		pos[i]     = issue_vector_loads(L[i], d[i], packed, excs + d[i].exc_off, tid, wave, patched[i]);
-		pr[i]      = PatchRegs {0u, 0ull};
-		if (patched[i]) {
-			pr[i] = issue_patch_loads(d[i], excs + d[i].exc_off, lane);
-			if constexpr (ALPGPU_DECODE_PATCH_MODE == 2) { patch_table_zero(L[i], wave, lane); }
-		}
+		no_mask[i] = false;
+		pos[i]     = issue_vector_loads(L[i], d[i], packed, excs + d[i].exc_off, tid, wave);
 	}
 	// ALP_RD vectors: the dictionary into the vector's LDS (four lanes; visible behind the barrier below)
 #pragma unroll
@@ -746,23 +601,17 @@ __global__ __launch_bounds__(64 * kDecWaves) void k_decode_column(const alpgpu_v
 	// exceptions or not, began with the zeroing write and a barrier in front of its first load.)
 	bool any_exc = false;
 #pragma unroll
-	for (int i = 0; i < V; ++i) { any_exc |= d[i].exc_cnt != 0 && !patched[i]; }
+	for (int i = 0; i < V; ++i) { any_exc |= d[i].exc_cnt != 0 && !no_mask[i]; }
 	if (any_exc) { // workgroup-uniform
 		if (tid < 32 * V) { L[tid >> 5].mask[tid & 31] = 0; }
 		asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // not __syncthreads(): its fence would wait for the loads in flight
 #pragma unroll
 		for (int i = 0; i < V; ++i) {
-			if (!patched[i]) { land_exceptions(L[i], d[i], excs + d[i].exc_off, pos[i], tid); }
+			if (!no_mask[i]) { land_exceptions(L[i], d[i], excs + d[i].exc_off, pos[i], tid); }
 		}
 	}
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // LDS-DMA completion is not tracked through the LDS for the compiler
 	__syncthreads();
-	if constexpr (SINK == kSinkStore && ALPGPU_DECODE_PATCH_MODE == 2) {
-#pragma unroll
-		for (int i = 0; i < V; ++i) {
-			if (patched[i]) { patch_table_fill(L[i], pr[i], d[i].exc_cnt, wave, lane); }
-		}
-	}
 
 	if constexpr (SINK != kSinkStore) {
 		// Per-vector sums: lane partial (step order) in each of the four wavefronts -> the four partials of a lane position combined as
@@ -793,13 +642,8 @@ __global__ __launch_bounds__(64 * kDecWaves) void k_decode_column(const alpgpu_v
 		__syncthreads();
 		if (wave < V && v0 + wave < n_vectors) { // wave-uniform: wavefront w finishes vector w
 			const double* part = reinterpret_cast<const double*>(L[wave].stage) + lane;
-#ifdef ALPGPU_EXPERIMENT_DEC_WAVES // timing experiments with another number of wavefronts per vector: the sums follow another order
-			double total = 0.0;
-			for (int w = 0; w < kDecWaves; ++w) { total += part[64 * w]; }
-#else
 			static_assert(kDecWaves == 4, "the documented summation order is for 4 wavefronts per vector");
 			double total = (part[0] + part[64]) + (part[128] + part[192]);
-#endif
 			total = wave_tree_sum_f64(total); // balanced tree over adjacent lanes (DPP, alp_device.hpp)
 			if (lane == 0) {
 				if constexpr (SINK == kSinkCount) {
@@ -814,125 +658,9 @@ __global__ __launch_bounds__(64 * kDecWaves) void k_decode_column(const alpgpu_v
 #pragma unroll
 	for (int i = 0; i < V; ++i) {
 		if (v0 + i < n_vectors) {
-			const alpgpu_vector_desc dd = patched[i] ? without_exceptions(d[i]) : d[i]; // (a patched vector unpacks as one without exceptions)
-			if (LDS::kStage == kStageBytes || vector_fits_stage<LDS>(d[i])) { // (always, with the full stage)
-				decode_staged_vector<NT_STORE, kSinkStore, LDS>(L[i], dd, dict[i], excs + d[i].exc_off, reinterpret_cast<double2*>(out + (v0 + i) * kVec), wave, lane, nullptr, 0.0, 0.0,
-				                                                ALPGPU_DECODE_PATCH_MODE == 2 && patched[i], pr[i]);
-			} else { // a wide vector in a narrow-stage launch: its words straight from HBM (bounded buffer loads, as in k_sink_direct)
-				ExcMask em {0u, 0};
-				if (dd.exc_cnt > 0) { em = load_exception_mask(L[i], lane); }
-				uint8_t*          first      = const_cast<uint8_t*>(packed + d[i].packed_off);
-				constexpr int     kRsrcFlags = 0x00020000;
-				const bool        is_alp     = d[i].scheme == ALPGPU_SCHEME_ALP;
-				const BufferWords words {__builtin_amdgcn_make_buffer_rsrc(first, 0, 128 * d[i].bw, kRsrcFlags),
-				                         __builtin_amdgcn_make_buffer_rsrc(first + 128u * d[i].bw, 0, is_alp ? 0 : 128 * d[i].lbw, kRsrcFlags)};
-				decode_vector_quarters<NT_STORE, kSinkStore, 1>(L[i], words, dd, dict[i], em, excs + d[i].exc_off, reinterpret_cast<double2*>(out + (v0 + i) * kVec), wave, lane,
-				                                                nullptr, 0.0, 0.0, ALPGPU_DECODE_PATCH_MODE == 2 && patched[i], pr[i]);
-			}
-			if constexpr (ALPGPU_DECODE_PATCH_MODE == 1) {
-				if (patched[i]) { apply_patches<NT_STORE>(pr[i], d[i].exc_cnt, out + (v0 + i) * kVec, wave, lane); }
-			}
+			const alpgpu_vector_desc dd = d[i];
+			decode_staged_vector<NT_STORE, kSinkStore, LDS>(L[i], dd, dict[i], excs + d[i].exc_off, reinterpret_cast<double2*>(out + (v0 + i) * kVec), wave, lane);
 		}
-	}
-}
-
-// ---- experiment (round 4): a workgroup that decides how to run its vectors from their descriptors ---------------------------------------------
-// The launch shape of k_decode_column is one decision per COLUMN (from its size hints), but a column's rowgroups differ: on the benchmark column
-// (widths 1..53 by rowgroup) the average says "one vector per workgroup" and the narrow third of the rowgroups runs in the shape that is 20-30 %
-// slower for it when a whole column looks like that.  Here every workgroup owns TWO consecutive vectors, reads both descriptors at once and decides:
-//   PAIRING 1: both narrow -> loads of both in flight together (k_decode_column<2>); else one after the other (the second one's descriptor
-//              round trip is already behind it)
-//   PAIRING 2: as 1, but the second vector's loads are issued as soon as the first one's have landed, in front of its unpack
-//   PAIRING 3: no decision: three vectors per two workgroups (even workgroups two together, odd ones one) — 12 vectors in flight per CU, between
-//              the 8 and the 16 of the two shapes of k_decode_column
-// Not the default anywhere: tools/sweep_pairing.py measures them (profiles/r04_decode_floor.txt, section 4).
-__device__ __forceinline__ bool vector_is_narrow(const alpgpu_vector_desc& d) {
-	return d.scheme == ALPGPU_SCHEME_ALP && static_cast<int>(d.bw) <= (d.exc_cnt >= 2 ? 20 : 16);
-}
-__device__ __forceinline__ void prepare_exceptions(DecodeLds& L, const alpgpu_vector_desc& d, const uint8_t* __restrict__ rec, uint32_t pos, int tid) {
-	if (d.exc_cnt != 0) { // workgroup-uniform
-		if (tid < 32) { L.mask[tid] = 0; }
-		asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-		land_exceptions(L, d, rec, pos, tid);
-	}
-}
-__device__ __forceinline__ void loads_have_landed() {
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	__syncthreads();
-}
-template <bool NT_STORE, int PAIRING>
-__global__ __launch_bounds__(64 * kDecWaves) void k_decode_pairs(const alpgpu_vector_desc* __restrict__ descs, const alpgpu_rowgroup_state* __restrict__ rgs,
-                                                                 const uint8_t* __restrict__ packed, const uint8_t* __restrict__ excs, double* __restrict__ out,
-                                                                 uint64_t n_vectors, uint64_t wg_offset, uint32_t patch_max) {
-	__shared__ DecodeLds L[2];
-	const int      tid  = static_cast<int>(threadIdx.x);
-	const int      lane = tid & 63;
-	const int      wave = wave_in_wg();
-	const uint64_t g    = wg_offset + blockIdx.x;
-	uint64_t       v0;
-	int            n_here;
-	if constexpr (PAIRING == 3) {
-		v0     = 3 * (g >> 1) + ((g & 1) ? 2 : 0);
-		n_here = (g & 1) ? 1 : 2;
-	} else {
-		v0     = 2 * g;
-		n_here = 2;
-	}
-	if (v0 >= n_vectors) { return; }
-	if (v0 + n_here > n_vectors) { n_here = 1; }
-	const uint64_t           v1 = n_here == 2 ? v0 + 1 : v0;
-	const alpgpu_vector_desc d0 = descs[v0], d1 = descs[v1];
-	const VectorConsts       c0 = load_vector_consts(rgs, v0, d0), c1 = load_vector_consts(rgs, v1, d1);
-	double2*                 o0 = reinterpret_cast<double2*>(out + v0 * kVec);
-	double2*                 o1 = reinterpret_cast<double2*>(out + v1 * kVec);
-	if (tid < 4) { // ALP_RD vectors: the dictionary into the vector's LDS (visible behind the barrier in front of the vector's unpack)
-		if (d0.scheme != ALPGPU_SCHEME_ALP) { reinterpret_cast<uint32_t*>(L[0].rdict)[tid] = static_cast<uint32_t>((tid < 2 ? c0.lo : c0.hi) >> (32 * (tid & 1))); }
-		if (d1.scheme != ALPGPU_SCHEME_ALP) { reinterpret_cast<uint32_t*>(L[1].rdict)[tid] = static_cast<uint32_t>((tid < 2 ? c1.lo : c1.hi) >> (32 * (tid & 1))); }
-	}
-	const bool together = n_here == 2 && (PAIRING == 3 || (vector_is_narrow(d0) && vector_is_narrow(d1))); // workgroup-uniform
-	// vectors whose exceptions are patched in after their stores (apply_patches): decoded as if they had none
-	// (ALPGPU_DECODE_PATCH_MODE 2 keeps its slot tables in k_decode_column only: here such vectors go through the mask)
-	const bool               pa0 = ALPGPU_DECODE_PATCH_MODE == 1 && vector_patches_after(d0, patch_max), pa1 = ALPGPU_DECODE_PATCH_MODE == 1 && vector_patches_after(d1, patch_max); // (compile-time false in the default build)
-	const alpgpu_vector_desc m0 = pa0 ? without_exceptions(d0) : d0, m1 = pa1 ? without_exceptions(d1) : d1;
-	PatchRegs                r0 {0u, 0ull}, r1 {0u, 0ull};
-	if (together) {
-		const uint32_t p0 = issue_vector_loads(L[0], m0, packed, excs + d0.exc_off, tid, wave);
-		const uint32_t p1 = issue_vector_loads(L[1], m1, packed, excs + d1.exc_off, tid, wave);
-		if (pa0) { r0 = issue_patch_loads(d0, excs + d0.exc_off, lane); }
-		if (pa1) { r1 = issue_patch_loads(d1, excs + d1.exc_off, lane); }
-		if (m0.exc_cnt != 0 || m1.exc_cnt != 0) {
-			if (tid < 64) { L[tid >> 5].mask[tid & 31] = 0; }
-			asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-			land_exceptions(L[0], m0, excs + d0.exc_off, p0, tid);
-			land_exceptions(L[1], m1, excs + d1.exc_off, p1, tid);
-		}
-		loads_have_landed();
-		decode_staged_vector<NT_STORE, kSinkStore, DecodeLds>(L[0], m0, c0, excs + d0.exc_off, o0, wave, lane);
-		if (pa0) { apply_patches<NT_STORE>(r0, d0.exc_cnt, out + v0 * kVec, wave, lane); }
-		decode_staged_vector<NT_STORE, kSinkStore, DecodeLds>(L[1], m1, c1, excs + d1.exc_off, o1, wave, lane);
-		if (pa1) { apply_patches<NT_STORE>(r1, d1.exc_cnt, out + v1 * kVec, wave, lane); }
-		return;
-	}
-	const uint32_t p0 = issue_vector_loads(L[0], m0, packed, excs + d0.exc_off, tid, wave);
-	if (pa0) { r0 = issue_patch_loads(d0, excs + d0.exc_off, lane); }
-	prepare_exceptions(L[0], m0, excs + d0.exc_off, p0, tid);
-	loads_have_landed();
-	uint32_t p1 = 0;
-	if (PAIRING == 2 && n_here == 2) {
-		p1 = issue_vector_loads(L[1], m1, packed, excs + d1.exc_off, tid, wave);
-		if (pa1) { r1 = issue_patch_loads(d1, excs + d1.exc_off, lane); }
-	}
-	decode_staged_vector<NT_STORE, kSinkStore, DecodeLds>(L[0], m0, c0, excs + d0.exc_off, o0, wave, lane);
-	if (pa0) { apply_patches<NT_STORE>(r0, d0.exc_cnt, out + v0 * kVec, wave, lane); }
-	if (n_here == 2) {
-		if (PAIRING != 2) {
-			p1 = issue_vector_loads(L[1], m1, packed, excs + d1.exc_off, tid, wave);
-			if (pa1) { r1 = issue_patch_loads(d1, excs + d1.exc_off, lane); }
-		}
-		prepare_exceptions(L[1], m1, excs + d1.exc_off, p1, tid);
-		loads_have_landed();
-		decode_staged_vector<NT_STORE, kSinkStore, DecodeLds>(L[1], m1, c1, excs + d1.exc_off, o1, wave, lane);
-		if (pa1) { apply_patches<NT_STORE>(r1, d1.exc_cnt, out + v1 * kVec, wave, lane); }
 	}
 }
 
@@ -944,20 +672,12 @@ __global__ __launch_bounds__(64 * kDecWaves) void k_decode_pairs(const alpgpu_ve
 // the two 16-byte units of each of its eight pairs straight from HBM (buffer loads bounded to the vector's words): 16 loads per wavefront
 // whatever the width; the 64 lanes of a load touch 8 runs of 128 bytes.  Results are bit-identical to k_decode_column's sinks: the lane keeps the four quarter partials p[q][L] apart,
 // then (p0 + p1) + (p2 + p3), then the adjacent-lane tree (include/alpgpu.h).
-#ifndef ALPGPU_SINK_DIRECT_OCC
-#define ALPGPU_SINK_DIRECT_OCC 8 // wavefronts per SIMD the register budget is sized for (8 -> <= 64 VGPRs; measured against 5 and 6: profiles/r03_consumers.txt)
-#endif
-#ifndef ALPGPU_SINK_STAGE
-#define ALPGPU_SINK_STAGE 3584 // bytes of packed words (bit widths <= 28) a wavefront of k_sink_direct stages in its LDS by LDS-DMA; with mask, values and prefixes 4992 B per wavefront = eight workgroups per CU (0: none)
-#endif
-#ifndef ALPGPU_SINK_STAGE_MAX_EXC
-#define ALPGPU_SINK_STAGE_MAX_EXC 48 // ... only for vectors with at most this many exceptions
-#endif
+constexpr int kSinkDirectOcc = 8; // wavefronts per SIMD the register budget is sized for (8 -> <= 64 VGPRs; measured against 5 and 6: profiles/r03_consumers.txt)
+constexpr int kSinkStage = 3584; // bytes of packed words (bit widths <= 28) a wavefront of k_sink_direct stages in its LDS by LDS-DMA; with mask, values and prefixes 4992 B per wavefront = eight workgroups per CU (0: none)
+constexpr int kSinkStageMaxExc = 48; // ... only for vectors with at most this many exceptions
 struct __attribute__((aligned(16))) SinkWaveLds {
 	static constexpr bool kPrefixInLds = true; // exception_hits_lds
-#if ALPGPU_SINK_STAGE > 0
-	uint8_t  stage[ALPGPU_SINK_STAGE + 128]; // + the unit row past the end that the unpack reads and masks off
-#endif
+	uint8_t  stage[kSinkStage + 128]; // + the unit row past the end that the unpack reads and masks off
 	uint32_t mask[32];
 	static constexpr uint32_t kExcBytes = kExcStageBytes;
 	uint8_t  excv[kExcStageBytes];
@@ -965,7 +685,7 @@ struct __attribute__((aligned(16))) SinkWaveLds {
 	uint16_t rdict[8]; // ALP_RD: the rowgroup's dictionary (DecodeLdsT)
 };
 template <int SINK>
-__global__ __launch_bounds__(64 * kDecWaves, ALPGPU_SINK_DIRECT_OCC) void k_sink_direct(const alpgpu_vector_desc* __restrict__ descs, const alpgpu_rowgroup_state* __restrict__ rgs,
+__global__ __launch_bounds__(64 * kDecWaves, kSinkDirectOcc) void k_sink_direct(const alpgpu_vector_desc* __restrict__ descs, const alpgpu_rowgroup_state* __restrict__ rgs,
                                                                    const uint8_t* __restrict__ packed, const uint8_t* __restrict__ excs, double* __restrict__ out,
                                                                    uint64_t n_vectors, uint64_t wg_offset, double lo, double hi) {
 	// gfx950 range-checks the single-register AMOUNT of a 64-bit shift (v_lshrrev_b64 / v_lshlrev_b64, which this kernel lives on) as a register
@@ -989,10 +709,9 @@ __global__ __launch_bounds__(64 * kDecWaves, ALPGPU_SINK_DIRECT_OCC) void k_sink
 	const bool               is_alp = d.scheme == ALPGPU_SCHEME_ALP;
 	const int                cnt  = d.exc_cnt;
 	ExcMask                  em {0u, 0};
-#if ALPGPU_SINK_STAGE > 0
 	// a narrow ALP vector's words whole into the wavefront's LDS by LDS-DMA (1 KiB per instruction, no registers): ONE round trip for all of
 	// them instead of two batches of register loads
-	const bool staged = is_alp && 128u * d.bw <= static_cast<uint32_t>(ALPGPU_SINK_STAGE) && cnt <= ALPGPU_SINK_STAGE_MAX_EXC; // wave-uniform
+	const bool staged = is_alp && 128u * d.bw <= static_cast<uint32_t>(kSinkStage) && cnt <= kSinkStageMaxExc; // wave-uniform
 	if (staged) {
 		typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
 		const ull2* g       = reinterpret_cast<const ull2*>(packed + d.packed_off);
@@ -1001,7 +720,6 @@ __global__ __launch_bounds__(64 * kDecWaves, ALPGPU_SINK_DIRECT_OCC) void k_sink
 			if (64 * j + lane < n_units) { __builtin_amdgcn_global_load_lds(g + 64 * j + lane, reinterpret_cast<ull2*>(L.stage) + 64 * j, 16, 0, 0); }
 		}
 	}
-#endif
 	if (cnt > 0) { // wave-uniform: values of the first kExcStage exceptions by LDS-DMA, the mask from the positions
 		const uint32_t val_bytes = (is_alp ? 8u : 2u) * static_cast<uint32_t>(cnt);
 		const int      dwords    = static_cast<int>(((val_bytes < kExcStageBytes ? val_bytes : kExcStageBytes) + 3u) >> 2);
@@ -1030,13 +748,11 @@ __global__ __launch_bounds__(64 * kDecWaves, ALPGPU_SINK_DIRECT_OCC) void k_sink
 		wave_lds_sync();
 	}
 	double part[kDecWaves] = {0.0, 0.0, 0.0, 0.0};
-#if ALPGPU_SINK_STAGE > 0
 	if (staged) {
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 		wave_lds_sync();
 		decode_vector_quarters<false, SINK, kDecWaves, 1>(L, StagedWords {L.stage}, d, dict, em, rec, nullptr, 0, lane, part, lo, hi);
 	} else
-#endif
 	if (is_alp) { // wave-uniform
 		decode_vector_quarters<false, SINK, kDecWaves, 1>(L, words, d, dict, em, rec, nullptr, 0, lane, part, lo, hi);
 	} else {
@@ -1065,46 +781,24 @@ int launch_sink_direct(hipStream_t stream, const alpgpu_column* col, double lo, 
 	const uint64_t n        = col->n_vectors;
 	const uint64_t n_wg     = (n + kDecWaves - 1) / kDecWaves;
 	const uint64_t kMaxGrid = 1ull << 30;
-	// experiment (ALPGPU_SINK_PAD_LDS_KIB): unused dynamic LDS that caps the workgroups resident per CU, as launch_decode_column does by width
-	static const unsigned pad_lds = std::getenv("ALPGPU_SINK_PAD_LDS_KIB") ? static_cast<unsigned>(std::atoi(std::getenv("ALPGPU_SINK_PAD_LDS_KIB"))) * 1024u : 0u;
 	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
 		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(64 * kDecWaves);
 		if (count) {
-			hipLaunchKernelGGL((k_sink_direct<kSinkCount>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_out), n, off, lo, hi);
+			hipLaunchKernelGGL((k_sink_direct<kSinkCount>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_out), n, off, lo, hi);
 		} else {
-			hipLaunchKernelGGL((k_sink_direct<kSinkSum>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_out), n, off, 0.0, 0.0);
+			hipLaunchKernelGGL((k_sink_direct<kSinkSum>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_out), n, off, 0.0, 0.0);
 		}
 	}
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }
 
-// whether this build has an arm that patches exceptions in after the stores (-DALPGPU_DECODE_PATCH_MODE=1 / 2; the default build has none: ALPGPU_OPT_DECODE_PATCH_AFTER is refused)
-bool decode_patch_arm_compiled() { return ALPGPU_DECODE_PATCH_MODE != 0; }
-
-int launch_decode_column(hipStream_t stream, const alpgpu_column* col, double* d_out, int variant, int n_cus, uint32_t patch_max, uint64_t* progress, uint64_t progress_tag, uint32_t gate) {
+int launch_decode_column(hipStream_t stream, const alpgpu_column* col, double* d_out, int variant, int n_cus, uint64_t* progress, uint64_t progress_tag, uint32_t gate) {
 	(void)n_cus;
-	if (patch_max > 64u) { patch_max = 64u; } // one lane per patched exception (apply_patches)
-	if (gate != 0 && progress != nullptr) { patch_max |= gate << 8; } // (k_decode_column: a candidate launch of an unhinted decode)
+	const uint32_t gate_word = gate != 0 && progress != nullptr ? gate << 8 : 0u; // (k_decode_column: a candidate launch of an unhinted decode)
 	const uint64_t n = col->n_vectors;
-	// variant bit 0: one vector per workgroup (default) instead of two; bit 1: plain instead of non-temporal stores; bit 2: FOUR vectors per
-	// workgroup over the narrow stage (columns of <= 16-bit vectors)
+	// variant bit 0: one vector per workgroup (default) instead of two; bit 1: plain instead of non-temporal stores
 	const bool     nt       = !(variant & 2);
-	const int      pairing  = (variant >> 3) & 3; // experiment: k_decode_pairs
-	if (pairing != 0) {
-		const unsigned pad_lds_p = static_cast<unsigned>((variant >> 8) & 0xFF) * 1024u; // residency cap, as below
-		const uint64_t n_wg_p   = pairing == 3 ? 2 * ((n + 2) / 3) : (n + 1) / 2;
-		const uint64_t kMaxGridP = 1ull << 30;
-		for (uint64_t off = 0; off < n_wg_p; off += kMaxGridP) {
-			const dim3 grid(static_cast<unsigned>(n_wg_p - off < kMaxGridP ? n_wg_p - off : kMaxGridP)), block(64 * kDecWaves);
-#define ALPGPU_LAUNCH_PAIRS(NT, P) hipLaunchKernelGGL((k_decode_pairs<NT, P>), grid, block, pad_lds_p, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, patch_max)
-			if (pairing == 1) { if (nt) { ALPGPU_LAUNCH_PAIRS(true, 1); } else { ALPGPU_LAUNCH_PAIRS(false, 1); } }
-			if (pairing == 2) { if (nt) { ALPGPU_LAUNCH_PAIRS(true, 2); } else { ALPGPU_LAUNCH_PAIRS(false, 2); } }
-			if (pairing == 3) { if (nt) { ALPGPU_LAUNCH_PAIRS(true, 3); } else { ALPGPU_LAUNCH_PAIRS(false, 3); } }
-#undef ALPGPU_LAUNCH_PAIRS
-		}
-		return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
-	}
-	const int      V        = (variant & 4) ? 4 : ((variant & 1) ? 1 : 2);
+	const int      V        = (variant & 1) ? 1 : 2;
 	// Unused dynamic LDS that caps the workgroups resident per CU (variant bits 8.. = KiB).  Wide vectors want FEWER
 	// streams in flight per CU than the eight the wavefront slots allow: a column of 40-53-bit vectors decodes at 0.81 of the HBM peak with six
 	// workgroups per CU and at 0.75 with eight, 34-38 bits like seven; up to 33 bits eight are best (tools/sweep_residency.py,
@@ -1114,20 +808,16 @@ int launch_decode_column(hipStream_t stream, const alpgpu_column* col, double* d
 	const uint64_t kMaxGrid = 1ull << 30; // a grid dimension holds < 2^31 workgroups -> chunk very long columns
 	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
 		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(64 * kDecWaves);
-		if (V == 4 && nt) {
-			hipLaunchKernelGGL((k_decode_column<4, true, kSinkStore, DecodeLdsNarrow>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, patch_max, progress, progress_tag);
-		} else if (V == 4) {
-			hipLaunchKernelGGL((k_decode_column<4, false, kSinkStore, DecodeLdsNarrow>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, patch_max, progress, progress_tag);
-		} else if (V == 2 && nt) {
-			hipLaunchKernelGGL((k_decode_column<2, true>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, patch_max, progress, progress_tag);
+		if (V == 2 && nt) {
+			hipLaunchKernelGGL((k_decode_column<2, true>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
 		} else if (V == 2) {
-			hipLaunchKernelGGL((k_decode_column<2, false>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, patch_max, progress, progress_tag);
+			hipLaunchKernelGGL((k_decode_column<2, false>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
 		} else if ((variant & 64) && nt) { // one vector per workgroup, the 256-entry exception stage (columns of exception-heavy vectors)
-			hipLaunchKernelGGL((k_decode_column<1, true, kSinkStore, DecodeLdsManyExc>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, patch_max, progress, progress_tag);
+			hipLaunchKernelGGL((k_decode_column<1, true, kSinkStore, DecodeLdsManyExc>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
 		} else if (nt) {
-			hipLaunchKernelGGL((k_decode_column<1, true>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, patch_max, progress, progress_tag);
+			hipLaunchKernelGGL((k_decode_column<1, true>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
 		} else {
-			hipLaunchKernelGGL((k_decode_column<1, false>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, patch_max, progress, progress_tag);
+			hipLaunchKernelGGL((k_decode_column<1, false>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
 		}
 	}
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;

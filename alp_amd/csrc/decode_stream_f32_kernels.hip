@@ -134,9 +134,6 @@ __device__ __forceinline__ void stream_issue_chunk(LDS& S, int db, int buf, cons
 			__builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t*>(rgs + rg) + 4 + (lane & 3), &S.dict[buf][0][0], 4, 0, 0);
 		}
 	}
-#if defined(ALPGPU_STREAM_DISSECT) && ALPGPU_STREAM_DISSECT == 1 // measurement build: no record is loaded (the unpack reads what lies in the arena)
-	return;
-#endif
 	if (flat) {
 		const ull2* g = reinterpret_cast<const ull2*>(packed + p0);
 		const int   n_units = static_cast<int>(pk_total >> 4);
@@ -300,11 +297,7 @@ __device__ __forceinline__ void stream_decode_vector(LDS& S, int buf, int tb, in
 				out[c] = (l << bw) | q[c];
 			}
 		}
-#if defined(ALPGPU_STREAM_DISSECT) && ALPGPU_STREAM_DISSECT == 2 // measurement build: (almost) nothing is stored
-		if ((out[0] ^ out[1] ^ out[2] ^ out[3]) == 0x13579BDFu) { __builtin_nontemporal_store(out, reinterpret_cast<u32x4*>(dst + 4 * tid)); }
-#else
 		__builtin_nontemporal_store(out, reinterpret_cast<u32x4*>(dst + 4 * tid));
-#endif
 	}
 }
 
@@ -422,23 +415,22 @@ static int launch_stream(hipStream_t stream, const alpgpu_column* col, float* d_
 // shape: 16 = chunks of 8 vectors over an 8 KiB arena; 17 = chunks of 16 over 16 KiB; 18 = chunks of 4 over 12 KiB (wide vectors)
 int launch_decode_stream_f32(hipStream_t stream, const alpgpu_column* col, float* d_out, int shape, int n_cus, uint64_t* progress, uint64_t progress_tag) {
 	if (col->n_vectors == 0) { return ALPGPU_OK; }
-	static const int env_wgs = std::getenv("ALPGPU_STREAM_WGS_PER_CU") ? std::atoi(std::getenv("ALPGPU_STREAM_WGS_PER_CU")) : 0;
 	if (n_cus <= 0) { n_cus = 256; }
-	const int wgs = env_wgs > 0 ? env_wgs : 2;
+	const int wgs = 2;
 	if (shape == 17) { return launch_stream<16, 16384, 2, 4>(stream, col, d_out, n_cus, wgs, progress, progress_tag); }
 	if (shape == 18) { return launch_stream<4, 12288, 3, 4>(stream, col, d_out, n_cus, wgs, progress, progress_tag); }
 	if (shape == 19) { return launch_stream<8, 8192, 1, 4>(stream, col, d_out, n_cus, wgs, progress, progress_tag); }
 	if (shape == 20) { return launch_stream<8, 8192, 2, 4>(stream, col, d_out, n_cus, wgs, progress, progress_tag); }
-	if (shape == 21) { return launch_stream<16, 16384, 2, 8>(stream, col, d_out, n_cus, env_wgs > 0 ? env_wgs : 1, progress, progress_tag); }
-	if (shape == 22) { return launch_stream<8, 8192, 2, 8>(stream, col, d_out, n_cus, env_wgs > 0 ? env_wgs : 1, progress, progress_tag); }
-	if (shape == 23) { return launch_stream<16, 16384, 2, 12>(stream, col, d_out, n_cus, env_wgs > 0 ? env_wgs : 1, progress, progress_tag); }
-	if (shape == 24) { return launch_stream<12, 12288, 2, 12>(stream, col, d_out, n_cus, env_wgs > 0 ? env_wgs : 1, progress, progress_tag); }
-	if (shape == 25) { return launch_stream<14, 14336, 2, 14>(stream, col, d_out, n_cus, env_wgs > 0 ? env_wgs : 1, progress, progress_tag); }
-	if (shape == 27) { return launch_stream<12, 24576, 2, 12>(stream, col, d_out, n_cus, env_wgs > 0 ? env_wgs : 1, progress, progress_tag); }
-	if (shape == 28) { return launch_stream<12, 49152, 1, 12>(stream, col, d_out, n_cus, env_wgs > 0 ? env_wgs : 1, progress, progress_tag); }
-	if (shape == 29) { return launch_stream<12, 12288, 4, 12>(stream, col, d_out, n_cus, env_wgs > 0 ? env_wgs : 1, progress, progress_tag); }
-	if (shape == 30) { return launch_stream<12, 12288, 1, 12>(stream, col, d_out, n_cus, env_wgs > 0 ? env_wgs : 1, progress, progress_tag); }
-	if (shape == 26) { return launch_stream<16, 16384, 1, 14>(stream, col, d_out, n_cus, env_wgs > 0 ? env_wgs : 1, progress, progress_tag); }
+	if (shape == 21) { return launch_stream<16, 16384, 2, 8>(stream, col, d_out, n_cus, 1, progress, progress_tag); }
+	if (shape == 22) { return launch_stream<8, 8192, 2, 8>(stream, col, d_out, n_cus, 1, progress, progress_tag); }
+	if (shape == 23) { return launch_stream<16, 16384, 2, 12>(stream, col, d_out, n_cus, 1, progress, progress_tag); }
+	if (shape == 24) { return launch_stream<12, 12288, 2, 12>(stream, col, d_out, n_cus, 1, progress, progress_tag); }
+	if (shape == 25) { return launch_stream<14, 14336, 2, 14>(stream, col, d_out, n_cus, 1, progress, progress_tag); }
+	if (shape == 27) { return launch_stream<12, 24576, 2, 12>(stream, col, d_out, n_cus, 1, progress, progress_tag); }
+	if (shape == 28) { return launch_stream<12, 49152, 1, 12>(stream, col, d_out, n_cus, 1, progress, progress_tag); }
+	if (shape == 29) { return launch_stream<12, 12288, 4, 12>(stream, col, d_out, n_cus, 1, progress, progress_tag); }
+	if (shape == 30) { return launch_stream<12, 12288, 1, 12>(stream, col, d_out, n_cus, 1, progress, progress_tag); }
+	if (shape == 26) { return launch_stream<16, 16384, 1, 14>(stream, col, d_out, n_cus, 1, progress, progress_tag); }
 	return launch_stream<8, 8192, 3, 4>(stream, col, d_out, n_cus, wgs, progress, progress_tag);
 }
 

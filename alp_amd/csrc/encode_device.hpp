@@ -16,9 +16,7 @@
 
 namespace alpgpu {
 
-#ifndef ALPGPU_ENCODE_GROUP
-#define ALPGPU_ENCODE_GROUP 2
-#endif
+constexpr int kEncodeGroup = 2;
 
 struct __attribute__((aligned(16))) EncodeLds {
 	uint64_t vals[kVec]; // (enc - base) or RD right parts, natural index order: 8 KiB
@@ -122,13 +120,7 @@ __device__ __forceinline__ VecIn load_vector(const double* __restrict__ in, uint
 	VecIn          r;
 #pragma unroll
 	for (int m = 0; m < 8; ++m) {
-#ifdef ALPGPU_ENC_NT_LOAD
-		typedef double d2v __attribute__((ext_vector_type(2)));
-		const d2v q = __builtin_nontemporal_load(reinterpret_cast<const d2v*>(p) + 64 * m + lane);
-		r.x[m]      = make_double2(q.x, q.y);
-#else
 		r.x[m] = p[64 * m + lane];
-#endif
 	}
 	return r;
 }
@@ -289,7 +281,7 @@ __device__ __forceinline__ void encode_alp_registers(const VecIn& in, int e, int
 	// scheduler can interleave them), then their lane masks, then ONE wave-uniform test for the rare literal route.  A branch per
 	// value step cuts the code into blocks of one 7-deep dependent chain each, and a wavefront with two or three neighbours on its
 	// SIMD spends most of such a block waiting for its own previous result.
-	constexpr int kGroup = ALPGPU_ENCODE_GROUP; // value steps (of 2 values) per group: 1, 2, 4 or 8
+	constexpr int kGroup = kEncodeGroup; // value steps (of 2 values) per group: 1, 2, 4 or 8
 #pragma unroll
 	for (int m0 = 0; m0 < 8; m0 += kGroup) {
 		double   vv[kGroup][2], tt[kGroup][2], rr[kGroup][2], dec[kGroup][2];
@@ -514,11 +506,7 @@ __device__ __forceinline__ void store_packed_units(const PackedUnits& P, int bw,
 	for (int t = 0; t < 8; ++t) {
 		const int u = lane + 64 * t;
 		if (64 * t < n_units && u < n_units) {
-#ifndef ALPGPU_ENC_NT_STORE
 			out[u] = P.acc[t];
-#else
-			__builtin_nontemporal_store(P.acc[t], out + u); // written once, read by nobody on this device soon
-#endif
 		}
 	}
 }

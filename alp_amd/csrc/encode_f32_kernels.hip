@@ -6,7 +6,7 @@
 //   ffor::ffor (int32 / uint32 / uint16)  include/fastlanes/ffor.hpp:7-15 -> src/fastlanes_generated_ffor.cpp:1776-7378, :357-1775
 //   alp::rd_encoder<float>::encode        include/alp/rd.hpp:109-147
 //
-// Single pass, same scheme as k_encode_fused (encode_kernels.hip): one wavefront per 1024-value vector, kFusedWaves vectors per
+// Single pass, same scheme as k_encode_lean (encode_lean_kernels.hip): one wavefront per 1024-value vector, kFusedWaves vectors per
 // workgroup (tile), output offsets in vector order from the decoupled look-back of encode_lookback.hpp.  The same kernel body,
 // compiled in two more modes, is the two-pass form (ALPGPU_OPT_ENCODE_TWO_PASS and the recovery route of a stalled single pass):
 // ANALYZE stops after the sizes are known and leaves them in the descriptors, PACK takes its offsets from the scan of those
@@ -22,9 +22,7 @@
 namespace alpgpu {
 
 enum FusedMode { kSinglePass = 0, kAnalyze = 1, kPack = 2 };
-#ifndef ALPGPU_F32_ENC_OCC
-#define ALPGPU_F32_ENC_OCC 8 // __launch_bounds__' second argument for the single pass: wavefronts per SIMD the register budget is sized for (round 4: 62 VGPRs, four tiles per CU)
-#endif
+constexpr int kF32EncOcc = 8; // __launch_bounds__' second argument for the single pass: wavefronts per SIMD the register budget is sized for (round 4: 62 VGPRs, four tiles per CU)
 constexpr int kScanTileF32 = 1024; // = kScanTile of encode_kernels.hip: vectors per tile of the two-pass scan
 
 struct FusedSharedF32 {
@@ -36,17 +34,6 @@ struct FusedSharedF32 {
 };
 
 // one tile (kFusedWaves vectors, one per wavefront) of k_encode_fused_f32
-// Measurement builds (-DALPGPU_F32_STOP_AT=n, as ALPGPU_LEAN_STOP_AT in encode_lean_kernels.hip): every wavefront of the single pass ends behind
-// stage n with one dependent store; the column is garbage, the counters of successive builds difference into instructions per stage.
-#ifdef ALPGPU_F32_STOP_AT
-#define ALPGPU_F32_STOP(n, expr)                                                                    \
-	if (MODE == kSinglePass && ALPGPU_F32_STOP_AT == (n)) {                                         \
-		if (lane == 0) { arg_descs()[v_read].base = static_cast<int64_t>(expr); }                   \
-		return;                                                                                     \
-	}
-#else
-#define ALPGPU_F32_STOP(n, expr)
-#endif
 // UNORDERED (single pass only; ALPGPU_OPT_ENCODE_UNORDERED, encode_lean_kernels.hip): the tile reserves its bytes with one atomic add instead of the look-back
 template <int MODE, bool UNORDERED = false>
 __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_t tile, const float* __restrict__ in, const alpgpu_rowgroup_state* __restrict__ rgs,
@@ -59,13 +46,9 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 		if ((threadIdx.x & 63) == 0 && vo < v_first + n_vectors_launch) { descs[vo] = empty_descriptor(); }
 		return;
 	}
-	// single pass: the arguments needed only behind the wait come from the kernarg segment where they are used (alp_device.hpp: late_kernel_arg;
-	// -DALPGPU_F32_ARGS_AT_ENTRY: the old form).  The other two modes are not short of scalar registers.
-#ifdef ALPGPU_F32_ARGS_AT_ENTRY
-	constexpr bool kLate = false;
-#else
+	// single pass: the arguments needed only behind the wait come from the kernarg segment where they are used (alp_device.hpp: late_kernel_arg).
+	// The other two modes are not short of scalar registers.
 	constexpr bool kLate = MODE == kSinglePass;
-#endif
 	auto arg_descs      = [&]() { if constexpr (kLate) { return late_kernel_arg<alpgpu_vector_desc*>(kArgDescs); } else { return descs; } };
 	auto arg_packed     = [&]() { if constexpr (kLate) { return late_kernel_arg<uint8_t*>(kArgPacked); } else { return packed; } };
 	auto arg_excs       = [&]() { if constexpr (kLate) { return late_kernel_arg<uint8_t*>(kArgExcs); } else { return excs; } };
@@ -78,16 +61,6 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 	uint32_t& s_ready                = S.s_ready;
 	const int lane = lane_id();
 	const int wave = wave_in_wg();
-#ifdef ALPGPU_F32_INIT_BARRIER_FIRST // (A/B: until late in round 4 the tile's two LDS words were set, and waited for, in front of the loads)
-	if (MODE == kSinglePass) { // (the other two modes share nothing between wavefronts)
-		if (threadIdx.x == 0) {
-			s_count = 0;
-			s_ready = 0;
-			s_excl  = ~0ull; // "stalled" until the look-back says otherwise (k_encode_lean: a wavefront 0 that gave up on its state never runs it)
-		}
-		__syncthreads();
-	}
-#endif
 
 	EncodeLdsF32&  L    = lds[wave];
 	const uint64_t vl   = tile * kFusedWaves + wave;
@@ -96,21 +69,12 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 	VecInF             x;
 	alpgpu_vector_desc d;
 	uint64_t           lacc[4] = {0, 0, 0, 0}; // ALP_RD: packed left streams of this lane's four lane64 columns
-	// Where the vector's exceptions are.  Default: sixteen lane masks (scalar register pairs), live from the value steps to the exception record.
-	// -DALPGPU_F32_BITS_ANALYSIS (late round 4, measured, NOT the default): per lane its own sixteen bits in one VGPR plus the count of every value
+	// Where the vector's exceptions are: sixteen lane masks (scalar register pairs), live from the value steps to the exception record.
+	// (Late round 4, measured and dropped: per lane its own sixteen bits in one VGPR plus the count of every value
 	// step — no lane mask outlives its value step (encode_f32_device.hpp: encode_alp_lean_f32): 89 -> 41 spilled scalar registers and 1017 -> 964
 	// vector instructions per vector, but the kernel then needs 66 VGPRs, seven of them go through scratch, and it is 3-4 % SLOWER
-	// (profiles/r04_float_encode.txt, late round 4, point f).
-#ifdef ALPGPU_F32_BITS_ANALYSIS
-	uint32_t           excbits  = 0;
-	uint32_t           cnt_m[4] = {0u, 0u, 0u, 0u};
-#define ALPGPU_F32_EXC_WITNESS excbits
-#define ALPGPU_F32_FOR_EACH_EXCEPTION(...) for_each_exception_bits_f32(excbits, cnt_m, lane, __VA_ARGS__)
-#else
+	// (profiles/r04_float_encode.txt, late round 4, point f).)
 	uint64_t           ballots[4][4];
-#define ALPGPU_F32_EXC_WITNESS static_cast<int64_t>(ballots[0][0] ^ ballots[3][3] ^ ballots[1][1])
-#define ALPGPU_F32_FOR_EACH_EXCEPTION(...) for_each_exception_f32(ballots, lane, __VA_ARGS__)
-#endif
 	uint32_t           pvals[4][4]; // what gets packed: value - base (ALP), right parts (ALP_RD)
 #pragma unroll
 	for (int m = 0; m < 4; ++m) { pvals[m][0] = pvals[m][1] = pvals[m][2] = pvals[m][3] = 0u; }
@@ -119,7 +83,7 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 	d.base                   = 0;
 	d.bw = d.e = d.f = d.lbw = 0;
 	d.exc_cnt = d.scheme = 0;
-	// The rowgroup's state once, into registers; async_states: published by the persistent search beside this kernel (see k_encode_fused).  Its
+	// The rowgroup's state once, into registers; async_states: published by the persistent search beside this kernel (see k_encode_lean).  Its
 	// (first) read is issued in FRONT of the vector's loads and looked at behind them: one round trip at the head of the wavefront, not two
 	// (until round 4 the vector was requested only after the state had arrived).
 	const uint64_t               v_read   = live ? v : v_first;
@@ -127,7 +91,6 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 	const bool                   polling  = MODE == kSinglePass && async_states;
 	const uint32_t               st_word  = polling ? rowgroup_state_poll_begin(rg_ptr, lane) : reinterpret_cast<const uint32_t*>(rg_ptr)[lane & 7];
 	x                                     = load_vector_f32(in, v_read, lane);
-#ifndef ALPGPU_F32_INIT_BARRIER_FIRST
 	if (MODE == kSinglePass) { // the tile's two LDS words, set behind the ISSUE of the loads (k_encode_lean): the barrier falls into the shadow of their round trip
 		if (threadIdx.x == 0) {
 			s_count = 0;
@@ -136,7 +99,6 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 		}
 		asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // not __syncthreads(): its fence would wait for the loads in flight
 	}
-#endif
 	bool                         state_ok = true;
 	const alpgpu_rowgroup_state  st       = polling ? rowgroup_state_poll_finish(rg_ptr, st_word, lane, spin_limit >> 4, state_ok) : unpack_rowgroup_state(st_word);
 	const alpgpu_rowgroup_state* rgp      = &st;
@@ -147,7 +109,6 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 	// bytes used by earlier launches of this column: constant while this launch runs (k_fused_finish updates them), read now so
 	// that nothing but the ordered offset stands between the wait and the stores
 	const uint64_t base_p = totals[0], base_e = totals[1];
-	ALPGPU_F32_STOP(1, __float_as_uint(x.x[0][0] + x.x[3][3]) + st.k);
 	if (live) {
 		d.scheme = rgp->scheme;
 		if (rgp->scheme == ALPGPU_SCHEME_ALP) {
@@ -158,17 +119,8 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 				e = rgp->combos[0];
 				f = rgp->combos[1];
 			}
-			ALPGPU_F32_STOP(2, e * 32 + f);
-#ifdef ALPGPU_F32_BITS_ANALYSIS
-			AlpEncodedLeanF R;
-			encode_alp_lean_f32(x, e, f, lane, R);
-			ALPGPU_F32_STOP(3, R.base + R.bw + R.cnt + R.excbits + R.enc[0][0] + R.enc[3][3] + R.enc[1][1] + R.enc[2][2]);
-			excbits = R.excbits;
-#else
 			AlpEncodedF R;
 			encode_alp_registers_f32(x, e, f, lane, R);
-			ALPGPU_F32_STOP(3, R.base + R.bw + R.cnt + static_cast<int64_t>(R.ballot[0][0] ^ R.ballot[3][3] ^ R.ballot[1][2] ^ R.ballot[2][1]) + R.enc[0][0] + R.enc[3][3] + R.enc[1][1] + R.enc[2][2]);
-#endif
 			d.base = R.base, d.bw = static_cast<uint8_t>(R.bw), d.e = static_cast<uint8_t>(e), d.f = static_cast<uint8_t>(f);
 			cnt = R.cnt;
 			const uint32_t base = static_cast<uint32_t>(R.base);
@@ -177,12 +129,8 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 				u32x4 q;
 #pragma unroll
 				for (int j = 0; j < 4; ++j) { q[j] = static_cast<uint32_t>(R.enc[m][j]) - base; }
-#ifdef ALPGPU_F32_BITS_ANALYSIS
-				cnt_m[m] = R.cnt_m[m];
-#else
 #pragma unroll
 				for (int j = 0; j < 4; ++j) { ballots[m][j] = R.ballot[m][j]; }
-#endif
 #pragma unroll
 				for (int j = 0; j < 4; ++j) { pvals[m][j] = q[j]; }
 			}
@@ -219,21 +167,13 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 						const int ridx = rd_exception_index(order, left);
 						idx            = exc ? ridx : idx;
 					}
-#ifdef ALPGPU_F32_BITS_ANALYSIS
-					cnt_m[m] += static_cast<uint32_t>(__builtin_popcountll(bj));
-					excbits = push_exception_bit(excbits, bj);
-#else
 					ballots[m][j] = bj;
 					cnt += __builtin_popcountll(bj);
-#endif
 					lacc[j] |= (static_cast<uint64_t>(idx) & lmask) << (row * lbw);
 				}
 #pragma unroll
 				for (int j = 0; j < 4; ++j) { pvals[m][j] = q[j]; }
 			}
-#ifdef ALPGPU_F32_BITS_ANALYSIS
-			cnt = static_cast<int>(cnt_m[0] + cnt_m[1] + cnt_m[2] + cnt_m[3]);
-#endif
 #pragma unroll
 			for (int j = 0; j < 4; ++j) {
 				lacc[j] |= static_cast<uint64_t>(__shfl_xor(static_cast<long long>(lacc[j]), 16));
@@ -242,7 +182,6 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 		}
 		d.exc_cnt = static_cast<uint16_t>(cnt);
 	}
-	ALPGPU_F32_STOP(4, d.base + d.bw + cnt + pvals[0][0] + pvals[3][3] + pvals[1][2] + pvals[2][1] + ALPGPU_F32_EXC_WITNESS);
 	uint64_t my_p = 0, my_e = 0;
 	if (live) { record_sizes<4>(d, my_p, my_e); }
 	if (MODE == kAnalyze) { // the sizes are all the scan needs
@@ -266,14 +205,12 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 			}
 		}
 	}
-	// Pack while the ordered offset is on its way (see k_encode_fused) — into the wavefront's 4 KiB image, which STAYS in LDS until the offset is
+	// Pack while the ordered offset is on its way (see k_encode_lean) — into the wavefront's 4 KiB image, which STAYS in LDS until the offset is
 	// there (round 4; until then the image was read back into sixteen registers and the record took its place): nothing vector-sized but the
 	// input itself is live across the wait.  The exception record is laid out behind the image's 128 * bw bytes when it fits what is left of the
 	// 4 KiB, and leaves as contiguous stores after the wait; else (a wide vector with many exceptions) it is written from the registers then.
 	// Pad bytes are zero.
-	ALPGPU_F32_STOP(5, base_p + base_e + my_p + my_e + pvals[0][0] + pvals[3][3]);
 	pack_u32_scatter_image(reinterpret_cast<uint32_t*>(L.vals), pvals, d.bw, lane);
-	ALPGPU_F32_STOP(6, reinterpret_cast<uint32_t*>(L.vals)[lane] + base_p + ALPGPU_F32_EXC_WITNESS);
 	const bool     alp_rec    = d.scheme == ALPGPU_SCHEME_ALP;
 	const uint32_t val_bytes  = alp_rec ? 4u * static_cast<uint32_t>(cnt) : 2u * static_cast<uint32_t>(cnt);
 	const uint32_t rec_off    = 128u * d.bw;
@@ -283,7 +220,7 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 		if (lane == 0) { reinterpret_cast<uint64_t*>(img)[(my_e >> 3) - 1] = 0ull; } // the pad lives in the last word
 		wave_lds_sync();
 		const int rbw = d.bw;
-		ALPGPU_F32_FOR_EACH_EXCEPTION([&](int r, int m, int j) {
+		for_each_exception_f32(ballots, lane, [&](int r, int m, int j) {
 			const uint32_t bits = __float_as_uint(x.x[m][j]);
 			if (alp_rec) {
 				reinterpret_cast<uint32_t*>(img)[r] = bits;
@@ -294,7 +231,6 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 		});
 		wave_lds_sync();
 	}
-	ALPGPU_F32_STOP(7, reinterpret_cast<uint32_t*>(L.vals)[lane] + reinterpret_cast<uint32_t*>(L.vals)[960 + lane] + base_p);
 	if (MODE == kSinglePass) {
 		// wavefront 0 finds the tile's offset; the others park at a workgroup barrier meanwhile (see k_encode_lean: a worker that spins on an LDS
 		// word takes issue slots from the wavefronts that still compute)
@@ -316,9 +252,8 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 		d.packed_off       = descs[v].packed_off + status[2 * st_];
 		d.exc_off          = descs[v].exc_off + status[2 * st_ + 1];
 	}
-	ALPGPU_F32_STOP(8, d.packed_off + d.exc_off + reinterpret_cast<uint32_t*>(L.vals)[lane]);
 	if (!live) { return; }
-	if (d.packed_off + my_p > arg_packed_cap() || d.exc_off + my_e > arg_exc_cap()) { // see k_encode_fused
+	if (d.packed_off + my_p > arg_packed_cap() || d.exc_off + my_e > arg_exc_cap()) { // see k_encode_lean
 		if (lane == 0) {
 			__hip_atomic_store(totals + 2, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			arg_descs()[v] = empty_descriptor();
@@ -336,7 +271,7 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 		} else { // no room behind the image: values, positions and pad straight from the registers
 			uint16_t* rpos = reinterpret_cast<uint16_t*>(rec + val_bytes);
 			const int rbw  = d.bw;
-			ALPGPU_F32_FOR_EACH_EXCEPTION([&](int r, int m, int j) {
+			for_each_exception_f32(ballots, lane, [&](int r, int m, int j) {
 				const uint32_t bits = __float_as_uint(x.x[m][j]);
 				if (alp_rec) {
 					reinterpret_cast<uint32_t*>(rec)[r] = bits;
@@ -370,14 +305,14 @@ __device__ __forceinline__ void encode_tile_f32(FusedSharedF32& S, const uint64_
 // registers the persistent rowgroup search needs to share the CU)
 // (the first nine parameters are read by offset in the single pass — alp_device.hpp: kArgDescs .. kArgExcCap — keep their order and types)
 template <int MODE, bool UNORDERED = false>
-__global__ __launch_bounds__(64 * kFusedWaves, MODE == kSinglePass ? ALPGPU_F32_ENC_OCC : 1) void k_encode_fused_f32(const float* __restrict__ in, const alpgpu_rowgroup_state* __restrict__ rgs,
+__global__ __launch_bounds__(64 * kFusedWaves, MODE == kSinglePass ? kF32EncOcc : 1) void k_encode_fused_f32(const float* __restrict__ in, const alpgpu_rowgroup_state* __restrict__ rgs,
                                                                        alpgpu_vector_desc* __restrict__ descs, uint8_t* __restrict__ packed,
                                                                        uint8_t* __restrict__ excs, uint64_t* __restrict__ status,
                                                                        uint64_t* __restrict__ totals, uint64_t packed_capacity, uint64_t exc_capacity,
                                                                        uint64_t v_first, uint64_t n_vectors_launch, const uint16_t* __restrict__ rd_order,
                                                                        uint32_t spin_limit, const uint64_t* __restrict__ gate, uint32_t async_states) {
 	if (MODE != kSinglePass && gate != nullptr && *gate == 0) { return; }
-	__builtin_amdgcn_s_setprio(2); // over the persistent rowgroup search that may share the CU (see k_encode_fused)
+	__builtin_amdgcn_s_setprio(2); // over the persistent rowgroup search that may share the CU (see k_encode_lean)
 	__shared__ FusedSharedF32 S;
 	if constexpr (MODE == kSinglePass) {
 		encode_tile_f32<MODE, UNORDERED>(S, blockIdx.x, in, rgs, descs, packed, excs, status, totals, packed_capacity, exc_capacity, v_first, n_vectors_launch, rd_order, spin_limit,

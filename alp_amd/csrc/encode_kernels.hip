@@ -8,8 +8,8 @@
 // and the caller's per-column loop (publication/source_code/bench_compression_ratio/alp.cpp:198-229).
 //
 // Variable-size output needs each vector's byte offsets.  Two forms, byte-identical output:
-//   default  k_encode_fused (+ k_fused_finish): one pass; offsets from the in-kernel two-level look-back of
-//            encode_lookback.hpp (description above the kernel)
+//   default  k_encode_lean (encode_lean_kernels.hip, + k_fused_finish): one pass; offsets from the in-kernel two-level look-back of
+//            encode_lookback.hpp (description below)
 //   fallback (ALPGPU_OPT_ENCODE_TWO_PASS):
 //     k_encode_analyze : one wave per vector; picks (e,f), counts exceptions, finds base/bw -> descriptor sizes
 //     k_scan_tiles     : exclusive scan of the sizes inside tiles of 1024 vectors, tile totals to a workspace
@@ -25,9 +25,6 @@
 namespace alpgpu {
 
 constexpr int kScanTile = 1024;
-#ifndef ALPGPU_ENC_PRIO
-#define ALPGPU_ENC_PRIO 2
-#endif
 
 // ---- pass 1: analysis -----------------------------------------------------------------------------------
 // `gate` (all kernels of this form): nullptr, or a word that must be non-zero for the kernel to do anything — the recovery route
@@ -254,7 +251,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg) void k_encode_pack(const double* 
 	}
 }
 
-// ---- single pass: analysis, ordered offsets (decoupled look-back) and pack in ONE kernel -------------------------------
+// ---- single pass: analysis, ordered offsets (decoupled look-back) and pack in ONE kernel (encode_lean_kernels.hip: k_encode_lean) ----------------
 // The two-pass form above reads the input twice and does the encode arithmetic twice.  Here a workgroup (tile) of kFusedWaves
 // wavefronts = kFusedWaves consecutive vectors
 //   1. encodes its vectors (registers -> LDS), knows their sizes,
@@ -272,287 +269,6 @@ __global__ __launch_bounds__(64 * kWavesPerWg) void k_encode_pack(const double* 
 // every spin is bounded, a stall sets totals[3] and nothing of a stalled tile is written; the two-pass kernels enqueued behind
 // every single-pass encode (gated on that flag: launch_encode_recovery) then redo the column on the same stream.  The field widths bound one launch to kFusedMaxVectors vectors;
 // longer columns are chained launch by launch through totals[0..1].  Where a wavefront's time goes: profiles/r01_fused_phases.txt.
-#ifdef ALPGPU_FUSED_TIMING // experiment (tools/fused_phases.py): per-wavefront phase marks, 10 ns ticks since the wavefront started
-__device__ int32_t* g_phase_buf = nullptr; // [n_vectors][8]
-#define PHASE_WAIT_MEM() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory")
-#define PHASE_MARK(k)                                                                                                        \
-	do {                                                                                                                 \
-		if (g_phase_buf != nullptr && lane == 0 && live) { g_phase_buf[8 * vl + (k)] = static_cast<int32_t>(wall_clock64() - phase_t0); } \
-	} while (0)
-#else
-#define PHASE_WAIT_MEM()
-#define PHASE_MARK(k)
-#endif
-__global__ __launch_bounds__(64 * kFusedWaves) void k_encode_fused(const double* __restrict__ in,
-                                                                   const alpgpu_rowgroup_state* __restrict__ rgs,
-                                                                   alpgpu_vector_desc* __restrict__ descs, uint8_t* __restrict__ packed,
-                                                                   uint8_t* __restrict__ excs, uint64_t* __restrict__ status,
-                                                                   uint64_t* __restrict__ totals, uint64_t packed_capacity,
-                                                                   uint64_t exc_capacity, uint64_t v_first, uint64_t n_vectors_launch,
-                                                                   const uint16_t* __restrict__ rd_order, uint32_t spin_limit, uint32_t async_states) {
-	// instruction-issue priority over the persistent rowgroup search that may share the CU (alpgpu_encode_f64 on a long column): the
-	// search then takes the issue slots this kernel leaves idle instead of competing for them (3.28 -> 3.14 ms per 1 Mi vectors)
-	__builtin_amdgcn_s_setprio(ALPGPU_ENC_PRIO);
-	__shared__ EncodeLds lds[kFusedWaves];
-	__shared__ uint64_t  s_size[kFusedWaves]; // per vector: (packed units << 31) | exception units
-	__shared__ uint64_t  s_excl;              // tile's exclusive prefix in the same packing, or ~0 on a stall
-	__shared__ uint32_t  s_count;             // worker wavefronts that have posted their size
-	__shared__ uint32_t  s_ready;             // set by the scout once s_excl is valid
-	const int            lane = lane_id();
-	const int            wave = wave_in_wg();
-	const uint64_t       tile = blockIdx.x;
-#ifdef ALPGPU_FUSED_TIMING
-	const uint64_t phase_t0 = wall_clock64();
-#endif
-	if (threadIdx.x == 0) {
-		s_count = 0;
-		s_ready = 0;
-	}
-	__syncthreads(); // the only workgroup barrier: nothing waits on memory here
-
-	// ---- the workers: one vector each -------------------------------------------------------------------------------
-	EncodeLds&     L    = lds[wave];
-	const uint64_t vl   = tile * kFusedWaves + wave; // vector index inside this launch
-	const bool     live = vl < n_vectors_launch;
-	const uint64_t v    = v_first + vl;
-	// ---- 1. encode into registers / LDS ----
-	VecIn              x;
-	alpgpu_vector_desc d;
-	uint64_t           acc0 = 0, acc1 = 0; // ALP_RD: packed left streams of this lane's two lane64 columns
-	uint64_t           ballots[8][2];
-	uint64_t           pvals[8][2]; // what gets packed: value - base (ALP), right parts (ALP_RD)
-	int                cnt = 0;
-#pragma unroll
-	for (int m = 0; m < 8; ++m) { pvals[m][0] = pvals[m][1] = 0; }
-	d.packed_off = d.exc_off = 0;
-	d.base                   = 0;
-	d.bw = d.e = d.f = d.lbw = 0;
-	d.exc_cnt = d.scheme = 0;
-	// The 8 KiB everything waits for are requested FIRST.  Requested behind the rowgroup state (whose unpacking into scalar
-	// registers makes the compiler wait for it on the spot) and behind the scalar read of the running totals, the vector loads
-	// started two memory round trips late — 20 % of a tile's life.  A wavefront past the end of the column reads the launch's
-	// first vector instead (nothing of it is stored).
-	const uint64_t v_read = live ? v : v_first;
-	const alpgpu_rowgroup_state* rg_ptr  = rgs + v_read / kRowgroup;
-	const uint32_t               st_word = async_states ? rowgroup_state_poll_begin(rg_ptr, lane) : reinterpret_cast<const uint32_t*>(rg_ptr)[lane & 7]; // in FRONT of the vector's loads (alp_device.hpp)
-#ifdef ALPGPU_EXPERIMENT_ENC_WRAP_TRAFFIC // timing experiment (profiles/r03_encode_levers.txt): every vector's 8 KiB come from the first 8192 vectors and go
-	// to the first 64 MiB / 8 MiB of the streams — the same arithmetic on a column that repeats its first 8192 vectors, without the HBM traffic
-	x = load_vector(in, v_read & 8191ull, lane);
-#else
-	x                     = load_vector(in, v_read, lane);
-#endif
-	// the rowgroup's state, once, into registers (alp_device.hpp); its read is in flight together with the input's
-	// async_states (alpgpu_encode_f64 on a long column): the states are being published by the persistent rowgroup search that runs
-	// beside this kernel on a second stream; a wavefront polls its rowgroup's tag (nearly always set long before: the search runs
-	// rowgroups ahead).  A state that does not arrive within the spin limit is a stall like a look-back that gives up: flag, no output
-	// of this tile, the recovery route (behind both streams) re-encodes.
-	bool                         state_ok = true;
-	const alpgpu_rowgroup_state  st  = async_states ? rowgroup_state_poll_finish(rg_ptr, st_word, lane, spin_limit >> 4, state_ok) : unpack_rowgroup_state(st_word);
-	const alpgpu_rowgroup_state* rgp = &st;
-	if (!state_ok) { // wave-uniform
-		if (lane == 0) { status_store(totals + 3, 1ull); }
-		return; // (the tile's other wavefronts and its successors run into their own spin limits: status words never appear)
-	}
-	if (live) {
-		PHASE_WAIT_MEM();
-		PHASE_MARK(0);
-		d.scheme = rgp->scheme;
-		if (rgp->scheme == ALPGPU_SCHEME_ALP) {
-			int e, f;
-#ifdef ALPGPU_ABLATE_SECOND
-			if (false) {
-#else
-			if (rgp->k > 1) {
-#endif
-				second_level_select(x, rgp, L, lane, e, f);
-			} else {
-				e = rgp->combos[0];
-				f = rgp->combos[1];
-			}
-			PHASE_MARK(1);
-			AlpEncoded R;
-			encode_alp_registers(x, e, f, lane, R);
-			PHASE_MARK(2);
-			d.base = R.base, d.bw = static_cast<uint8_t>(R.bw), d.e = static_cast<uint8_t>(e), d.f = static_cast<uint8_t>(f);
-			cnt = R.cnt;
-			const uint64_t base = static_cast<uint64_t>(R.base);
-#pragma unroll
-			for (int m = 0; m < 8; ++m) {
-				pvals[m][0]   = static_cast<uint64_t>(R.enc[m][0]) - base;
-				pvals[m][1]   = static_cast<uint64_t>(R.enc[m][1]) - base;
-				ballots[m][0] = R.ballot[m][0];
-				ballots[m][1] = R.ballot[m][1];
-			}
-		} else {
-			RdEncoded R;
-			encode_rd_registers(x, *rgp, lane, R, rd_order ? rd_order + (v / kRowgroup) * ALPGPU_RD_ORDER_STRIDE : nullptr, async_states != 0);
-			d.bw = rgp->rd_rbw, d.lbw = rgp->rd_lbw;
-			cnt = R.cnt;
-			const int      lbw   = d.lbw;
-			const uint64_t lmask = (1ull << lbw) - 1ull;
-#pragma unroll
-			for (int m = 0; m < 8; ++m) {
-				pvals[m][0]   = R.right[m][0];
-				pvals[m][1]   = R.right[m][1];
-				ballots[m][0] = R.ballot[m][0];
-				ballots[m][1] = R.ballot[m][1];
-				const int row     = 2 * m + (lane >> 5);
-				acc0 |= (static_cast<uint64_t>(R.idx[m][0]) & lmask) << (row * lbw);
-				acc1 |= (static_cast<uint64_t>(R.idx[m][1]) & lmask) << (row * lbw);
-			}
-			acc0 |= static_cast<uint64_t>(__shfl_xor(static_cast<long long>(acc0), 32));
-			acc1 |= static_cast<uint64_t>(__shfl_xor(static_cast<long long>(acc1), 32));
-		}
-		d.exc_cnt = static_cast<uint16_t>(cnt);
-	}
-	uint64_t my_p = 0, my_e = 0; // bytes
-	if (live) { record_sizes<8>(d, my_p, my_e); }
-	// post this vector's size; the last worker to arrive publishes the tile's aggregate (so successors never wait for
-	// this tile's own look-back), then everybody waits — on LDS words only — for the scout's exclusive prefix
-	if (lane == 0) {
-		s_size[wave] = status_pack(0, my_p >> 7, my_e >> 3);
-		const uint32_t arrived = __hip_atomic_fetch_add(&s_count, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-		if (arrived == kFusedWaves - 1) {
-			uint64_t aggregate = 0;
-#pragma unroll
-			for (int w = 0; w < kFusedWaves; ++w) { aggregate += s_size[w]; }
-			status_store(status + tile, kFlagAggregate | aggregate); // the tile word is written exactly once
-		}
-	}
-	// bytes used by earlier launches of this column: constant while this launch runs (k_fused_finish updates them); read here, so
-	// that the read is neither in front of the vector's loads nor behind the wait for the ordered offset
-	const uint64_t base_p = totals[0], base_e = totals[1];
-	// The packed words do not depend on where they will be stored: build them now, in registers, while the ordered offset is
-	// still on its way (a wavefront otherwise idles ~40 % of its life here: profiles/r01_fused_phases.txt); wavefront 0 packs
-	// first as well, its look-back then finds more of its predecessors already posted.
-	PHASE_MARK(3);
-	PackedUnits packed_units;
-#ifdef ALPGPU_ABLATE_PACK
-#pragma unroll
-	for (int t = 0; t < 8; ++t) { packed_units.acc[t] = ull2v{0ull, 0ull}; }
-#elif defined(ALPGPU_PACK_GATHER) // the round-2 form (A/B): values staged in natural order, every output word gathers its rows
-	{
-		ulonglong2* lv = reinterpret_cast<ulonglong2*>(L.vals);
-#pragma unroll
-		for (int m = 0; m < 8; ++m) { lv[64 * m + lane] = make_ulonglong2(pvals[m][0], pvals[m][1]); }
-		wave_lds_sync();
-		pack_u64_units(L.vals, d.bw, lane, packed_units);
-	}
-#else
-	pack_u64_scatter(L.vals, pvals, d.bw, lane, packed_units);
-#endif
-	PHASE_MARK(4);
-	// Likewise the exception record: its image is laid out in the (now free) staging area, so that after the wait it leaves as a
-	// few contiguous 8-byte-per-lane stores instead of two one-lane stores per exception step, and the input values need not
-	// stay in registers across the wait.  The values always fit (8 B x 1024); the positions follow them when the whole record
-	// fits (<= 819 exceptions; always for ALP_RD), else they are written from the ballots after the wait.  Pad bytes are zero.
-	const bool     alp_rec      = d.scheme == ALPGPU_SCHEME_ALP;
-	const uint32_t val_bytes    = alp_rec ? 8u * static_cast<uint32_t>(cnt) : 2u * static_cast<uint32_t>(cnt);
-	const bool     pos_staged   = my_e <= sizeof(L.vals);
-	const uint32_t staged_bytes = pos_staged ? static_cast<uint32_t>(my_e) : val_bytes;
-#ifdef ALPGPU_ABLATE_EXC
-	if (false) {
-#else
-	if (cnt > 0) {
-#endif
-		uint8_t* img = reinterpret_cast<uint8_t*>(L.vals);
-		wave_lds_sync(); // the pack's reads of the staging area are issued; the LDS executes one wavefront's operations in order
-		if (lane == 0) { reinterpret_cast<uint64_t*>(img)[(staged_bytes >> 3) - 1] = 0ull; } // the pad lives in the last word
-		wave_lds_sync();
-		const int rbw = d.bw;
-		for_each_exception(ballots, lane, [&](int r, int m, int j) {
-			const uint64_t bits = static_cast<uint64_t>(__double_as_longlong(j == 0 ? x.x[m].x : x.x[m].y));
-			const uint16_t pos  = static_cast<uint16_t>(128 * m + 2 * lane + j);
-			if (alp_rec) {
-				reinterpret_cast<uint64_t*>(img)[r] = bits;
-			} else {
-				reinterpret_cast<uint16_t*>(img)[r] = static_cast<uint16_t>(bits >> rbw);
-			}
-			if (pos_staged) { reinterpret_cast<uint16_t*>(img + val_bytes)[r] = pos; }
-		});
-		wave_lds_sync();
-	}
-	PHASE_MARK(5);
-	if (wave == 0) { tile_lookback(tile, status, totals, s_size, &s_count, &s_excl, &s_ready, lane, spin_limit); }
-	{
-		uint32_t spins = 0;
-		while (__hip_atomic_load(&s_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
-			if (++spins > 64u * kSpinLimit) { return; }
-			__builtin_amdgcn_s_sleep(2);
-		}
-	}
-	uint64_t local = 0;
-#pragma unroll
-	for (int w = 0; w < kFusedWaves; ++w) { local += w < wave ? s_size[w] : 0; }
-	const uint64_t excl = s_excl;
-	if (excl == ~0ull) { return; } // stalled: nothing of this tile is written
-	PHASE_MARK(6);
-
-	// ---- 4. write at the final offsets ----
-	const uint64_t pre    = excl + local;
-	d.packed_off          = base_p + ((pre >> 31) & 0x7FFFFFFFull) * 128ull;
-	d.exc_off             = base_e + (pre & 0x7FFFFFFFull) * 8ull;
-	if (!live) { return; }
-	if (d.packed_off + my_p > packed_capacity || d.exc_off + my_e > exc_capacity) {
-		// this vector does not fit: report, write nothing past the buffers, and leave a descriptor that a decoder can follow
-		// without leaving them (bit width 0, no exceptions: the column's content is unspecified, its extents are not)
-		if (lane == 0) {
-			__hip_atomic_store(totals + 2, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			descs[v] = empty_descriptor();
-		}
-		return;
-	}
-#ifdef ALPGPU_EXPERIMENT_ENC_WRAP_TRAFFIC
-	uint8_t* dst = packed + (d.packed_off & ((64ull << 20) - 1));
-	uint8_t* rec = excs + (d.exc_off & ((8ull << 20) - 1));
-#else
-	uint8_t* dst = packed + d.packed_off;
-	uint8_t* rec = excs + d.exc_off;
-#endif
-#ifdef ALPGPU_ABLATE_STORES // timing experiment: everything but the output stores
-	if (packed_capacity == 1) {
-#endif
-#ifdef ALPGPU_ABLATE_EXC
-	if (false) {
-#else
-	if (cnt > 0) {
-#endif
-		const uint64_t* img64 = reinterpret_cast<const uint64_t*>(L.vals);
-		uint64_t*       rec64 = reinterpret_cast<uint64_t*>(rec);
-		const int       n_w   = static_cast<int>(staged_bytes >> 3);
-		for (int w = lane; w < n_w; w += 64) {
-#ifndef ALPGPU_ENC_NT_STORE
-			rec64[w] = img64[w];
-#else
-			__builtin_nontemporal_store(img64[w], rec64 + w);
-#endif
-		}
-		if (!pos_staged) { // > 819 exceptions in an ALP vector: positions (and their pad) straight from the ballots
-			uint16_t* rpos = reinterpret_cast<uint16_t*>(rec + val_bytes);
-			for_each_exception(ballots, lane, [&](int r, int m, int j) { rpos[r] = static_cast<uint16_t>(128 * m + 2 * lane + j); });
-			const int n_pos = static_cast<int>((my_e - val_bytes) >> 1);
-			if (cnt + lane < n_pos) { rpos[cnt + lane] = 0; }
-		}
-	}
-	store_packed_units(packed_units, d.bw, reinterpret_cast<ull2v*>(dst), lane);
-	if (d.scheme != ALPGPU_SCHEME_ALP && lane < 32) {
-		uint32_t* out32 = reinterpret_cast<uint32_t*>(dst + 128ull * d.bw);
-		for (int k = 0; k < d.lbw; ++k) {
-			out32[32 * k + lane] = (static_cast<uint32_t>(acc0 >> (16 * k)) & 0xFFFFu) | ((static_cast<uint32_t>(acc1 >> (16 * k)) & 0xFFFFu) << 16);
-		}
-	}
-#ifdef ALPGPU_ABLATE_STORES
-	}
-#endif
-	if (lane == 0) { descs[v] = d; }
-	PHASE_MARK(7);
-}
-
-#ifdef ALPGPU_FUSED_TIMING
-extern "C" __attribute__((visibility("default"))) int alpgpu_debug_fused_phases(void* buf) {
-	return hipMemcpyToSymbol(HIP_SYMBOL(g_phase_buf), &buf, sizeof(buf)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 // publishes the running totals after a fused launch (single thread; keeps totals[0..1] stable while the launch runs) and
 // latches the stall flag into totals[6], the gate of the recovery kernels (k_scan_totals clears totals[3] on its way)
@@ -627,7 +343,7 @@ int launch_encode_reset_totals(hipStream_t stream, const alpgpu_column* col) {
 void launch_k_encode_lean(hipStream_t stream, unsigned n_tiles, const double* d_in, const alpgpu_column* col, uint64_t* d_workspace, uint64_t first, uint64_t n_launch,
                           uint32_t spin_limit, uint32_t async_states, bool unordered); // encode_lean_kernels.hip
 int launch_encode_fused_range(hipStream_t stream, const double* d_in, const alpgpu_column* col, uint64_t* d_workspace, uint64_t v_first, uint64_t n_range,
-                              bool force_stall, bool async_states, hipEvent_t async_join, hipEvent_t async_head, int kernel) {
+                              bool force_stall, bool async_states, hipEvent_t async_join, hipEvent_t async_head, bool unordered) {
 	for (uint64_t first = v_first; first < v_first + n_range; first += kFusedMaxVectors) {
 		const uint64_t left     = v_first + n_range - first;
 		const uint64_t n_launch = left < kFusedMaxVectors ? left : kFusedMaxVectors;
@@ -636,15 +352,8 @@ int launch_encode_fused_range(hipStream_t stream, const double* d_in, const alpg
 		if (async_states && first == v_first && async_head != nullptr) { // the head of the search (side stream) is what the first tiles need
 			if (hipStreamWaitEvent(stream, async_head, 0) != hipSuccess) { return ALPGPU_ERR_HIP; }
 		}
-		const bool      unordered = kernel == (ALPGPU_ENCODE_KERNEL_LEAN | kEncodeUnorderedFlag); // (the lean kernel only; force_stall has nothing to stall there)
-		const uint64_t* reserve   = unordered ? d_workspace + lookback_words(n_tiles) : nullptr;
-		if ((kernel & ~kEncodeUnorderedFlag) == ALPGPU_ENCODE_KERNEL_LEAN) {
-			launch_k_encode_lean(stream, static_cast<unsigned>(n_tiles), d_in, col, d_workspace, first, n_launch, force_stall ? 0u : kSpinLimit, async_states ? 1u : 0u, unordered);
-		} else {
-			hipLaunchKernelGGL(k_encode_fused, dim3(static_cast<unsigned>(n_tiles)), dim3(64 * kFusedWaves), 0, stream, d_in, col->d_rowgroups,
-			                   col->d_vectors, col->d_packed, col->d_exc, d_workspace, col->d_totals, col->packed_capacity, col->exc_capacity, first,
-			                   n_launch, col->d_rd_order, force_stall ? 0u : kSpinLimit, async_states ? 1u : 0u);
-		}
+		const uint64_t* reserve = unordered ? d_workspace + lookback_words(n_tiles) : nullptr; // (force_stall has nothing to stall in the unordered form)
+		launch_k_encode_lean(stream, static_cast<unsigned>(n_tiles), d_in, col, d_workspace, first, n_launch, force_stall ? 0u : kSpinLimit, async_states ? 1u : 0u, unordered);
 		const bool last = first + n_launch >= v_first + n_range;
 		if (async_states && last) {
 			if (hipStreamWaitEvent(stream, async_join, 0) != hipSuccess) { return ALPGPU_ERR_HIP; }
@@ -657,9 +366,9 @@ int launch_encode_fused_range(hipStream_t stream, const double* d_in, const alpg
 }
 
 int launch_encode_fused(hipStream_t stream, const double* d_in, uint64_t n_vectors, const alpgpu_column* col, uint64_t* d_workspace, bool force_stall,
-                        bool async_states, hipEvent_t async_join, hipEvent_t async_head, int kernel) {
+                        bool async_states, hipEvent_t async_join, hipEvent_t async_head, bool unordered) {
 	if (launch_encode_reset_totals(stream, col) != ALPGPU_OK) { return ALPGPU_ERR_HIP; }
-	return launch_encode_fused_range(stream, d_in, col, d_workspace, 0, n_vectors, force_stall, async_states, async_join, async_head, kernel);
+	return launch_encode_fused_range(stream, d_in, col, d_workspace, 0, n_vectors, force_stall, async_states, async_join, async_head, unordered);
 }
 
 // the scan of the two-pass form (shared with the float column kernels): descriptor sizes -> offsets, totals, overflow flag

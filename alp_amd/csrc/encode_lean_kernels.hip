@@ -1,6 +1,6 @@
 // encode_lean_kernels.hip — the single-pass column encode (double) in the shape that keeps THREE tiles of eight vectors resident per CU.
 //
-// Same reference functions, same bytes and the same ordered-offset machinery as k_encode_fused (encode_kernels.hip; file:line relative to
+// Same reference functions, same bytes and the same ordered-offset machinery as the classic k_encode_fused it replaced (encode_kernels.hip until the variants were pruned; file:line relative to
 // /root/reference: encoder.hpp:241-305 second-level sampling, :307-400 encode_simdized, :109-120 analyze_ffor,
 // src/fastlanes_generated_ffor.cpp:7379-29749 ffor u64, :357-1775 ffor u16, rd.hpp:109-147 rd_encoder::encode).  What differs is what a
 // wavefront HOLDS while it lives (residency is capped by the tile's 66 KiB of LDS as much as by its 97 VGPRs):
@@ -16,31 +16,15 @@
 //                                                                persistent rowgroup search's one (6 x 72 + 64 <= 512 registers, 3 x 48.2 + 14 KiB LDS)
 //
 // A vector whose exception record does not fit behind its image (more than ~200 exceptions on a 32-bit vector) writes the record from its
-// registers after the wait, as the two-pass form does.  Selected by ALPGPU_OPT_ENCODE_KERNEL (include/alpgpu.h); DESIGN.md §3.2 has the numbers.
+// registers after the wait, as the two-pass form does.  DESIGN.md §3.2 has the numbers.
 #include "encode_device.hpp"
 #include "encode_lookback.hpp"
 #include "launch.hpp"
 
 namespace alpgpu {
 
-#ifndef ALPGPU_ENC_PRIO
-#define ALPGPU_ENC_PRIO 1 // issue priority over the search workgroup that shares the CU: 1 and 2 alike on ALP columns (3.01 / 3.02 ms), 1 better on ALP_RD columns, whose search paces the encode (4.43 against 4.58 ms); 0: 3.16 / 4.46
-#endif
-#ifndef ALPGPU_LEAN_OCC
-#define ALPGPU_LEAN_OCC 6 // __launch_bounds__ second argument (wavefronts per SIMD the register budget must admit): 6 -> <= 80 VGPRs (what three 48 KiB tiles per CU need), 7 -> <= 72, 8 -> <= 64
-#endif
-
-// Measurement builds (-DALPGPU_LEAN_STOP_AT=n): every wavefront ends behind stage n with ONE store that depends on what the stage produced, so the
-// counters of successive builds (tools/pmc_busy.sh) difference into instructions per stage.  The column such a build writes is garbage.
-#ifdef ALPGPU_LEAN_STOP_AT
-#define ALPGPU_LEAN_STOP(n, expr)                                             \
-	if (ALPGPU_LEAN_STOP_AT == (n)) {                                         \
-		if (lane == 0) { LEAN_ARG_DESCS[v_read].base = static_cast<int64_t>(expr); }   \
-		return;                                                               \
-	}
-#else
-#define ALPGPU_LEAN_STOP(n, expr)
-#endif
+constexpr int kEncPrio = 1; // issue priority over the search workgroup that shares the CU: 1 and 2 alike on ALP columns (3.01 / 3.02 ms), 1 better on ALP_RD columns, whose search paces the encode (4.43 against 4.58 ms); 0: 3.16 / 4.46
+constexpr int kLeanOcc = 6; // __launch_bounds__ second argument (wavefronts per SIMD the register budget must admit): 6 -> <= 80 VGPRs (what three 48 KiB tiles per CU need), 7 -> <= 72, 8 -> <= 64
 
 constexpr int kLeanImageWords = 32;                    // stream words per column pair that fit the image
 constexpr int kLeanImageBytes = 128 * kLeanImageWords; // 4 KiB
@@ -87,7 +71,7 @@ __device__ __forceinline__ void lean_analyze_alp(const VecIn& in, int e, int f, 
 	R.wide_steps         = 0;
 	const double qnan    = __longlong_as_double(0x7FF8000000000000ll);
 	double       rmin = qnan, rmax = qnan;
-	constexpr int kGroup = ALPGPU_ENCODE_GROUP;
+	constexpr int kGroup = kEncodeGroup;
 #pragma unroll
 	for (int m0 = 0; m0 < 8; m0 += kGroup) {
 		double   vv[kGroup][2], rr[kGroup][2], dec[kGroup][2];
@@ -138,11 +122,6 @@ __device__ __forceinline__ void lean_analyze_alp(const VecIn& in, int e, int f, 
 			}
 		}
 	}
-#if defined(ALPGPU_LEAN_STOP_AT) && ALPGPU_LEAN_STOP_AT == 3
-	R.base = __double_as_longlong(rmin) ^ __double_as_longlong(rmax) ^ static_cast<int64_t>(R.ballot[0][0] ^ R.ballot[7][1] ^ R.ballot[3][0] ^ R.ballot[5][1]);
-	R.filler = 0, R.bw = R.cnt;
-	return;
-#endif
 	// filler = encoded value at the first non-exception position p (encoder.hpp:382-388); 0 when there is none or when p == 1023
 	int64_t      filler  = 0;
 	bool         found   = false;
@@ -333,33 +312,18 @@ __device__ __forceinline__ void lean_pack_rd(uint64_t* image, const VecIn& x, in
 __device__ __forceinline__ void lean_store_image(const uint64_t* image, int n_units, ull2v* __restrict__ out, int lane) {
 	const ull2v*  img2 = reinterpret_cast<const ull2v*>(image);
 	constexpr int kT   = kLeanImageBytes / 1024;
-#ifdef ALPGPU_LEAN_STORES_ONE_BY_ONE // (A/B: the form until late in round 5)
-#pragma unroll
-	for (int t = 0; t < kT; ++t) {
-		const int u = lane + 64 * t;
-		if (64 * t < n_units && u < n_units) { __builtin_nontemporal_store(img2[u], out + u); }
-	}
-#else
 	ull2v r[kT];
 #pragma unroll
 	for (int t = 0; t < kT; ++t) { r[t] = img2[lane + 64 * t]; } // (inside the image whatever n_units is)
 #pragma unroll
 	for (int t = 0; t < kT; ++t) {
 		const int u = lane + 64 * t;
-#ifdef ALPGPU_LEAN_PLAIN_STORES // (A/B: until late in round 4 the lean kernel wrote its packed words with plain stores)
-		if (64 * t < n_units && u < n_units) { out[u] = r[t]; }
-#else
 		if (64 * t < n_units && u < n_units) { __builtin_nontemporal_store(r[t], out + u); } // written once, read by nobody on this device soon
-#endif
 	}
-#endif
 }
 
 // The five arguments needed only behind the wait are read from the kernarg segment where they are used (alp_device.hpp: late_kernel_arg):
-// v_writelane 46 -> 24 and 1034 -> 981 vector instructions per vector (-DALPGPU_LEAN_ARGS_AT_ENTRY: the old form).
-#ifndef ALPGPU_LEAN_ARGS_AT_ENTRY
-#define ALPGPU_LEAN_LATE_ARGS 1
-#endif
+// v_writelane 46 -> 24 and 1034 -> 981 vector instructions per vector against reading them at entry.
 
 // UNORDERED (ALPGPU_OPT_ENCODE_UNORDERED, round 5): the tile does not wait for its predecessors' sizes.  Its last-arriving wavefront reserves the
 // tile's packed / exception bytes with ONE agent-scope atomic add on a counter word behind the status words (same packing as a status word, so
@@ -368,26 +332,13 @@ __device__ __forceinline__ void lean_store_image(const uint64_t* image, int n_un
 // instead of vector order (the eight vectors of a tile stay together, in order).  A decoder never notices: descriptors carry offsets.
 // (the first nine parameters are read by offset — alp_device.hpp: kArgDescs .. kArgExcCap — keep their order and types)
 template <bool UNORDERED>
-__global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_lean(const double* __restrict__ in, const alpgpu_rowgroup_state* __restrict__ rgs,
+__global__ __launch_bounds__(64 * kFusedWaves, kLeanOcc) void k_encode_lean(const double* __restrict__ in, const alpgpu_rowgroup_state* __restrict__ rgs,
                                                                                     alpgpu_vector_desc* __restrict__ descs_entry, uint8_t* __restrict__ packed_entry,
                                                                                     uint8_t* __restrict__ excs_entry, uint64_t* __restrict__ status, uint64_t* __restrict__ totals,
                                                                                     uint64_t packed_capacity_entry, uint64_t exc_capacity_entry, uint64_t v_first, uint64_t n_vectors_launch,
                                                                                     const uint16_t* __restrict__ rd_order, uint32_t spin_limit, uint32_t async_states) {
-	__builtin_amdgcn_s_setprio(ALPGPU_ENC_PRIO);
-#ifdef ALPGPU_LEAN_LATE_ARGS
-	(void)descs_entry, (void)packed_entry, (void)excs_entry, (void)packed_capacity_entry, (void)exc_capacity_entry;
-#define LEAN_ARG_DESCS late_kernel_arg<alpgpu_vector_desc*>(kArgDescs)
-#define LEAN_ARG_PACKED late_kernel_arg<uint8_t*>(kArgPacked)
-#define LEAN_ARG_EXCS late_kernel_arg<uint8_t*>(kArgExcs)
-#define LEAN_ARG_PACKED_CAP late_kernel_arg<uint64_t>(kArgPackedCap)
-#define LEAN_ARG_EXC_CAP late_kernel_arg<uint64_t>(kArgExcCap)
-#else
-#define LEAN_ARG_DESCS descs_entry
-#define LEAN_ARG_PACKED packed_entry
-#define LEAN_ARG_EXCS excs_entry
-#define LEAN_ARG_PACKED_CAP packed_capacity_entry
-#define LEAN_ARG_EXC_CAP exc_capacity_entry
-#endif
+	__builtin_amdgcn_s_setprio(kEncPrio);
+	(void)descs_entry, (void)packed_entry, (void)excs_entry, (void)packed_capacity_entry, (void)exc_capacity_entry; // (read late: see above)
 	__shared__ LeanLds  lds[kFusedWaves];
 	__shared__ uint64_t s_size[kFusedWaves];
 	__shared__ uint64_t s_excl;
@@ -396,14 +347,6 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 	const int           lane = lane_id();
 	const int           wave = wave_in_wg();
 	const uint64_t      tile = blockIdx.x;
-#ifdef ALPGPU_LEAN_INIT_BARRIER_FIRST // (A/B: until late in round 4 the tile's two LDS words were set, and waited for, in front of the loads)
-	if (threadIdx.x == 0) {
-		s_count = 0;
-		s_ready = 0;
-		s_excl  = ~0ull;
-	}
-	__syncthreads();
-#endif
 
 	uint64_t*      buf  = lds[wave].buf;
 	const uint64_t vl   = tile * kFusedWaves + wave;
@@ -416,25 +359,7 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 	// The input is read once and the packed words are written once: both non-temporal (round 4: 3.02 -> 2.91 ms per 1 Mi vectors on the mixed
 	// column with both, 2.95 with the stores alone) — except the input of wavefront 0, which reads its vector a second time when it is wider
 	// than the image (every ALP_RD vector) and should find it in the L2 / Infinity Cache then (all loads non-temporal: ALP_RD column 4.28 -> 4.41 ms).
-#ifdef ALPGPU_LEAN_PREFETCH_TILES
-	// Experiment: one 4-byte read per 128-byte line of the vector a wavefront ALPGPU_LEAN_PREFETCH_TILES tiles further on will load (about one
-	// wavefront's life later): the line is then in the memory-side cache, a shorter trip than HBM under load.  Issued in front of this
-	// wavefront's own loads and "used" right behind them, so that its register lives through the load phase only.
-	uint32_t pf_word = 0;
-	{
-		const uint64_t vp = vl + static_cast<uint64_t>(ALPGPU_LEAN_PREFETCH_TILES) * kFusedWaves;
-		if (vp < n_vectors_launch) { pf_word = *reinterpret_cast<const volatile uint32_t*>(reinterpret_cast<const uint8_t*>(in + (v_first + vp) * kVec) + 128 * lane); }
-	}
-#endif
-#ifdef ALPGPU_LEAN_PLAIN_LOADS
-	const VecIn                  x        = load_vector(in, v_read, lane);
-#else
 	const VecIn                  x        = load_vector_policy(in, v_read, lane, wave != 0);
-#endif
-#ifdef ALPGPU_LEAN_PREFETCH_TILES
-	asm volatile("" ::"v"(pf_word));
-#endif
-#ifndef ALPGPU_LEAN_INIT_BARRIER_FIRST
 	// the tile's two LDS words, set behind the ISSUE of the loads: the barrier that publishes them falls into the shadow of the input's round trip
 	// (no wavefront touches them before its analysis is done).  s_excl starts as "stalled": should wavefront 0 give up on the rowgroup's state and
 	// leave, it never runs the look-back, and the wavefronts the barrier below then releases must find ~0 there, not an earlier workgroup's
@@ -445,14 +370,12 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 		s_excl  = ~0ull;
 	}
 	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // not __syncthreads(): its fence would wait for the loads in flight
-#endif
 	bool                         state_ok = true;
 	const alpgpu_rowgroup_state  st       = async_states ? rowgroup_state_poll_finish(rgp, st_word, lane, spin_limit >> 4, state_ok) : unpack_rowgroup_state(st_word);
 	if (!state_ok) { // wave-uniform
 		if (lane == 0) { status_store(totals + 3, 1ull); }
 		return;
 	}
-	ALPGPU_LEAN_STOP(1, __double_as_longlong(x.x[0].x + x.x[7].y) + st.k);
 	alpgpu_vector_desc d;
 	d.packed_off = d.exc_off = 0;
 	d.base                   = 0;
@@ -471,20 +394,14 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 		d.scheme = st.scheme;
 		if (st.scheme == ALPGPU_SCHEME_ALP) {
 			int e, f;
-#ifdef ALPGPU_LEAN_NO_SECOND
-			if (false) {
-#else
 			if (st.k > 1) {
-#endif
 				second_level_select(x, &st, reinterpret_cast<double*>(buf), lane, e, f);
 			} else {
 				e = st.combos[0];
 				f = st.combos[1];
 			}
-			ALPGPU_LEAN_STOP(2, e * 32 + f);
 			LeanAlp R;
 			lean_analyze_alp(x, e, f, lane, R);
-			ALPGPU_LEAN_STOP(3, R.base + R.bw);
 			d.base = R.base, d.bw = static_cast<uint8_t>(R.bw), d.e = static_cast<uint8_t>(e), d.f = static_cast<uint8_t>(f);
 			cnt             = R.cnt;
 			wide_steps      = R.wide_steps;
@@ -495,7 +412,6 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 #pragma unroll
 			for (int m = 0; m < 8; ++m) { ballots[m][0] = R.ballot[m][0], ballots[m][1] = R.ballot[m][1]; }
 		} else {
-#ifndef ALPGPU_LEAN_NO_RD
 			LeanRd R;
 			lean_analyze_rd(x, st, lane, R, rd_order ? rd_order + (v / kRowgroup) * ALPGPU_RD_ORDER_STRIDE : nullptr, async_states != 0);
 			d.bw = st.rd_rbw, d.lbw = st.rd_lbw;
@@ -503,11 +419,9 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 			acc0 = R.acc0, acc1 = R.acc1;
 #pragma unroll
 			for (int m = 0; m < 8; ++m) { ballots[m][0] = R.ballot[m][0], ballots[m][1] = R.ballot[m][1]; }
-#endif
 		}
 		d.exc_cnt = static_cast<uint16_t>(cnt);
 	}
-	ALPGPU_LEAN_STOP(4, d.base + d.bw + cnt + static_cast<int64_t>(fill_minus_base ^ ballots[0][0] ^ ballots[7][1] ^ ballots[2][1] ^ ballots[5][0]) + wide_steps);
 	uint64_t my_p = 0, my_e = 0; // bytes
 	if (live) { record_sizes<8>(d, my_p, my_e); }
 	uint64_t reserved = ~0ull; // UNORDERED: the tile's exclusive prefix, in the lane that asked for it
@@ -529,12 +443,6 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 	}
 	const uint64_t base_p = totals[0], base_e = totals[1];
 
-	ALPGPU_LEAN_STOP(5, base_p + base_e + my_p + my_e);
-	LookbackFirst look_first {0, 0};
-	(void)look_first;
-#ifdef ALPGPU_LEAN_LOOK_AHEAD_EARLY // experiment: in front of the pack already (the predecessors are mostly not there yet)
-	if (wave == 0) { look_first = tile_lookback_begin(tile, status, lane); }
-#endif
 	// ---- pack (first window) and exception record: both into LDS, neither depends on where it will be stored ----
 	const bool alp = d.scheme == ALPGPU_SCHEME_ALP;
 	const int  bw  = d.bw;
@@ -546,7 +454,6 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 	// the same image.
 	const int  words_a = bw < kLeanImageWords ? bw : kLeanImageWords; // stream words per column pair in the first window
 	const bool wide_v  = bw > kLeanImageWords;                         // wave-uniform
-#ifndef ALPGPU_LEAN_NO_PACK
 	if (alp) {
 		if (!wide_v) {
 			lean_pack_alp<false>(buf, x, A, ballots, bw, 0, words_a, lane);
@@ -556,25 +463,13 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 	} else {
 		lean_pack_rd(buf, x, bw, 0, words_a, lane);
 	}
-#endif
-	ALPGPU_LEAN_STOP(6, buf[lane] + base_p);
-	// Experiment (-DALPGPU_LEAN_LOOK_AHEAD): wavefront 0 asks for the status words of its look-back HERE, the exception record's stage below being
-	// about one trip across the fabric long.  Measured: 3.04-3.09 ms against 2.90-2.95 without (mixed column) — the predecessors are in the same
-	// stage at the same time, the early words are mostly not there yet and the round is simply spent twice.
-#if defined(ALPGPU_LEAN_LOOK_AHEAD) && !defined(ALPGPU_LEAN_LOOK_AHEAD_EARLY)
-	if (wave == 0) { look_first = tile_lookback_begin(tile, status, lane); }
-#endif
 	// exception record: cnt x value (8 B original bits, or the 2 B left part of an ALP_RD exception), then cnt x u16 position, pad zero; staged
 	// behind the image when it fits there, else written from the registers after the wait
 	const uint32_t rec_off    = static_cast<uint32_t>(128 * words_a);
 	const bool     rec_staged = my_e <= kLeanBufBytes - rec_off;
 	const uint32_t val_bytes  = alp ? 8u * static_cast<uint32_t>(cnt) : 2u * static_cast<uint32_t>(cnt);
 	uint8_t*       img        = reinterpret_cast<uint8_t*>(buf) + rec_off;
-#ifdef ALPGPU_LEAN_NO_EXC
-	if (false) {
-#else
 	if (cnt > 0 && rec_staged) {
-#endif
 		if (lane == 0) { reinterpret_cast<uint64_t*>(img)[(my_e >> 3) - 1] = 0ull; } // the pad lives in the last word
 		wave_lds_sync();
 		for_each_exception(ballots, lane, [&](int r, int m, int j) {
@@ -589,33 +484,17 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 		wave_lds_sync();
 	}
 
-	ALPGPU_LEAN_STOP(7, buf[lane] + buf[600 + lane] + base_p);
 	// ---- the ordered offset ----
 	// Wavefront 0 finds the tile's offset; the others have nothing left to do but their stores, so they PARK at a workgroup barrier until it
-	// arrives there too (k_encode_fused keeps its workers spinning on an LDS word: they used to pack meanwhile; here a spinning worker would
+	// arrives there too (k_encode_fused kept its workers spinning on an LDS word: they used to pack meanwhile; here a spinning worker would
 	// only take issue slots from the five other wavefronts of its SIMD — measured: with the pack or the record removed the kernel got SLOWER,
 	// its wavefronts reached the spin earlier).  A wavefront that ended early (a stall) does not take part in the barrier any more.
-#ifdef ALPGPU_LEAN_SPIN_WAIT
-	if (wave == 0) { tile_lookback(tile, status, totals, s_size, &s_count, &s_excl, &s_ready, lane, spin_limit); }
-	{
-		uint32_t spins = 0;
-		while (__hip_atomic_load(&s_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
-			if (++spins > 64u * kSpinLimit) { return; }
-			__builtin_amdgcn_s_sleep(ALPGPU_LEAN_SPIN_WAIT);
-		}
-	}
-#else
-#if defined(ALPGPU_LEAN_LOOK_AHEAD) || defined(ALPGPU_LEAN_LOOK_AHEAD_EARLY)
-	if (wave == 0) { tile_lookback(tile, status, totals, s_size, &s_count, &s_excl, &s_ready, lane, spin_limit, &look_first); }
-#else
 	if constexpr (UNORDERED) {
 		if (reserver) { s_excl = reserved; } // (one lane of one wavefront; every wavefront of the tile had posted its size when it asked)
 	} else {
 		if (wave == 0) { tile_lookback(tile, status, totals, s_size, &s_count, &s_excl, &s_ready, lane, spin_limit); }
 	}
-#endif
 	__syncthreads();
-#endif
 	// sizes posted by the tile's earlier wavefronts: lane w < wave takes s_size[w], one DPP tree (both 31-bit fields stay apart: no carry between them)
 	const uint64_t mine_sz = lane < wave ? s_size[lane & (kFusedWaves - 1)] : 0ull;
 	const uint64_t local   = wave_sum_u64(mine_sz);
@@ -625,16 +504,15 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 	d.packed_off       = base_p + ((pre >> 31) & 0x7FFFFFFFull) * 128ull;
 	d.exc_off          = base_e + (pre & 0x7FFFFFFFull) * 8ull;
 	if (!live) { return; }
-	if (d.packed_off + my_p > LEAN_ARG_PACKED_CAP || d.exc_off + my_e > LEAN_ARG_EXC_CAP) {
+	if (d.packed_off + my_p > late_kernel_arg<uint64_t>(kArgPackedCap) || d.exc_off + my_e > late_kernel_arg<uint64_t>(kArgExcCap)) {
 		if (lane == 0) {
 			__hip_atomic_store(totals + 2, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			LEAN_ARG_DESCS[v] = empty_descriptor();
+			late_kernel_arg<alpgpu_vector_desc*>(kArgDescs)[v] = empty_descriptor();
 		}
 		return;
 	}
-	ALPGPU_LEAN_STOP(8, d.packed_off + d.exc_off + buf[lane]);
-	uint8_t* dst = LEAN_ARG_PACKED + d.packed_off;
-	uint8_t* rec = LEAN_ARG_EXCS + d.exc_off;
+	uint8_t* dst = late_kernel_arg<uint8_t*>(kArgPacked) + d.packed_off;
+	uint8_t* rec = late_kernel_arg<uint8_t*>(kArgExcs) + d.exc_off;
 
 	// ---- stores at the final offsets ----
 	if (cnt > 0) {
@@ -642,11 +520,6 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 			const uint64_t* img64 = reinterpret_cast<const uint64_t*>(img);
 			uint64_t*       rec64 = reinterpret_cast<uint64_t*>(rec);
 			const int       n_w   = static_cast<int>(my_e >> 3);
-#if defined(ALPGPU_LEAN_PLAIN_STORES)
-			for (int w = lane; w < n_w; w += 64) { rec64[w] = img64[w]; }
-#elif defined(ALPGPU_LEAN_STORES_ONE_BY_ONE)
-			for (int w = lane; w < n_w; w += 64) { __builtin_nontemporal_store(img64[w], rec64 + w); }
-#else
 			for (int w0 = 0; w0 < n_w; w0 += 256) { // four words per lane and round in registers of their own (lean_store_image: no store waits for the one before it)
 				uint64_t q[4];
 #pragma unroll
@@ -660,7 +533,6 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 					if (w < n_w) { __builtin_nontemporal_store(q[k], rec64 + w); }
 				}
 			}
-#endif
 		} else { // a record larger than its staging room (rare): the vector is read again and the record written from it (as the two-pass form's pack kernel does)
 			const VecIn xr   = load_vector(in, v, lane);
 			uint16_t*   rpos = reinterpret_cast<uint16_t*>(rec + val_bytes);
@@ -678,7 +550,6 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 		}
 	}
 	lean_store_image(buf, 8 * words_a, reinterpret_cast<ull2v*>(dst), lane);
-#ifndef ALPGPU_LEAN_NO_WIDE
 	if (wide_v) { // words 32.. of every column pair: the image is free again once its reads above are issued (one wavefront's LDS operations run in order)
 		// The input is still in the registers of wavefronts 1..7, which only slept on an LDS word meanwhile; wavefront 0 ran the look-back, whose
 		// registers the input would not fit beside (the budget of three tiles per CU): it reads its vector again (an L2 / Infinity-Cache hit).
@@ -693,14 +564,13 @@ __global__ __launch_bounds__(64 * kFusedWaves, ALPGPU_LEAN_OCC) void k_encode_le
 		}
 		lean_store_image(buf, 8 * words_b, reinterpret_cast<ull2v*>(dst + kLeanImageBytes), lane);
 	}
-#endif
 	if (!alp && lane < 32) {
 		uint32_t* out32 = reinterpret_cast<uint32_t*>(dst + 128ull * d.bw);
 		for (int k = 0; k < d.lbw; ++k) {
 			out32[32 * k + lane] = (static_cast<uint32_t>(acc0 >> (16 * k)) & 0xFFFFu) | ((static_cast<uint32_t>(acc1 >> (16 * k)) & 0xFFFFu) << 16);
 		}
 	}
-	if (lane == 0) { LEAN_ARG_DESCS[v] = d; }
+	if (lane == 0) { late_kernel_arg<alpgpu_vector_desc*>(kArgDescs)[v] = d; }
 }
 
 // the same launch sequence as launch_encode_fused_range (encode_kernels.hip) with the kernel above

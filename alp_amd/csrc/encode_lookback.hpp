@@ -1,7 +1,7 @@
-// encode_lookback.hpp — the ordered-offset machinery of the single-pass encode kernels (double: encode_kernels.hip,
+// encode_lookback.hpp — the ordered-offset machinery of the single-pass encode kernels (double: encode_lean_kernels.hip,
 // float: encode_f32_kernels.hip): one 64-bit status word per tile {flag | packed 128-byte units | exception 8-byte units}
-// and the decoupled look-back that turns the tiles' sizes into vector-order stream offsets.  See the description above
-// k_encode_fused in encode_kernels.hip.
+// and the decoupled look-back that turns the tiles' sizes into vector-order stream offsets.  See the single-pass description
+// above k_fused_finish in encode_kernels.hip.
 #pragma once
 #include "alp_device.hpp"
 
@@ -11,13 +11,8 @@ constexpr uint64_t kFusedMaxVectors = 1ull << 20; // 2^20 vectors * 1280 excepti
 constexpr uint64_t kFlagAggregate   = 1ull << 62;
 constexpr uint64_t kFlagPrefix      = 2ull << 62;
 constexpr uint32_t kSpinLimit       = 1u << 20;
-#ifndef ALPGPU_LOOK_WINDOW
-#define ALPGPU_LOOK_WINDOW 64
-#endif
-#ifndef ALPGPU_LOOK_SLEEP
-#define ALPGPU_LOOK_SLEEP 16 // x64 cycles between polls of a window that still holds an unfinished tile (with 8-vector tiles: 8-24 -> 3.12 ms, 64 -> 3.22)
-#endif
-constexpr int      kLookWindow      = ALPGPU_LOOK_WINDOW; // status words examined per look-back round
+constexpr int      kLookWindow      = 64; // status words examined per look-back round
+constexpr int      kLookSleep       = 16; // x64 cycles between polls of a window that still holds an unfinished tile (with 8-vector tiles: 8-24 -> 3.12 ms, 64 -> 3.22)
 
 __device__ __forceinline__ uint64_t status_pack(uint64_t flag, uint64_t packed_units, uint64_t exc_units) {
 	return flag | (packed_units << 31) | exc_units;
@@ -78,21 +73,12 @@ __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
 // N_SIZES = vectors per tile (entries of s_size); s_count counts the tile's kFusedWaves wavefronts.
 // spin_limit: unsuccessful polls before the tile gives up (kSpinLimit; 0 makes every tile that has to wait give up at once —
 // the debug option that exercises the recovery route).
-// The first round of both levels, issued ahead of time (k_encode_lean: in front of the exception record's stage, whose work then covers the
-// trip across the fabric): the words a tile_lookback would begin with.  Words that are not there yet are simply polled again by tile_lookback.
+// begun: the first round's words of both levels, read ahead of time by the caller.  No caller does any more (a measured loss: issued in front of
+// the exception record's stage, the predecessors' words were mostly not there yet); the parameter stays because the kernels' instructions follow
+// the form of the code below.
 struct LookbackFirst {
 	uint64_t w1, w2;
 };
-__device__ __forceinline__ LookbackFirst tile_lookback_begin(uint64_t tile, const uint64_t* __restrict__ status, int lane) {
-	const uint64_t* bstatus = status + gridDim.x;
-	const uint64_t  block   = tile / kBlockTiles;
-	const int       i       = static_cast<int>(tile % kBlockTiles);
-	LookbackFirst   f;
-	f.w1 = lane < i ? status_load(status + (tile - 1 - lane)) : kFlagAggregate;
-	f.w2 = (block != 0 && static_cast<int64_t>(block) - 1 - lane >= 0) ? status_load(bstatus + (block - 1 - lane)) : kFlagPrefix;
-	return f;
-}
-
 template <int N_SIZES = kFusedWaves>
 __device__ __forceinline__ void tile_lookback(uint64_t tile, uint64_t* __restrict__ status, uint64_t* __restrict__ totals, const uint64_t* s_size,
                                               uint32_t* s_count, uint64_t* s_excl, uint32_t* s_ready, int lane, uint32_t spin_limit = kSpinLimit,
@@ -105,13 +91,6 @@ __device__ __forceinline__ void tile_lookback(uint64_t tile, uint64_t* __restric
 	uint32_t       spins   = 0;
 	// the stall flag of another tile is a far-side read like the status words: looked at every 16th unsuccessful round only
 	auto give_up = [&]() { return ++spins > spin_limit || ((spins & 15u) == 0 && status_load(totals + 3) != 0); };
-#ifdef ALPGPU_ABLATE_LOOKBACK // timing experiment: worst-case strides instead of the scan (the output is NOT compact)
-	if (lane == 0) {
-		*s_excl = status_pack(0, tile * N_SIZES * 66, tile * N_SIZES * 1280);
-		__hip_atomic_store(s_ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-	}
-	return;
-#endif
 
 	// level 1: the sizes of the i predecessors inside this block
 	uint64_t local = 0;
@@ -125,16 +104,9 @@ __device__ __forceinline__ void tile_lookback(uint64_t tile, uint64_t* __restric
 	}
 	bool     fresh1 = true, fresh2 = true;
 	if (i != 0) {
-#ifdef ALPGPU_LOOK_REPOLL_MISSING // experiment (round 5, call 36): a word that has arrived is not read again — tile words are written once.  No difference (2.91-2.98 against 2.89-2.97 ms): off
-		uint64_t st = first1;
-		for (;;) {
-			if (!fresh1 && lane < i && (st >> 62) == 0) { st = status_load(status + (tile - 1 - lane)); }
-			fresh1 = false;
-#else
 		for (;;) {
 			const uint64_t st = fresh1 ? first1 : (lane < i ? status_load(status + (tile - 1 - lane)) : kFlagAggregate);
 			fresh1            = false;
-#endif
 			if (ballot64((st >> 62) == 0) == 0) {
 				local = wave_sum_u64(st & ~(3ull << 62));
 				break;
@@ -143,7 +115,7 @@ __device__ __forceinline__ void tile_lookback(uint64_t tile, uint64_t* __restric
 				stalled = true;
 				break;
 			}
-			__builtin_amdgcn_s_sleep(ALPGPU_LOOK_SLEEP);
+			__builtin_amdgcn_s_sleep(kLookSleep);
 		}
 	}
 	// a closing tile needs its own size as well (LDS only): it publishes the block's aggregate before looking further back
@@ -165,24 +137,9 @@ __device__ __forceinline__ void tile_lookback(uint64_t tile, uint64_t* __restric
 	uint64_t base = 0;
 	if (block != 0 && !stalled) {
 		int64_t look = static_cast<int64_t>(block) - 1; // nearest block not yet accounted for
-#ifdef ALPGPU_LOOK_REPOLL_MISSING
-		uint64_t st      = first2;
-		int64_t  st_look = look; // the window st was read for
-#endif
 		while (look >= 0) {
 			const int64_t  idx        = look - lane;
-#ifdef ALPGPU_LOOK_REPOLL_MISSING
-			if (!fresh2) {
-				if (st_look != look) {
-					st      = idx >= 0 ? status_load(bstatus + idx) : kFlagPrefix;
-					st_look = look;
-				} else if (idx >= 0 && (st >> 62) == 0) {
-					st = status_load(bstatus + idx);
-				}
-			}
-#else
 			const uint64_t st         = fresh2 ? first2 : (idx >= 0 ? status_load(bstatus + idx) : kFlagPrefix);
-#endif
 			fresh2                    = false;
 			const uint64_t fl         = st >> 62;
 			const uint64_t has_prefix = ballot64(fl == 2);
@@ -205,7 +162,7 @@ __device__ __forceinline__ void tile_lookback(uint64_t tile, uint64_t* __restric
 						stalled = true;
 						break;
 					}
-					__builtin_amdgcn_s_sleep(ALPGPU_LOOK_SLEEP);
+					__builtin_amdgcn_s_sleep(kLookSleep);
 					continue;
 				}
 			}

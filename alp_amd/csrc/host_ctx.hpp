@@ -60,29 +60,19 @@ struct alpgpu_ctx {
 	int         n_cus;
 	int         decode_variant;
 	int         decode_auto;     // 1: vectors per decode workgroup chosen from the column's size hints
-	double      decode_four_bits, decode_four_bits_exc; // auto rule: four vectors per workgroup up to this many packed bits per value (without / with exceptions)
-	int         decode_vpw;      // the value last given to ALPGPU_OPT_DECODE_VECTORS_PER_WG (0 auto, 1, 2, 4); float decode reads this
+	int         decode_vpw;      // the value last given to ALPGPU_OPT_DECODE_VECTORS_PER_WG (0 auto, 1, 2, 4, 8, 16-30); float decode reads this
 	char        name[128];
 	uint64_t    hbm_bytes;
 	int         encode_two_pass; // 0 (default): single-pass encode with look-back offsets; 1: analysis + scan + pack
 	int         force_stall;     // debug: the single pass gives up in its look-back, the recovery route re-encodes
-	int         async_init_wg_per_cu; // persistent search workgroups per CU (1; ALPGPU_ASYNC_INIT_WG_PER_CU for experiments)
-	int         async_init_adaptive;  // three per CU when the column's head is mostly ALP_RD (default; ALPGPU_ASYNC_INIT_ADAPTIVE=0 for A/B runs)
 	int         async_init;      // 1 (default): alpgpu_encode_* of a long column runs the rowgroup search BESIDE the vector encode (second stream)
 	hipStream_t init_stream;     // ... on this stream (highest priority: its few workgroups are placed first)
 	hipEvent_t  ev_fork, ev_head, ev_join;
-	int         encode_kernel;   // ALPGPU_ENCODE_KERNEL_LEAN (default) / _CLASSIC
 	int         encode_unordered; // ALPGPU_OPT_ENCODE_UNORDERED: tiles reserve their stream bytes with one atomic add (lean kernel, device columns only)
-	int         decode_pairing;  // ALPGPU_OPT_DECODE_PAIRING: 0 auto, 1..3 -> k_decode_pairs
-	int         decode_pairs_auto; // the auto rule may pick the pair kernel (ALPGPU_DECODE_PAIRS_AUTO=0 for A/B runs)
 	int         decode_pad_kib;    // ALPGPU_OPT_DECODE_RESIDENCY_PAD: KiB of unused dynamic LDS per decode workgroup (-1: chosen from the column's hints)
-	int         decode_patch_max;  // ALPGPU_OPT_DECODE_PATCH_AFTER: ALP vectors with 1..this many exceptions are patched after their stores (0: never; <= 64)
-	int         decode_patch_shape; // 1 (default): a column whose vectors are patched picks its launch shape like a column without exceptions (ALPGPU_DECODE_PATCH_SHAPE=0 for A/B runs)
 	int         read_ahead;        // ALPGPU_OPT_DECODE_READ_AHEAD: the store decode runs with a read-ahead into the Infinity Cache on the second stream (read_ahead_kernels.hip)
 	int         streams_serialize; // the process runs with GPU_MAX_HW_QUEUES=1 / AMD_SERIALIZE_KERNEL / HIP_LAUNCH_BLOCKING: left to itself (-1) the library starts no read-ahead
 	int         read_ahead_us;     // ... this many microseconds ahead of the decode kernel (0: 12 + 6.5 us per packed bit of the vectors, at most 60)
-	int         read_ahead_grid;   // ... by this many eight-wavefront workgroups
-	int         read_ahead_bits;   // ... records of vectors of at most this many packed bits per value (the descriptors of all)
 	uint64_t*   d_progress;        // ... paced by this word of device memory (2 KiB; the map of its words: decode_policy.hpp)
 	uint64_t    progress_gen;      // ... whose tag changes with every launch
 	uint32_t    wall_tick_ps;      // picoseconds per tick of the device's wall_clock64() (the read-ahead's naps)

@@ -23,18 +23,12 @@ namespace alpgpu {
 
 constexpr int kMaxSampledVectors = 9; // ceil(100 / 12)
 constexpr int kInitThreads       = 64 * kMaxSampledVectors;
-#ifndef ALPGPU_INIT_ASYNC_WAVES
-#define ALPGPU_INIT_ASYNC_WAVES 4
-#endif
 // The persistent form beside two encode tiles (2 x 8 wavefronts x 96 VGPRs = 384 of a SIMD's 512 registers, 2 x 66 KiB of LDS): ONE
 // wavefront per SIMD (4 per workgroup).  Measured (profiles/r03_async_init.txt): with the 128 VGPRs that exactly fill the SIMD the
 // workgroup does NOT share the CU with two tiles (the encode beside it ran at half speed), with <= 96 it does; the 7 spilled dwords are
 // outside the sample walk.  8 wavefronts of 64 VGPRs spill into the walk itself.
-constexpr int kInitAsyncWaves        = ALPGPU_INIT_ASYNC_WAVES;
-#ifndef ALPGPU_INIT_ASYNC_OCC
-#define ALPGPU_INIT_ASYNC_OCC (ALPGPU_INIT_ASYNC_WAVES == 4 ? 5 : 8)
-#endif
-constexpr int kInitAsyncWavesPerSimd = ALPGPU_INIT_ASYNC_OCC; // __launch_bounds__ second argument: 4 -> <= 128 VGPRs, 5 -> <= 96, 8 -> <= 64
+constexpr int kInitAsyncWaves        = 4;
+constexpr int kInitAsyncWavesPerSimd = 5; // __launch_bounds__ second argument: 4 -> <= 128 VGPRs, 5 -> <= 96, 8 -> <= 64
 
 // (wave_scan_add_u32: alp_device.hpp)  The cut search below is a chain of dependent scans per 64-sample chunk; as __shfl_up steps
 // (ds_bpermute, one LDS-crossbar round trip each) that chain was the latency that bounded ALP_RD rowgroups.
@@ -153,11 +147,7 @@ __global__ __launch_bounds__(64 * W, (init_waves_per_simd<ASYNC, W, P::kBits>())
 	// encode tiles room on the CU WHEREVER the allocator put it (measured with 26 KiB: placed between two tiles it kept the second tile
 	// out for as long as it lived — the encode ran at half speed beside it).
 	constexpr int kRdScratch = W > 4 ? W : 4;
-#ifdef ALPGPU_EXPERIMENT_INIT_SMALL_LDS // residency experiment: no ALP_RD search, 3 KiB of LDS (ALP-only columns!)
-	__shared__ RdWaveScratch s_rd[1];
-#else
 	__shared__ RdWaveScratch s_rd[kRdScratch];
-#endif
 	__shared__ uint32_t      s_first[kMaxSamples];
 	__shared__ double        s_cut_est[17];
 	__shared__ uint8_t       s_cut_ds[17];
@@ -352,9 +342,6 @@ __global__ __launch_bounds__(64 * W, (init_waves_per_simd<ASYNC, W, P::kBits>())
 	}
 	__syncthreads();
 	if (s_scheme != ALPGPU_SCHEME_ALP_RD) { continue; }
-#ifdef ALPGPU_EXPERIMENT_INIT_SMALL_LDS
-	continue;
-#endif
 
 	// ---- ALP_RD: find the cut and the dictionary (rd.hpp:89-104, :33-87) ----
 	// The samples are sorted ONCE (by their top 16 bits, see rd_left_of); for every cut position the equal left parts are then
@@ -400,17 +387,10 @@ __global__ __launch_bounds__(64 * W, (init_waves_per_simd<ASYNC, W, P::kBits>())
 	}
 	__syncthreads();
 
-#ifdef ALPGPU_EXPERIMENT_RD_STOP_AFTER_SORT // timing experiments (profiles/r04_rd_search.txt): where the ALP_RD half of the search spends its time
-	continue;
-#endif
 	RdWaveScratch& WS = s_rd[wave];
 	// force_rd = 0x100 | cut: rd_encoder::build_left_parts_dictionary for ONE cut position (rd.hpp:33-87, called on its own): the other cuts
 	// get an estimate nothing beats, so the dictionary below is that cut's
-#ifdef ALPGPU_EXPERIMENT_RD_ONE_CUT
-	const int forced_cut = 12;
-#else
 	const int forced_cut = (force_rd & 0x100) ? (force_rd & 0xFF) : 0;
-#endif
 	for (int cut = wave + 1; cut <= 16; cut += W) { // wave-uniform
 		const int rbw = P::kBits - cut;
 		if (forced_cut != 0 && cut != forced_cut) {
@@ -500,9 +480,7 @@ __global__ __launch_bounds__(64 * W, (init_waves_per_simd<ASYNC, W, P::kBits>())
 		}
 		wave_lds_sync();
 		// the reference's order of equally frequent left parts is libstdc++'s (rd_dictionary_order.hpp): replayed by one lane
-#ifndef ALPGPU_EXPERIMENT_SKIP_RD_ORDER
 		if (lane == 0) { rd_reference_order(s_order, distinct); }
-#endif
 		wave_lds_sync();
 		if (rd_order) { // the whole sorted order, for the encoders' exception-slot indices (alpgpu_column.d_rd_order)
 			uint16_t* o = rd_order + rg * ALPGPU_RD_ORDER_STRIDE;
@@ -566,8 +544,7 @@ int launch_rowgroup_init_async(hipStream_t stream, const double* d_in, uint64_t 
 }
 int launch_rowgroup_init_async_f32(hipStream_t stream, const float* d_in, uint64_t n_vectors, alpgpu_rowgroup_state* d_rgs, uint16_t* d_rd_order, uint64_t rg_first,
                                    uint64_t rg_count, int grid) {
-	static const bool tile = std::getenv("ALPGPU_F32_SEARCH_TILE") != nullptr; // A/B: the eight-wavefront (64-register, spilling) form instead of four wavefronts of 96
-	return launch_rowgroup_init_async_t<PrecF32>(stream, d_in, n_vectors, d_rgs, d_rd_order, rg_first, rg_count, grid, tile);
+	return launch_rowgroup_init_async_t<PrecF32>(stream, d_in, n_vectors, d_rgs, d_rd_order, rg_first, rg_count, grid, false); // (four wavefronts of 96 registers)
 }
 
 int launch_state_from_samples(hipStream_t stream, const double* d_samples, uint32_t n_samples, alpgpu_rowgroup_state* d_state, int force_rd, double* d_cut_estimate) {

@@ -12,12 +12,10 @@ namespace alpgpu {
 constexpr int kStateUnpublished = 0xFF;
 
 // decode_kernels.hip
-// patch_max: ALP vectors with 1..patch_max (<= 64) exceptions are decoded without any per-value lookup and patched after their stores (0: never)
 // progress (nullable): a word of device memory the kernel's workgroups report their position to, tagged (read_ahead_kernels.hip)
 // gate (unhinted decode, api_decode.hip): != 0 -> the launch runs only if the context's shape word (progress[kCtxWordShape], decode_policy.hpp) holds this value
-int launch_decode_column(hipStream_t stream, const alpgpu_column* col, double* d_out, int variant, int n_cus, uint32_t patch_max, uint64_t* progress = nullptr,
-                         uint64_t progress_tag = 0, uint32_t gate = 0);
-bool decode_patch_arm_compiled();
+int launch_decode_column(hipStream_t stream, const alpgpu_column* col, double* d_out, int variant, int n_cus, uint64_t* progress = nullptr, uint64_t progress_tag = 0,
+                         uint32_t gate = 0);
 // read_ahead_kernels.hip: the column's descriptors, packed words and exception records read into the Infinity Cache a bounded distance ahead of the decode
 // kernel that reports to d_progress with this tag (lead_min / lead_max in vectors; value_bytes 8 or 4; grid workgroups of four wavefronts)
 // ps_per_vector: picoseconds the decode needs per vector AT LEAST (the read-ahead's workgroups sleep by it between looks at the progress word);
@@ -61,18 +59,16 @@ int launch_rowgroup_init_async_f32(hipStream_t stream, const float* d_in, uint64
 
 // encode_kernels.hip
 uint64_t encode_workspace_bytes(uint64_t n_vectors);
-// or-ed into `kernel` (lean kernel only): tiles reserve their bytes with one atomic add instead of waiting for their predecessors' sizes
-// (ALPGPU_OPT_ENCODE_UNORDERED; encode_lean_kernels.hip)
-constexpr int kEncodeUnorderedFlag = 0x100;
-// single pass (force_stall: debug, every look-back that has to wait gives up — exercises the recovery route)
-// kernel: ALPGPU_ENCODE_KERNEL_LEAN (encode_lean_kernels.hip: 6 KiB of LDS and <= 72 VGPRs per wavefront, three tiles per CU) or _CLASSIC (k_encode_fused)
+// single pass, k_encode_lean (encode_lean_kernels.hip: 6 KiB of LDS and <= 72 VGPRs per wavefront, three tiles per CU; force_stall: debug, every look-back
+// that has to wait gives up — exercises the recovery route).  unordered: tiles reserve their bytes with one atomic add instead of waiting for their
+// predecessors' sizes (ALPGPU_OPT_ENCODE_UNORDERED)
 int launch_encode_fused(hipStream_t stream, const double* d_in, uint64_t n_vectors, const alpgpu_column* col, uint64_t* d_workspace, bool force_stall = false,
-                        bool async_states = false, hipEvent_t async_join = nullptr, hipEvent_t async_head = nullptr, int kernel = ALPGPU_ENCODE_KERNEL_LEAN);
+                        bool async_states = false, hipEvent_t async_join = nullptr, hipEvent_t async_head = nullptr, bool unordered = false);
 // pieces of the above for a caller that interleaves other work: zero d_totals, then vector ranges in ascending order
 int launch_encode_reset_totals(hipStream_t stream, const alpgpu_column* col);
 int launch_encode_fused_range(hipStream_t stream, const double* d_in, const alpgpu_column* col, uint64_t* d_workspace, uint64_t v_first, uint64_t n_range,
                               bool force_stall = false, bool async_states = false, hipEvent_t async_join = nullptr, hipEvent_t async_head = nullptr,
-                              int kernel = ALPGPU_ENCODE_KERNEL_LEAN);
+                              bool unordered = false);
 // two pass; gate = nullptr: unconditionally, else a device word that must be non-zero for the kernels to do anything (d_totals + 6)
 int launch_encode_vectors(hipStream_t stream, const double* d_in, uint64_t n_vectors, const alpgpu_column* col, uint64_t* d_workspace,
                           int n_cus, const uint64_t* gate = nullptr);

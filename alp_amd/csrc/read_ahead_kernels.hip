@@ -20,10 +20,7 @@
 
 namespace alpgpu {
 
-#ifndef ALPGPU_AHEAD_WAVES
-#define ALPGPU_AHEAD_WAVES 8
-#endif
-constexpr int      kAheadWaves  = ALPGPU_AHEAD_WAVES; // wavefronts per read-ahead workgroup (few, fat workgroups: one lane of each polls)
+constexpr int      kAheadWaves  = 8; // wavefronts per read-ahead workgroup (few, fat workgroups: one lane of each polls)
 constexpr int      kAheadUnroll = 16;       // 16-byte loads in flight per lane and round (16 KiB per wavefront)
 constexpr uint64_t kAheadVecMask = (1ull << 40) - 1ull;
 // Patience (round 6): how long a workgroup goes without news from the decode before it leaves.  Until round 5 a flat 50 ms — wherever
@@ -72,9 +69,9 @@ __device__ __forceinline__ uint32_t touch_span(const uint8_t* __restrict__ strea
 	return x;
 }
 
-// mode (experiments, ALPGPU_READ_AHEAD_MODE): bit 0 = pace only, read nothing; bit 1 = read without pacing; bit 2 = sleep ~1.5 ms and leave; bit 4 = the lead stays as given
-// mode bit 3 (set by the launcher, not an experiment): the lead, the pace and the widest record come from the context's plan words (decode_policy.hpp: an UNHINTED
-// decode, whose sizes were summed on this stream a moment ago; a lead of 0 there = this column gets no read-ahead: leave)
+// mode bit 3: the lead, the pace and the widest record come from the context's plan words (decode_policy.hpp: an UNHINTED decode, whose sizes were summed on
+// this stream a moment ago; a lead of 0 there = this column gets no read-ahead: leave).  Bit 4 (always set by the launcher): the lead stays as given.
+// Bits 0-2 (pace only / read without pacing / sleep ~1.5 ms and leave) and burst_ticks != 0 are measurement arms the launcher never asks for.
 template <int VALUE_BYTES>
 __global__ __launch_bounds__(64 * kAheadWaves) void k_read_ahead(const alpgpu_vector_desc* __restrict__ descs, const uint8_t* __restrict__ packed,
                                                                 const uint8_t* __restrict__ excs, uint64_t n_vectors, uint64_t* __restrict__ ctx_words,
@@ -89,7 +86,7 @@ __global__ __launch_bounds__(64 * kAheadWaves) void k_read_ahead(const alpgpu_ve
 	uint32_t*       hole     = reinterpret_cast<uint32_t*>(ctx_words + kCtxWordHole);
 	const int      lane  = lane_id();
 	const int      wave  = wave_in_wg();
-	if (mode & 4u) { // experiment: resident for ~1.5 ms, touching nothing
+	if (mode & 4u) { // (measurement arm: resident for ~1.5 ms, touching nothing)
 		for (int k = 0; k < 440; ++k) { __builtin_amdgcn_s_sleep(127); }
 		return;
 	}
@@ -132,8 +129,8 @@ __global__ __launch_bounds__(64 * kAheadWaves) void k_read_ahead(const alpgpu_ve
 					const uint64_t until = wall_clock64() + ticks;
 					while (wall_clock64() < until) { __builtin_amdgcn_s_sleep(32); }
 				}
-				// experiment (ALPGPU_READ_AHEAD_BURST_US): every workgroup's reads go out on the same beat of the device's wall clock — the memory controllers see reads in
-				// bursts between the decode's writes instead of one here, one there (each of which turns a channel around on its own)
+				// (burst_ticks, a measurement arm: every workgroup's reads go out on the same beat of the device's wall clock — the memory controllers see reads in
+				// bursts between the decode's writes instead of one here, one there)
 				if (go && burst_ticks != 0) {
 					while (wall_clock64() % burst_ticks > burst_ticks / 8) { __builtin_amdgcn_s_sleep(8); }
 				}
@@ -191,24 +188,20 @@ __global__ __launch_bounds__(64 * kAheadWaves) void k_read_ahead(const alpgpu_ve
 int launch_read_ahead(hipStream_t stream, const alpgpu_column* col, int value_bytes, uint64_t* d_ctx_words, uint64_t tag, uint32_t lead_min, uint32_t lead_max,
                       uint32_t ps_per_vector, uint32_t ps_per_tick, uint32_t max_bits, int grid, bool from_plan) {
 	if (col->n_vectors == 0 || grid <= 0) { return ALPGPU_OK; }
-	static const uint32_t env_mode = std::getenv("ALPGPU_READ_AHEAD_MODE") ? static_cast<uint32_t>(std::atoi(std::getenv("ALPGPU_READ_AHEAD_MODE"))) : 0u;
 	// (the self-stretching lead: built, measured — call 1b: +4-5 points where the lead is 20-30 % short, nothing where it is half, -1.5 % at the shipped lead on columns with
-	//  exceptions — and OFF unless ALPGPU_READ_AHEAD_ADAPT=1: profiles/r06_decode_policy.txt)
-	static const bool     no_adapt = !(std::getenv("ALPGPU_READ_AHEAD_ADAPT") && std::atoi(std::getenv("ALPGPU_READ_AHEAD_ADAPT")) != 0);
-	const uint32_t mode = (env_mode & ~8u) | (from_plan ? 8u : 0u) | (no_adapt ? 16u : 0u);
+	//  exceptions — and OFF: mode bit 4, profiles/r06_decode_policy.txt)
+	const uint32_t mode = (from_plan ? 8u : 0u) | 16u;
 	// patience: see above.  The decode's duration at the full HBM rate (ps_per_vector), in ticks
 	const uint64_t est   = col->n_vectors * static_cast<uint64_t>(ps_per_vector) / (ps_per_tick ? ps_per_tick : 1u);
 	const uint64_t floor_t = 200000000ull / (ps_per_tick ? ps_per_tick : 1u);
 	const uint64_t first = est / 4 > floor_t ? est / 4 : floor_t, steady = 2 * est > floor_t ? 2 * est : floor_t;
 	const uint32_t pf = first > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(first), ps = steady > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(steady);
-	static const uint32_t burst_us = std::getenv("ALPGPU_READ_AHEAD_BURST_US") ? static_cast<uint32_t>(std::atoi(std::getenv("ALPGPU_READ_AHEAD_BURST_US"))) : 0u;
-	const uint32_t burst = static_cast<uint32_t>(static_cast<uint64_t>(burst_us) * 1000000ull / (ps_per_tick ? ps_per_tick : 1u));
 	if (value_bytes == 8) {
 		hipLaunchKernelGGL((k_read_ahead<8>), dim3(static_cast<unsigned>(grid)), dim3(64 * kAheadWaves), 0, stream, col->d_vectors, col->d_packed, col->d_exc, col->n_vectors,
-		                   d_ctx_words, tag, lead_min, lead_max, ps_per_vector, ps_per_tick, max_bits, mode, pf, ps, burst);
+		                   d_ctx_words, tag, lead_min, lead_max, ps_per_vector, ps_per_tick, max_bits, mode, pf, ps, 0u);
 	} else {
 		hipLaunchKernelGGL((k_read_ahead<4>), dim3(static_cast<unsigned>(grid)), dim3(64 * kAheadWaves), 0, stream, col->d_vectors, col->d_packed, col->d_exc, col->n_vectors,
-		                   d_ctx_words, tag, lead_min, lead_max, ps_per_vector, ps_per_tick, max_bits, mode, pf, ps, burst);
+		                   d_ctx_words, tag, lead_min, lead_max, ps_per_vector, ps_per_tick, max_bits, mode, pf, ps, 0u);
 	}
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }

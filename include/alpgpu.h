@@ -155,8 +155,7 @@ int         alpgpu_synchronize(alpgpu_ctx* ctx);
  * wavefronts several chunks ahead, decoding wavefronts that own whole vectors; the values name chunk size / arena / wavefront counts, 27 = chunks of 12 vectors,
  * 24 KiB of records per chunk, 12 decoding + 2 loading wavefronts, one workgroup per CU).  0 = 2, and 27 for hinted columns of >= 32 768 vectors with more
  * than 1.5 and at most 8.5 packed bits per value and fewer than ~2 exceptions per vector (round 6: 0.65-0.72 of the HBM peak against 0.60-0.62).
- * 4 (double columns; round 4) = four vectors per workgroup over a 2.25 KiB stage, vectors wider than 17 bits read straight from HBM:
- * built to lift the narrow widths' floor, measured SLOWER than 2 at every width (profiles/r04_decode_floor.txt), never chosen by 0.
+ * Double columns run 4 as 2 (round 4's four-vectors-per-workgroup shape lost at every width and is gone: profiles/r04_decode_floor.txt).
  * ALPGPU_OPT_DECODE_PLAIN_STORES: 1 = ordinary instead of non-temporal stores. */
 #define ALPGPU_OPT_DECODE_VECTORS_PER_WG 1
 #define ALPGPU_OPT_DECODE_PLAIN_STORES 2
@@ -187,25 +186,16 @@ int         alpgpu_synchronize(alpgpu_ctx* ctx);
  * one-wavefront kernel does a quarter of its scalar work per vector and is 7-30 % faster on ALP and ALP_RD columns alike (while its ALP_RD
  * arm still spilled, the default chose between the two by alpgpu_column::alp_rd_rowgroups_hint); the ring kernel is slower than both. */
 #define ALPGPU_OPT_CONSUMER_PIPELINED 5
-/* ALPGPU_OPT_ENCODE_KERNEL: which single-pass kernel alpgpu_encode_f64 / alpgpu_encode_vectors_f64 launch (same bytes either way).
- * ALPGPU_ENCODE_KERNEL_LEAN (default): the input is the only vector-sized thing a wavefront holds — the analysis keeps lane masks, the pack
- * recomputes each integer as it shifts it into a 4 KiB LDS image that also waits for the ordered offset — 6 KiB of LDS and <= 72 VGPRs per
- * wavefront, three 8-vector tiles per CU.  ALPGPU_ENCODE_KERNEL_CLASSIC: round 3's kernel (input + integers + packed units in registers,
- * 8 KiB image, two tiles per CU).  DESIGN.md §3.2. */
+/* Retired options: alpgpu_set_option accepts the values it always accepted and they have no effect (the variants they selected lost and are gone).
+ * ALPGPU_OPT_ENCODE_KERNEL (ALPGPU_ENCODE_KERNEL_LEAN / _CLASSIC): the single-pass double encode is always the lean kernel.
+ * ALPGPU_OPT_DECODE_PAIRING (0..3): workgroups that owned two vectors and chose from their descriptors how to run them.
+ * ALPGPU_OPT_DECODE_PATCH_AFTER (0..64): exceptions patched in after the stores (profiles/r05_decode_exceptions.txt). */
 #define ALPGPU_OPT_ENCODE_KERNEL 7
 #define ALPGPU_ENCODE_KERNEL_LEAN 0
 #define ALPGPU_ENCODE_KERNEL_CLASSIC 1
-/* ALPGPU_OPT_DECODE_PAIRING (double store decode only; 0 = the library's choice, the default — since round 5 never this kernel): workgroups that own two consecutive vectors and choose how to
- * run them from the two descriptors — 1: together when both are narrow, else one after the other; 2: as 1 with the second vector's loads issued in front
- * of the first one's unpack; 3: three vectors per two workgroups.  Same output bytes as every other shape (tests/test_decode_gpu.py). */
 #define ALPGPU_OPT_DECODE_PAIRING 8
-/* ALPGPU_OPT_DECODE_PATCH_AFTER (double store decode; round 5; an EXPERIMENT that lost — effective only in builds of decode_kernels.hip with
- * -DALPGPU_DECODE_PATCH_MODE=1 or 2, ignored by the default build; default 0): an ALP vector with 1..value exceptions (value <= 64) is unpacked as
- * if it had none — no exception mask, no rank lookup — and its exceptions are put in afterwards: mode 1 by 8-byte stores over the stored values (the
- * reference's own order, include/alp/decoder.hpp:141-149), mode 2 in registers through a per-wavefront slot table.  Same output bytes
- * (tests/test_decode_gpu.py runs every exception count 0..1024 under every limit); measured against the mask route in profiles/r05_decode_exceptions.txt. */
 #define ALPGPU_OPT_DECODE_PATCH_AFTER 9
-/* ALPGPU_OPT_ENCODE_UNORDERED (double columns under ALPGPU_ENCODE_KERNEL_LEAN, and float columns; round 5; default 0): 1 = alpgpu_encode_* / alpgpu_encode_vectors_* do not
+/* ALPGPU_OPT_ENCODE_UNORDERED (double and float columns; round 5; default 0): 1 = alpgpu_encode_* / alpgpu_encode_vectors_* do not
  * assign stream offsets in vector order.  Each 8-vector tile reserves its packed / exception bytes with ONE atomic add when its analysis is done,
  * instead of waiting for the sizes of every tile before it (the ordered form's look-back).  Every vector's record — descriptor fields, packed words,
  * exception values and positions — is byte for byte what the ordered form writes; what changes is WHERE in d_packed / d_exc a tile's records lie
@@ -251,7 +241,8 @@ int         alpgpu_synchronize(alpgpu_ctx* ctx);
 #define ALPGPU_OPT_DECODE_UNHINTED 15
 int         alpgpu_set_option(alpgpu_ctx* ctx, int option, int64_t value);
 /* the launch shape alpgpu_decode_f64 (is_f32 = 0) or alpgpu_decode_f32 (1) would use for this column now: vectors per decode
- * workgroup (1, 2 or 4), from ALPGPU_OPT_DECODE_VECTORS_PER_WG and the column's size hints; negative on bad arguments */
+ * workgroup — double: 1 or 2; float: 1, 2, 4 or 8, or 16..30 for the streamed shapes — from ALPGPU_OPT_DECODE_VECTORS_PER_WG and the column's size hints;
+ * negative on bad arguments */
 int         alpgpu_decode_vectors_per_wg(alpgpu_ctx* ctx, const alpgpu_column* col, int is_f32);
 /* ... and whether that decode would run with the read-ahead beside it (ALPGPU_OPT_DECODE_READ_AHEAD): 1 / 0; negative on bad arguments */
 int         alpgpu_decode_reads_ahead(alpgpu_ctx* ctx, const alpgpu_column* col, int is_f32);

@@ -82,15 +82,16 @@ def test_falp_every_bit_width_class(ctx, oracle, bw):
     got = gpu_decode(ctx, enc)
     assert np.array_equal(got.view(np.uint64), want.view(np.uint64))
     from alp_amd import capi
-    try:  # four vectors per workgroup over the narrow stage (widths <= 17 staged, wider ones read straight from HBM): the same bits
+    try:  # ALPGPU_OPT_DECODE_VECTORS_PER_WG = 4 is accepted for double columns and runs as two vectors per workgroup: the same bits
         ctx.set_option(capi.OPT_DECODE_VECTORS_PER_WG, 4)
         got4 = gpu_decode(ctx, enc)
+        assert ctx.decode_vectors_per_wg(capi.DeviceColumn.from_host(*layout.compact(enc))) == 2
     finally:
         ctx.set_option(capi.OPT_DECODE_VECTORS_PER_WG, 0)
     assert np.array_equal(got4.view(np.uint64), want.view(np.uint64))
 
 
-@pytest.mark.parametrize("vectors_per_wg,plain", [(2, 0), (2, 1), (1, 1), (4, 0), (4, 1)])  # 4: the narrow stage; wide and ALP_RD vectors take its straight-from-HBM arm
+@pytest.mark.parametrize("vectors_per_wg,plain", [(2, 0), (2, 1), (1, 1)])
 def test_tuning_options_do_not_change_results(ctx, oracle, vectors_per_wg, plain):
     from alp_amd import capi
     try:
@@ -122,28 +123,6 @@ def test_residency_pad_does_not_change_results(ctx, oracle, pad_kib):
     finally:
         ctx.set_option(capi.OPT_DECODE_RESIDENCY_PAD, -1)
         ctx.set_option(capi.OPT_DECODE_VECTORS_PER_WG, 0)
-
-
-@pytest.mark.parametrize("pairing", [1, 2, 3])
-def test_pairing_workgroups_write_the_same_bytes(ctx, oracle, pairing):
-    """ALPGPU_OPT_DECODE_PAIRING (k_decode_pairs: workgroups that own two vectors and decide from their descriptors how to run them): every
-    column class incl. odd vector counts, ALP_RD, exception-heavy and adversarial vectors decodes to the same bits as the default shape"""
-    from alp_amd import capi
-    try:
-        ctx.set_option(capi.OPT_DECODE_PAIRING, pairing)
-        for name in ("mixed_1pct", "mixed_30pct", "rd_latlon", "adversarial", "one_vector", "decimal2"):
-            if name not in COLUMNS:
-                continue
-            col = COLUMNS[name]()
-            for cut in (len(col), max(1024, (len(col) // 1024 - 1) * 1024), 3 * 1024, 4 * 1024, 5 * 1024):  # even, odd and short vector counts
-                part = col[: min(cut, len(col))]
-                if len(part) == 0:
-                    continue
-                enc = oracle.encode_column(part)
-                got = gpu_decode(ctx, enc)
-                assert np.array_equal(got.view(np.uint64), part.view(np.uint64)), (name, pairing, len(part))
-    finally:
-        ctx.set_option(capi.OPT_DECODE_PAIRING, 0)
 
 
 def _alp_vectors_with_exception_counts(rng, counts, bw, placement="random"):
@@ -178,8 +157,8 @@ def _alp_vectors_with_exception_counts(rng, counts, bw, placement="random"):
 @pytest.mark.parametrize("bw", [0, 6, 17, 52])
 def test_exceptions_patched_after_the_stores_or_through_the_mask(ctx, oracle, bw, placement):
     """the three loops a store-decode wavefront picks from per vector (no exceptions / all values staged in LDS / values beyond the stage read from HBM:
-    counts 0, 1..128, 129..1024) in every launch shape, positions on the quarter boundaries; and ALPGPU_OPT_DECODE_PATCH_AFTER under every limit — a no-op
-    in the default build, the patch arms in an -DALPGPU_DECODE_PATCH_MODE=1 / 2 build selected with ALPGPU_LIB — the same bits as the oracle"""
+    counts 0, 1..128, 129..1024) in every launch shape, positions on the quarter boundaries; and the retired ALPGPU_OPT_DECODE_PATCH_AFTER / _PAIRING under
+    every value, accepted and without effect — the same bits as the oracle"""
     from alp_amd import capi
     rng = np.random.default_rng(7000 + bw)
     counts = [0, 1, 2, 3, 7, 8, 9, 20, 31, 32, 33, 63, 64, 65, 100, 128, 129, 300, 1024, 1, 64, 0, 5]
@@ -202,8 +181,8 @@ def test_exceptions_patched_after_the_stores_or_through_the_mask(ctx, oracle, bw
 
 
 def test_patched_exceptions_on_a_full_chip(ctx, oracle):
-    """a column long enough to keep every CU busy for many waves of workgroups (store -> patch ordering under load): 40 000 narrow vectors with 20
-    exceptions each (the bench's 2 % sweep), decoded three times with each route; the patch route against the mask route bit for bit"""
+    """a column long enough to keep every CU busy for many waves of workgroups: 40 000 narrow vectors with 20 exceptions each (the bench's 2 % sweep),
+    decoded in every launch shape with and without the retired ALPGPU_OPT_DECODE_PATCH_AFTER (accepted, no effect): the same bits every time"""
     import torch
     from alp_amd import capi
     rng = np.random.default_rng(99)
@@ -270,7 +249,7 @@ def test_shortcut_arithmetic_at_every_width(ctx, oracle, exceptions):
         enc["exc"][v, :c] = rng.integers(0, 2**64, c, dtype=np.uint64).view(np.float64)
     want = oracle.decode_column(enc)
     try:
-        for vpw in (0, 1, 2, 4):
+        for vpw in (0, 1, 2):
             ctx.set_option(capi.OPT_DECODE_VECTORS_PER_WG, vpw)
             got = gpu_decode(ctx, enc)
             bad = np.nonzero((got.view(np.uint64) != want.view(np.uint64)).reshape(n, 1024).any(axis=1))[0]

@@ -180,9 +180,8 @@ def test_two_pass_encode_gives_the_same_column(ctx, oracle, name):
 
 @pytest.mark.parametrize("name", ["mixed_1pct", "mixed_10pct", "drifting_k", "adversarial", "rd_unit", "every_width", "long_mixed"])
 def test_classic_single_pass_kernel_gives_the_same_column(ctx, name):
-    """ALPGPU_OPT_ENCODE_KERNEL = ALPGPU_ENCODE_KERNEL_CLASSIC (round 3's k_encode_fused: integers and packed units in registers, two tiles per CU) is a
-    shipped option: the same bytes as the default lean kernel on ALP, ALP_RD, every packed width, heavy exception loads and a column of > 1000 look-back
-    tiles, and the decode of its column is the input."""
+    """ALPGPU_OPT_ENCODE_KERNEL = ALPGPU_ENCODE_KERNEL_CLASSIC (round 3's k_encode_fused, since removed) is a retired option: accepted, and the column is
+    the same bytes as the default on ALP, ALP_RD, every packed width, heavy exception loads and a column of > 1000 look-back tiles, and its decode is the input."""
     from alp_amd import capi
     col_np = {"rd_unit": lambda: datagen.rd_column(210, seed=12), "every_width": lambda: datagen.every_bit_width_column(),
               "long_mixed": lambda: datagen.mixed_column(9000, seed=78, exc_rate=0.03)}.get(name, COLUMNS.get(name))()
@@ -413,7 +412,7 @@ def test_alp_vectors_of_every_packed_width(ctx, oracle, route, exceptions):
         ctx.set_option(capi.OPT_ENCODE_TWO_PASS, 0)
     for a, b, what in zip(dcol.to_host(), want, ("rowgroup states", "descriptors", "packed stream", "exception stream")):
         assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), f"{route}: {what}"
-    for vpw in (1, 2, 4):
+    for vpw in (1, 2):
         ctx.set_option(capi.OPT_DECODE_VECTORS_PER_WG, vpw)
         out = ctx.decode(dcol)
         ctx.synchronize()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B micro-benchmark of the decode kernel variants (ALPGPU_DECODE_VARIANT) + HBM copy/fill calibration.
+"""Micro-benchmark of the decode launch shapes (one / two vectors per workgroup) + HBM copy/fill calibration.
 Usage on the GPU box: python tools/bench_decode_variants.py [n_vectors]"""
 import os
 import sys
@@ -67,16 +67,16 @@ def main():
     print(f"calib fill  : median {ms:.3f} ms -> {n*8192/ms/1e9:.2f} TB/s write-only (best {n*8192/mn/1e9:.2f})")
     del src
     ctxs = {}
-    for variant in (1, 0, 4):
-        os.environ["ALPGPU_DECODE_VARIANT"] = str(variant)
-        ctxs[variant] = capi.Context(0)
+    for vpw in (1, 2):
+        ctxs[vpw] = capi.Context(0)
+        ctxs[vpw].set_option(capi.OPT_DECODE_VECTORS_PER_WG, vpw)
     for bw, exc in ((8, 0), (16, 0), (16, 20), (28, 0), (28, 10), (40, 0)):
         col, rec = make_column(n, bw, exc, seed=bw)
         alg = n * (32 + 128 * bw + rec + 8192)
         line = f"bw={bw:2d} exc={exc:3d}  bytes/vec={alg//n}:"
         for variant, ctx in ctxs.items():
             ms, mn = timeit(lambda: ctx.decode(col, out))
-            line += f"  v{variant}: {ms:.3f} ms {n*8192/ms/1e9:.2f} TB/s out, {alg/ms/1e9:.2f} TB/s traffic ({alg/ms/1e9/8.0*100:.0f}% of 8TB/s)"
+            line += f"  vpw{variant}: {ms:.3f} ms {n*8192/ms/1e9:.2f} TB/s out, {alg/ms/1e9:.2f} TB/s traffic ({alg/ms/1e9/8.0*100:.0f}% of 8TB/s)"
         print(line, flush=True)
         del col
     print("device:", list(ctxs.values())[0].device_info())

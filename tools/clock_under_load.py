@@ -46,6 +46,6 @@ while time.perf_counter() - t0 < secs:
     torch.cuda.synchronize(); k += 20
 el = time.perf_counter() - t0
 stop = True; th.join()
-print(f"{kind}: {k} launches in {el:.2f} s = {el / k * 1e3:.3f} ms each (kernel={os.environ.get('ALPGPU_ENCODE_KERNEL', 'default')})")
+print(f"{kind}: {k} launches in {el:.2f} s = {el / k * 1e3:.3f} ms each")
 for s in samples[:3] + samples[len(samples) // 2: len(samples) // 2 + 3] + samples[-2:]:
     print("  ", s[:400])

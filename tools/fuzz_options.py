@@ -25,7 +25,6 @@ ctx = capi.Context(0)
 
 ENC_OPTS = {  # option -> values a round may pick (first = default)
     capi.OPT_ENCODE_TWO_PASS: (0, 1),
-    capi.OPT_ENCODE_KERNEL: (0, 1),
     capi.OPT_ENCODE_ASYNC_INIT: (1, 0, 2),
     capi.OPT_ENCODE_UNORDERED: (0, 1),
     capi.OPT_DEBUG_FORCE_STALL: (0, 0, 0, 1),
@@ -33,7 +32,6 @@ ENC_OPTS = {  # option -> values a round may pick (first = default)
 DEC_OPTS = {
     capi.OPT_DECODE_VECTORS_PER_WG: (0, 1, 2, 4),
     capi.OPT_DECODE_PLAIN_STORES: (0, 1),
-    capi.OPT_DECODE_PAIRING: (0, 1, 2, 3),
     capi.OPT_DECODE_RESIDENCY_PAD: (-1, 0, 6, 14, 60),
     capi.OPT_DECODE_READ_AHEAD: (-1, 0, 1),
     capi.OPT_DECODE_READ_AHEAD_US: (0, 1, 25, 400),

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """prof_decode_shapes.py [n]: the decode under the auto rule on columns that take its other launch shapes (for rocprofv3): 8 bits with 20 exceptions per
-vector (k_decode_pairs), 12 bits (two vectors per workgroup, six workgroups per CU), 44 bits (one vector per workgroup, six per CU)"""
+vector, 12 bits (two vectors per workgroup, six workgroups per CU), 44 bits (one vector per workgroup, six per CU)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

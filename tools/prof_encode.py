@@ -18,7 +18,7 @@ else:
     x = synthetic_input(kind, n, dev, seed=42)
 col = capi.DeviceColumn(n, 0)
 med, mean = time_launches(lambda: ctx.encode(x, col), 5, 2)
-if os.environ.get("ALPGPU_PROF_ENCODE_ONLY"):  # measurement builds that write garbage columns (-DALPGPU_LEAN_STOP_AT): nothing may read what they wrote
+if os.environ.get("ALPGPU_PROF_ENCODE_ONLY"):  # encode timing alone, the column is not read back
     print(f"{kind}: n={n} encode median {med:.3f} ms (encode only)")
     sys.exit(0)
 pb, eb, ov = ctx.column_totals(col)

@@ -8,7 +8,7 @@
 #   cons: python tools/prof_consumers.py 0 1048576                     (k_sink_direct, k_decode_column<2, false, kSinkSum>, k_consume_column: the fused SUM consumer, all three kernels)
 #   narrow: python tools/time_one.py 8:1048576:2                         (k_decode_column<2, true>: the two-vectors-per-workgroup decode of a narrow column)
 #   sinkf: python tools/prof_sink_direct_f32.py 1048576                  (k_sink_direct_f32 and the staged float SUM sink)
-#   shapes: python tools/prof_decode_shapes.py 1048576                   (the auto rule's other decode launches: k_decode_pairs, two vectors x six workgroups per CU, one x six)
+#   shapes: python tools/prof_decode_shapes.py 1048576                   (the auto rule's other decode launches: two vectors x six workgroups per CU, one x six)
 #   ahead: python tools/prof_read_ahead.py 1048576                       (k_read_ahead beside k_decode_column<1> / <2> on 3- and 4-bit columns; kernel stats only mean something without --pmc)
 #   streamf: BWS=4 EXCS=0 SHAPES=2 SIZES=1048576 python tools/time_f32_narrow.py   (a 4-bit float column: k_decode_column_f32<2> and, by the rule, k_decode_stream_f32<12, 24576, 2, 12>)
 # (enc / encrd also decode what they encoded: the ALP_RD column's k_decode_column row; encf runs the float search in front of the float encode)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """time_consumers.py [n_vectors]: the fused consumers on bench.py's configs[1] column (bit widths 1-53 by rowgroup) and on columns with
 exceptions — alpgpu_decode_sum_f64 (default: one workgroup per two vectors), the count consumer, the column total, and the SUM
-through the persistent LDS-ring kernel (ALPGPU_OPT_CONSUMER_PIPELINED).  One process = one library (ALPGPU_LIB selects an A/B build: tools/build_variant.sh)."""
+through the persistent LDS-ring kernel (ALPGPU_OPT_CONSUMER_PIPELINED).  One process = one library (ALPGPU_LIB selects another build of the library)."""
 import os
 import sys
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""time_decode_f32.py [n]: alpgpu_decode_f32 of bench.py's two float columns (run it under ALPGPU_DECODE_F32_PAD_LDS_KIB=... for the residency experiment)"""
+"""time_decode_f32.py [n]: alpgpu_decode_f32 of bench.py's two float columns """
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -33,4 +33,4 @@ for kind in ("decimal_mixed", "rd"):
     ok = bool(torch.equal(out.view(torch.int32), xf.view(torch.int32)))
     row.append(f"{kind}: {best:.3f} ms = {(n * (4096 + 13) + pb + eb) / best / 1e6 / 8000:.3f} of peak (round trip {ok})")
     del xf, col, out
-print(f"float decode, vectors per workgroup {os.environ.get('SWEEP_VPW', 'auto')}, pad {os.environ.get('ALPGPU_DECODE_F32_PAD_LDS_KIB', '0'):>2s} KiB: " + " | ".join(row), flush=True)
+print(f"float decode, vectors per workgroup {os.environ.get('SWEEP_VPW', 'auto')}: " + " | ".join(row), flush=True)

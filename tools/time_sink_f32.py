@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """time_sink_f32.py [n]: alpgpu_decode_sum_f32 on bench.py's float columns (one wavefront per vector), with the columns' width / exception profile;
-ALPGPU_LIB selects an A/B build (e.g. -DALPGPU_SINK_STAGE_F32=0: no LDS stage; -DALPGPU_SINK_STAGE_F32_MAX_EXC=n)."""
+ALPGPU_LIB selects another build of the library."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
