@@ -82,6 +82,7 @@ try:  # (round 6; an A/B library of an earlier round selected with ALPGPU_LIB do
     _sig("alpgpu_debug_read_ahead_batches", _int, _vp, C.POINTER(_u64))
     _sig("alpgpu_debug_unhinted_plan", _int, _vp, C.POINTER(_u64 * 6))
     _sig("alpgpu_debug_forget_column", _int, _vp, C.POINTER(CColumn))
+    _sig("alpgpu_debug_decode_plan", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64 * 4))
 except AttributeError:
     pass
 _sig("alpgpu_debug_traffic_probe", _int, _vp, _vp, _vp, _u64, C.c_uint32)
@@ -301,6 +302,22 @@ class Context:
         _check(lib.alpgpu_debug_unhinted_plan(self.h, C.byref(w)), "alpgpu_debug_unhinted_plan")
         return {"shape": int(w[0]), "lead_min": int(w[1] & 0xFFFFFFFF), "lead_max": int(w[1] >> 32), "ps_per_vector": int(w[2] & 0xFFFFFFFF), "max_bits": int(w[2] >> 32),
                 "packed_bytes": int(w[3]), "exceptions": int(w[4]), "rd_vectors": int(w[5])}
+
+    def decode_plan(self, col: "DeviceColumn"):
+        """the launch decode() of this column would make now, as a whole (include/alpgpu.h: alpgpu_debug_decode_plan): None for an unhinted decode planned on the device,
+        else {"word", "vectors_per_wg", "many_exc", "pad_kib", "packed_bytes", "exc_bytes", "rd_rowgroups_hint"} (float: vectors_per_wg is the shape, pad_kib None = none)"""
+        w = (_u64 * 4)()
+        rc = int(lib.alpgpu_debug_decode_plan(self.h, C.byref(col.c), 1 if col.dtype == "f32" else 0, C.byref(w)))
+        if rc < 0:
+            _check(rc, "alpgpu_debug_decode_plan")
+        if rc == 0:
+            return None
+        word = int(w[0])
+        if col.dtype == "f32":
+            vpw, many, pad = word & 0xFF, False, (None if (word >> 8) == 0xFF else word >> 8)
+        else:
+            vpw, many, pad = (1 if word & 1 else 2), bool(word & 64), word >> 8
+        return {"word": word, "vectors_per_wg": vpw, "many_exc": many, "pad_kib": pad, "packed_bytes": int(w[1]), "exc_bytes": int(w[2]), "rd_rowgroups_hint": int(w[3])}
 
     def decode_reads_ahead(self, col: "DeviceColumn") -> bool:
         """decode() of this column would start the read-ahead beside the decode kernel (OPT_DECODE_READ_AHEAD)"""

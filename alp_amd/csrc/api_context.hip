@@ -144,6 +144,7 @@ int alpgpu_ctx_create(int device, alpgpu_ctx** out_ctx) {
 		(void)hipGetLastError();
 		ctx->h_learn = nullptr;
 	} else {
+		std::memset(ctx->h_learn, 0, sizeof(uint64_t) * kLearnSlots * 3 * kMaxSegments); // (no slot reads words no copy has written)
 		for (auto& l : ctx->learn) {
 			if (hipEventCreateWithFlags(&l.ev, hipEventDisableTiming) != hipSuccess) {
 				(void)hipGetLastError();

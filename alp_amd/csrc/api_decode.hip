@@ -144,8 +144,10 @@ void segment_table_forget(alpgpu_ctx* ctx, const alpgpu_column* col) {
 	segment_tables_drop(ctx, col);
 	for (auto& l : ctx->learn) { // ... and what an unhinted decode of the old content left behind (decode_unhinted)
 		if (l.state != 0 && l.key == col->d_vectors) {
-			if (l.state == 1) { (void)hipEventSynchronize(l.ev); } // (its copy targets the slot's host words: let it land before the slot is reused)
-			l.state = 0;
+			// (a copy in flight targets the slot's host words: the slot is abandoned, not waited for — no host synchronisation, and every alpgpu_encode_* comes here,
+			//  inside a stream capture too; decode_unhinted takes it again once its event has completed)
+			l.state = l.state == 1 ? 3 : 0;
+			l.key   = nullptr;
 		}
 	}
 }
@@ -379,7 +381,7 @@ constexpr uint64_t kUnhintedMinVectors = 65536;
 
 static LearnSlot* learn_slot_of(alpgpu_ctx* ctx, const alpgpu_column* col, int value_bytes) {
 	for (auto& l : ctx->learn) {
-		if (l.state != 0 && l.key == col->d_vectors && l.d_packed == col->d_packed && l.n_vectors == col->n_vectors && l.value_bytes == value_bytes) { return &l; }
+		if ((l.state == 1 || l.state == 2) && l.key == col->d_vectors && l.d_packed == col->d_packed && l.n_vectors == col->n_vectors && l.value_bytes == value_bytes) { return &l; }
 	}
 	return nullptr;
 }
@@ -410,8 +412,9 @@ static bool learned_hints(alpgpu_ctx* ctx, const alpgpu_column* col, int value_b
 	return true;
 }
 
+// (learn = false: the stream is capturing — the sums are not sent anywhere)
 template <int VB>
-static int decode_unhinted(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_out) {
+static int decode_unhinted(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_out, bool learn) {
 	uint64_t* words = ctx->d_progress;
 	const uint64_t seg_vectors = segment_vectors_for(col->n_vectors);
 	const uint32_t n_seg       = static_cast<uint32_t>((col->n_vectors + seg_vectors - 1) / seg_vectors);
@@ -448,7 +451,7 @@ static int decode_unhinted(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_ou
 		ALPGPU_HIP(hipEventRecord(ctx->ev_join, ctx->init_stream));
 	}
 	// the sums, for the next decode of this column: to page-locked memory behind an event that is only ever queried (enqueued BEHIND the decode: the copy delays nothing)
-	if (ctx->h_learn != nullptr) {
+	if (learn && ctx->h_learn != nullptr) {
 		LearnSlot* l = learn_slot_of(ctx, col, VB);
 		if (!l) {
 			l               = &ctx->learn[ctx->learn_next];
@@ -456,7 +459,7 @@ static int decode_unhinted(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_ou
 		}
 		// (a slot whose copy is still in flight — the same column decoded again before its sizes arrived, or a fifth unhinted column within microseconds — is left
 		//  alone: no host synchronisation here either; the earlier copy lands, or this column simply stays unhinted a little longer)
-		const bool busy = l->state == 1 && hipEventQuery(l->ev) != hipSuccess;
+		const bool busy = (l->state == 1 || l->state == 3) && hipEventQuery(l->ev) != hipSuccess;
 		if (busy) {
 			(void)hipGetLastError();
 		} else {
@@ -475,6 +478,21 @@ static int decode_unhinted(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_ou
 	return ALPGPU_OK;
 }
 
+// the column's sizes are unknown to the host and the decode takes them on the stream (decode_unhinted), or from what an earlier one learned
+static bool decodes_unhinted(const alpgpu_ctx* ctx, const alpgpu_column* col, int value_bytes) {
+	const bool unhinted   = col->packed_bytes_hint == 0 && col->exc_bytes_hint == 0;
+	const bool free_shape = ctx->decode_auto && ctx->decode_pad_kib < 0 && (value_bytes == 8 || ctx->decode_vpw == 0);
+	return unhinted && ctx->decode_unhinted && free_shape && ctx->d_progress != nullptr && col->n_vectors >= kUnhintedMinVectors;
+}
+static bool stream_capturing(hipStream_t s) {
+	hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+	if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+		(void)hipGetLastError();
+		return true; // (cannot tell: the learn slots are left alone)
+	}
+	return st != hipStreamCaptureStatusNone;
+}
+
 template <int VB>
 static int decode_column(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_out) {
 	ALPGPU_CHECK_CTX(ctx);
@@ -482,13 +500,14 @@ static int decode_column(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_out)
 	if (col->n_vectors == 0) { return ALPGPU_OK; }
 	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
 	alpgpu_column hinted;
-	const bool    unhinted = col->packed_bytes_hint == 0 && col->exc_bytes_hint == 0;
-	const bool    free_shape = ctx->decode_auto && ctx->decode_pad_kib < 0 && (VB == 8 || ctx->decode_vpw == 0);
-	if (unhinted && ctx->decode_unhinted && free_shape && ctx->d_progress != nullptr && col->n_vectors >= kUnhintedMinVectors) {
+	if (decodes_unhinted(ctx, col, VB)) {
+		// Captured into a graph: the device-side plan only.  A slot's event recorded and its copy made only in a capture would be queried by the next eager decode
+		// before any replay wrote the host words (and every replay would write them again behind the host's back).
+		if (stream_capturing(ctx->stream)) { return decode_unhinted<VB>(ctx, col, d_out, false); }
 		if (learned_hints(ctx, col, VB, &hinted)) {
 			col = &hinted; // an earlier decode of this column took its sizes: planned on the host from here on
 		} else {
-			return decode_unhinted<VB>(ctx, col, d_out);
+			return decode_unhinted<VB>(ctx, col, d_out, true);
 		}
 	}
 	DecodeRun runs[kMaxRuns];
@@ -530,6 +549,24 @@ int alpgpu_debug_unhinted_plan(alpgpu_ctx* ctx, uint64_t* out6) {
 	out6[0] = w[alpgpu::kCtxWordShape], out6[1] = w[alpgpu::kCtxWordLead], out6[2] = w[alpgpu::kCtxWordPace];
 	out6[3] = w[alpgpu::kCtxWordTotals], out6[4] = w[alpgpu::kCtxWordTotals + 1], out6[5] = w[alpgpu::kCtxWordTotals + 2];
 	return ALPGPU_OK;
+}
+
+// debug aid (tests): the launch decode() of this column would make now, for the column as a whole (a region plan gives each run its own: alpgpu_decode_runs).
+// out4[0] the double variant word (decode_variant_for: bit 0 one vector per workgroup, bit 1 plain stores, bit 6 the 256-entry exception stage, bits 8.. the residency
+// pad in KiB) or the float shape word (decode_shape_f32: vectors per workgroup or streamed shape, bits 8.. the pad, 0xFF none); [1..3] the sizes it is planned from
+// (packed_bytes_hint, exc_bytes_hint, alp_rd_rowgroups_hint — for an unhinted column, what an earlier decode of it learned).  Returns 1: planned on the host; 0: an
+// unhinted decode whose plan is made on the device (out4 untouched); negative on bad arguments.  Waits for nothing.
+int alpgpu_debug_decode_plan(alpgpu_ctx* ctx, const alpgpu_column* col, int is_f32, uint64_t* out4) {
+	ALPGPU_CHECK_CTX(ctx); // (learned_hints queries an event)
+	if (!col || !out4) { return fail(ALPGPU_ERR_INVALID, "null column or output"); }
+	alpgpu_column hinted;
+	if (decodes_unhinted(ctx, col, is_f32 ? 4 : 8)) {
+		if (!learned_hints(ctx, col, is_f32 ? 4 : 8, &hinted)) { return 0; }
+		col = &hinted;
+	}
+	out4[0] = static_cast<uint64_t>(is_f32 ? decode_shape_f32(ctx, col) : decode_variant_for(ctx, col));
+	out4[1] = col->packed_bytes_hint, out4[2] = col->exc_bytes_hint, out4[3] = col->alp_rd_rowgroups_hint;
+	return 1;
 }
 
 // how many launches alpgpu_decode_f64 would make for this column now: 1, or the number of runs of plan_decode_runs; negative on bad arguments

@@ -40,7 +40,9 @@ struct SegmentTable {
 };
 
 // What an UNHINTED decode learned about a column (api_decode.hip: decode_unhinted): the per-segment sums taken on the stream travel to page-locked host words behind
-// an event that is only ever queried; once there, the next decode of the same column is planned on the host.  state 0: empty, 1: copy in flight, 2: sizes known.
+// an event that is only ever queried; once there, the next decode of the same column is planned on the host.  state 0: empty, 1: copy in flight, 2: sizes known,
+// 3: abandoned with its copy perhaps still in flight (the column was encoded again: segment_table_forget) — reused once its event has completed, never waited for.
+// A decode enqueued on a capturing stream neither reads nor writes slots: an event recorded and a copy made only in a graph would land at some later replay.
 constexpr int kLearnSlots = 4;
 struct LearnSlot {
 	const void* key;       // col->d_vectors

@@ -258,6 +258,12 @@ int         alpgpu_debug_read_ahead_batches(alpgpu_ctx* ctx, uint64_t* batches);
 int         alpgpu_debug_unhinted_plan(alpgpu_ctx* ctx, uint64_t* out6);
 /* ... and: forget what the context remembers about this column (its segments, what an unhinted decode learned), as every alpgpu_encode_* into it does */
 int         alpgpu_debug_forget_column(alpgpu_ctx* ctx, const alpgpu_column* col);
+/* ... and: the launch alpgpu_decode_f64 (is_f32 = 0) / _f32 (1) would make for this column now, as a whole (without a region plan; waits for nothing): out4[0] the
+ * double variant word (bit 0: one vector per workgroup, bit 1: plain stores, bit 6: the 256-entry exception stage, bits 8..: residency pad in KiB) or the float shape
+ * word (bits 0-7: vectors per workgroup or streamed shape, bits 8..: pad in KiB, 0xFF none), out4[1..3] the packed bytes, exception bytes and ALP_RD rowgroups + 1 it is
+ * planned from (for an unhinted column: what an earlier decode of it learned).  Returns 1 (planned on the host), 0 (an unhinted decode, planned on the device;
+ * out4 untouched) or negative on bad arguments. */
+int         alpgpu_debug_decode_plan(alpgpu_ctx* ctx, const alpgpu_column* col, int is_f32, uint64_t* out4);
 /* ---- host-resident columns -----------------------------------------------------------------------------------------------
  * The reference's callers (publication/source_code/bench_compression_ratio/alp.cpp:198-229) hold the column and what they
  * compress it into in host memory.  These entry points take it from there: n_values values at h_in (the last vector may be

@@ -134,6 +134,132 @@ torch.cuda.synchronize()
 t_eager = (time.perf_counter() - t0) / 20
 print("RESULT", ok, "encode+decode of %%d vectors: %%.0f us per replay, %%.0f us eager" %% (n, t_graph * 1e6, t_eager * 1e6))
 """,
+    # columns long enough for the unhinted decode (>= 65 536 vectors, both hints 0: sizes summed and the shape chosen on the stream), double and float, captured with
+    # nothing learned before: replays write the eager bytes, the capture leaves the context nothing to plan from, and what it learns eagerly afterwards is the truth
+    "unhinted_decode": r"""
+ok = True
+ref_ctx = capi.Context(0)
+for vb in (8, 4):
+    col, _, _ = bench.build_decode_column(70000, 0, seed=13, exc_per_vec=20, value_bytes=vb)
+    col.c.packed_bytes_hint = col.c.exc_bytes_hint = col.c.alp_rd_rowgroups_hint = 0
+    ref = ref_ctx.decode(col).clone()     # (another context: this one learns nothing before the capture; the kernels are loaded)
+    torch.cuda.synchronize()
+    out = torch.zeros_like(ref)
+    with torch.cuda.stream(side):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=side):
+            ctx.decode(col, out)
+    for _ in range(3):
+        out.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        ok = ok and same(out, ref)
+    ok = ok and ctx.decode_plan(col) is None  # nothing to plan from: the capture learned nothing
+    for _ in range(2):                        # eager: the first decode learns, the second is planned from what it learned
+        out.zero_()
+        ctx.decode(col, out)
+        torch.cuda.synchronize()
+        ok = ok and same(out, ref)
+    learned = ctx.decode_plan(col)
+    out.zero_()
+    g.replay()                                # a replay after them leaves what the context learned alone
+    torch.cuda.synchronize()
+    ok = ok and same(out, ref) and ctx.decode_plan(col) == learned
+    pb, eb, _ = ref_ctx.column_totals(col)
+    ok = ok and learned is not None and (learned["packed_bytes"], learned["exc_bytes"]) == (pb, eb)
+    dcol = ctx.encode(ref)                    # and an eager encode + decode of the same values
+    back = ctx.decode(dcol)
+    torch.cuda.synchronize()
+    ok = ok and same(back, ref)
+    print(vb, ok, learned, pb, eb)
+    del g
+print("RESULT", ok, "replays of unhinted decodes, then eager ones")
+""",
+    # an eager unhinted decode (its sizes on their way to the host) and right behind it a capture of encode + decode of the same column: the encode forgets what the
+    # context learned about the column inside the capture, without waiting for it; replays over three inputs give the eager streams and the input's bits
+    "encode_decode_after_unhinted": r"""
+n = 70000
+gen = torch.Generator(device="cuda:0")
+def make(seed):
+    gen.manual_seed(seed)
+    x = torch.round(torch.rand(n * 1024, dtype=torch.float64, device="cuda:0", generator=gen) * 1e4, decimals=2)
+    x[::97] = torch.rand(x[::97].shape, dtype=torch.float64, device="cuda:0", generator=gen)  # exceptions
+    x[n // 2 * 1024:] = torch.rand(n * 1024 - n // 2 * 1024, dtype=torch.float64, device="cuda:0", generator=gen)  # full precision: ALP_RD rowgroups
+    return x
+def streams(c):
+    tot = c.totals.cpu()
+    return [c.rowgroups.clone(), c.vectors.clone(), c.packed[: int(tot[0])].clone(), c.exc[: int(tot[1])].clone()]
+xs = [make(s) for s in (1, 2, 3)]
+x = xs[0].clone()
+col = capi.DeviceColumn(n)
+out = torch.zeros_like(x)
+eager = []
+for xi in xs:
+    x.copy_(xi)
+    ctx.encode(x, col)
+    eager.append(streams(col))
+x.copy_(xs[0])
+with torch.cuda.stream(side):
+    ctx.encode(x, col)
+    ctx.decode(col, out)                  # unhinted: the sizes travel to the host behind it
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        ctx.encode(x, col)
+        ctx.decode(col, out)
+ok = True
+for xi, want in zip(xs, eager):
+    x.copy_(xi)
+    out.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    ok = ok and same(out, xi) and all(torch.equal(a, b) for a, b in zip(streams(col), want))
+for _ in range(2):                        # eager afterwards: learns, then decodes from what it learned
+    ctx.encode(x, col)
+    out.zero_()
+    ctx.decode(col, out)
+    torch.cuda.synchronize()
+    ok = ok and same(out, x)
+print("RESULT", ok, "capture of encode + decode behind an eager unhinted decode")
+""",
+    # encode + decode of a >= 70 000-vector mixed double column and a float column in one graph: several look-back tiles and more than one fused launch each
+    "encode_decode_long": r"""
+n = 70000
+gen = torch.Generator(device="cuda:0")
+def make(seed):
+    gen.manual_seed(seed)
+    x = torch.round(torch.rand(n * 1024, dtype=torch.float64, device="cuda:0", generator=gen) * 1e4, decimals=2)
+    x[::89] = torch.rand(x[::89].shape, dtype=torch.float64, device="cuda:0", generator=gen)
+    x[2 * n // 5 * 1024: 3 * n // 5 * 1024] = torch.rand(n // 5 * 1024, dtype=torch.float64, device="cuda:0", generator=gen)
+    return x, torch.round(x[: n * 1024].float(), decimals=1)
+def streams(c):
+    tot = c.totals.cpu()
+    return [c.rowgroups.clone(), c.vectors.clone(), c.packed[: int(tot[0])].clone(), c.exc[: int(tot[1])].clone()]
+inputs = [make(s) for s in (4, 5, 6)]
+x, y = inputs[0][0].clone(), inputs[0][1].clone()
+cx, cy = capi.DeviceColumn(n), capi.DeviceColumn(n, dtype="f32")
+ox, oy = torch.zeros_like(x), torch.zeros_like(y)
+eager = []
+for xi, yi in inputs:
+    x.copy_(xi); y.copy_(yi)
+    ctx.encode(x, cx); ctx.encode(y, cy)
+    eager.append((streams(cx), streams(cy)))
+with torch.cuda.stream(side):
+    ctx.encode(x, cx); ctx.decode(cx, ox); ctx.encode(y, cy); ctx.decode(cy, oy)
+    side.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        ctx.encode(x, cx); ctx.decode(cx, ox)
+        ctx.encode(y, cy); ctx.decode(cy, oy)
+ok = True
+for (xi, yi), (wx, wy) in zip(inputs, eager):
+    x.copy_(xi); y.copy_(yi)
+    ox.zero_(); oy.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    ok = ok and same(ox, xi) and same(oy, yi)
+    ok = ok and all(torch.equal(a, b) for a, b in zip(streams(cx), wx)) and all(torch.equal(a, b) for a, b in zip(streams(cy), wy))
+print("RESULT", ok, "replays of encode + decode of %%d-vector double and float columns" %% n)
+""",
 }
 
 
