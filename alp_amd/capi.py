@@ -109,6 +109,10 @@ _sig("alpgpu_decode_count_range_f64", _int, _vp, C.POINTER(CColumn), C.c_double,
 _sig("alpgpu_column_sum_f64", _int, _vp, C.POINTER(CColumn), _vp)
 _sig("alpgpu_column_sum_f32", _int, _vp, C.POINTER(CColumn), _vp)
 _sig("alpgpu_tree_sum_f64", _int, _vp, _vp, _u64, _vp)
+_sig("alpgpu_gather_f64", _int, _vp, C.POINTER(CColumn), _vp, _u64, _vp)
+_sig("alpgpu_gather_f32", _int, _vp, C.POINTER(CColumn), _vp, _u64, _vp)
+_sig("alpgpu_decode_slice_f64", _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp)
+_sig("alpgpu_decode_slice_f32", _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -520,6 +524,30 @@ class Context:
             out = torch.empty(col.n_vectors * VECTOR_SIZE, dtype=tdt, device=f"cuda:{self.device}")
         assert out.is_contiguous() and out.numel() >= col.n_vectors * VECTOR_SIZE and out.dtype == tdt
         self._call("decode", col.dtype, C.byref(col.c), _vp(out.data_ptr()))
+        return out
+
+    # ---- random access (include/alpgpu.h: alpgpu_gather_*, alpgpu_decode_slice_*) -----------------------------------
+    def gather(self, col: "DeviceColumn", idx, out=None):
+        """the values at the value indices idx (a contiguous int64 tensor on this context's device; any order, repeats allowed) as a float64 /
+        float32 tensor; an index outside [0, n_vectors * 1024) gives the canonical quiet NaN"""
+        import torch
+        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or not idx.is_cuda or idx.device.index != self.device or not idx.is_contiguous():
+            raise ValueError("idx must be a contiguous int64 tensor on cuda:%d" % self.device)
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        if out is None:
+            out = torch.empty(idx.numel(), dtype=tdt, device=f"cuda:{self.device}")
+        assert out.is_contiguous() and out.numel() >= idx.numel() and out.dtype == tdt
+        self._call("gather", col.dtype, C.byref(col.c), _vp(idx.data_ptr()), idx.numel(), _vp(out.data_ptr()))
+        return out
+
+    def decode_slice(self, col: "DeviceColumn", first: int, n: int, out=None):
+        """values first .. first + n - 1 of the column (any first); AlpGpuError if the slice reaches past the column's n_vectors * 1024 values"""
+        import torch
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        if out is None:
+            out = torch.empty(max(0, int(n)), dtype=tdt, device=f"cuda:{self.device}")
+        assert out.is_contiguous() and out.numel() >= n and out.dtype == tdt
+        self._call("decode_slice", col.dtype, C.byref(col.c), first, n, _vp(out.data_ptr()))
         return out
 
     # ---- batch primitives, 32-bit words (float) --------------------------------------------------------

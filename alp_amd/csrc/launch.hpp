@@ -36,6 +36,10 @@ int launch_consume_sum(hipStream_t stream, const alpgpu_column* col, double* d_s
 int launch_consume_count_range(hipStream_t stream, const alpgpu_column* col, double lo, double hi, uint32_t* d_counts, int n_cus);
 int launch_tree_sum(hipStream_t stream, const double* d_in, uint64_t n, double* d_scratch, double* d_total);
 
+// gather_kernels.hip: d_out[k] = value d_idx[k] of the column (d_idx != nullptr; out of range: the canonical quiet NaN) or value first + k (d_idx ==
+// nullptr; the caller checked the range), k < n; value_bytes 8 or 4
+int launch_gather(hipStream_t stream, const alpgpu_column* col, const int64_t* d_idx, uint64_t first, uint64_t n, void* d_out, int value_bytes);
+
 // guard_kernels.hip
 int launch_validate_column(hipStream_t stream, const alpgpu_column* col, uint32_t value_bytes, unsigned long long* d_first_bad);
 int launch_count_rd_rowgroups(hipStream_t stream, const alpgpu_column* col, uint64_t* d_count);

@@ -390,6 +390,53 @@ struct column {
 		}
 		return out;
 	}
+	// The n values at value indices idx[0 .. n) of a serialized column (include/alpgpu.h: alpgpu_gather_*): the blob goes up whole (validated by
+	// alpgpu_column_from_blob*), the values are gathered where they lie and only they come back.  An index at or past n_vectors * 1024 gives the
+	// canonical quiet NaN.
+	static std::vector<PT> take(const uint8_t* blob, size_t size, const uint64_t* idx, size_t n) {
+		if (size < sizeof(alpgpu_blob_header)) { throw std::runtime_error("alp::gpu::column::take: blob shorter than its header"); }
+		alpgpu_blob_header h;
+		std::memcpy(&h, blob, sizeof(h));
+		std::vector<PT> out(n);
+		// buffers sized by the header; alpgpu_column_from_blob* checks the header and every descriptor against them before it copies anything
+		struct device_buffers {
+			std::vector<void*> p;
+			~device_buffers() {
+				for (void* q : p) { alpgpu_free(context(), q); }
+			}
+			void* get(size_t bytes) {
+				void* q = nullptr;
+				check(alpgpu_malloc(context(), &q, bytes ? bytes : 1), "alpgpu_malloc");
+				p.push_back(q);
+				return q;
+			}
+		} buf;
+		if (h.n_vectors > (uint64_t(1) << 40) || h.packed_bytes > (uint64_t(1) << 50) || h.exc_bytes > (uint64_t(1) << 50) ||
+		    alpgpu_blob_size(h.n_vectors, h.packed_bytes, h.exc_bytes) > size) { // (nothing is allocated beyond what the blob itself holds)
+			throw std::runtime_error("alp::gpu::column::take: blob header is implausible");
+		}
+		alpgpu_column col {};
+		col.n_vectors       = h.n_vectors;
+		col.n_rowgroups     = (h.n_vectors + config::N_VECTORS_PER_ROWGROUP - 1) / config::N_VECTORS_PER_ROWGROUP;
+		col.d_rowgroups     = static_cast<alpgpu_rowgroup_state*>(buf.get(col.n_rowgroups * sizeof(alpgpu_rowgroup_state)));
+		col.d_vectors       = static_cast<alpgpu_vector_desc*>(buf.get(col.n_vectors * sizeof(alpgpu_vector_desc)));
+		col.packed_capacity = h.packed_bytes;
+		col.d_packed        = static_cast<uint8_t*>(buf.get(h.packed_bytes));
+		col.exc_capacity    = h.exc_bytes;
+		col.d_exc           = static_cast<uint8_t*>(buf.get(h.exc_bytes));
+		col.d_totals        = static_cast<uint64_t*>(buf.get(8 * sizeof(uint64_t)));
+		uint64_t n_values   = 0;
+		check(sizeof(PT) == 8 ? alpgpu_column_from_blob(context(), blob, size, &col, &n_values) : alpgpu_column_from_blob_f32(context(), blob, size, &col, &n_values),
+		      "alpgpu_column_from_blob");
+		if (n == 0) { return out; }
+		int64_t* d_idx = static_cast<int64_t*>(buf.get(n * sizeof(int64_t)));
+		PT*      d_out = static_cast<PT*>(buf.get(n * sizeof(PT)));
+		check(alpgpu_memcpy_h2d(context(), d_idx, idx, n * sizeof(int64_t)), "alpgpu_memcpy_h2d"); // (an index >= 2^63 reads as negative: out of range either way)
+		check(sizeof(PT) == 8 ? alpgpu_gather_f64(context(), &col, d_idx, n, reinterpret_cast<double*>(d_out)) : alpgpu_gather_f32(context(), &col, d_idx, n, reinterpret_cast<float*>(d_out)),
+		      "alpgpu_gather");
+		check(alpgpu_memcpy_d2h(context(), out.data(), d_out, n * sizeof(PT)), "alpgpu_memcpy_d2h");
+		return out;
+	}
 };
 
 }} // namespace alp::gpu

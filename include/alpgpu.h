@@ -398,6 +398,31 @@ int alpgpu_column_sum_f64(alpgpu_ctx* ctx, const alpgpu_column* col, double* d_t
 int alpgpu_column_sum_f32(alpgpu_ctx* ctx, const alpgpu_column* col, double* d_total);
 int alpgpu_tree_sum_f64(alpgpu_ctx* ctx, const double* d_in, uint64_t n, double* d_total);
 
+/* ---- random access ----------------------------------------------------------------------------------------------------
+ * Value index r of a column = value r & 1023 of vector r >> 10 (ALPGPU_VECTOR_SIZE values per vector; tail padding included), so a column has
+ * n_vectors * 1024 value indices.  (The names say "index" and "slice": a "row" is a FastLanes row inside a lane)  Each value
+ * is read where it lies — its vector's descriptor, one or two packed words, for ALP_RD a left index and a dictionary entry, and a binary search
+ * of the vector's exception positions — and no vector is decoded whole.
+ *   alpgpu_gather_*        d_out[k] (k < n) = value d_idx[k]: bit for bit what alpgpu_decode_* writes at d_out[d_idx[k]], exceptions patched in
+ *                          (NaN payloads, +-inf and -0.0 included).  Indices may come in any order and may repeat.  An index below 0 or at or above
+ *                          n_vectors * 1024 gets the canonical quiet NaN, bits 0x7FF8000000000000 (float: 0x7FC00000), stored as an integer; nothing
+ *                          is read for it.  d_idx: n int64 in device memory.
+ *   alpgpu_decode_slice_*  d_out[k] (k < n) = value first + k, for any first — inside a vector or inside a rowgroup as well.  first + n greater than
+ *                          n_vectors * 1024 (also when n == 0), or a first + n that overflows, returns ALPGPU_ERR_INVALID and nothing is enqueued (first
+ *                          and n are host values: the check is made on the host).
+ * Both: n == 0 with otherwise valid arguments returns ALPGPU_OK and launches nothing.  A NULL ctx, col or d_out with n > 0 (gather: or a NULL d_idx)
+ * returns ALPGPU_ERR_INVALID.  One kernel launch, asynchronous on the context's stream; d_out needs no alignment beyond its value type.
+ * TRUST: as for alpgpu_decode_f64, the descriptors are followed as found.  One more precondition: within each vector the exception positions
+ * strictly ascend.  Every encoder of this library writes them so (as does the reference), and the store decode's rank lookup assumes it too, but
+ * alpgpu_column_validate does not check the order.
+ * Read-only and stateless: no host synchronisation, and none of what the context remembers about columns (segment tables, the learned sizes of
+ * unhinted decodes, the progress word, the read-ahead) is read or written.  So both are safe inside a stream capture, and a decode planned before a
+ * gather is planned the same way after it. */
+int alpgpu_gather_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const int64_t* d_idx, uint64_t n, double* d_out);
+int alpgpu_gather_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const int64_t* d_idx, uint64_t n, float* d_out);
+int alpgpu_decode_slice_f64(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, double* d_out);
+int alpgpu_decode_slice_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, float* d_out);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
