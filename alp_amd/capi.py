@@ -113,6 +113,10 @@ _sig("alpgpu_gather_f64", _int, _vp, C.POINTER(CColumn), _vp, _u64, _vp)
 _sig("alpgpu_gather_f32", _int, _vp, C.POINTER(CColumn), _vp, _u64, _vp)
 _sig("alpgpu_decode_slice_f64", _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp)
 _sig("alpgpu_decode_slice_f32", _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp)
+_sig("alpgpu_select_scratch_bytes", _u64, _u64)
+_sig("alpgpu_select_range_f64", _int, _vp, C.POINTER(CColumn), _u64, _u64, C.c_double, C.c_double, _vp, _vp, _u64, _vp, _vp)
+_sig("alpgpu_select_range_f32", _int, _vp, C.POINTER(CColumn), _u64, _u64, C.c_float, C.c_float, _vp, _vp, _u64, _vp, _vp)
+_sig("alpgpu_debug_select_scan", _int, _vp, _vp, _u64, _vp, _vp, _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -549,6 +553,67 @@ class Context:
         assert out.is_contiguous() and out.numel() >= n and out.dtype == tdt
         self._call("decode_slice", col.dtype, C.byref(col.c), first, n, _vp(out.data_ptr()))
         return out
+
+    # ---- selection (include/alpgpu.h: alpgpu_select_range_*) --------------------------------------------------------
+    def _check_tensor(self, t, dtype, name):
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or t.device.index != self.device or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor on cuda:%d" % (name, str(dtype).replace("torch.", ""), self.device))
+
+    def select_scratch(self, col: "DeviceColumn"):
+        """a scratch tensor for select_range_into on this column (alpgpu_select_scratch_bytes; torch allocations are at least 16-byte aligned)"""
+        import torch
+        return torch.empty(lib.alpgpu_select_scratch_bytes(col.n_vectors), dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    def select_range_into(self, col: "DeviceColumn", lo: float, hi: float, idx_out, count_out, vals_out=None, first: int = 0, n: int = None, scratch=None):
+        """the raw form of alpgpu_select_range_*: the ascending value indices r of [first, first + n) (n None: to the column's end) whose value x
+        has lo <= x <= hi go to idx_out (int64; its numel() is the capacity, None or empty: a count), their values to vals_out (optional, at
+        least as long), their number to count_out (one int64, the full count also beyond the capacity).  Nothing is synchronised and nothing
+        read back; with a scratch given (select_scratch) nothing is allocated either, so the call can be captured into a graph."""
+        import torch
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        self._check_tensor(count_out, torch.int64, "count_out")
+        if count_out.numel() < 1:
+            raise ValueError("count_out must hold one int64")
+        capacity = 0
+        if idx_out is not None:
+            self._check_tensor(idx_out, torch.int64, "idx_out")
+            capacity = idx_out.numel()
+        if vals_out is not None:
+            self._check_tensor(vals_out, tdt, "vals_out")
+            if vals_out.numel() < capacity:
+                raise ValueError("vals_out is shorter than idx_out")
+        first = int(first)
+        n = col.n_vectors * VECTOR_SIZE - first if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        if scratch is None:
+            scratch = self.select_scratch(col)
+        else:
+            self._check_tensor(scratch, torch.uint8, "scratch")
+            if scratch.numel() < lib.alpgpu_select_scratch_bytes(col.n_vectors) or scratch.data_ptr() % 16:
+                raise ValueError("scratch must hold alpgpu_select_scratch_bytes(n_vectors) bytes, 16-byte aligned")
+        self._call("select_range", col.dtype, C.byref(col.c), first, n, lo, hi, _vp(idx_out.data_ptr()) if capacity else None,
+                   _vp(vals_out.data_ptr()) if vals_out is not None and capacity else None, capacity, _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
+
+    def select_range(self, col: "DeviceColumn", lo: float, hi: float, first: int = 0, n: int = None, values: bool = False, capacity: int = None):
+        """the ascending value indices of [first, first + n) whose value lies in [lo, hi] as an int64 tensor, or (indices, values) with
+        values=True.  capacity None: the call counts first (one device-to-host read of the count, which synchronises the stream), allocates
+        exactly and selects; with a capacity given there is no read-back before the selection, one after it to trim the result to
+        min(count, capacity)."""
+        import torch
+        dev = f"cuda:{self.device}"
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        scratch = self.select_scratch(col)
+        if capacity is None:
+            self.select_range_into(col, lo, hi, None, count, first=first, n=n, scratch=scratch)
+            capacity = int(count.item())
+        idx = torch.empty(int(capacity), dtype=torch.int64, device=dev)
+        vals = torch.empty(int(capacity), dtype=tdt, device=dev) if values else None
+        self.select_range_into(col, lo, hi, idx, count, vals, first=first, n=n, scratch=scratch)
+        k = min(int(count.item()), int(capacity))
+        return (idx[:k], vals[:k]) if values else idx[:k]
 
     # ---- batch primitives, 32-bit words (float) --------------------------------------------------------
     def ffor_i32(self, vals, packed, bw, base):

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "alp_device_f32.hpp"
+#include "lane_field.hpp"
 #include "launch.hpp"
 
 namespace alpgpu {
@@ -37,22 +38,6 @@ __device__ __forceinline__ int exception_rank(const uint16_t* __restrict__ pos, 
 		len                 = less ? len - half - 1 : half;
 	}
 	return hit;
-}
-
-// Field `row` (width bw) of a FastLanes lane stream of U words that lie STRIDE words apart from w on.  The second word is read only if the
-// field reaches into it: nothing past the vector's words is read.
-template <class U, int STRIDE>
-__device__ __forceinline__ U lane_field(const U* __restrict__ w, uint32_t row, uint32_t bw) {
-	typedef typename std::conditional<sizeof(U) == 8, uint64_t, uint32_t>::type C; // (u16 lanes are computed in 32 bits)
-	constexpr uint32_t kBits = 8 * sizeof(U);
-	if (bw == 0) { return 0; }
-	const uint32_t bit = row * bw;
-	const uint32_t s   = bit & (kBits - 1);
-	const U*       at  = w + STRIDE * (bit / kBits);
-	const C        lo  = at[0];
-	const C        hi  = s + bw > kBits ? C(at[STRIDE]) : C(0);
-	const C        msk = bw >= kBits ? C(static_cast<U>(~U(0))) : ((C(1) << bw) - C(1));
-	return static_cast<U>(((lo >> s) | ((hi << 1) << (kBits - 1 - s))) & msk); // (hi << (kBits - s)) without the undefined shift by kBits when s == 0
 }
 
 // the bits alpgpu_decode_* writes for value p of vector v (VB = 8: double, 4: float)

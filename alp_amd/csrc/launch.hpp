@@ -40,6 +40,14 @@ int launch_tree_sum(hipStream_t stream, const double* d_in, uint64_t n, double* 
 // nullptr; the caller checked the range), k < n; value_bytes 8 or 4
 int launch_gather(hipStream_t stream, const alpgpu_column* col, const int64_t* d_idx, uint64_t first, uint64_t n, void* d_out, int value_bytes);
 
+// select_kernels.hip: the value indices r of [first, first + n) (n > 0, range checked by the caller) whose value x has lo <= x <= hi, ascending, into
+// d_idx (and the values into d_vals, nullable) up to capacity; *d_count = how many qualify; d_scratch: select_scratch_bytes(col->n_vectors) bytes
+uint64_t select_scratch_bytes(uint64_t n_vectors);
+int launch_select_range(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int64_t* d_idx, void* d_vals, uint64_t capacity,
+                        uint64_t* d_count, void* d_scratch, int value_bytes);
+// ... its scan alone: d_offsets[i] = d_counts[0] + ... + d_counts[i - 1], *d_total = the sum of all n (n > 0); d_levels: select_scratch_bytes(n) bytes suffice
+int launch_select_scan(hipStream_t stream, const uint32_t* d_counts, uint64_t n, uint64_t* d_offsets, uint64_t* d_total, uint64_t* d_levels);
+
 // guard_kernels.hip
 int launch_validate_column(hipStream_t stream, const alpgpu_column* col, uint32_t value_bytes, unsigned long long* d_first_bad);
 int launch_count_rd_rowgroups(hipStream_t stream, const alpgpu_column* col, uint64_t* d_count);

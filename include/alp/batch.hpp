@@ -17,6 +17,7 @@
 #define ALP_BATCH_HPP
 #include <cstring>
 #include <stdexcept>
+#include <string>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -390,51 +391,100 @@ struct column {
 		}
 		return out;
 	}
+	// Device buffers freed with the object.  A type of its own: as a complete member (or local) its destructor also runs when the code that fills
+	// it throws half way, a constructor of the owner included.
+	struct device_buffers {
+		std::vector<void*> p;
+		device_buffers() = default;
+		device_buffers(const device_buffers&)            = delete;
+		device_buffers& operator=(const device_buffers&) = delete;
+		~device_buffers() {
+			for (void* q : p) { alpgpu_free(context(), q); }
+		}
+		void* get(size_t bytes) {
+			void* q = nullptr;
+			check(alpgpu_malloc(context(), &q, bytes ? bytes : 1), "alpgpu_malloc");
+			p.push_back(q);
+			return q;
+		}
+	};
+	// A serialized column uploaded whole for the calls that read it where it lies (take, select_range): buffers sized by the blob's header and freed
+	// with the object — also when the upload throws (a blob alpgpu_column_from_blob* refuses, an allocation that fails): `buf` is complete by then.
+	// alpgpu_column_from_blob* checks the header and every descriptor against the buffers before it copies anything.
+	struct uploaded_column {
+		device_buffers buf;
+		alpgpu_column  col {};
+		uint64_t       n_values = 0;
+		uploaded_column(const uint8_t* blob, size_t size, const std::string& who) {
+			if (size < sizeof(alpgpu_blob_header)) { throw std::runtime_error(who + ": blob shorter than its header"); }
+			alpgpu_blob_header h;
+			std::memcpy(&h, blob, sizeof(h));
+			if (h.n_vectors > (uint64_t(1) << 40) || h.packed_bytes > (uint64_t(1) << 50) || h.exc_bytes > (uint64_t(1) << 50) ||
+			    alpgpu_blob_size(h.n_vectors, h.packed_bytes, h.exc_bytes) > size) { // (nothing is allocated beyond what the blob itself holds)
+				throw std::runtime_error(who + ": blob header is implausible");
+			}
+			col.n_vectors       = h.n_vectors;
+			col.n_rowgroups     = (h.n_vectors + config::N_VECTORS_PER_ROWGROUP - 1) / config::N_VECTORS_PER_ROWGROUP;
+			col.d_rowgroups     = static_cast<alpgpu_rowgroup_state*>(get(col.n_rowgroups * sizeof(alpgpu_rowgroup_state)));
+			col.d_vectors       = static_cast<alpgpu_vector_desc*>(get(col.n_vectors * sizeof(alpgpu_vector_desc)));
+			col.packed_capacity = h.packed_bytes;
+			col.d_packed        = static_cast<uint8_t*>(get(h.packed_bytes));
+			col.exc_capacity    = h.exc_bytes;
+			col.d_exc           = static_cast<uint8_t*>(get(h.exc_bytes));
+			col.d_totals        = static_cast<uint64_t*>(get(8 * sizeof(uint64_t)));
+			check(sizeof(PT) == 8 ? alpgpu_column_from_blob(context(), blob, size, &col, &n_values) : alpgpu_column_from_blob_f32(context(), blob, size, &col, &n_values),
+			      "alpgpu_column_from_blob");
+		}
+		void* get(size_t bytes) { return buf.get(bytes); }
+	};
 	// The n values at value indices idx[0 .. n) of a serialized column (include/alpgpu.h: alpgpu_gather_*): the blob goes up whole (validated by
 	// alpgpu_column_from_blob*), the values are gathered where they lie and only they come back.  An index at or past n_vectors * 1024 gives the
 	// canonical quiet NaN.
 	static std::vector<PT> take(const uint8_t* blob, size_t size, const uint64_t* idx, size_t n) {
-		if (size < sizeof(alpgpu_blob_header)) { throw std::runtime_error("alp::gpu::column::take: blob shorter than its header"); }
-		alpgpu_blob_header h;
-		std::memcpy(&h, blob, sizeof(h));
+		uploaded_column up(blob, size, "alp::gpu::column::take");
 		std::vector<PT> out(n);
-		// buffers sized by the header; alpgpu_column_from_blob* checks the header and every descriptor against them before it copies anything
-		struct device_buffers {
-			std::vector<void*> p;
-			~device_buffers() {
-				for (void* q : p) { alpgpu_free(context(), q); }
-			}
-			void* get(size_t bytes) {
-				void* q = nullptr;
-				check(alpgpu_malloc(context(), &q, bytes ? bytes : 1), "alpgpu_malloc");
-				p.push_back(q);
-				return q;
-			}
-		} buf;
-		if (h.n_vectors > (uint64_t(1) << 40) || h.packed_bytes > (uint64_t(1) << 50) || h.exc_bytes > (uint64_t(1) << 50) ||
-		    alpgpu_blob_size(h.n_vectors, h.packed_bytes, h.exc_bytes) > size) { // (nothing is allocated beyond what the blob itself holds)
-			throw std::runtime_error("alp::gpu::column::take: blob header is implausible");
-		}
-		alpgpu_column col {};
-		col.n_vectors       = h.n_vectors;
-		col.n_rowgroups     = (h.n_vectors + config::N_VECTORS_PER_ROWGROUP - 1) / config::N_VECTORS_PER_ROWGROUP;
-		col.d_rowgroups     = static_cast<alpgpu_rowgroup_state*>(buf.get(col.n_rowgroups * sizeof(alpgpu_rowgroup_state)));
-		col.d_vectors       = static_cast<alpgpu_vector_desc*>(buf.get(col.n_vectors * sizeof(alpgpu_vector_desc)));
-		col.packed_capacity = h.packed_bytes;
-		col.d_packed        = static_cast<uint8_t*>(buf.get(h.packed_bytes));
-		col.exc_capacity    = h.exc_bytes;
-		col.d_exc           = static_cast<uint8_t*>(buf.get(h.exc_bytes));
-		col.d_totals        = static_cast<uint64_t*>(buf.get(8 * sizeof(uint64_t)));
-		uint64_t n_values   = 0;
-		check(sizeof(PT) == 8 ? alpgpu_column_from_blob(context(), blob, size, &col, &n_values) : alpgpu_column_from_blob_f32(context(), blob, size, &col, &n_values),
-		      "alpgpu_column_from_blob");
 		if (n == 0) { return out; }
-		int64_t* d_idx = static_cast<int64_t*>(buf.get(n * sizeof(int64_t)));
-		PT*      d_out = static_cast<PT*>(buf.get(n * sizeof(PT)));
+		int64_t* d_idx = static_cast<int64_t*>(up.get(n * sizeof(int64_t)));
+		PT*      d_out = static_cast<PT*>(up.get(n * sizeof(PT)));
 		check(alpgpu_memcpy_h2d(context(), d_idx, idx, n * sizeof(int64_t)), "alpgpu_memcpy_h2d"); // (an index >= 2^63 reads as negative: out of range either way)
-		check(sizeof(PT) == 8 ? alpgpu_gather_f64(context(), &col, d_idx, n, reinterpret_cast<double*>(d_out)) : alpgpu_gather_f32(context(), &col, d_idx, n, reinterpret_cast<float*>(d_out)),
+		check(sizeof(PT) == 8 ? alpgpu_gather_f64(context(), &up.col, d_idx, n, reinterpret_cast<double*>(d_out)) : alpgpu_gather_f32(context(), &up.col, d_idx, n, reinterpret_cast<float*>(d_out)),
 		      "alpgpu_gather");
 		check(alpgpu_memcpy_d2h(context(), out.data(), d_out, n * sizeof(PT)), "alpgpu_memcpy_d2h");
+		return out;
+	}
+	// The values x of a serialized column with lo <= x <= hi and their value indices, ascending (include/alpgpu.h: alpgpu_select_range_*): the blob
+	// goes up whole, the predicate is evaluated on the compressed column over [0, n_values) — the tail padding of the last vector never qualifies —
+	// and only the selected indices and values come back.  NaN never qualifies; lo > hi selects nothing.
+	struct selection {
+		std::vector<uint64_t> indices;
+		std::vector<PT>       values;
+	};
+	static selection select_range(const uint8_t* blob, size_t size, PT lo, PT hi) {
+		uploaded_column up(blob, size, "alp::gpu::column::select_range");
+		selection       out;
+		if (up.n_values == 0) { return out; }
+		uint64_t* d_count   = static_cast<uint64_t*>(up.get(sizeof(uint64_t)));
+		void*     d_scratch = up.get(alpgpu_select_scratch_bytes(up.col.n_vectors));
+		auto      call      = [&](int64_t* d_idx, PT* d_vals, uint64_t capacity) {
+			if constexpr (sizeof(PT) == 8) {
+				check(alpgpu_select_range_f64(context(), &up.col, 0, up.n_values, lo, hi, d_idx, reinterpret_cast<double*>(d_vals), capacity, d_count, d_scratch),
+				      "alpgpu_select_range_f64");
+			} else {
+				check(alpgpu_select_range_f32(context(), &up.col, 0, up.n_values, lo, hi, d_idx, reinterpret_cast<float*>(d_vals), capacity, d_count, d_scratch),
+				      "alpgpu_select_range_f32");
+			}
+		};
+		uint64_t count = 0;
+		call(nullptr, nullptr, 0); // count first, then allocate exactly
+		check(alpgpu_memcpy_d2h(context(), &count, d_count, sizeof(count)), "alpgpu_memcpy_d2h");
+		if (count == 0) { return out; }
+		int64_t* d_idx  = static_cast<int64_t*>(up.get(count * sizeof(int64_t)));
+		PT*      d_vals = static_cast<PT*>(up.get(count * sizeof(PT)));
+		call(d_idx, d_vals, count);
+		out.indices.resize(count);
+		out.values.resize(count);
+		check(alpgpu_memcpy_d2h(context(), out.indices.data(), d_idx, count * sizeof(int64_t)), "alpgpu_memcpy_d2h");
+		check(alpgpu_memcpy_d2h(context(), out.values.data(), d_vals, count * sizeof(PT)), "alpgpu_memcpy_d2h");
 		return out;
 	}
 };

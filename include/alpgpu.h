@@ -423,6 +423,44 @@ int alpgpu_gather_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const int64_t* 
 int alpgpu_decode_slice_f64(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, double* d_out);
 int alpgpu_decode_slice_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, float* d_out);
 
+/* ---- selection --------------------------------------------------------------------------------------------------------
+ * A range predicate evaluated on the compressed column: which values qualify, as a list of value indices (the numbering of the random-access
+ * section) that alpgpu_gather_* takes as it is — "filter on column A, fetch the matching values of column B" runs on compressed columns:
+ * select_range(A) -> d_idx, gather(B, d_idx).  The decoded column never reaches device memory.
+ * Predicate: value index r qualifies when first <= r < first + n and lo <= x <= hi for x = the decoded value, exceptions patched in — the
+ *   comparison of alpgpu_decode_count_range_*: NaN never qualifies (as a value or as a bound), -0.0 == 0.0, lo > hi selects nothing, +-inf are
+ *   ordinary bounds and ordinary values.  So over the whole column (first = 0, n = n_vectors * 1024) the number of selected indices of vector v
+ *   is d_counts[v] of alpgpu_decode_count_range_* with the same bounds.
+ * Output: *d_count (one uint64_t in device memory) = the number of qualifying values, also when it exceeds capacity.  d_idx[j] for
+ *   j < min(*d_count, capacity) = the j-th qualifying index in ASCENDING order.  d_vals (may be NULL): d_vals[j] = that value, bit for bit what
+ *   alpgpu_decode_* writes at d_out[d_idx[j]] (a selected -0.0 keeps its sign, a selected exception its bits).  Nothing is written at or behind
+ *   capacity, and nothing at j >= *d_count.  The result is a function of the column and the arguments only: it does not depend on the launch
+ *   shape, on how workgroups are scheduled or on the order they arrive in (positions come from a prefix sum, never from an atomic).
+ * Range: first and n are host values and checked on the host like alpgpu_decode_slice_*: first + n greater than n_vectors * 1024, or
+ *   overflowing, returns ALPGPU_ERR_INVALID and nothing is enqueued.  The tail padding of the last vector is excluded by passing n = n_values.
+ *   n == 0 is valid: *d_count becomes 0 (that one write is enqueued).
+ * Arguments: capacity == 0 is valid and makes the call a count (d_idx and d_vals may then be NULL).  A NULL ctx, col or d_count, a NULL
+ *   d_scratch with n > 0, or a NULL d_idx with capacity > 0 returns ALPGPU_ERR_INVALID.
+ * Scratch: caller-owned like every buffer of this ABI (the context's scan workspace grows by allocation and orders itself with events, which
+ *   would make the call stateful).  alpgpu_select_scratch_bytes(col->n_vectors) bytes of device memory, 16-byte aligned; what they hold before
+ *   does not matter, what they hold after is unspecified.  That is 12 bytes per vector (a u64 offset and a u32 count) plus the block sums of
+ *   the prefix sum, in all at most 12 * n_vectors + n_vectors / 100 + 256 bytes (n_vectors above 2^54: UINT64_MAX); never 0.
+ * Asynchronous and stateless, as the random access is: everything is enqueued on the context's stream and on that stream only (a captured graph
+ *   gets no parallel branches), there is no host synchronisation and no allocation, and none of what the context remembers about columns
+ *   (segment tables, the learned sizes of unhinted decodes, the progress word, the read-ahead) is read or written.  Safe inside a stream
+ *   capture.  No workgroup waits for another: the phases (count per vector, prefix sum, emit) are separate launches.
+ * Cost: the compressed column is read once, and once more for the vectors that hold a qualifying value; 8 (+ 8 or 4) bytes are written per
+ *   selected value.
+ * TRUST: as for alpgpu_decode_* and alpgpu_gather_* (descriptors followed as found; exception positions ascend within a vector). */
+uint64_t alpgpu_select_scratch_bytes(uint64_t n_vectors);
+int alpgpu_select_range_f64(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int64_t* d_idx, double* d_vals,
+                            uint64_t capacity, uint64_t* d_count, void* d_scratch);
+int alpgpu_select_range_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, float lo, float hi, int64_t* d_idx, float* d_vals,
+                            uint64_t capacity, uint64_t* d_count, void* d_scratch);
+/* debug / test: the selection's prefix sum alone, so that its deeper levels can be exercised without a column of millions of vectors.
+ * d_offsets[i] = d_counts[0] + ... + d_counts[i - 1] (i < n, n > 0), *d_total = the sum of all n; d_scratch: alpgpu_select_scratch_bytes(n) bytes. */
+int alpgpu_debug_select_scan(alpgpu_ctx* ctx, const uint32_t* d_counts, uint64_t n, uint64_t* d_offsets, uint64_t* d_total, void* d_scratch);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
