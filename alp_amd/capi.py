@@ -117,6 +117,11 @@ _sig("alpgpu_select_scratch_bytes", _u64, _u64)
 _sig("alpgpu_select_range_f64", _int, _vp, C.POINTER(CColumn), _u64, _u64, C.c_double, C.c_double, _vp, _vp, _u64, _vp, _vp)
 _sig("alpgpu_select_range_f32", _int, _vp, C.POINTER(CColumn), _u64, _u64, C.c_float, C.c_float, _vp, _vp, _u64, _vp, _vp)
 _sig("alpgpu_debug_select_scan", _int, _vp, _vp, _u64, _vp, _vp, _vp)
+for _t, _ft in (("f64", C.c_double), ("f32", C.c_float)):
+    _sig("alpgpu_zone_map_" + _t, _int, _vp, C.POINTER(CColumn), _vp)
+    _sig("alpgpu_zone_map_of_values_" + _t, _int, _vp, _vp, _u64, _vp)
+    _sig("alpgpu_zones_minmax_" + _t, _int, _vp, _vp, _u64, _vp)
+    _sig("alpgpu_select_range_zoned_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _u64, _u64, _ft, _ft, _vp, _vp, _u64, _vp, _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -565,11 +570,12 @@ class Context:
         import torch
         return torch.empty(lib.alpgpu_select_scratch_bytes(col.n_vectors), dtype=torch.uint8, device=f"cuda:{self.device}")
 
-    def select_range_into(self, col: "DeviceColumn", lo: float, hi: float, idx_out, count_out, vals_out=None, first: int = 0, n: int = None, scratch=None):
+    def select_range_into(self, col: "DeviceColumn", lo: float, hi: float, idx_out, count_out, vals_out=None, first: int = 0, n: int = None, scratch=None, zones=None):
         """the raw form of alpgpu_select_range_*: the ascending value indices r of [first, first + n) (n None: to the column's end) whose value x
         has lo <= x <= hi go to idx_out (int64; its numel() is the capacity, None or empty: a count), their values to vals_out (optional, at
         least as long), their number to count_out (one int64, the full count also beyond the capacity).  Nothing is synchronised and nothing
-        read back; with a scratch given (select_scratch) nothing is allocated either, so the call can be captured into a graph."""
+        read back; with a scratch given (select_scratch) nothing is allocated either, so the call can be captured into a graph.
+        zones (zone_map(col)): alpgpu_select_range_zoned_* — the same result, vectors whose record excludes or contains them are not decoded."""
         import torch
         tdt = torch.float64 if col.dtype == "f64" else torch.float32
         self._check_tensor(count_out, torch.int64, "count_out")
@@ -593,10 +599,15 @@ class Context:
             self._check_tensor(scratch, torch.uint8, "scratch")
             if scratch.numel() < lib.alpgpu_select_scratch_bytes(col.n_vectors) or scratch.data_ptr() % 16:
                 raise ValueError("scratch must hold alpgpu_select_scratch_bytes(n_vectors) bytes, 16-byte aligned")
-        self._call("select_range", col.dtype, C.byref(col.c), first, n, lo, hi, _vp(idx_out.data_ptr()) if capacity else None,
-                   _vp(vals_out.data_ptr()) if vals_out is not None and capacity else None, capacity, _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
+        outs = (_vp(idx_out.data_ptr()) if capacity else None, _vp(vals_out.data_ptr()) if vals_out is not None and capacity else None, capacity,
+                _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
+        if zones is None:
+            self._call("select_range", col.dtype, C.byref(col.c), first, n, lo, hi, *outs)
+        else:
+            self._check_zones(zones, tdt, col.n_vectors)
+            self._call("select_range_zoned", col.dtype, C.byref(col.c), _vp(zones.data_ptr()), first, n, lo, hi, *outs)
 
-    def select_range(self, col: "DeviceColumn", lo: float, hi: float, first: int = 0, n: int = None, values: bool = False, capacity: int = None):
+    def select_range(self, col: "DeviceColumn", lo: float, hi: float, first: int = 0, n: int = None, values: bool = False, capacity: int = None, zones=None):
         """the ascending value indices of [first, first + n) whose value lies in [lo, hi] as an int64 tensor, or (indices, values) with
         values=True.  capacity None: the call counts first (one device-to-host read of the count, which synchronises the stream), allocates
         exactly and selects; with a capacity given there is no read-back before the selection, one after it to trim the result to
@@ -607,13 +618,62 @@ class Context:
         count = torch.empty(1, dtype=torch.int64, device=dev)
         scratch = self.select_scratch(col)
         if capacity is None:
-            self.select_range_into(col, lo, hi, None, count, first=first, n=n, scratch=scratch)
+            self.select_range_into(col, lo, hi, None, count, first=first, n=n, scratch=scratch, zones=zones)
             capacity = int(count.item())
         idx = torch.empty(int(capacity), dtype=torch.int64, device=dev)
         vals = torch.empty(int(capacity), dtype=tdt, device=dev) if values else None
-        self.select_range_into(col, lo, hi, idx, count, vals, first=first, n=n, scratch=scratch)
+        self.select_range_into(col, lo, hi, idx, count, vals, first=first, n=n, scratch=scratch, zones=zones)
         k = min(int(count.item()), int(capacity))
         return (idx[:k], vals[:k]) if values else idx[:k]
+
+    # ---- zone maps (include/alpgpu.h: alpgpu_zone_map_*, alpgpu_zones_minmax_*) ---------------------------------------
+    def _check_zones(self, zones, dtype, n_vectors):
+        self._check_tensor(zones, dtype, "zones")
+        if zones.dim() != 2 or zones.shape[1] != 2 or zones.shape[0] < n_vectors or zones.data_ptr() % (2 * zones.element_size()):
+            raise ValueError("zones must be a [n_vectors, 2] tensor {min, max}, aligned to its records (16 bytes for float64, 8 for float32)")
+
+    def zone_map(self, col: "DeviceColumn", out=None):
+        """the zone map of an encoded column, a [n_vectors, 2] tensor of the column's value type: row v = {min, max} of vector v's decoded
+        values, NaNs ignored, -0.0 < +0.0, {+inf, -inf} for a vector of NaNs only (alpgpu_zone_map_f64 / _f32)"""
+        import torch
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        if out is None:
+            out = torch.empty((col.n_vectors, 2), dtype=tdt, device=f"cuda:{self.device}")
+        else:
+            self._check_zones(out, tdt, col.n_vectors)
+        self._call("zone_map", col.dtype, C.byref(col.c), _vp(out.data_ptr()))
+        return out
+
+    def zone_map_of_values(self, x, out=None):
+        """the same records from the raw values: x is a contiguous float64 / float32 tensor of whole vectors on this context's device"""
+        import torch
+        if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float64, torch.float32):
+            raise ValueError("x must be a float64 or float32 tensor")
+        self._check_tensor(x, x.dtype, "x")
+        if x.numel() % VECTOR_SIZE or x.data_ptr() % 16:
+            raise ValueError("x must hold whole vectors of 1024 values, 16-byte aligned")
+        nv = x.numel() // VECTOR_SIZE
+        if out is None:
+            out = torch.empty((nv, 2), dtype=x.dtype, device=x.device)
+        else:
+            self._check_zones(out, x.dtype, nv)
+        self._call("zone_map_of_values", self._sfx(x), _vp(x.data_ptr()), nv, _vp(out.data_ptr()))
+        return out
+
+    def column_minmax(self, zones, out=None):
+        """the column's {min, max} as a 2-element tensor: the reduction of a zone map (alpgpu_zones_minmax_f64 / _f32); {+inf, -inf} for no records"""
+        import torch
+        if not isinstance(zones, torch.Tensor) or zones.dtype not in (torch.float64, torch.float32):
+            raise ValueError("zones must be a float64 or float32 tensor")
+        self._check_zones(zones, zones.dtype, 0)
+        if out is None:
+            out = torch.empty(2, dtype=zones.dtype, device=zones.device)
+        else:
+            self._check_tensor(out, zones.dtype, "out")
+            if out.numel() < 2:
+                raise ValueError("out must hold two values")
+        self._call("zones_minmax", self._sfx(zones), _vp(zones.data_ptr()), zones.shape[0], _vp(out.data_ptr()))
+        return out
 
     # ---- batch primitives, 32-bit words (float) --------------------------------------------------------
     def ffor_i32(self, vals, packed, bw, base):

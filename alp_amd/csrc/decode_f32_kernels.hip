@@ -16,6 +16,7 @@
 #include "decode_f32_device.hpp"
 #include "decode_policy.hpp"
 #include "launch.hpp"
+#include "wave_minmax.hpp"
 #include <cstdlib>
 
 namespace alpgpu {
@@ -136,6 +137,8 @@ __device__ __forceinline__ RdDict load_vector_consts_f32(const alpgpu_rowgroup_s
 // SINK (as in decode_kernels.hip) = kSinkStoreF: the quad is stored.  kSinkSumF: its four values are widened to double
 // (exact) and added to `acc` in index order.  kSinkCountF: `acc` counts the values v with lo <= v <= hi (NaN never does).
 constexpr int kSinkStoreF = 0, kSinkSumF = 1, kSinkCountF = 2;
+// kSinkMinMaxF (alpgpu_zone_map_f32): mm[0] / mm[1] = the smallest / largest value that is not a NaN (wave_minmax.hpp: minmax_take); `acc` is unused.
+constexpr int kSinkMinMaxF = 3;
 __device__ __constant__ const uint32_t kShortcutBoundF[11] = {16777216u, 16777216u, 16777216u, 2147483u, 214748u, 21474u, 2147u, 214u, 21u, 2u, 0u};
 // HBM_EXC = false: the caller knows (wave-uniform) that every exception value of the vector is in the LDS stage — this instance has no load from HBM in it, so
 // the compiler puts no s_waitcnt vmcnt(0) in front of the quad's store (stores count in vmcnt on gfx9: with the rare load in the code, every store of a
@@ -143,7 +146,7 @@ __device__ __constant__ const uint32_t kShortcutBoundF[11] = {16777216u, 1677721
 template <bool NT_STORE, int SINK, class LDS, bool HBM_EXC = true>
 __device__ __forceinline__ void finish_quad_f32(const LDS& L, const QuadWords& w, const alpgpu_vector_desc& d, const RdDict& dict, const ExcMaskF& em,
                                                 const uint8_t* __restrict__ rec, float* __restrict__ dst, int tid, int wave, int lane, double* acc,
-                                                float range_lo, float range_hi) {
+                                                float range_lo, float range_hi, float* mm = nullptr) {
 	const int bw   = d.bw;
 	const int cnt  = d.exc_cnt;
 	const int a    = tid & 7;
@@ -211,10 +214,10 @@ __device__ __forceinline__ void finish_quad_f32(const LDS& L, const QuadWords& w
 			for (int c = 0; c < 4; ++c) { out[c] = __float_as_uint(decode_value_f32(static_cast<int32_t>(q[c] + base), fact, frac)); }
 		}
 		if constexpr (kApart) {
-			// (the sinks: an exception position contributes +0.0f — (double)(+0.0f) added to a partial that is never -0.0 leaves it as it is — or, for COUNT, a NaN)
+			// (the sinks: an exception position contributes +0.0f — (double)(+0.0f) added to a partial that is never -0.0 leaves it as it is — or, for COUNT and MIN / MAX, a NaN)
 #pragma unroll
 			for (int c = 0; c < 4; ++c) {
-				if (hits & (1u << c)) { out[c] = SINK == kSinkCountF ? 0x7FC00000u : 0u; }
+				if (hits & (1u << c)) { out[c] = SINK == kSinkSumF ? 0u : 0x7FC00000u; }
 			}
 		} else if (hits) { // (a branch-free form — every lane reads the staged value it WOULD take, then selects — was measured in round 5: no difference, 64 VGPRs; profiles/r05_float_sink.txt)
 #pragma unroll
@@ -257,6 +260,9 @@ __device__ __forceinline__ void finish_quad_f32(const LDS& L, const QuadWords& w
 			const float v = __uint_as_float(out[c]);
 			*acc += (v >= range_lo && v <= range_hi) ? 1.0 : 0.0;
 		}
+	} else if constexpr (SINK == kSinkMinMaxF) {
+#pragma unroll
+		for (int c = 0; c < 4; ++c) { minmax_take(mm[0], mm[1], __uint_as_float(out[c])); }
 	} else {
 		store_quad<NT_STORE>(dst + 4 * tid, out);
 		// (the two instances' stores must stay two stores: merged into one behind the join of their callers' branch, the wait for the rare load is back in front of it)
@@ -285,6 +291,20 @@ __device__ __forceinline__ void sink_exception_values_f32(const LDS& L, const ui
 		} else {
 			total += static_cast<double>(v);
 		}
+	}
+}
+
+// ... the same pass for MIN / MAX: an exception value that is a NaN is dropped like any other NaN of the vector
+template <class LDS>
+__device__ __forceinline__ void minmax_exception_values_f32(const LDS& L, const uint8_t* __restrict__ rec, int cnt, int lane, float& mn, float& mx) {
+	for (int j = lane; j < cnt; j += 64) {
+		uint32_t bits;
+		if (j < kExcStageF) {
+			bits = reinterpret_cast<const uint32_t*>(L.excv)[j];
+		} else {
+			bits = reinterpret_cast<const uint32_t*>(rec)[j];
+		}
+		minmax_take(mn, mx, __uint_as_float(bits));
 	}
 }
 
@@ -545,6 +565,15 @@ __global__ __launch_bounds__(kDecThreadsF, 8) void k_sink_direct_f32(const alpgp
 		}
 		return;
 	}
+	if constexpr (SINK == kSinkMinMaxF) { // the record {min, max}: the quads, then an ALP vector's exception values, then the wavefront; one 8-byte store per vector
+		float mm[2] = {__builtin_inff(), -__builtin_inff()};
+#pragma unroll
+		for (int q = 0; q < 4; ++q) { finish_quad_f32<false, SINK>(L, w[q], d, dict, em, rec, nullptr, 64 * q + lane, q, lane, nullptr, 0.0f, 0.0f, mm); }
+		if (is_alp && cnt > 0) { minmax_exception_values_f32(L, rec, cnt, lane, mm[0], mm[1]); }
+		wave_minmax_f32(mm[0], mm[1]);
+		if (lane == 0) { reinterpret_cast<float2*>(out)[v] = make_float2(mm[0], mm[1]); }
+		return;
+	}
 	double part[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
 	for (int q = 0; q < 4; ++q) { finish_quad_f32<false, SINK>(L, w[q], d, dict, em, rec, nullptr, 64 * q + lane, q, lane, &part[q], lo, hi); }
@@ -583,6 +612,16 @@ int launch_sink_direct_f32(hipStream_t stream, const alpgpu_column* col, float l
 		} else {
 			hipLaunchKernelGGL((k_sink_direct_f32<kSinkSumF>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_out), n, off, 0.0f, 0.0f, static_cast<uint64_t*>(nullptr), 0ull);
 		}
+	}
+	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
+}
+
+// d_zones[v] = {min, max} of vector v's decoded values, NaNs ignored (include/alpgpu.h: zone maps); n_vectors > 0
+int launch_zone_map_f32(hipStream_t stream, const alpgpu_column* col, void* d_zones) {
+	const uint64_t n = col->n_vectors, per_wg = kDecThreadsF / 64, n_wg = (n + per_wg - 1) / per_wg, kMaxGrid = 1ull << 30;
+	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
+		hipLaunchKernelGGL((k_sink_direct_f32<kSinkMinMaxF>), dim3(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), dim3(kDecThreadsF), 0, stream, col->d_vectors,
+		                   col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_zones), n, off, 0.0f, 0.0f, static_cast<uint64_t*>(nullptr), 0ull);
 	}
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }

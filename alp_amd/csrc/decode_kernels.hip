@@ -30,6 +30,7 @@
 #include "alp_device.hpp"
 #include "decode_policy.hpp"
 #include "launch.hpp"
+#include "wave_minmax.hpp"
 #include <cstdlib>
 
 namespace alpgpu {
@@ -169,11 +170,21 @@ constexpr int kSinkStore = 0, kSinkSum = 1, kSinkCount = 2;
 // kSinkProbe (alpgpu_debug_decode_probe): the consumers' memory traffic and latency chain without the unpack — descriptors, packed
 // words into LDS, exceptions, the barrier — every thread then just adds up the staged 16-byte units it would have unpacked.
 constexpr int kSinkProbe = 3;
+// kSinkMinMax (alpgpu_zone_map_f64): acc[0] / acc[1] = the smallest / largest value that is not a NaN (wave_minmax.hpp: minmax_take).  Minimum and
+// maximum do not depend on the order, so every quarter of a vector goes into the same pair (sink_acc).
+constexpr int kSinkMinMax = 4;
+template <int SINK>
+__device__ __forceinline__ double* sink_acc(double* acc, int quarter) {
+	return SINK == kSinkMinMax ? acc : acc + quarter;
+}
 template <int SINK>
 __device__ __forceinline__ void consume_pair(double ox, double oy, double* acc, double lo, double hi) {
 	if constexpr (SINK == kSinkSum) {
 		*acc += ox;
 		*acc += oy;
+	} else if constexpr (SINK == kSinkMinMax) {
+		minmax_take(acc[0], acc[1], ox);
+		minmax_take(acc[0], acc[1], oy);
 	} else {
 		*acc += (ox >= lo && ox <= hi) ? 1.0 : 0.0; // small integers: exact in double
 		*acc += (oy >= lo && oy <= hi) ? 1.0 : 0.0;
@@ -373,16 +384,16 @@ __device__ __forceinline__ void decode_vector_quarters(const LDS& L, const WORDS
 						const uint32_t uy = __builtin_amdgcn_alignbit(low ? y1 : y2, low ? y0 : y1, sft) & mask32;
 						const double   dx = __longlong_as_double(static_cast<long long>(0x4338000000000000ull | ux)) - magic_mb;
 						const double   dy = __longlong_as_double(static_cast<long long>(0x4338000000000000ull | uy)) - magic_mb;
-						finish_pair(exc_mode, m, (dx * fact_d) * frac, (dy * fact_d) * frac, acc + (b + i) / kStepsPerWave);
+						finish_pair(exc_mode, m, (dx * fact_d) * frac, (dy * fact_d) * frac, sink_acc<SINK>(acc, (b + i) / kStepsPerWave));
 						continue;
 					}
 					const U64Pair u = extract(bw, mask, 8 * m + r0, w[i]);
 					if constexpr (SHORT == 1) {
 						finish_pair(exc_mode, m, ((__longlong_as_double(static_cast<long long>(u.x + kbits)) - kMagic) * fact_d) * frac,
-						            ((__longlong_as_double(static_cast<long long>(u.y + kbits)) - kMagic) * fact_d) * frac, acc + (b + i) / kStepsPerWave);
+						            ((__longlong_as_double(static_cast<long long>(u.y + kbits)) - kMagic) * fact_d) * frac, sink_acc<SINK>(acc, (b + i) / kStepsPerWave));
 					} else {
 						finish_pair(exc_mode, m, decode_value(static_cast<int64_t>(u.x + base), fact, frac), decode_value(static_cast<int64_t>(u.y + base), fact, frac),
-						            acc + (b + i) / kStepsPerWave);
+						            sink_acc<SINK>(acc, (b + i) / kStepsPerWave));
 					}
 				}
 			}
@@ -440,7 +451,7 @@ __device__ __forceinline__ void decode_vector_quarters(const LDS& L, const WORDS
 #pragma unroll
 				for (int i = 0; i < kBatchRd; ++i) {
 					const int      m   = kStepsPerWave * q0 + b + i;
-					double*        acc_q = acc + (b + i) / kStepsPerWave;
+					double*        acc_q = sink_acc<SINK>(acc, (b + i) / kStepsPerWave);
 					U64Pair        u   = extract(rbw, mask, 8 * m + r0, rw[i]);
 					if constexpr (ONLY == 2) { asm volatile("" : "+v"(u.x), "+v"(u.y)); } // (k_sink_direct) the right parts extracted HERE: their four words die before the left parts' work begins
 					const int      s   = ((2 * m + (lane >> 5)) * lbw) & 15;
@@ -464,6 +475,7 @@ __device__ __forceinline__ void decode_vector_quarters(const LDS& L, const WORDS
 					const double oy = __longlong_as_double(static_cast<long long>((l1 << rbw) | u.y));
 					if constexpr (SINK != kSinkStore) {
 						consume_pair<SINK>(ox, oy, acc_q, range_lo, range_hi);
+						if constexpr (ONLY == 2 && SINK == kSinkMinMax) { asm volatile("" : "+v"(acc_q[1])); }
 						if constexpr (ONLY == 2) { asm volatile("" : "+v"(*acc_q)); } // ... and the pair added HERE: left to itself the compiler keeps all sixteen results for the end (208 bytes of scratch, 3.7 x the time)
 					} else {
 						store_pair<NT_STORE>(dst + 64 * m + lane, ox, oy);
@@ -748,6 +760,10 @@ __global__ __launch_bounds__(64 * kDecWaves, kSinkDirectOcc) void k_sink_direct(
 		wave_lds_sync();
 	}
 	double part[kDecWaves] = {0.0, 0.0, 0.0, 0.0};
+	if constexpr (SINK == kSinkMinMax) { // part[0] / part[1]: the lane's minimum / maximum, from the empty interval
+		part[0] = __builtin_inf();
+		part[1] = -__builtin_inf();
+	}
 	if (staged) {
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 		wave_lds_sync();
@@ -761,9 +777,14 @@ __global__ __launch_bounds__(64 * kDecWaves, kSinkDirectOcc) void k_sink_direct(
 		// without them 208 bytes of scratch and 5.4 ms)
 #pragma unroll
 		for (int q = 0; q < kDecWaves; ++q) {
-			decode_vector_quarters<false, SINK, 1, 2>(L, words, d, dict, em, rec, nullptr, q, lane, &part[q], lo, hi);
+			decode_vector_quarters<false, SINK, 1, 2>(L, words, d, dict, em, rec, nullptr, q, lane, sink_acc<SINK>(part, q), lo, hi);
 			asm volatile("" ::: "memory"); // the next quarter's requests stay behind this one's use
 		}
+	}
+	if constexpr (SINK == kSinkMinMax) { // the record {min, max}: one 16-byte store per vector
+		wave_minmax_f64(part[0], part[1]);
+		if (lane == 0) { reinterpret_cast<double2*>(out)[v] = make_double2(part[0], part[1]); }
+		return;
 	}
 	static_assert(kDecWaves == 4, "the documented summation order is for 4 quarters per vector");
 	double total = (part[0] + part[1]) + (part[2] + part[3]);
@@ -788,6 +809,18 @@ int launch_sink_direct(hipStream_t stream, const alpgpu_column* col, double lo, 
 		} else {
 			hipLaunchKernelGGL((k_sink_direct<kSinkSum>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_out), n, off, 0.0, 0.0);
 		}
+	}
+	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
+}
+
+// d_zones[v] = {min, max} of vector v's decoded values, NaNs ignored (include/alpgpu.h: zone maps); n_vectors > 0
+int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones) {
+	const uint64_t n        = col->n_vectors;
+	const uint64_t n_wg     = (n + kDecWaves - 1) / kDecWaves;
+	const uint64_t kMaxGrid = 1ull << 30;
+	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
+		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(64 * kDecWaves);
+		hipLaunchKernelGGL((k_sink_direct<kSinkMinMax>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_zones), n, off, 0.0, 0.0);
 	}
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }

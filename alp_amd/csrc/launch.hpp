@@ -44,9 +44,17 @@ int launch_gather(hipStream_t stream, const alpgpu_column* col, const int64_t* d
 // d_idx (and the values into d_vals, nullable) up to capacity; *d_count = how many qualify; d_scratch: select_scratch_bytes(col->n_vectors) bytes
 uint64_t select_scratch_bytes(uint64_t n_vectors);
 int launch_select_range(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int64_t* d_idx, void* d_vals, uint64_t capacity,
-                        uint64_t* d_count, void* d_scratch, int value_bytes);
+                        uint64_t* d_count, void* d_scratch, int value_bytes, const void* d_zones = nullptr);
 // ... its scan alone: d_offsets[i] = d_counts[0] + ... + d_counts[i - 1], *d_total = the sum of all n (n > 0); d_levels: select_scratch_bytes(n) bytes suffice
 int launch_select_scan(hipStream_t stream, const uint32_t* d_counts, uint64_t n, uint64_t* d_offsets, uint64_t* d_total, uint64_t* d_levels);
+
+// zone maps (include/alpgpu.h).  decode_kernels.hip / decode_f32_kernels.hip: d_zones[v] = {min, max} of vector v, decoded in registers by the
+// one-wavefront sink kernels (col->n_vectors > 0)
+int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones);
+int launch_zone_map_f32(hipStream_t stream, const alpgpu_column* col, void* d_zones);
+// zone_kernels.hip: the same records from the raw values (n_vectors > 0), and the reduction of n records (n >= 0) to d_minmax[2]; value_bytes 8 or 4
+int launch_zone_map_of_values(hipStream_t stream, const void* d_in, uint64_t n_vectors, void* d_zones, int value_bytes);
+int launch_zones_minmax(hipStream_t stream, const void* d_zones, uint64_t n, void* d_minmax, int value_bytes);
 
 // guard_kernels.hip
 int launch_validate_column(hipStream_t stream, const alpgpu_column* col, uint32_t value_bytes, unsigned long long* d_first_bad);

@@ -3,6 +3,8 @@
 //
 // Three phases, ordered by kernel boundaries on one stream (no workgroup ever waits for another):
 //   count  k_select<VB, false>  one wavefront per vector decodes it in registers and writes counts[v] = its number of qualifying values (u32)
+//          k_select<VB, false, const void*>  alpgpu_select_range_zoned_*: the same after a look at the vector's zone record {min, max}; a vector the record
+//                               excludes, or admits whole, is counted from those 16 (8) bytes and its descriptor alone
 //   scan   k_scan_*             exclusive prefix sum counts -> offsets (u64), blocks of 1024, block sums scanned the same way one level up;
 //                               the top level writes *d_count
 //   emit   k_select<VB, true>   one wavefront per vector: counts[v] == 0 -> gone after a 4-byte read; else the same decode again, and every
@@ -43,12 +45,19 @@ constexpr uint32_t kSelBatch   = 8;          // steps of a vector whose words ar
 
 // EMIT = false: counts[k] = qualifying values of vector v0 + k.  EMIT = true: their indices (and values) at offsets[k] + rank.
 // [first, end) is the selected index range; the launch covers exactly the vectors it touches (v0 = first >> 10, n_range of them).
-template <int VB, bool EMIT>
+// ZONES: empty, or one `const void*` behind the other arguments = the zoned count pass of alpgpu_select_range_zoned_*: zones[v] = {min, max} (one
+// record per vector of the COLUMN, indexed by v, not by v - v0) is read first.  A vector whose zone misses [lo, hi] is counted 0 and one whose
+// zone lies inside it, and which cannot hold a NaN, is counted whole; neither has its packed words or exception record read.  (A trailing
+// parameter pack and not a plain parameter: the unzoned instantiations keep their argument list and with it their instructions.)
+__device__ __forceinline__ const void* zone_records(const void* zones) { return zones; }
+template <int VB, bool EMIT, class... ZONES>
 __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc* __restrict__ descs, const alpgpu_rowgroup_state* __restrict__ rgs,
                                                         const uint8_t* __restrict__ packed, const uint8_t* __restrict__ excs, uint64_t v0, uint64_t n_range,
                                                         uint64_t wg_off, uint64_t first, uint64_t end, double range_lo, double range_hi,
                                                         uint32_t* __restrict__ counts, const uint64_t* __restrict__ offsets, int64_t* __restrict__ d_idx,
-                                                        void* __restrict__ d_vals, uint64_t capacity) {
+                                                        void* __restrict__ d_vals, uint64_t capacity, ZONES... zones) {
+	constexpr bool ZONED = sizeof...(ZONES) == 1;
+	static_assert(sizeof...(ZONES) <= 1 && !(ZONED && EMIT), "at most the zone map, and the emit pass reads the counts, not the zones");
 	typedef typename std::conditional<VB == 8, uint64_t, uint32_t>::type U;
 	typedef typename std::conditional<VB == 8, double, float>::type      T;
 	constexpr uint32_t kLanes = VB == 8 ? 16u : 32u; // FastLanes lanes of the value streams
@@ -80,8 +89,26 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
 		}
 	}
 
+	bool inside = false; // ZONED: every value the zone admits qualifies
+	if constexpr (ZONED) {
+		const T* zone = reinterpret_cast<const T*>(zone_records(zones...)) + 2 * v; // (wave-uniform)
+		const T  z_min = zone[0], z_max = zone[1];
+		const T z_lo = static_cast<T>(range_lo), z_hi = static_cast<T>(range_hi);
+		if (!(z_max >= z_lo && z_min <= z_hi)) { // excluded (a NaN bound excludes every vector): the record is all that was read
+			if (lane == 0u) { counts[k] = 0u; }
+			return;
+		}
+		inside = z_min >= z_lo && z_max <= z_hi;
+	}
 	const alpgpu_vector_desc d     = descs[v];
 	const bool               alp   = d.scheme == ALPGPU_SCHEME_ALP;
+	if constexpr (ZONED) {
+		// contained: only a vector that cannot hold a NaN — ALP without exceptions (a NaN never round-trips through ALP, so it is always an exception)
+		if (inside && alp && d.exc_cnt == 0u) {
+			if (lane == 0u) { counts[k] = p_end - p_begin; }
+			return;
+		}
+	}
 	const uint32_t           bw    = d.bw < 8u * VB ? d.bw : 8u * VB;
 	const uint32_t           cnt   = d.exc_cnt < 1024u ? d.exc_cnt : 1024u;
 	const uint8_t*           rec   = excs + d.exc_off;
@@ -296,17 +323,38 @@ static int launch_select_pass(hipStream_t stream, const alpgpu_column* col, uint
 	return ALPGPU_OK;
 }
 
+template <int VB>
+static int launch_select_count_zoned(hipStream_t stream, const alpgpu_column* col, const void* d_zones, uint64_t v0, uint64_t n_range, uint64_t first, uint64_t end,
+                                     double lo, double hi, uint32_t* counts) {
+	const uint64_t n_wg = (n_range + kSelWaves - 1) / kSelWaves;
+	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
+		const uint64_t g = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;
+		hipLaunchKernelGGL((k_select<VB, false, const void*>), dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed,
+		                   col->d_exc, v0, n_range, off, first, end, lo, hi, counts, static_cast<const uint64_t*>(nullptr), static_cast<int64_t*>(nullptr), static_cast<void*>(nullptr),
+		                   0ull, d_zones);
+		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
+	}
+	return ALPGPU_OK;
+}
+
 // n > 0 and first + n <= n_vectors * 1024 (the caller checked); d_scratch: select_scratch_bytes(col->n_vectors) bytes, 16-byte aligned
+// d_zones (nullable): the column's zone map, one record per vector — the count pass then reads a vector's record before the vector
 int launch_select_range(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int64_t* d_idx, void* d_vals,
-                        uint64_t capacity, uint64_t* d_count, void* d_scratch, int value_bytes) {
+                        uint64_t capacity, uint64_t* d_count, void* d_scratch, int value_bytes, const void* d_zones) {
 	const uint64_t end     = first + n;
 	const uint64_t v0      = first >> 10;
 	const uint64_t n_range = ((end - 1) >> 10) - v0 + 1;
 	uint64_t*      offsets = static_cast<uint64_t*>(d_scratch);
 	uint32_t*      counts  = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_scratch) + align16(8ull * col->n_vectors));
 	uint64_t*      levels  = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(counts) + align16(4ull * col->n_vectors));
-	int            rc      = value_bytes == 8 ? launch_select_pass<8, false>(stream, col, v0, n_range, first, end, lo, hi, counts, nullptr, nullptr, nullptr, 0)
-	                                          : launch_select_pass<4, false>(stream, col, v0, n_range, first, end, lo, hi, counts, nullptr, nullptr, nullptr, 0);
+	int            rc;
+	if (d_zones != nullptr) {
+		rc = value_bytes == 8 ? launch_select_count_zoned<8>(stream, col, d_zones, v0, n_range, first, end, lo, hi, counts)
+		                      : launch_select_count_zoned<4>(stream, col, d_zones, v0, n_range, first, end, lo, hi, counts);
+	} else {
+		rc = value_bytes == 8 ? launch_select_pass<8, false>(stream, col, v0, n_range, first, end, lo, hi, counts, nullptr, nullptr, nullptr, 0)
+		                      : launch_select_pass<4, false>(stream, col, v0, n_range, first, end, lo, hi, counts, nullptr, nullptr, nullptr, 0);
+	}
 	if (rc != ALPGPU_OK) { return rc; }
 	rc = launch_select_scan(stream, counts, n_range, offsets, d_count, levels);
 	if (rc != ALPGPU_OK || capacity == 0) { return rc; }

@@ -18,6 +18,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -459,13 +460,75 @@ struct column {
 		std::vector<uint64_t> indices;
 		std::vector<PT>       values;
 	};
-	static selection select_range(const uint8_t* blob, size_t size, PT lo, PT hi) {
+	static selection select_range(const uint8_t* blob, size_t size, PT lo, PT hi) { return select_range_with(blob, size, lo, hi, nullptr); }
+	// One record per vector of a column (include/alpgpu.h, "zone maps"): min / max of the vector's values that are not NaN, -0.0 below +0.0,
+	// {+inf, -inf} when there is none.  A caller who persists a blob keeps its records beside it and hands them to select_range.
+	using zone = typename std::conditional<sizeof(PT) == 8, alpgpu_zone_f64, alpgpu_zone_f32>::type;
+	static std::vector<zone> zone_map(const uint8_t* blob, size_t size) {
+		uploaded_column   up(blob, size, "alp::gpu::column::zone_map");
+		std::vector<zone> out(up.col.n_vectors);
+		if (out.empty()) { return out; }
+		zone* d_zones = static_cast<zone*>(up.get(out.size() * sizeof(zone)));
+		make_zone_map(up, d_zones);
+		check(alpgpu_memcpy_d2h(context(), out.data(), d_zones, out.size() * sizeof(zone)), "alpgpu_memcpy_d2h");
+		return out;
+	}
+	// The column's {min, max} (alpgpu_zones_minmax_*): {+inf, -inf} for an empty column or one of NaNs only.
+	static zone min_max(const uint8_t* blob, size_t size) {
+		uploaded_column up(blob, size, "alp::gpu::column::min_max");
+		zone*           d_zones = static_cast<zone*>(up.get(up.col.n_vectors * sizeof(zone)));
+		PT*             d_mm    = static_cast<PT*>(up.get(2 * sizeof(PT)));
+		make_zone_map(up, d_zones);
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_zones_minmax_f64(context(), d_zones, up.col.n_vectors, reinterpret_cast<double*>(d_mm)), "alpgpu_zones_minmax_f64");
+		} else {
+			check(alpgpu_zones_minmax_f32(context(), d_zones, up.col.n_vectors, reinterpret_cast<float*>(d_mm)), "alpgpu_zones_minmax_f32");
+		}
+		zone out;
+		check(alpgpu_memcpy_d2h(context(), &out, d_mm, sizeof(out)), "alpgpu_memcpy_d2h");
+		return out;
+	}
+	// select_range with the column's zone map (one record per vector, e.g. zone_map() of the same blob): the same selection; vectors whose
+	// record misses [lo, hi] are not decoded (alpgpu_select_range_zoned_*).  Records must contain their vectors' values.
+	static selection select_range(const uint8_t* blob, size_t size, PT lo, PT hi, const std::vector<zone>& zones) {
+		if (size >= sizeof(alpgpu_blob_header)) {
+			alpgpu_blob_header h;
+			std::memcpy(&h, blob, sizeof(h));
+			if (zones.size() != h.n_vectors) { throw std::runtime_error("alp::gpu::column::select_range: the zone map must hold one record per vector"); }
+		}
+		return select_range_with(blob, size, lo, hi, &zones);
+	}
+
+private:
+	static void make_zone_map(uploaded_column& up, zone* d_zones) {
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_zone_map_f64(context(), &up.col, d_zones), "alpgpu_zone_map_f64");
+		} else {
+			check(alpgpu_zone_map_f32(context(), &up.col, d_zones), "alpgpu_zone_map_f32");
+		}
+	}
+	static selection select_range_with(const uint8_t* blob, size_t size, PT lo, PT hi, const std::vector<zone>* zones) {
 		uploaded_column up(blob, size, "alp::gpu::column::select_range");
 		selection       out;
 		if (up.n_values == 0) { return out; }
 		uint64_t* d_count   = static_cast<uint64_t*>(up.get(sizeof(uint64_t)));
 		void*     d_scratch = up.get(alpgpu_select_scratch_bytes(up.col.n_vectors));
+		zone*     d_zones   = nullptr;
+		if (zones != nullptr) {
+			d_zones = static_cast<zone*>(up.get(zones->size() * sizeof(zone)));
+			check(alpgpu_memcpy_h2d(context(), d_zones, zones->data(), zones->size() * sizeof(zone)), "alpgpu_memcpy_h2d");
+		}
 		auto      call      = [&](int64_t* d_idx, PT* d_vals, uint64_t capacity) {
+			if (d_zones != nullptr) {
+				if constexpr (sizeof(PT) == 8) {
+					check(alpgpu_select_range_zoned_f64(context(), &up.col, d_zones, 0, up.n_values, lo, hi, d_idx, reinterpret_cast<double*>(d_vals), capacity, d_count, d_scratch),
+					      "alpgpu_select_range_zoned_f64");
+				} else {
+					check(alpgpu_select_range_zoned_f32(context(), &up.col, d_zones, 0, up.n_values, lo, hi, d_idx, reinterpret_cast<float*>(d_vals), capacity, d_count, d_scratch),
+					      "alpgpu_select_range_zoned_f32");
+				}
+				return;
+			}
 			if constexpr (sizeof(PT) == 8) {
 				check(alpgpu_select_range_f64(context(), &up.col, 0, up.n_values, lo, hi, d_idx, reinterpret_cast<double*>(d_vals), capacity, d_count, d_scratch),
 				      "alpgpu_select_range_f64");

@@ -461,6 +461,65 @@ int alpgpu_select_range_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t 
  * d_offsets[i] = d_counts[0] + ... + d_counts[i - 1] (i < n, n > 0), *d_total = the sum of all n; d_scratch: alpgpu_select_scratch_bytes(n) bytes. */
 int alpgpu_debug_select_scan(alpgpu_ctx* ctx, const uint32_t* d_counts, uint64_t n, uint64_t* d_offsets, uint64_t* d_total, void* d_scratch);
 
+/* ---- zone maps --------------------------------------------------------------------------------------------------------
+ * A zone map is one record {min, max} per vector of a column: a plain array in device memory, caller-allocated like every buffer of this ABI
+ * and indexed by vector (alpgpu_zone_f64: 16 bytes, the array 16-byte aligned; alpgpu_zone_f32: 8 bytes, 8-byte aligned; a misaligned array,
+ * or a d_in that is not 16-byte aligned, returns ALPGPU_ERR_INVALID).  It is not part of alpgpu_column
+ * and not part of the serialized container: a caller who persists a blob keeps the n_vectors records beside it.
+ * The record of vector v, defined bit for bit:
+ *   - min / max range over the 1024 decoded values of the vector, exceptions patched in: exactly the values alpgpu_decode_* writes (the tail
+ *     padding of the last vector included; it repeats a value of the vector, so it changes nothing);
+ *   - NaNs are ignored, quiet and signalling alike, whatever their payload, in an exception record (ALP) as in the packed words (ALP_RD);
+ *   - +-inf are ordinary values;
+ *   - zeros are ordered -0.0 < +0.0 (IEEE 754-2019 minimumNumber / maximumNumber): a vector holding both zeros and nothing smaller has
+ *     min = -0.0, sign bit set; the mirror image for max;
+ *   - a vector without a single value that is not a NaN has the empty interval min = +inf, max = -inf.
+ *   alpgpu_zone_map_*            the records of an encoded column: a third fused consumer beside alpgpu_decode_sum_* and
+ *                                alpgpu_decode_count_range_* — each vector is decoded in registers by one wavefront and reduced to its two values;
+ *                                nothing but the records is written.  d_zones: col->n_vectors records.
+ *   alpgpu_zone_map_of_values_*  the same records from the raw values (d_in: n_vectors * 1024 values in device memory, 16-byte aligned), for a
+ *                                caller who still holds them at encode time: one streaming read.  The codec is lossless, so this gives the same
+ *                                bytes as alpgpu_zone_map_* of the encoded column.
+ *   alpgpu_zones_minmax_*        the column's MIN / MAX: d_minmax[0] / d_minmax[1] (device memory) = the reduction of n_vectors records under the
+ *                                same ordering; {+inf, -inf} for an empty column (n_vectors == 0: that write is still enqueued) or one of NaNs only.
+ *                                Minimum and maximum are exactly associative and commutative, so the result is a function of the records alone
+ *                                although workgroups join it with atomics; no scratch.
+ *   alpgpu_select_range_zoned_*  alpgpu_select_range_* with the zone map of the column (col->n_vectors records, whatever first and n are).  Contract,
+ *                                scratch (alpgpu_select_scratch_bytes), argument checks, ordering, determinism and capture-safety are those of
+ *                                alpgpu_select_range_*; in addition a NULL d_zones with n > 0 returns ALPGPU_ERR_INVALID.  The count pass reads a
+ *                                vector's record first:
+ *                                  excluded   !(max >= lo && min <= hi) (a NaN bound excludes everything): the vector counts 0; its descriptor,
+ *                                             packed words and exception record are not read;
+ *                                  contained  min >= lo && max <= hi and the vector cannot hold a NaN (an ALP vector without exceptions; ALP_RD
+ *                                             vectors never take this arm): the vector counts its whole share of [first, first + n) after its
+ *                                             descriptor alone, and the emit pass writes its indices without decoding when no values are wanted;
+ *                                  otherwise  the vector is decoded as in alpgpu_select_range_*.
+ *                                GUARANTEE: for any zone map in which every vector's record contains that vector's true interval, the call
+ *                                returns bit for bit what alpgpu_select_range_* returns — exact records, widened records and {-inf, +inf}
+ *                                everywhere alike.  A record that is too narrow gives a wrong selection but never an out-of-bounds access: a
+ *                                record only ever makes the kernel read less.
+ * All of them: everything is enqueued on the context's stream and on that stream only, asynchronous, no host synchronisation, no allocation, and
+ *   none of what the context remembers about columns is read or written; safe inside a stream capture.  n_vectors == 0 (for alpgpu_zone_map_*:
+ *   col->n_vectors == 0) is ALPGPU_OK and, except for the reset of alpgpu_zones_minmax_*, launches nothing.  A NULL ctx, col, d_in, d_zones or
+ *   d_minmax with n_vectors > 0 returns ALPGPU_ERR_INVALID.
+ * TRUST: alpgpu_zone_map_* and alpgpu_select_range_zoned_* as for alpgpu_decode_* (descriptors followed as found). */
+typedef struct alpgpu_zone_f64 {
+	double min, max;
+} alpgpu_zone_f64;
+typedef struct alpgpu_zone_f32 {
+	float min, max;
+} alpgpu_zone_f32;
+int alpgpu_zone_map_f64(alpgpu_ctx* ctx, const alpgpu_column* col, alpgpu_zone_f64* d_zones);
+int alpgpu_zone_map_f32(alpgpu_ctx* ctx, const alpgpu_column* col, alpgpu_zone_f32* d_zones);
+int alpgpu_zone_map_of_values_f64(alpgpu_ctx* ctx, const double* d_in, uint64_t n_vectors, alpgpu_zone_f64* d_zones);
+int alpgpu_zone_map_of_values_f32(alpgpu_ctx* ctx, const float* d_in, uint64_t n_vectors, alpgpu_zone_f32* d_zones);
+int alpgpu_zones_minmax_f64(alpgpu_ctx* ctx, const alpgpu_zone_f64* d_zones, uint64_t n_vectors, double* d_minmax);
+int alpgpu_zones_minmax_f32(alpgpu_ctx* ctx, const alpgpu_zone_f32* d_zones, uint64_t n_vectors, float* d_minmax);
+int alpgpu_select_range_zoned_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const alpgpu_zone_f64* d_zones, uint64_t first, uint64_t n, double lo, double hi,
+                                  int64_t* d_idx, double* d_vals, uint64_t capacity, uint64_t* d_count, void* d_scratch);
+int alpgpu_select_range_zoned_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const alpgpu_zone_f32* d_zones, uint64_t first, uint64_t n, float lo, float hi,
+                                  int64_t* d_idx, float* d_vals, uint64_t capacity, uint64_t* d_count, void* d_scratch);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
