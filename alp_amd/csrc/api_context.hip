@@ -89,15 +89,11 @@ int alpgpu_ctx_create(int device, alpgpu_ctx** out_ctx) {
 	ctx->async_init     = 1;
 	ctx->n_cus          = prop.multiProcessorCount;
 	ctx->hbm_bytes      = prop.totalGlobalMem;
-	ctx->decode_variant  = 1; // bit 0: one vector per decode workgroup, bit 1: plain stores
-	ctx->decode_auto     = 1;
-	ctx->decode_vpw      = 0;
+	ctx->decode_opt      = alpgpu::DecodeOptions {0, -1, -1, false, false}; // shape and pad by the rule, the read-ahead by the column (decode_policy.hpp: policy_read_ahead)
 	ctx->encode_two_pass = 0;
 	ctx->force_stall     = 0;
 	ctx->pipelined_consumer = 0;
-	ctx->decode_pad_kib  = -1;
 	ctx->encode_unordered = 0;
-	ctx->read_ahead      = -1; // -1: by the column (read_ahead_for)
 	ctx->read_ahead_us   = 0;  // 0: by the vectors' width (alpgpu_decode_f64)
 	ctx->decode_segments = 1;
 	for (auto& t : ctx->seg_tables) { t.key = nullptr; }
@@ -112,7 +108,7 @@ int alpgpu_ctx_create(int device, alpgpu_ctx** out_ctx) {
 		const char* ser = std::getenv("AMD_SERIALIZE_KERNEL");
 		const char* blk = std::getenv("HIP_LAUNCH_BLOCKING");
 		const char* q   = std::getenv("GPU_MAX_HW_QUEUES");
-		ctx->streams_serialize = ((ser && std::atoi(ser) != 0) || (blk && std::atoi(blk) != 0) || (q && std::atoi(q) == 1)) ? 1 : 0;
+		ctx->decode_opt.streams_serialize = (ser && std::atoi(ser) != 0) || (blk && std::atoi(blk) != 0) || (q && std::atoi(q) == 1);
 	}
 	ctx->d_progress      = nullptr;
 	ctx->progress_gen    = 0;
@@ -206,15 +202,13 @@ int alpgpu_set_option(alpgpu_ctx* ctx, int option, int64_t value) {
 		if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && !(value >= 16 && value <= 30)) {
 			return fail(ALPGPU_ERR_INVALID, "decode vectors per workgroup must be 0 (auto), 1, 2, 4 or (float columns) 8: one wavefront per vector, 16-30: streamed by persistent workgroups");
 		}
-		ctx->decode_auto    = value == 0;
-		ctx->decode_vpw     = static_cast<int>(value);
-		ctx->decode_variant = (ctx->decode_variant & ~1) | ((value == 2 || value == 4) ? 0 : 1); // (double columns run 4 as 2; 8 and up: float columns only, double columns take 1)
+		ctx->decode_opt.forced_vpw = static_cast<int>(value); // (double columns run 4 as 2; 8 and up: float columns only, double columns take 1 — decode_policy.hpp)
 		return ALPGPU_OK;
 	case ALPGPU_OPT_ENCODE_TWO_PASS:
 		ctx->encode_two_pass = value ? 1 : 0;
 		return ALPGPU_OK;
 	case ALPGPU_OPT_DECODE_PLAIN_STORES:
-		ctx->decode_variant = (ctx->decode_variant & ~2) | (value ? 2 : 0);
+		ctx->decode_opt.plain_stores = value != 0;
 		return ALPGPU_OK;
 	case ALPGPU_OPT_DEBUG_FORCE_STALL:
 		ctx->force_stall = value ? 1 : 0;
@@ -231,7 +225,7 @@ int alpgpu_set_option(alpgpu_ctx* ctx, int option, int64_t value) {
 		return ALPGPU_OK;
 	case ALPGPU_OPT_DECODE_RESIDENCY_PAD:
 		if (value < -1 || value > 150) { return fail(ALPGPU_ERR_INVALID, "decode residency pad: -1 (by the library's rule) or 0..150 KiB"); }
-		ctx->decode_pad_kib = static_cast<int>(value);
+		ctx->decode_opt.forced_pad_kib = static_cast<int>(value);
 		return ALPGPU_OK;
 	case ALPGPU_OPT_ENCODE_UNORDERED:
 		ctx->encode_unordered = value ? 1 : 0;
@@ -245,7 +239,7 @@ int alpgpu_set_option(alpgpu_ctx* ctx, int option, int64_t value) {
 		return ALPGPU_OK;
 	case ALPGPU_OPT_DECODE_READ_AHEAD:
 		if (value < -1 || value > 1) { return fail(ALPGPU_ERR_INVALID, "decode read-ahead: -1 (columns of narrow vectors: the default), 0 (off) or 1 (on)"); }
-		ctx->read_ahead = value;
+		ctx->decode_opt.read_ahead = static_cast<int>(value);
 		return ALPGPU_OK;
 	case ALPGPU_OPT_DECODE_READ_AHEAD_US:
 		if (value < 0 || value > 10000) { return fail(ALPGPU_ERR_INVALID, "decode read-ahead lead: 0 (by the vectors' width) or 1..10000 microseconds"); }

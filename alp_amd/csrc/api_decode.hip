@@ -1,116 +1,25 @@
-// api_decode.hip — the store decode's LAUNCH POLICY (vectors per workgroup, residency, read-ahead, region by region), the decode entry points, the fused
-// consumers and alpgpu_column_totals (which records what the policy needs) of include/alpgpu.h (see host_ctx.hpp for the map).
+// api_decode.hip — the store decode's entry points and the HOST STATE its launch plan lives in (the per-segment tables of a column decoded region by region, what an unhinted
+// decode learned, the streams and events of the read-ahead), the fused consumers and alpgpu_column_totals (which records what the plan needs) of include/alpgpu.h (see host_ctx.hpp for
+// the map).  The launch RULE — shape, residency, read-ahead — is decode_policy.hpp: pure functions of a stretch's sizes and the context's options, evaluated once per launch (planned).
 #include "decode_policy.hpp"
 #include "host_ctx.hpp"
-
-using alpgpu::kReadAheadBits;
-using alpgpu::kReadAheadBitsExc;
-using alpgpu::kReadAheadVectors;
 
 constexpr int      kReadAheadGrid    = 64;  // the read-ahead's eight-wavefront workgroups
 constexpr uint32_t kReadAheadMaxBits = 128; // ... read the records of vectors of at most this many packed bits per value (the descriptors of all)
 
 extern "C" {
 
-// "the column's vectors carry exceptions" as far as the decode's launch shape is concerned: about two or more per vector
-static bool column_decodes_with_exceptions(const alpgpu_ctx*, const alpgpu_column* col) {
-	return static_cast<double>(col->exc_bytes_hint) >= 16.0 * static_cast<double>(col->n_vectors);
-}
-
-// The store decode of this column runs with the read-ahead (read_ahead_kernels.hip).  Asked for (1): any column long enough to be worth a second launch whose
-// sizes are known (the lead is in vectors per microsecond).  Left to the library (-1, the default): columns of NARROW vectors only — there the decode is bound
-// by its two dependent reads under a write-dominated stream (0.68-0.72 of the HBM peak at 2-6 bits, 0.60-0.69 with exceptions) and gains from finding them in
-// the Infinity Cache: +3-14 % up to 6 bits (one vector per workgroup), with exceptions +5-24 % up to 7 bits (two per workgroup).  At 7 bits without exceptions
-// it is even across six closing runs (-1 %), and an extension to 11 / 9 bits that single-column A/B runs suggested (+2-7 %, call 49) lost 3-6 % in the bench line of
-// another box (call 50): the limits are where the gain is robust.  Beyond, the second stream of reads costs more than the hits save (benchmark column 0.77 -> 0.73).
-// The lead that goes with a width: alpgpu_decode_f64.  tools/r05_read_ahead*.py, profiles/r05_read_ahead.txt.
-// (float columns, round 6: the same kernel beside k_decode_column_f32, limits of their own — decode_policy.hpp, profiles/r06_float_decode.txt)
-static bool read_ahead_for(const alpgpu_ctx* ctx, const alpgpu_column* col, int value_bytes = 8) {
-	if (ctx->read_ahead == 0 || col->packed_bytes_hint == 0 || ctx->d_progress == nullptr) { return false; }
-	if (ctx->read_ahead > 0) { return col->n_vectors >= 32768; }
-	if (ctx->streams_serialize) { return false; } // (the two kernels cannot run side by side in this process: api_context.hip)
-	return alpgpu::policy_read_ahead_auto(col->n_vectors, static_cast<double>(col->packed_bytes_hint), column_decodes_with_exceptions(ctx, col), value_bytes);
-}
-
-static int decode_variant_for(const alpgpu_ctx* ctx, const alpgpu_column* col) {
-	int variant = ctx->decode_variant;
-	if (ctx->decode_auto) { // pick the launch shape from the host-side size hints, if any
-		const double n        = static_cast<double>(col->n_vectors);
-		const bool   hinted   = col->packed_bytes_hint != 0 || col->exc_bytes_hint != 0;
-		// More vectors per workgroup = more bytes in flight per CU, which is what narrow vectors lack (two dependent round trips for 8 KiB of
-		// output) and what wide ones pay for.  Crossovers measured at 1-bit resolution on 1 Mi-vector columns (tools/sweep_vpw_fine.py,
-		// profiles/r04_decode_floor.txt): without exceptions one vector per workgroup wins from 17 bits on (16 itself — whole KiB per vector —
-		// still prefers more), with ~2 or more exceptions per vector from 21 bits on; every ALP_RD column is far beyond either.
-		const bool   with_exc = column_decodes_with_exceptions(ctx, col);
-		const double bits     = static_cast<double>(col->packed_bytes_hint) / (128.0 * (n > 0 ? n : 1.0));
-		const bool   narrow   = bits <= (with_exc ? alpgpu::kTwoVectorsBitsExc : alpgpu::kTwoVectorsBits); // (17.5: with the residency caps below two vectors per workgroup win through 17 bits; with exceptions through 22: round 5)
-		variant               = (variant & ~1) | ((hinted && narrow) ? 0 : 1);
-		// narrow vectors under the read-ahead: their reads hit the Infinity Cache, and ONE vector per workgroup — the shape that suffers most from the two round
-		// trips (0.53 at 2-6 bits) — becomes the best one (0.75-0.80); with exceptions two per workgroup stay ahead (0.68-0.74 against 0.64-0.68)
-		if (ctx->read_ahead < 0 && read_ahead_for(ctx, col) && !with_exc) { variant |= 1; }
-		// (almost) nothing but 0-bit vectors — a pure stream of stores, e.g. the gov26 shape: one vector per workgroup (and six workgroups per CU, below): 0.71 -> 0.82 (call 2)
-		if (hinted && bits <= alpgpu::kEmptyVectorsBits) { variant |= 1; }
-	}
-	// Residency by width (decode_kernels.hip: launch_decode_column; unused dynamic LDS): what a CU wants is a certain amount of bytes in flight, not a
-	// certain number of workgroups.  One vector per workgroup: eight workgroups per CU up to 33 bits, seven up to 35, six beyond; seven for ALP_RD
-	// columns.  Two vectors per workgroup: eight / seven / six workgroups by width.  ALPGPU_OPT_DECODE_RESIDENCY_PAD overrides (0 = never cap).
-	int pad_kib = ctx->decode_pad_kib >= 0 ? ctx->decode_pad_kib : 0; // -1: by the rule below
-	if (ctx->decode_pad_kib < 0 && ctx->decode_auto && col->packed_bytes_hint != 0 && col->n_vectors != 0 && !(ctx->read_ahead < 0 && read_ahead_for(ctx, col))) { // (under the read-ahead no cap helps)
-		const double n        = static_cast<double>(col->n_vectors);
-		const double bits     = static_cast<double>(col->packed_bytes_hint) / (128.0 * n);
-		const bool   with_exc = column_decodes_with_exceptions(ctx, col);
-		const bool   mostly_rd = col->alp_rd_rowgroups_hint != 0 && 2.0 * static_cast<double>(col->alp_rd_rowgroups_hint - 1) * 100.0 > n;
-		// (re-measured in round 5 with the per-vector decode loops — a workgroup's stores no longer wait for one another, workgroups live shorter and a CU
-		//  wants somewhat fewer of them: tools/r05_decode_resid.py, profiles/r05_decode_exceptions.txt)
-		if (variant & 1) {
-			// one vector per workgroup: up to ~30 bits a 6 KiB pad (ten workgroups' worth of LDS for eight: 0.77-0.80 -> 0.79-0.81, with exceptions
-			// 0.75-0.79 -> 0.78-0.82 up to 38 bits); 30-38 bits without exceptions none; from 38 bits on seven, then six workgroups per CU
-			// (+5-7 %); ALP_RD columns — more arithmetic per value — seven
-			if (mostly_rd) {
-				pad_kib = 11;
-			} else if (bits <= alpgpu::kEmptyVectorsBits) {
-				pad_kib = 14; // a pure stream of stores wants few workgroups per CU, like wide vectors
-			} else if (with_exc) {
-				pad_kib = bits >= 46.0 ? 14 : (bits >= 38.0 ? 11 : 6);
-			} else {
-				pad_kib = bits >= 38.0 ? 14 : (bits >= 30.0 ? 0 : 6);
-			}
-		} else if (!with_exc) {
-			// two vectors per workgroup, no exceptions: sixteen vectors in flight per CU up to 8 bits, fourteen (seven workgroups) beyond.  With
-			// exceptions the caps lose.
-			pad_kib = bits > 8.5 ? 3 : 0;
-		}
-	}
-	// exception-heavy columns (more exceptions per vector than the 128-entry stage holds, on average): the instance with the 256-entry stage (decode_kernels.hip:
-	// DecodeLdsManyExc; one vector per workgroup, non-temporal stores): 0.72 -> 0.77 on bench.py's 10 %-exceptions column (call 6)
-	int many_exc = 0;
-	if (ctx->decode_auto && (variant & 3) == 1 && col->n_vectors != 0 && static_cast<double>(col->exc_bytes_hint) >= 10.0 * 128.0 * static_cast<double>(col->n_vectors) &&
-	    !(col->alp_rd_rowgroups_hint != 0 && 2.0 * static_cast<double>(col->alp_rd_rowgroups_hint - 1) * 100.0 > static_cast<double>(col->n_vectors))) {
-		many_exc = 64;
-	}
-	return (variant & 3) | many_exc | (pad_kib << 8);
-}
-
-// Float columns (round 6): vectors per workgroup — 2 (the bytes in flight of one double vector), FOUR for columns of narrow vectors whose sizes are known, what
-// ALPGPU_OPT_DECODE_VECTORS_PER_WG says otherwise — and the residency pad (ALPGPU_OPT_DECODE_RESIDENCY_PAD, else none).  tools/sweep_f32_decode.py,
-// profiles/r06_float_decode.txt.  Returns vectors per workgroup | pad KiB << 8 (pad 0xFF: none).
-static int decode_shape_f32(const alpgpu_ctx* ctx, const alpgpu_column* col) {
-	int vpw = ctx->decode_vpw ? ctx->decode_vpw : 2;
-	if (ctx->decode_vpw == 0 && ctx->decode_auto && col->packed_bytes_hint != 0 && col->n_vectors != 0) {
-		const double bits = static_cast<double>(col->packed_bytes_hint) / (128.0 * static_cast<double>(col->n_vectors));
-		const double four = column_decodes_with_exceptions(ctx, col) ? alpgpu::kFourVectorsBitsExcF32 : alpgpu::kFourVectorsBitsF32; // (0: never — decode_policy.hpp)
-		if (four > 0.0 && bits <= four) { vpw = 4; }
-		// narrow vectors without exceptions: streamed by persistent workgroups (decode_policy.hpp: policy_stream_f32)
-		if (alpgpu::policy_stream_f32(col->n_vectors, static_cast<double>(col->packed_bytes_hint), column_decodes_with_exceptions(ctx, col))) { vpw = alpgpu::kStreamShapeF32; }
-	}
-	return vpw | ((ctx->decode_pad_kib >= 0 ? ctx->decode_pad_kib : 0xFF) << 8);
+// the launch of this column (or run) as a whole, from its size hints and the context's options
+static alpgpu::DecodePlan planned(const alpgpu_ctx* ctx, const alpgpu_column* col, int value_bytes) {
+	const alpgpu::ColumnSizes sizes {col->n_vectors, col->packed_bytes_hint, col->exc_bytes_hint, alpgpu::policy_rd_vectors_of_hint(col->alp_rd_rowgroups_hint)};
+	return alpgpu::policy_decode_plan(sizes, value_bytes, ctx->decode_opt); // (a context always has the progress words the read-ahead needs: alpgpu_ctx_create fails without)
 }
 
 // ---- a launch rule that sees more than the column's averages (round 5) -------------------------------------------------------------------------
 // alpgpu_column_totals and alpgpu_column_from_blob record, per segment of the column, what they record for the whole: packed bytes, exceptions, ALP_RD
-// vectors.  alpgpu_decode_f64 of that column (same context, same descriptor buffer) merges adjacent segments of the same KIND — by packed width: up to the
-// read-ahead's 7 bits / up to the two-vectors-per-workgroup limit / below 38 bits / beyond; with or without exceptions — into runs and decodes run by run,
-// each through the rule above with the run's own sizes: a column whose first half is 6-bit vectors with exceptions and whose second half is 44-bit vectors
+// vectors.  alpgpu_decode_f64 of that column (same context, same descriptor buffer) merges adjacent segments of the same KIND (decode_policy.hpp:
+// policy_stretch_kind) into runs and decodes run by run, each through the rule (policy_decode_plan) with the run's own sizes: a column whose first half is
+// 6-bit vectors with exceptions and whose second half is 44-bit vectors
 // (bench.py: decode_bimodal) gets two vectors per workgroup + the read-ahead for the first and one per workgroup, six workgroups per CU, for the second,
 // instead of the shape of their average.  One kind, or more than kMaxRuns runs (a column that changes every few thousand vectors is served by its average): the
 // whole column in one launch, as before.  ALPGPU_OPT_DECODE_SEGMENTS = 0: never.  Launch shapes only: the bytes cannot differ.
@@ -171,25 +80,9 @@ SegmentTable* segment_table_new(alpgpu_ctx* ctx, const alpgpu_column* col, uint6
 	return t;
 }
 
-// the kind of a stretch of vectors, from its sums (see above); float columns: up to the read-ahead's limit / up to the four-vectors limit / beyond
-static int stretch_kind(const alpgpu_ctx* ctx, uint64_t n, uint64_t packed, uint64_t exc_bytes, int value_bytes) {
-	alpgpu_column v {};
-	v.n_vectors = n, v.packed_bytes_hint = packed ? packed : 1, v.exc_bytes_hint = exc_bytes;
-	const bool   with_exc = column_decodes_with_exceptions(ctx, &v);
-	const double bits     = static_cast<double>(packed) / (128.0 * static_cast<double>(n));
-	int          band;
-	if (value_bytes == 8) {
-		band = bits <= (with_exc ? kReadAheadBitsExc : kReadAheadBits) ? 0 : (bits <= (with_exc ? alpgpu::kTwoVectorsBitsExc : alpgpu::kTwoVectorsBits) ? 1 : (bits < 38.0 ? 2 : 3));
-	} else {
-		band = bits <= (with_exc ? alpgpu::kReadAheadBitsExcF32 : alpgpu::kReadAheadBitsF32) ? 0 : (bits <= (with_exc ? alpgpu::kFourVectorsBitsExcF32 : alpgpu::kFourVectorsBitsF32) ? 1 : 2);
-	}
-	return 2 * band + (with_exc ? 1 : 0);
-}
-
 // runs[0 .. return) cover the column; 0 = no plan (decode the column whole)
-static int plan_decode_runs(alpgpu_ctx* ctx, const alpgpu_column* col, DecodeRun* runs, int value_bytes = 8) {
-	if (!ctx->decode_segments || !ctx->decode_auto || ctx->decode_pad_kib >= 0) { return 0; } // (a forced shape is a forced shape)
-	if (value_bytes == 4 && ctx->decode_vpw != 0) { return 0; }
+static int plan_decode_runs(alpgpu_ctx* ctx, const alpgpu_column* col, DecodeRun* runs, int value_bytes) {
+	if (!ctx->decode_segments || ctx->decode_opt.forced_vpw != 0 || ctx->decode_opt.forced_pad_kib >= 0) { return 0; } // (a forced shape is a forced shape)
 	const SegmentTable* t = segment_table_of(ctx, col);
 	if (!t || t->n_seg < 2) { return 0; }
 	int n_runs = 0, kind = -1;
@@ -197,7 +90,7 @@ static int plan_decode_runs(alpgpu_ctx* ctx, const alpgpu_column* col, DecodeRun
 		const uint64_t v0 = s * t->seg_vectors;
 		const uint64_t n  = v0 + t->seg_vectors < t->n_vectors ? t->seg_vectors : t->n_vectors - v0;
 		const uint64_t eb = (value_bytes + 2ull) * t->exc_cnt[s]; // (ALP: the value + a 2-byte position; ALP_RD records are smaller and their vectors wide anyway)
-		const int      k  = stretch_kind(ctx, n, t->packed[s], eb, value_bytes);
+		const int      k  = alpgpu::policy_stretch_kind(n, t->packed[s], eb, value_bytes);
 		if (k != kind) {
 			if (n_runs == kMaxRuns) { return 0; }
 			runs[n_runs++] = DecodeRun {v0, 0, 0, 0, 0};
@@ -225,15 +118,13 @@ static alpgpu_column run_view(const alpgpu_column* col, const DecodeRun& r) {
 // what alpgpu_decode_f64 / _f32 would launch for this column right now (option + size hints): vectors per decode workgroup
 int alpgpu_decode_vectors_per_wg(alpgpu_ctx* ctx, const alpgpu_column* col, int is_f32) {
 	if (!ctx || !col) { return fail(ALPGPU_ERR_INVALID, "null context or column"); }
-	if (is_f32) { return decode_shape_f32(ctx, col) & 0xFF; }
-	return (decode_variant_for(ctx, col) & 1) ? 1 : 2;
+	return alpgpu::decode_shape_number(planned(ctx, col, is_f32 ? 4 : 8).shape);
 }
 
 // ... and whether it would start the read-ahead beside the decode kernel (ALPGPU_OPT_DECODE_READ_AHEAD): 1 / 0; negative on bad arguments
 int alpgpu_decode_reads_ahead(alpgpu_ctx* ctx, const alpgpu_column* col, int is_f32) {
 	if (!ctx || !col) { return fail(ALPGPU_ERR_INVALID, "null context or column"); }
-	if (is_f32 && (decode_shape_f32(ctx, col) & 0xFF) >= 16) { return 0; } // (streamed by persistent workgroups: no read-ahead beside it)
-	return read_ahead_for(ctx, col, is_f32 ? 4 : 8) ? 1 : 0;
+	return planned(ctx, col, is_f32 ? 4 : 8).ahead ? 1 : 0;
 }
 
 // measurement aid: what alpgpu_decode_sum_f64 costs with its unpack arithmetic left out (decode_kernels.hip: kSinkProbe)
@@ -250,30 +141,26 @@ int alpgpu_debug_decode_probe_f64(alpgpu_ctx* ctx, const alpgpu_column* col, dou
 // columns (0.81 against 0.91 ms per 1 Mi vectors of the benchmark column) and, since its ALP_RD arm stopped spilling, on ALP_RD columns too
 // (1.41 against 1.51 ms); 1: the persistent LDS-ring kernel; 3: the staged four-wavefront kernel.  (alp_rd_rowgroups_hint, which chose
 // between the two while the ALP_RD arm spilled, is still kept up to date in the column for callers that want to know.)
-static bool use_direct_sink(const alpgpu_ctx* ctx, const alpgpu_column*) { return ctx->pipelined_consumer == 0 || ctx->pipelined_consumer == 2; }
-static int sum_launch(alpgpu_ctx* ctx, const alpgpu_column* col, double* d_sums) {
+// Float columns: the one-wavefront kernel whatever the column holds too (0.99 against 1.08 ms for the staged kernel on the decimal column, 1.04
+// against 1.06 on an all-ALP_RD one); options 1 and 3 select the staged kernel (there is no ring kernel).
+static bool use_direct_sink(const alpgpu_ctx* ctx) { return ctx->pipelined_consumer == 0 || ctx->pipelined_consumer == 2; }
+static int sum_launch(alpgpu_ctx* ctx, const alpgpu_column* col, double* d_sums, bool f32) {
+	if (f32) { return use_direct_sink(ctx) ? alpgpu::launch_sink_direct_f32(ctx->stream, col, 0.0f, 0.0f, d_sums, false) : alpgpu::launch_decode_sum_f32(ctx->stream, col, d_sums); }
 	if (ctx->pipelined_consumer == 1) { return alpgpu::launch_consume_sum(ctx->stream, col, d_sums, ctx->n_cus); }
-	if (use_direct_sink(ctx, col)) { return alpgpu::launch_sink_direct(ctx->stream, col, 0.0, 0.0, d_sums, false); }
+	if (use_direct_sink(ctx)) { return alpgpu::launch_sink_direct(ctx->stream, col, 0.0, 0.0, d_sums, false); }
 	return alpgpu::launch_decode_sum(ctx->stream, col, d_sums, 2);
 }
 
-// Float columns: the one-wavefront kernel whatever the column holds (0.99 against 1.08 ms for the staged kernel on the decimal column, 1.04
-// against 1.06 on an all-ALP_RD one); options 1 and 3 select the staged kernel (there is no ring kernel).
-static bool use_direct_sink_f32(const alpgpu_ctx* ctx, const alpgpu_column*) { return ctx->pipelined_consumer == 0 || ctx->pipelined_consumer == 2; }
-static int  sum_launch_f32(alpgpu_ctx* ctx, const alpgpu_column* col, double* d_sums) {
-	if (use_direct_sink_f32(ctx, col)) { return alpgpu::launch_sink_direct_f32(ctx->stream, col, 0.0f, 0.0f, d_sums, false); }
-	return alpgpu::launch_decode_sum_f32(ctx->stream, col, d_sums);
-}
-
-int alpgpu_decode_sum_f64(alpgpu_ctx* ctx, const alpgpu_column* col, double* d_sums) {
+static int decode_sum(alpgpu_ctx* ctx, const alpgpu_column* col, double* d_sums, bool f32) {
 	ALPGPU_CHECK_CTX(ctx);
 	if (!col || (!d_sums && col->n_vectors)) { return fail(ALPGPU_ERR_INVALID, "null column or output"); }
 	if (col->n_vectors == 0) { return ALPGPU_OK; }
 	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
-	const int rc = sum_launch(ctx, col, d_sums);
-	if (rc != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "decode-sum launch failed", hipGetLastError()); }
+	if (sum_launch(ctx, col, d_sums, f32) != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "decode-sum launch failed", hipGetLastError()); }
 	return ALPGPU_OK;
 }
+int alpgpu_decode_sum_f64(alpgpu_ctx* ctx, const alpgpu_column* col, double* d_sums) { return decode_sum(ctx, col, d_sums, false); }
+int alpgpu_decode_sum_f32(alpgpu_ctx* ctx, const alpgpu_column* col, double* d_sums) { return decode_sum(ctx, col, d_sums, true); }
 
 // The whole column's total (the reference's consumer keeps ONE accumulator across vectors, q1.cpp:91-100): per-vector sums into the
 // context's workspace, then the documented tree over them.  Everything stays on the stream; *d_total is device memory.
@@ -289,8 +176,7 @@ static int column_sum(alpgpu_ctx* ctx, const alpgpu_column* col, double* d_total
 	const uint64_t l1 = (n + 1023) / 1024;
 	if (int rc = ensure_workspace(ctx, 8ull * (n + 2 * l1) + 64)) { return rc; }
 	double* sums = static_cast<double*>(ctx->workspace);
-	int     rc   = f32 ? sum_launch_f32(ctx, col, sums)
-	                   : sum_launch(ctx, col, sums);
+	int     rc   = sum_launch(ctx, col, sums, f32);
 	if (rc == ALPGPU_OK) { rc = alpgpu::launch_tree_sum(ctx->stream, sums, n, sums + n, d_total); }
 	if (rc != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "column-sum launch failed", hipGetLastError()); }
 	return workspace_used(ctx);
@@ -309,17 +195,22 @@ int alpgpu_tree_sum_f64(alpgpu_ctx* ctx, const double* d_in, uint64_t n, double*
 	return workspace_used(ctx);
 }
 
-int alpgpu_decode_count_range_f64(alpgpu_ctx* ctx, const alpgpu_column* col, double lo, double hi, uint32_t* d_counts) {
+// (a float column's bounds are floats: they pass through double unchanged)
+static int decode_count_range(alpgpu_ctx* ctx, const alpgpu_column* col, double lo, double hi, uint32_t* d_counts, bool f32) {
 	ALPGPU_CHECK_CTX(ctx);
 	if (!col || (!d_counts && col->n_vectors)) { return fail(ALPGPU_ERR_INVALID, "null column or output"); }
 	if (col->n_vectors == 0) { return ALPGPU_OK; }
 	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
-	const int rc = ctx->pipelined_consumer == 1 ? alpgpu::launch_consume_count_range(ctx->stream, col, lo, hi, d_counts, ctx->n_cus)
-	               : use_direct_sink(ctx, col)  ? alpgpu::launch_sink_direct(ctx->stream, col, lo, hi, d_counts, true)
-	                                            : alpgpu::launch_decode_count_range(ctx->stream, col, lo, hi, d_counts);
+	const float flo = static_cast<float>(lo), fhi = static_cast<float>(hi);
+	const int   rc  = f32 ? (use_direct_sink(ctx) ? alpgpu::launch_sink_direct_f32(ctx->stream, col, flo, fhi, d_counts, true) : alpgpu::launch_decode_count_range_f32(ctx->stream, col, flo, fhi, d_counts))
+	                : ctx->pipelined_consumer == 1 ? alpgpu::launch_consume_count_range(ctx->stream, col, lo, hi, d_counts, ctx->n_cus)
+	                : use_direct_sink(ctx)         ? alpgpu::launch_sink_direct(ctx->stream, col, lo, hi, d_counts, true)
+	                                               : alpgpu::launch_decode_count_range(ctx->stream, col, lo, hi, d_counts);
 	if (rc != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "decode-count launch failed", hipGetLastError()); }
 	return ALPGPU_OK;
 }
+int alpgpu_decode_count_range_f64(alpgpu_ctx* ctx, const alpgpu_column* col, double lo, double hi, uint32_t* d_counts) { return decode_count_range(ctx, col, lo, hi, d_counts, false); }
+int alpgpu_decode_count_range_f32(alpgpu_ctx* ctx, const alpgpu_column* col, float lo, float hi, uint32_t* d_counts) { return decode_count_range(ctx, col, lo, hi, d_counts, true); }
 
 extern "C++" {
 // the next tag of the context's progress word (its top 24 bits: a stale value of an earlier launch reads as "not started")
@@ -335,8 +226,9 @@ static int decode_one(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_out) {
 	// The read-ahead (read_ahead_kernels.hip): a few persistent workgroups on the context's second stream pull the column's streams into the Infinity
 	// Cache a bounded distance ahead of the decode kernel, which tells them where it is.  Started first so that it is ahead from the first workgroup on.
 	// (a float column streamed by persistent workgroups prefetches for itself; the read-ahead beside it changed nothing: call 14)
-	const bool ahead = read_ahead_for(ctx, col, VB) && !(VB == 4 && (decode_shape_f32(ctx, col) & 0xFF) >= 16);
-	uint64_t   tag   = 0;
+	const alpgpu::DecodePlan plan  = planned(ctx, col, VB);
+	const bool               ahead = plan.ahead;
+	uint64_t                 tag   = 0;
 	if (ahead) {
 		tag = next_progress_tag(ctx);
 		ALPGPU_HIP(hipEventRecord(ctx->ev_fork, ctx->stream)); // (the read-ahead may start where the decode may)
@@ -346,14 +238,11 @@ static int decode_one(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_out) {
 	// that is not even enqueued leaves, and that decode then runs without one).  The side stream has the higher priority: its few workgroups are placed at once.
 	int rc;
 	if constexpr (VB == 8) {
-		rc = alpgpu::launch_decode_column(ctx->stream, col, static_cast<double*>(d_out), decode_variant_for(ctx, col), ctx->n_cus, ahead ? ctx->d_progress : nullptr, tag);
+		rc = alpgpu::launch_decode_column(ctx->stream, col, static_cast<double*>(d_out), plan.shape, ctx->n_cus, ahead ? ctx->d_progress : nullptr, tag);
+	} else if (plan.shape.family == alpgpu::kDecodeStreamed) { // persistent workgroups (decode_stream_f32_kernels.hip): no read-ahead beside it, nothing to report
+		rc = alpgpu::launch_decode_stream_f32(ctx->stream, col, static_cast<float*>(d_out), plan.shape.stream_shape, ctx->n_cus, nullptr, 0);
 	} else {
-		const int shape = decode_shape_f32(ctx, col);
-		if ((shape & 0xFF) >= 16) { // the column streamed by persistent workgroups (decode_stream_f32_kernels.hip): no read-ahead beside it, nothing to report
-			rc = alpgpu::launch_decode_stream_f32(ctx->stream, col, static_cast<float*>(d_out), shape & 0xFF, ctx->n_cus, ahead ? ctx->d_progress : nullptr, tag);
-		} else {
-			rc = alpgpu::launch_decode_column_f32(ctx->stream, col, static_cast<float*>(d_out), shape & 0xFF, (ctx->decode_variant & 2) != 0, (shape >> 8) == 0xFF ? -1 : (shape >> 8), ahead ? ctx->d_progress : nullptr, tag);
-		}
+		rc = alpgpu::launch_decode_column_f32(ctx->stream, col, static_cast<float*>(d_out), plan.shape, ahead ? ctx->d_progress : nullptr, tag);
 	}
 	if (ahead) {
 		const alpgpu::ReadAheadPace pace = alpgpu::policy_read_ahead_pace(static_cast<double>(col->n_vectors), static_cast<double>(col->packed_bytes_hint),
@@ -419,29 +308,25 @@ static int decode_unhinted(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_ou
 	const uint64_t seg_vectors = segment_vectors_for(col->n_vectors);
 	const uint32_t n_seg       = static_cast<uint32_t>((col->n_vectors + seg_vectors - 1) / seg_vectors);
 	if (alpgpu::launch_segment_sums(ctx->stream, col, seg_vectors, n_seg, words + alpgpu::kCtxWordSegments) != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "segment sums launch failed", hipGetLastError()); }
-	if (alpgpu::launch_unhinted_plan(ctx->stream, words, n_seg, col->n_vectors, VB, (ctx->read_ahead < 0 && ctx->streams_serialize) ? 0 : ctx->read_ahead, ctx->read_ahead_us, kReadAheadMaxBits) != ALPGPU_OK) {
+	if (alpgpu::launch_unhinted_plan(ctx->stream, words, n_seg, col->n_vectors, VB, (ctx->decode_opt.read_ahead < 0 && ctx->decode_opt.streams_serialize) ? 0 : ctx->decode_opt.read_ahead, ctx->read_ahead_us, kReadAheadMaxBits) != ALPGPU_OK) {
 		return fail(ALPGPU_ERR_HIP, "plan launch failed", hipGetLastError());
 	}
 	const uint64_t tag        = next_progress_tag(ctx);
-	const bool     with_ahead = ctx->read_ahead > 0 || (ctx->read_ahead < 0 && !ctx->streams_serialize);
+	const bool     with_ahead = ctx->decode_opt.read_ahead > 0 || (ctx->decode_opt.read_ahead < 0 && !ctx->decode_opt.streams_serialize);
 	if (with_ahead) { ALPGPU_HIP(hipEventRecord(ctx->ev_fork, ctx->stream)); }
-	const bool plain = (ctx->decode_variant & 2) != 0;
-	int        rc    = ALPGPU_OK;
+	int rc = ALPGPU_OK;
 	// Which launch.  A closed candidate is not free: the dispatcher hands out ~5.5 workgroups per nanosecond, so 1 Mi empty workgroups cost 0.19 ms — 10-17 % of a
 	// decode (call 1b: first unhinted decode 0.59-0.68 of peak against 0.72-0.81 hinted with all three candidates launched).  Default (1) therefore: ONE launch in the
-	// shape a column without hints always got (double: one vector per workgroup, 6 KiB pad; float: two), un-gated, and the device-side plan steers the read-ahead only —
-	// which is what narrow columns gain most from — while the sizes travel to the host for the next decode.  2: every candidate, gated (the measured alternative).
-	if constexpr (VB == 8) { // decode_policy.hpp: 1 = one vector per workgroup + 6 KiB, 2 = two per workgroup, 3 = one per workgroup + 11 KiB
-		if (ctx->decode_unhinted == 2) {
-			const int variants[alpgpu::kUnhintedShapesF64] = {1 | (6 << 8), 0, 1 | (11 << 8)};
-			for (int c = 0; c < alpgpu::kUnhintedShapesF64 && rc == ALPGPU_OK; ++c) {
-				rc = alpgpu::launch_decode_column(ctx->stream, col, static_cast<double*>(d_out), variants[c] | (plain ? 2 : 0), ctx->n_cus, words, tag, static_cast<uint32_t>(c + 1));
-			}
-		} else {
-			rc = alpgpu::launch_decode_column(ctx->stream, col, static_cast<double*>(d_out), 1 | (6 << 8) | (plain ? 2 : 0), ctx->n_cus, words, tag, 0u);
-		}
-	} else {
-		rc = alpgpu::launch_decode_column_f32(ctx->stream, col, static_cast<float*>(d_out), 2, plain, 0, words, tag, 0u);
+	// shape a column without hints always got (the first candidate — double: one vector per workgroup, 6 KiB pad; float: two), un-gated, and the device-side plan steers
+	// the read-ahead only — which is what narrow columns gain most from — while the sizes travel to the host for the next decode.  2: every candidate, gated (the
+	// measured alternative).  The candidates: decode_policy.hpp, beside policy_unhinted, which numbers them.
+	const int n_launch = ctx->decode_unhinted == 2 ? (VB == 8 ? alpgpu::kUnhintedShapesF64 : alpgpu::kUnhintedShapesF32) : 1;
+	for (int c = 0; c < n_launch && rc == ALPGPU_OK; ++c) {
+		alpgpu::DecodeShape shape = VB == 8 ? alpgpu::kUnhintedCandidatesF64[c] : alpgpu::kUnhintedCandidatesF32[c];
+		shape.plain_stores        = ctx->decode_opt.plain_stores;
+		const uint32_t gate       = n_launch > 1 ? static_cast<uint32_t>(c + 1) : 0u;
+		rc = VB == 8 ? alpgpu::launch_decode_column(ctx->stream, col, static_cast<double*>(d_out), shape, ctx->n_cus, words, tag, gate)
+		             : alpgpu::launch_decode_column_f32(ctx->stream, col, static_cast<float*>(d_out), shape, words, tag, gate);
 	}
 	if (with_ahead) { // behind the decode's launch (decode_one says why); the kernel leaves at once when the plan says "no read-ahead for this column"
 		ALPGPU_HIP(hipStreamWaitEvent(ctx->init_stream, ctx->ev_fork, 0));
@@ -481,7 +366,7 @@ static int decode_unhinted(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_ou
 // the column's sizes are unknown to the host and the decode takes them on the stream (decode_unhinted), or from what an earlier one learned
 static bool decodes_unhinted(const alpgpu_ctx* ctx, const alpgpu_column* col, int value_bytes) {
 	const bool unhinted   = col->packed_bytes_hint == 0 && col->exc_bytes_hint == 0;
-	const bool free_shape = ctx->decode_auto && ctx->decode_pad_kib < 0 && (value_bytes == 8 || ctx->decode_vpw == 0);
+	const bool free_shape = ctx->decode_opt.forced_vpw == 0 && ctx->decode_opt.forced_pad_kib < 0;
 	return unhinted && ctx->decode_unhinted && free_shape && ctx->d_progress != nullptr && col->n_vectors >= kUnhintedMinVectors;
 }
 static bool stream_capturing(hipStream_t s) {
@@ -552,8 +437,7 @@ int alpgpu_debug_unhinted_plan(alpgpu_ctx* ctx, uint64_t* out6) {
 }
 
 // debug aid (tests): the launch decode() of this column would make now, for the column as a whole (a region plan gives each run its own: alpgpu_decode_runs).
-// out4[0] the double variant word (decode_variant_for: bit 0 one vector per workgroup, bit 1 plain stores, bit 6 the 256-entry exception stage, bits 8.. the residency
-// pad in KiB) or the float shape word (decode_shape_f32: vectors per workgroup or streamed shape, bits 8.. the pad, 0xFF none); [1..3] the sizes it is planned from
+// out4[0] the shape as the word include/alpgpu.h documents (decode_policy.hpp: decode_debug_word); [1..3] the sizes it is planned from
 // (packed_bytes_hint, exc_bytes_hint, alp_rd_rowgroups_hint — for an unhinted column, what an earlier decode of it learned).  Returns 1: planned on the host; 0: an
 // unhinted decode whose plan is made on the device (out4 untouched); negative on bad arguments.  Waits for nothing.
 int alpgpu_debug_decode_plan(alpgpu_ctx* ctx, const alpgpu_column* col, int is_f32, uint64_t* out4) {
@@ -564,24 +448,20 @@ int alpgpu_debug_decode_plan(alpgpu_ctx* ctx, const alpgpu_column* col, int is_f
 		if (!learned_hints(ctx, col, is_f32 ? 4 : 8, &hinted)) { return 0; }
 		col = &hinted;
 	}
-	out4[0] = static_cast<uint64_t>(is_f32 ? decode_shape_f32(ctx, col) : decode_variant_for(ctx, col));
+	out4[0] = alpgpu::decode_debug_word(planned(ctx, col, is_f32 ? 4 : 8).shape, is_f32 ? 4 : 8);
 	out4[1] = col->packed_bytes_hint, out4[2] = col->exc_bytes_hint, out4[3] = col->alp_rd_rowgroups_hint;
 	return 1;
 }
 
 // how many launches alpgpu_decode_f64 would make for this column now: 1, or the number of runs of plan_decode_runs; negative on bad arguments
-int alpgpu_decode_runs(alpgpu_ctx* ctx, const alpgpu_column* col) {
+static int decode_runs(alpgpu_ctx* ctx, const alpgpu_column* col, int value_bytes) {
 	if (!ctx || !col) { return fail(ALPGPU_ERR_INVALID, "null context or column"); }
 	DecodeRun runs[kMaxRuns];
-	const int n_runs = plan_decode_runs(ctx, col, runs, 8);
+	const int n_runs = plan_decode_runs(ctx, col, runs, value_bytes);
 	return n_runs == 0 ? 1 : n_runs;
 }
-int alpgpu_decode_runs_f32(alpgpu_ctx* ctx, const alpgpu_column* col) {
-	if (!ctx || !col) { return fail(ALPGPU_ERR_INVALID, "null context or column"); }
-	DecodeRun runs[kMaxRuns];
-	const int n_runs = plan_decode_runs(ctx, col, runs, 4);
-	return n_runs == 0 ? 1 : n_runs;
-}
+int alpgpu_decode_runs(alpgpu_ctx* ctx, const alpgpu_column* col) { return decode_runs(ctx, col, 8); }
+int alpgpu_decode_runs_f32(alpgpu_ctx* ctx, const alpgpu_column* col) { return decode_runs(ctx, col, 4); }
 int alpgpu_column_totals(alpgpu_ctx* ctx, alpgpu_column* col, uint64_t* packed_bytes, uint64_t* exc_bytes, int* overflow) {
 	ALPGPU_CHECK_CTX(ctx);
 	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }
@@ -620,24 +500,4 @@ int alpgpu_column_totals(alpgpu_ctx* ctx, alpgpu_column* col, uint64_t* packed_b
 	if (t[3]) { return fail(ALPGPU_ERR_HIP, "single-pass encode stalled in its offset look-back and was not recovered"); }
 	return t[2] ? fail(ALPGPU_ERR_CAPACITY, "an output stream overflowed its capacity") : ALPGPU_OK;
 }
-int alpgpu_decode_sum_f32(alpgpu_ctx* ctx, const alpgpu_column* col, double* d_sums) {
-	ALPGPU_CHECK_CTX(ctx);
-	if (!col || (!d_sums && col->n_vectors)) { return fail(ALPGPU_ERR_INVALID, "null column or output"); }
-	if (col->n_vectors == 0) { return ALPGPU_OK; }
-	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
-	if (sum_launch_f32(ctx, col, d_sums) != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "decode-sum launch failed", hipGetLastError()); }
-	return ALPGPU_OK;
-}
-
-int alpgpu_decode_count_range_f32(alpgpu_ctx* ctx, const alpgpu_column* col, float lo, float hi, uint32_t* d_counts) {
-	ALPGPU_CHECK_CTX(ctx);
-	if (!col || (!d_counts && col->n_vectors)) { return fail(ALPGPU_ERR_INVALID, "null column or output"); }
-	if (col->n_vectors == 0) { return ALPGPU_OK; }
-	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
-	if ((use_direct_sink_f32(ctx, col) ? alpgpu::launch_sink_direct_f32(ctx->stream, col, lo, hi, d_counts, true) : alpgpu::launch_decode_count_range_f32(ctx->stream, col, lo, hi, d_counts)) != ALPGPU_OK) {
-		return fail(ALPGPU_ERR_HIP, "decode-count launch failed", hipGetLastError());
-	}
-	return ALPGPU_OK;
-}
-
 } // extern "C"

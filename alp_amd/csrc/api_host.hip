@@ -33,14 +33,14 @@ struct HostPipe { // everything a call allocates, released on every return path
 		ctx              = c;
 		saved            = c->stream;
 		saved_unordered  = c->encode_unordered;
-		saved_read_ahead = c->read_ahead, saved_unhinted = c->decode_unhinted;
-		c->read_ahead = 0, c->decode_unhinted = 0;
+		saved_read_ahead = c->decode_opt.read_ahead, saved_unhinted = c->decode_unhinted;
+		c->decode_opt.read_ahead = 0, c->decode_unhinted = 0;
 	}
 	~HostPipe() {
 		if (ctx) {
 			ctx->stream           = saved;
 			ctx->encode_unordered = saved_unordered;
-			ctx->read_ahead = saved_read_ahead, ctx->decode_unhinted = saved_unhinted;
+			ctx->decode_opt.read_ahead = saved_read_ahead, ctx->decode_unhinted = saved_unhinted;
 		}
 		for (int k = 0; k < 2; ++k) {
 			if (stream[k]) { (void)hipStreamSynchronize(stream[k]); }

@@ -417,35 +417,29 @@ __global__ __launch_bounds__(kDecThreadsF) void k_decode_column_f32(const alpgpu
 }
 
 template <int V>
-static void launch_v(hipStream_t stream, const alpgpu_column* col, float* d_out, bool nt, int pad_kib, uint64_t* progress, uint64_t tag, uint32_t gate) {
-	const uint64_t n        = col->n_vectors;
-	const uint64_t n_wg     = (n + V - 1) / V;
-	const uint64_t kMaxGrid = 1ull << 30;
-	// unused dynamic LDS that caps the workgroups resident per CU, as the double decode does by width (pad_kib < 0: none)
-	const unsigned pad_lds = static_cast<unsigned>(pad_kib >= 0 ? pad_kib : 0) * 1024u;
+static void launch_v(hipStream_t stream, const alpgpu_column* col, float* d_out, const DecodeShape& shape, uint64_t* progress, uint64_t tag, uint32_t gate) {
+	const uint64_t n = col->n_vectors;
+	// unused dynamic LDS that caps the workgroups resident per CU, as the double decode does by width
+	const unsigned pad_lds = shape.pad_kib > 0 ? static_cast<unsigned>(shape.pad_kib) * 1024u : 0u;
 	if (gate != 0 && progress == nullptr) { gate = 0; }
-	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
-		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(kDecThreadsF);
-		if (nt) {
+	launch_in_grid_chunks((n + V - 1) / V, [&](dim3 grid, uint64_t off) {
+		const dim3 block(kDecThreadsF);
+		if (!shape.plain_stores) {
 			hipLaunchKernelGGL((k_decode_column_f32<V, true>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0f, 0.0f, progress, tag, gate);
 		} else {
 			hipLaunchKernelGGL((k_decode_column_f32<V, false>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0f, 0.0f, progress, tag, gate);
 		}
-	}
+	});
 }
 
 static int launch_store_direct_f32(hipStream_t stream, const alpgpu_column* col, float* d_out, int pad_kib, uint64_t* progress, uint64_t progress_tag); // (below, behind its kernel)
-// vectors_per_wg in {1, 2, 4}; 8 = one wavefront per vector
-int launch_decode_column_f32(hipStream_t stream, const alpgpu_column* col, float* d_out, int vectors_per_wg, bool plain_stores, int pad_kib, uint64_t* progress, uint64_t progress_tag,
-                             uint32_t gate) {
+int launch_decode_column_f32(hipStream_t stream, const alpgpu_column* col, float* d_out, const DecodeShape& shape, uint64_t* progress, uint64_t progress_tag, uint32_t gate) {
 	if (col->n_vectors == 0) { return ALPGPU_OK; }
-	if (vectors_per_wg == 8) { return launch_store_direct_f32(stream, col, d_out, pad_kib, progress, progress_tag); } // (no gate: never a candidate of an unhinted decode)
-	if (vectors_per_wg == 1) {
-		launch_v<1>(stream, col, d_out, !plain_stores, pad_kib, progress, progress_tag, gate);
-	} else if (vectors_per_wg == 2) {
-		launch_v<2>(stream, col, d_out, !plain_stores, pad_kib, progress, progress_tag, gate);
-	} else {
-		launch_v<4>(stream, col, d_out, !plain_stores, pad_kib, progress, progress_tag, gate);
+	if (shape.family == kDecodeWaveDirect) { return launch_store_direct_f32(stream, col, d_out, shape.pad_kib, progress, progress_tag); } // (no gate: never a candidate of an unhinted decode)
+	switch (shape.vectors_per_wg) {
+	case 1: launch_v<1>(stream, col, d_out, shape, progress, progress_tag, gate); break;
+	case 2: launch_v<2>(stream, col, d_out, shape, progress, progress_tag, gate); break;
+	default: launch_v<4>(stream, col, d_out, shape, progress, progress_tag, gate); break;
 	}
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }
@@ -454,13 +448,10 @@ template <int SINK, int V>
 static int launch_sink_f32(hipStream_t stream, const alpgpu_column* col, void* d_result, float lo, float hi) {
 	const uint64_t n = col->n_vectors;
 	if (n == 0) { return ALPGPU_OK; }
-	const uint64_t n_wg     = (n + V - 1) / V;
-	const uint64_t kMaxGrid = 1ull << 30;
-	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
-		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(kDecThreadsF);
-		hipLaunchKernelGGL((k_decode_column_f32<V, false, SINK>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc,
+	launch_in_grid_chunks((n + V - 1) / V, [&](dim3 grid, uint64_t off) {
+		hipLaunchKernelGGL((k_decode_column_f32<V, false, SINK>), grid, dim3(kDecThreadsF), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc,
 		                   static_cast<float*>(d_result), n, off, lo, hi, static_cast<uint64_t*>(nullptr), 0ull, 0u);
-	}
+	});
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }
 
@@ -591,38 +582,36 @@ __global__ __launch_bounds__(kDecThreadsF, 8) void k_sink_direct_f32(const alpgp
 
 // one wavefront per vector, four vectors per workgroup, no barrier: k_sink_direct_f32 as a store decoder (non-temporal stores)
 static int launch_store_direct_f32(hipStream_t stream, const alpgpu_column* col, float* d_out, int pad_kib, uint64_t* progress, uint64_t progress_tag) {
-	const uint64_t n = col->n_vectors, n_wg = (n + 3) / 4, kMaxGrid = 1ull << 30;
-	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
-		hipLaunchKernelGGL((k_sink_direct_f32<kSinkStoreF>), dim3(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), dim3(kDecThreadsF), pad_kib > 0 ? static_cast<unsigned>(pad_kib) * 1024u : 0u, stream,
+	const uint64_t n = col->n_vectors;
+	launch_in_grid_chunks((n + 3) / 4, [&](dim3 grid, uint64_t off) {
+		hipLaunchKernelGGL((k_sink_direct_f32<kSinkStoreF>), grid, dim3(kDecThreadsF), pad_kib > 0 ? static_cast<unsigned>(pad_kib) * 1024u : 0u, stream,
 		                   col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, reinterpret_cast<double*>(d_out), n, off, 0.0f, 0.0f, progress, progress_tag);
-	}
+	});
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }
 
 int launch_sink_direct_f32(hipStream_t stream, const alpgpu_column* col, float lo, float hi, void* d_out, bool count) {
 	const uint64_t n = col->n_vectors;
 	if (n == 0) { return ALPGPU_OK; }
-	const uint64_t per_wg   = kDecThreadsF / 64;
-	const uint64_t n_wg     = (n + per_wg - 1) / per_wg;
-	const uint64_t kMaxGrid = 1ull << 30;
-	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
-		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(kDecThreadsF);
+	const uint64_t per_wg = kDecThreadsF / 64;
+	launch_in_grid_chunks((n + per_wg - 1) / per_wg, [&](dim3 grid, uint64_t off) {
+		const dim3 block(kDecThreadsF);
 		if (count) {
 			hipLaunchKernelGGL((k_sink_direct_f32<kSinkCountF>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_out), n, off, lo, hi, static_cast<uint64_t*>(nullptr), 0ull);
 		} else {
 			hipLaunchKernelGGL((k_sink_direct_f32<kSinkSumF>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_out), n, off, 0.0f, 0.0f, static_cast<uint64_t*>(nullptr), 0ull);
 		}
-	}
+	});
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }
 
 // d_zones[v] = {min, max} of vector v's decoded values, NaNs ignored (include/alpgpu.h: zone maps); n_vectors > 0
 int launch_zone_map_f32(hipStream_t stream, const alpgpu_column* col, void* d_zones) {
-	const uint64_t n = col->n_vectors, per_wg = kDecThreadsF / 64, n_wg = (n + per_wg - 1) / per_wg, kMaxGrid = 1ull << 30;
-	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
-		hipLaunchKernelGGL((k_sink_direct_f32<kSinkMinMaxF>), dim3(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), dim3(kDecThreadsF), 0, stream, col->d_vectors,
+	const uint64_t n = col->n_vectors, per_wg = kDecThreadsF / 64;
+	launch_in_grid_chunks((n + per_wg - 1) / per_wg, [&](dim3 grid, uint64_t off) {
+		hipLaunchKernelGGL((k_sink_direct_f32<kSinkMinMaxF>), grid, dim3(kDecThreadsF), 0, stream, col->d_vectors,
 		                   col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_zones), n, off, 0.0f, 0.0f, static_cast<uint64_t*>(nullptr), 0ull);
-	}
+	});
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }
 

@@ -56,7 +56,7 @@ using DecodeLds = DecodeLdsT<kStageBytes>;
 // Round 6: columns whose vectors carry MORE exceptions than the 128-entry stage holds on average (bench.py's 10 %-exceptions column: 187 per vector) decode every
 // value beyond the stage with a load from HBM in the unpack loop (the run-time form of decode_vector_quarters).  A 256-entry stage lifts that column from 0.72 to 0.77
 // of the HBM peak — and costs every OTHER column 2-6 % (1 KiB more LDS per vector: city_temperature 0.78 -> 0.74, nyc29 0.81 -> 0.78; call 6), so it is an instance
-// of its own, launched for columns whose hints say so (api_decode.hip: decode_variant_for, variant bit 6).
+// of its own, launched for columns whose hints say so (decode_policy.hpp: policy_shape_f64, DecodeShape::many_exc).
 using DecodeLdsManyExc = DecodeLdsT<kStageBytes, 2 * kExcStage>;
 
 // The exception mask (32 words) as seen by one wavefront: lane l < 32 holds word l and the number of exceptions in the
@@ -799,103 +799,87 @@ __global__ __launch_bounds__(64 * kDecWaves, kSinkDirectOcc) void k_sink_direct(
 }
 
 int launch_sink_direct(hipStream_t stream, const alpgpu_column* col, double lo, double hi, void* d_out, bool count) {
-	const uint64_t n        = col->n_vectors;
-	const uint64_t n_wg     = (n + kDecWaves - 1) / kDecWaves;
-	const uint64_t kMaxGrid = 1ull << 30;
-	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
-		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(64 * kDecWaves);
+	const uint64_t n = col->n_vectors;
+	launch_in_grid_chunks((n + kDecWaves - 1) / kDecWaves, [&](dim3 grid, uint64_t off) {
+		const dim3 block(64 * kDecWaves);
 		if (count) {
 			hipLaunchKernelGGL((k_sink_direct<kSinkCount>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_out), n, off, lo, hi);
 		} else {
 			hipLaunchKernelGGL((k_sink_direct<kSinkSum>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_out), n, off, 0.0, 0.0);
 		}
-	}
+	});
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }
 
 // d_zones[v] = {min, max} of vector v's decoded values, NaNs ignored (include/alpgpu.h: zone maps); n_vectors > 0
 int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones) {
-	const uint64_t n        = col->n_vectors;
-	const uint64_t n_wg     = (n + kDecWaves - 1) / kDecWaves;
-	const uint64_t kMaxGrid = 1ull << 30;
-	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
-		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(64 * kDecWaves);
-		hipLaunchKernelGGL((k_sink_direct<kSinkMinMax>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_zones), n, off, 0.0, 0.0);
-	}
+	const uint64_t n = col->n_vectors;
+	launch_in_grid_chunks((n + kDecWaves - 1) / kDecWaves, [&](dim3 grid, uint64_t off) {
+		hipLaunchKernelGGL((k_sink_direct<kSinkMinMax>), grid, dim3(64 * kDecWaves), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_zones), n, off, 0.0, 0.0);
+	});
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }
 
-int launch_decode_column(hipStream_t stream, const alpgpu_column* col, double* d_out, int variant, int n_cus, uint64_t* progress, uint64_t progress_tag, uint32_t gate) {
+int launch_decode_column(hipStream_t stream, const alpgpu_column* col, double* d_out, const DecodeShape& shape, int n_cus, uint64_t* progress, uint64_t progress_tag, uint32_t gate) {
 	(void)n_cus;
 	const uint32_t gate_word = gate != 0 && progress != nullptr ? gate << 8 : 0u; // (k_decode_column: a candidate launch of an unhinted decode)
 	const uint64_t n = col->n_vectors;
-	// variant bit 0: one vector per workgroup (default) instead of two; bit 1: plain instead of non-temporal stores
-	const bool     nt       = !(variant & 2);
-	const int      V        = (variant & 1) ? 1 : 2;
-	// Unused dynamic LDS that caps the workgroups resident per CU (variant bits 8.. = KiB).  Wide vectors want FEWER
+	const bool     nt       = !shape.plain_stores;
+	const int      V        = shape.vectors_per_wg == 1 ? 1 : 2;
+	// Unused dynamic LDS that caps the workgroups resident per CU (shape.pad_kib).  Wide vectors want FEWER
 	// streams in flight per CU than the eight the wavefront slots allow: a column of 40-53-bit vectors decodes at 0.81 of the HBM peak with six
 	// workgroups per CU and at 0.75 with eight, 34-38 bits like seven; up to 33 bits eight are best (tools/sweep_residency.py,
-	// profiles/r04_decode_floor.txt section 6).  decode_variant_for (api_decode.hip) sets it from the column's size hints.
-	const unsigned pad_lds  = static_cast<unsigned>((variant >> 8) & 0xFF) * 1024u;
-	const uint64_t n_wg     = (n + V - 1) / V;
-	const uint64_t kMaxGrid = 1ull << 30; // a grid dimension holds < 2^31 workgroups -> chunk very long columns
-	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
-		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(64 * kDecWaves);
+	// profiles/r04_decode_floor.txt section 6).  policy_shape_f64 (decode_policy.hpp) sets it from the column's size hints.
+	const unsigned pad_lds  = shape.pad_kib > 0 ? static_cast<unsigned>(shape.pad_kib) * 1024u : 0u;
+	launch_in_grid_chunks((n + V - 1) / V, [&](dim3 grid, uint64_t off) {
+		const dim3 block(64 * kDecWaves);
 		if (V == 2 && nt) {
 			hipLaunchKernelGGL((k_decode_column<2, true>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
 		} else if (V == 2) {
 			hipLaunchKernelGGL((k_decode_column<2, false>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
-		} else if ((variant & 64) && nt) { // one vector per workgroup, the 256-entry exception stage (columns of exception-heavy vectors)
+		} else if (shape.many_exc && nt) { // one vector per workgroup, the 256-entry exception stage (columns of exception-heavy vectors)
 			hipLaunchKernelGGL((k_decode_column<1, true, kSinkStore, DecodeLdsManyExc>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
 		} else if (nt) {
 			hipLaunchKernelGGL((k_decode_column<1, true>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
 		} else {
 			hipLaunchKernelGGL((k_decode_column<1, false>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
 		}
-	}
+	});
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }
 
 // vectors_per_wg in {1, 2}.  There is no output stream to compete with, so two vectors in flight per workgroup is the default
 // (measured on the benchmark column: 1.39 / 1.16 / 1.43 ms for 1 / 2 / 4 vectors per workgroup).
 int launch_decode_sum(hipStream_t stream, const alpgpu_column* col, double* d_sums, int vectors_per_wg) {
-	const uint64_t n        = col->n_vectors;
-	const int      V        = vectors_per_wg == 1 ? 1 : 2;
-	const uint64_t n_wg     = (n + V - 1) / V;
-	const uint64_t kMaxGrid = 1ull << 30;
-	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
-		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(64 * kDecWaves);
+	const uint64_t n = col->n_vectors;
+	const int      V = vectors_per_wg == 1 ? 1 : 2;
+	launch_in_grid_chunks((n + V - 1) / V, [&](dim3 grid, uint64_t off) {
+		const dim3 block(64 * kDecWaves);
 		if (V == 2) {
 			hipLaunchKernelGGL((k_decode_column<2, false, kSinkSum>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_sums, n, off, 0.0, 0.0, 0u, static_cast<uint64_t*>(nullptr), 0ull);
 		} else {
 			hipLaunchKernelGGL((k_decode_column<1, false, kSinkSum>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_sums, n, off, 0.0, 0.0, 0u, static_cast<uint64_t*>(nullptr), 0ull);
 		}
-	}
+	});
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }
 
 // measurement aid: the fused consumers' loads, barrier and reduction with the unpack left out (two vectors per workgroup, like them)
 int launch_decode_probe(hipStream_t stream, const alpgpu_column* col, double* d_sums) {
-	const uint64_t n        = col->n_vectors;
-	const uint64_t n_wg     = (n + 1) / 2;
-	const uint64_t kMaxGrid = 1ull << 30;
-	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
-		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(64 * kDecWaves);
-		hipLaunchKernelGGL((k_decode_column<2, false, kSinkProbe>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_sums, n, off, 0.0, 0.0, 0u, static_cast<uint64_t*>(nullptr), 0ull);
-	}
+	const uint64_t n = col->n_vectors;
+	launch_in_grid_chunks((n + 1) / 2, [&](dim3 grid, uint64_t off) {
+		hipLaunchKernelGGL((k_decode_column<2, false, kSinkProbe>), grid, dim3(64 * kDecWaves), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_sums, n, off, 0.0, 0.0, 0u, static_cast<uint64_t*>(nullptr), 0ull);
+	});
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }
 
 // per-vector number of values in [lo, hi]: the same kernel with the predicate as its consumer (two vectors per workgroup)
 int launch_decode_count_range(hipStream_t stream, const alpgpu_column* col, double lo, double hi, uint32_t* d_counts) {
-	const uint64_t n        = col->n_vectors;
-	const uint64_t n_wg     = (n + 1) / 2;
-	const uint64_t kMaxGrid = 1ull << 30;
-	for (uint64_t off = 0; off < n_wg; off += kMaxGrid) {
-		const dim3 grid(static_cast<unsigned>(n_wg - off < kMaxGrid ? n_wg - off : kMaxGrid)), block(64 * kDecWaves);
-		hipLaunchKernelGGL((k_decode_column<2, false, kSinkCount>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc,
+	const uint64_t n = col->n_vectors;
+	launch_in_grid_chunks((n + 1) / 2, [&](dim3 grid, uint64_t off) {
+		hipLaunchKernelGGL((k_decode_column<2, false, kSinkCount>), grid, dim3(64 * kDecWaves), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc,
 		                   reinterpret_cast<double*>(d_counts), n, off, lo, hi, 0u, static_cast<uint64_t*>(nullptr), 0ull);
-	}
+	});
 	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
 }
 

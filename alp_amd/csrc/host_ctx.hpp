@@ -2,7 +2,8 @@
 // macros and the few helpers more than one of them uses.  The extern "C" surface is spread over
 //   api_context.hip    contexts, options, streams, memory, the scan workspace
 //   api_encode.hip     rowgroup search + vector encode entry points (and the encode's measurement probes)
-//   api_decode.hip     the store decode's LAUNCH POLICY (shape, residency, read-ahead, region by region), the fused consumers, alpgpu_column_totals
+//   api_decode.hip     the store decode's entry points and the host state of its launch plan (segment tables, learn slots, streams and events), the fused
+//                      consumers, alpgpu_column_totals; the launch RULE itself is decode_policy.hpp: pure functions, shared with the device and the CPU tests
 //   api_primitives.hip the reference's per-vector primitives in batch form
 //   api_container.hip  the serialized column (blob) and the descriptor checks
 //   api_host.hip       columns that live in host memory: the chunked two-stream pipelines, one or several contexts
@@ -60,9 +61,7 @@ struct alpgpu_ctx {
 	hipStream_t own_stream;
 	hipStream_t stream;
 	int         n_cus;
-	int         decode_variant;
-	int         decode_auto;     // 1: vectors per decode workgroup chosen from the column's size hints
-	int         decode_vpw;      // the value last given to ALPGPU_OPT_DECODE_VECTORS_PER_WG (0 auto, 1, 2, 4, 8, 16-30); float decode reads this
+	alpgpu::DecodeOptions decode_opt; // what the store decode's launch rule takes from alpgpu_set_option (decode_policy.hpp): forced shape, forced pad, read-ahead, plain stores
 	char        name[128];
 	uint64_t    hbm_bytes;
 	int         encode_two_pass; // 0 (default): single-pass encode with look-back offsets; 1: analysis + scan + pack
@@ -71,10 +70,7 @@ struct alpgpu_ctx {
 	hipStream_t init_stream;     // ... on this stream (highest priority: its few workgroups are placed first)
 	hipEvent_t  ev_fork, ev_head, ev_join;
 	int         encode_unordered; // ALPGPU_OPT_ENCODE_UNORDERED: tiles reserve their stream bytes with one atomic add (lean kernel, device columns only)
-	int         decode_pad_kib;    // ALPGPU_OPT_DECODE_RESIDENCY_PAD: KiB of unused dynamic LDS per decode workgroup (-1: chosen from the column's hints)
-	int         read_ahead;        // ALPGPU_OPT_DECODE_READ_AHEAD: the store decode runs with a read-ahead into the Infinity Cache on the second stream (read_ahead_kernels.hip)
-	int         streams_serialize; // the process runs with GPU_MAX_HW_QUEUES=1 / AMD_SERIALIZE_KERNEL / HIP_LAUNCH_BLOCKING: left to itself (-1) the library starts no read-ahead
-	int         read_ahead_us;     // ... this many microseconds ahead of the decode kernel (0: 12 + 6.5 us per packed bit of the vectors, at most 60)
+	int         read_ahead_us;     // the read-ahead (decode_opt.read_ahead; read_ahead_kernels.hip) runs this many microseconds ahead of the decode kernel (0: 12 + 6.5 us per packed bit of the vectors, at most 60)
 	uint64_t*   d_progress;        // ... paced by this word of device memory (2 KiB; the map of its words: decode_policy.hpp)
 	uint64_t    progress_gen;      // ... whose tag changes with every launch
 	uint32_t    wall_tick_ps;      // picoseconds per tick of the device's wall_clock64() (the read-ahead's naps)

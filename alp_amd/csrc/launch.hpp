@@ -4,8 +4,16 @@
 #include <stdint.h>
 
 #include "../../include/alpgpu.h"
+#include "decode_policy.hpp"
 
 namespace alpgpu {
+
+// A grid dimension holds < 2^31 workgroups: a launch over n_wg workgroups goes out in chunks of at most 2^30, and launch(grid, first workgroup of the chunk) makes
+// each — the kernels take that offset as an argument.
+inline uint64_t grid_chunk(uint64_t n_wg_left) { constexpr uint64_t kMaxGrid = 1ull << 30; return n_wg_left < kMaxGrid ? n_wg_left : kMaxGrid; }
+template <class Launch> inline void launch_in_grid_chunks(uint64_t n_wg, Launch&& launch) {
+	for (uint64_t off = 0; off < n_wg; off += grid_chunk(n_wg - off)) { launch(dim3(static_cast<unsigned>(grid_chunk(n_wg - off))), off); }
+}
 
 // what alpgpu_encode_* memsets the rowgroup states to in front of a search that PUBLISHES them beside the encode: every byte 0xFF = "not there"
 // (alp_device.hpp: rowgroup_state_is_whole — no word of a real state is all-ones, so a torn read of a state being published is recognised)
@@ -14,7 +22,7 @@ constexpr int kStateUnpublished = 0xFF;
 // decode_kernels.hip
 // progress (nullable): a word of device memory the kernel's workgroups report their position to, tagged (read_ahead_kernels.hip)
 // gate (unhinted decode, api_decode.hip): != 0 -> the launch runs only if the context's shape word (progress[kCtxWordShape], decode_policy.hpp) holds this value
-int launch_decode_column(hipStream_t stream, const alpgpu_column* col, double* d_out, int variant, int n_cus, uint64_t* progress = nullptr, uint64_t progress_tag = 0,
+int launch_decode_column(hipStream_t stream, const alpgpu_column* col, double* d_out, const DecodeShape& shape, int n_cus, uint64_t* progress = nullptr, uint64_t progress_tag = 0,
                          uint32_t gate = 0);
 // read_ahead_kernels.hip: the column's descriptors, packed words and exception records read into the Infinity Cache a bounded distance ahead of the decode
 // kernel that reports to d_progress with this tag (lead_min / lead_max in vectors; value_bytes 8 or 4; grid workgroups of four wavefronts)
@@ -131,9 +139,8 @@ int launch_rd_decode(hipStream_t stream, int n_cus, double* out, const uint64_t*
 
 
 // ---- single precision (decode_f32_kernels.hip, encode_f32_kernels.hip, init_kernels.hip, primitive_f32_kernels.hip) ----
-// pad_kib: unused dynamic LDS per workgroup (residency cap); progress / tag / gate: as launch_decode_column
-int launch_decode_column_f32(hipStream_t stream, const alpgpu_column* col, float* d_out, int vectors_per_wg, bool plain_stores, int pad_kib = -1, uint64_t* progress = nullptr,
-                             uint64_t progress_tag = 0, uint32_t gate = 0);
+// shape: staged or one wavefront per vector (a streamed one goes to launch_decode_stream_f32); progress / tag / gate: as launch_decode_column
+int launch_decode_column_f32(hipStream_t stream, const alpgpu_column* col, float* d_out, const DecodeShape& shape, uint64_t* progress = nullptr, uint64_t progress_tag = 0, uint32_t gate = 0);
 // decode_stream_f32_kernels.hip: persistent workgroups, three chunks in flight each; shape 16: chunks of 8 vectors / 8 KiB of records, 17: 16 / 16 KiB, 18: 4 / 12 KiB
 int launch_decode_stream_f32(hipStream_t stream, const alpgpu_column* col, float* d_out, int shape, int n_cus, uint64_t* progress = nullptr, uint64_t progress_tag = 0);
 int launch_rowgroup_init_f32(hipStream_t stream, const float* d_in, uint64_t n_vectors, alpgpu_rowgroup_state* d_rgs, uint16_t* d_rd_order,

@@ -5,7 +5,7 @@ decode learns — and api_decode.hip holds that this state picks launch shapes o
 1. A content battery — ALP vectors of every bit width with 0 .. 1024 exceptions (sorted positions that include the first and the last slot, arbitrary bit patterns,
    NaN payloads among them), ALP_RD vectors with 0 .. 1024 exceptions, runs of 0-bit vectors, all of it mixed inside rowgroups — built by hand in the oracle's layout,
    tiled past two plan segments (>= 65 600 vectors), with its records in vector order and out of it.
-2. The lie matrix: hints that drive every arm of the launch rule (decode_variant_for, decode_shape_f32, read_ahead_for) over that content, with the read-ahead left
+2. The lie matrix (decode_lies.py): hints that drive every arm of the launch rule (decode_policy.hpp: policy_decode_plan) over that content, with the read-ahead left
    to the library, off and forced on.  Each arm is shown to be the one launched (alpgpu_debug_decode_plan) and writes the oracle's bytes.
 3. Stale plans: a region plan or learned sizes applied to other content in the same buffers (a D2D copy, another context's encode).
 Everything is compared bit for bit, NaNs included."""
@@ -14,10 +14,10 @@ import pytest
 import torch
 
 import layout
+from decode_lies import LIES_F32, LIES_F64, TILED_VECTORS, lie_hints
 
 pytestmark = pytest.mark.gpu
 
-TILED_VECTORS = 65600  # two segments of kSegmentMinVectors (api_decode.hip); more than the 32 768 the float stream shape and the forced read-ahead need
 EXC_COUNTS = [0, 1, 127, 128, 129, 255, 256, 257, 1023, 1024]
 RD_EXC_COUNTS = [0, 511, 512, 513, 1024]  # (2-byte ALP_RD exceptions: staged four times as deep as 8-byte ALP ones)
 NAN_PATTERNS = {8: [0x7FF0000000000001, 0x7FF8000000000000, 0xFFF8000000000123, 0x7FFFFFFFFFFFFFFF, 0x8000000000000000, 0x7FF0000000000000],
@@ -156,9 +156,7 @@ class Tiled:
 
     def lie(self, packed_bits, exc_bytes_per_vector, rd):
         c = self.col.c
-        c.packed_bytes_hint = max(1, int(packed_bits * 128 * self.n))
-        c.exc_bytes_hint = int(exc_bytes_per_vector * self.n)
-        c.alp_rd_rowgroups_hint = 1 + ((self.n + 99) // 100 if rd else 0)
+        c.packed_bytes_hint, c.exc_bytes_hint, c.alp_rd_rowgroups_hint = lie_hints(self.n, packed_bits, exc_bytes_per_vector, rd)
         assert 1 <= c.packed_bytes_hint <= c.packed_capacity and c.exc_bytes_hint <= c.exc_capacity
 
     def check(self, ctx, what):
@@ -186,37 +184,6 @@ def tiled(oracle, of32, vb, ordered):
         want = oracle.decode_column(enc) if vb == 8 else of32.decode_column(enc)
         _BATTERIES[key] = Tiled(enc, vb, want, ordered)
     return _BATTERIES[key]
-
-
-# name: (packed bits per value, exception bytes per vector, every rowgroup ALP_RD) -> the arm expected (double: vectors per workgroup, 256-entry stage, pad KiB)
-LIES_F64 = {
-    "all_0_bit":             ((1 / 128 / TILED_VECTORS, 0, False), (1, False, 14)),
-    "narrow_2_bits":         ((2, 0, False), (2, False, 0)),
-    "narrow_6_bits":         ((6, 0, False), (2, False, 0)),
-    "narrow_with_exc":       ((6, 200, False), (2, False, 0)),
-    "two_per_wg_capped":     ((12, 0, False), (2, False, 3)),
-    "one_per_wg_6k":         ((20, 0, False), (1, False, 6)),
-    "one_per_wg_uncapped":   ((32, 0, False), (1, False, 0)),
-    "band_30_with_exc":      ((30, 200, False), (1, False, 6)),
-    "band_38_with_exc":      ((38, 200, False), (1, False, 11)),
-    "band_46_with_exc":      ((46, 200, False), (1, False, 14)),
-    "band_38_no_exc":        ((38, 0, False), (1, False, 14)),
-    "exception_heavy":       ((40, 1300, False), (1, True, 11)),
-    "exception_heavy_26_bits": ((26, 1300, False), (1, True, 6)),
-    "exception_heavy_all_rd": ((40, 1300, True), (1, False, 11)),
-    "all_rd":                ((56, 0, True), (1, False, 11)),
-}
-# float: (vectors per workgroup or streamed shape)
-LIES_F32 = {
-    "all_0_bit":         ((1 / 128 / TILED_VECTORS, 0, False), 2),
-    "narrow_2_bits":     ((2, 0, False), 27),
-    "narrow_6_bits":     ((6, 0, False), 27),
-    "narrow_8_bits":     ((8, 0, False), 27),
-    "narrow_with_exc":   ((6, 120, False), 2),
-    "wide":              ((20, 0, False), 2),
-    "exception_heavy":   ((30, 1300, False), 2),
-    "all_rd":            ((28, 0, True), 2),
-}
 
 
 def _stream_direct_vectors(col_np_vec, n, chunk=12, arena=24576):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """decode: one against two vectors per workgroup over (bit width x exceptions per vector), 1 Mi vectors, plus GPU-encoded mixed / ALP_RD
-columns: the data behind the launch-shape rule of alpgpu_decode_f64 (api.hip: decode_variant_for).  sweep_vpw_exc.py [n_vectors]"""
+columns: the data behind the launch-shape rule of alpgpu_decode_f64 (decode_policy.hpp: policy_shape_f64).  sweep_vpw_exc.py [n_vectors]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """sweep_vpw_fine.py: decode of a 1 Mi-vector column of ONE bit width, one against two vectors per workgroup, for every width 1..40, without and
-with 20 exceptions per vector — where exactly the launch-shape rule of decode_variant_for (api.hip) should switch."""
+with 20 exceptions per vector — where exactly the launch-shape rule (decode_policy.hpp: policy_shape_f64) should switch."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
