@@ -201,3 +201,41 @@ def every_bit_width_column(n_vectors=208, seed=77, exceptions=True):
             vals[idx] = rng.choice([np.nan, 0.5, -0.0, 1e300, -2.5e-7], idx.size)
         col[o:o + 1024] = vals
     return col
+
+
+def every_bit_width_column_f32(n_vectors=200, seed=77, exceptions=True):
+    """ALP vectors of every packed width 0..32 inside ALP float rowgroups.  A float rowgroup goes to ALP_RD once the sampler's best estimate reaches
+    22 bits per value, so the sampled vectors (index % 12 == 0 inside a rowgroup) hold 2^30 + 128 m, m < 2^13: their range stays below 22 bits and
+    times ten they leave int32, so the rowgroup is ALP with k = 1 and (e,f) = (0,0).  Under (0,0) an integer-valued float encodes exactly if the
+    encoder's rounding (x + 1.5 * 2^23 - 1.5 * 2^23) keeps it: every integer in [-2^24, 2^22] does, and so does every multiple of 2^(w-24) below 2^31
+    in magnitude.  Vector j gets width (j mod 33): a constant (0), integers B + m with m < 2^w inside [-2^24, 2^22] (w <= 24), or multiples of
+    2^(w-24) spanning (-2^23, 2^23) steps (w >= 25), both extremes present.  With `exceptions`, every third vector also carries a few
+    NaN / 0.5 / -0.0 / 1e30 / -2.5e-7 values, never at the positions of its extremes (the width stays the one aimed at); which third moves by one
+    with every period of 33 vectors (33 is a multiple of 3), so that three periods give every width its exceptions."""
+    rng = np.random.default_rng(seed)
+    col = np.empty(n_vectors * VEC, np.float32)
+    for v in range(n_vectors):
+        o = v * VEC
+        if (v % 100) % 12 == 0:
+            col[o:o + VEC] = (2.0**30 + 128.0 * rng.integers(0, 2**13, VEC)).astype(np.float32)
+            continue
+        w = v % 33
+        if w == 0:
+            vals = np.full(VEC, float(rng.integers(-2**24 + 1, 2**22)))
+        elif w <= 24:
+            base = int(rng.integers(-2**24 + 1, 2**22 - 2**w + 2))  # base + 2^w - 1 <= 2^22
+            m = rng.integers(0, 2**w, VEC)
+            m[0], m[1] = 0, 2**w - 1
+            vals = (base + m).astype(np.float64)
+        else:
+            m = rng.integers(-2**23 + 1, 2**23, VEC)
+            m[0], m[1] = -2**23 + 1, 2**23 - 1  # range 2^24 - 2 steps: needs w bits
+            vals = m.astype(np.float64) * float(2 ** (w - 24))
+        rng.shuffle(vals)
+        vals = vals.astype(np.float32)  # exact: every value above is a float
+        if exceptions and (v + v // 33) % 3 == 1:
+            inner = np.nonzero((vals != vals.min()) & (vals != vals.max()))[0] if w > 0 else np.arange(VEC)
+            idx = rng.choice(inner, min(inner.size, int(rng.integers(1, 40))), replace=False)
+            vals[idx] = rng.choice(np.array([np.nan, 0.5, -0.0, 1e30, -2.5e-7], np.float32), idx.size)
+        col[o:o + VEC] = vals
+    return col
