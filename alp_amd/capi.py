@@ -122,6 +122,11 @@ for _t, _ft in (("f64", C.c_double), ("f32", C.c_float)):
     _sig("alpgpu_zone_map_of_values_" + _t, _int, _vp, _vp, _u64, _vp)
     _sig("alpgpu_zones_minmax_" + _t, _int, _vp, _vp, _u64, _vp)
     _sig("alpgpu_select_range_zoned_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _u64, _u64, _ft, _ft, _vp, _vp, _u64, _vp, _vp)
+MASK_SET, MASK_AND, MASK_OR = 0, 1, 2  # ALPGPU_MASK_*
+for _t, _ft in (("f64", C.c_double), ("f32", C.c_float)):
+    _sig("alpgpu_select_mask_" + _t, _int, _vp, C.POINTER(CColumn), _u64, _u64, _ft, _ft, _int, _vp)
+    _sig("alpgpu_decode_sum_masked_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp)
+_sig("alpgpu_mask_to_indices", _int, _vp, _vp, _u64, _vp, _u64, _vp, _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -625,6 +630,94 @@ class Context:
         self.select_range_into(col, lo, hi, idx, count, vals, first=first, n=n, scratch=scratch, zones=zones)
         k = min(int(count.item()), int(capacity))
         return (idx[:k], vals[:k]) if values else idx[:k]
+
+    # ---- selection bitmaps (include/alpgpu.h: alpgpu_select_mask_*, alpgpu_mask_to_indices, alpgpu_decode_sum_masked_*) ---
+    _MASK_OPS = {"set": MASK_SET, "and": MASK_AND, "or": MASK_OR}
+
+    def _check_mask(self, mask, n_vectors=None):
+        import torch
+        self._check_tensor(mask, torch.int64, "mask")
+        if mask.dim() != 1 or mask.numel() % 16 or (n_vectors is not None and mask.numel() != 16 * n_vectors):
+            raise ValueError("mask must be a one-dimensional int64 tensor of 16 words per vector" + ("" if n_vectors is None else " (%d)" % (16 * n_vectors)))
+
+    def select_mask(self, col: "DeviceColumn", lo: float, hi: float, first: int = 0, n: int = None, op: str = "set", mask=None):
+        """the qualify mask of lo <= x <= hi over the value indices [first, first + n) (n None: to the column's end) as a selection bitmap: an int64
+        tensor of 16 words per vector, bit r & 63 of word r >> 6 = value index r.  op "set" writes it (mask None: a new tensor), "and" / "or"
+        combine it into the mask given: "and" clears the bits outside the range, "or" leaves them.  Returns the mask.  Nothing is
+        synchronised; with a mask given nothing is allocated either (alpgpu_select_mask_f64 / _f32)."""
+        import torch
+        if op not in self._MASK_OPS:
+            raise ValueError('op must be "set", "and" or "or"')
+        if mask is None:
+            if op != "set":
+                raise ValueError('op "%s" combines into a mask: pass one' % op)
+            mask = torch.empty(16 * col.n_vectors, dtype=torch.int64, device=f"cuda:{self.device}")
+        else:
+            self._check_mask(mask, col.n_vectors)
+        first = int(first)
+        n = col.n_vectors * VECTOR_SIZE - first if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        self._call("select_mask", col.dtype, C.byref(col.c), first, n, lo, hi, self._MASK_OPS[op], _vp(mask.data_ptr()))
+        return mask
+
+    def mask_to_indices_into(self, mask, idx_out, count_out, scratch=None):
+        """the raw form of alpgpu_mask_to_indices: the set bits of the mask as ascending value indices into idx_out (int64; its numel() is the
+        capacity, None or empty: a count), their number into count_out (one int64, the full count also beyond the capacity).  Nothing is
+        synchronised; with a scratch given (alpgpu_select_scratch_bytes(mask.numel() // 16) bytes of uint8) nothing is allocated."""
+        import torch
+        self._check_mask(mask)
+        n_vectors = mask.numel() // 16
+        self._check_tensor(count_out, torch.int64, "count_out")
+        if count_out.numel() < 1:
+            raise ValueError("count_out must hold one int64")
+        capacity = 0
+        if idx_out is not None:
+            self._check_tensor(idx_out, torch.int64, "idx_out")
+            capacity = idx_out.numel()
+        need = lib.alpgpu_select_scratch_bytes(n_vectors)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
+        else:
+            self._check_tensor(scratch, torch.uint8, "scratch")
+            if scratch.numel() < need or scratch.data_ptr() % 16:
+                raise ValueError("scratch must hold alpgpu_select_scratch_bytes(n_vectors) bytes, 16-byte aligned")
+        _check(lib.alpgpu_mask_to_indices(self.h, _vp(mask.data_ptr()), n_vectors, _vp(idx_out.data_ptr()) if capacity else None, capacity,
+                                          _vp(count_out.data_ptr()), _vp(scratch.data_ptr())), "alpgpu_mask_to_indices")
+
+    def mask_to_indices(self, mask, capacity: int = None):
+        """the set bits of a selection bitmap as an ascending int64 tensor of value indices.  capacity None: the call counts first (one read of
+        the count, which synchronises the stream) and allocates exactly; with a capacity the result is trimmed to min(count, capacity)."""
+        import torch
+        dev = f"cuda:{self.device}"
+        self._check_mask(mask)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(lib.alpgpu_select_scratch_bytes(mask.numel() // 16), dtype=torch.uint8, device=dev)
+        if capacity is None:
+            self.mask_to_indices_into(mask, None, count, scratch)
+            capacity = int(count.item())
+        idx = torch.empty(int(capacity), dtype=torch.int64, device=dev)
+        self.mask_to_indices_into(mask, idx, count, scratch)
+        return idx[:min(int(count.item()), int(capacity))]
+
+    def decode_sum_masked(self, col: "DeviceColumn", mask, out=None, counts=None):
+        """per-vector sums (float64) of the decoded values whose bit is set in the mask, in the order include/alpgpu.h documents for
+        alpgpu_decode_sum_masked_f64 / _f32; counts (optional, int32, one per vector) receives each vector's number of set bits.  The column's
+        total is tree_sum(out)."""
+        import torch
+        self._check_mask(mask, col.n_vectors)
+        if out is None:
+            out = torch.empty(col.n_vectors, dtype=torch.float64, device=f"cuda:{self.device}")
+        else:
+            self._check_tensor(out, torch.float64, "out")
+            if out.numel() < col.n_vectors:
+                raise ValueError("out must hold one float64 per vector")
+        if counts is not None:
+            self._check_tensor(counts, torch.int32, "counts")
+            if counts.numel() < col.n_vectors:
+                raise ValueError("counts must hold one int32 per vector")
+        self._call("decode_sum_masked", col.dtype, C.byref(col.c), _vp(mask.data_ptr()), _vp(out.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None)
+        return out
 
     # ---- zone maps (include/alpgpu.h: alpgpu_zone_map_*, alpgpu_zones_minmax_*) ---------------------------------------
     def _check_zones(self, zones, dtype, n_vectors):

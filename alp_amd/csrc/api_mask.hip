@@ -1,0 +1,77 @@
+// api_mask.hip — selection bitmaps of include/alpgpu.h: alpgpu_select_mask_* (a range predicate's qualify mask, set into or combined with a caller's
+// bitmap), alpgpu_mask_to_indices (its set bits as ascending value indices) and alpgpu_decode_sum_masked_* (per-vector sums of the values whose bit is
+// set).  A call is a handful of launches of mask_kernels.hip on the context's stream and nothing else: no host synchronisation, no second stream, no
+// allocation, and none of what the context remembers about columns is read or written.
+#include "host_ctx.hpp"
+
+extern "C++" {
+static int select_mask(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int op, uint64_t* d_mask, int value_bytes) {
+	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }
+	if (op != ALPGPU_MASK_SET && op != ALPGPU_MASK_AND && op != ALPGPU_MASK_OR) { return fail(ALPGPU_ERR_INVALID, "op is none of ALPGPU_MASK_SET / _AND / _OR"); }
+	if (col->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
+	const uint64_t n_values = col->n_vectors << 10;
+	if (first > n_values || n > n_values - first) { return fail(ALPGPU_ERR_INVALID, "range reaches past the column's last value"); } // (first + n without the overflow)
+	if (reinterpret_cast<uintptr_t>(d_mask) & 7u) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	if (col->n_vectors == 0) { return ALPGPU_OK; }
+	if (!d_mask) { return fail(ALPGPU_ERR_INVALID, "null bitmap"); }
+	if (n == 0) { // nothing qualifies: SET and AND clear every bit, OR changes none
+		if (op != ALPGPU_MASK_OR) { ALPGPU_HIP(hipMemsetAsync(d_mask, 0, 128ull * col->n_vectors, ctx->stream)); }
+		return ALPGPU_OK;
+	}
+	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	const int rc = alpgpu::launch_select_mask(ctx->stream, col, first, n, lo, hi, op, d_mask, value_bytes);
+	if (rc != ALPGPU_OK) { return fail(rc, "select_mask launch failed"); } // (the launcher has read the HIP error)
+	return ALPGPU_OK;
+}
+
+static int sum_masked(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts, int value_bytes) {
+	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }
+	if (reinterpret_cast<uintptr_t>(d_mask) & 7u) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	if (col->n_vectors == 0) { return ALPGPU_OK; }
+	if (!d_mask || !d_sums) { return fail(ALPGPU_ERR_INVALID, "null bitmap or sums"); }
+	if (col->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
+	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	const int rc = alpgpu::launch_sum_masked(ctx->stream, col, d_mask, d_sums, d_counts, value_bytes);
+	if (rc != ALPGPU_OK) { return fail(rc, "decode_sum_masked launch failed"); }
+	return ALPGPU_OK;
+}
+} // extern "C++"
+
+extern "C" {
+
+int alpgpu_select_mask_f64(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int op, uint64_t* d_mask) {
+	ALPGPU_CHECK_CTX(ctx);
+	return select_mask(ctx, col, first, n, lo, hi, op, d_mask, 8);
+}
+int alpgpu_select_mask_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, float lo, float hi, int op, uint64_t* d_mask) {
+	ALPGPU_CHECK_CTX(ctx);
+	return select_mask(ctx, col, first, n, lo, hi, op, d_mask, 4);
+}
+
+int alpgpu_mask_to_indices(alpgpu_ctx* ctx, const uint64_t* d_mask, uint64_t n_vectors, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch) {
+	ALPGPU_CHECK_CTX(ctx);
+	if (!d_count) { return fail(ALPGPU_ERR_INVALID, "null count"); }
+	if (n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "n_vectors is implausible"); }
+	if (reinterpret_cast<uintptr_t>(d_mask) & 7u) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	if (capacity > 0 && !d_idx) { return fail(ALPGPU_ERR_INVALID, "null index output with a capacity"); }
+	if (n_vectors == 0) { // no bit at all: the count alone is written
+		ALPGPU_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
+		return ALPGPU_OK;
+	}
+	if (!d_mask) { return fail(ALPGPU_ERR_INVALID, "null bitmap"); }
+	if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15u)) { return fail(ALPGPU_ERR_INVALID, "scratch is null or not 16-byte aligned"); }
+	const int rc = alpgpu::launch_mask_to_indices(ctx->stream, d_mask, n_vectors, d_idx, capacity, d_count, d_scratch);
+	if (rc != ALPGPU_OK) { return fail(rc, "mask_to_indices launch failed"); }
+	return ALPGPU_OK;
+}
+
+int alpgpu_decode_sum_masked_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts) {
+	ALPGPU_CHECK_CTX(ctx);
+	return sum_masked(ctx, col, d_mask, d_sums, d_counts, 8);
+}
+int alpgpu_decode_sum_masked_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts) {
+	ALPGPU_CHECK_CTX(ctx);
+	return sum_masked(ctx, col, d_mask, d_sums, d_counts, 4);
+}
+
+} // extern "C"

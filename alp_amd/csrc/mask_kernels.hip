@@ -1,0 +1,105 @@
+// mask_kernels.hip — selection bitmaps (include/alpgpu.h): a predicate's qualify mask kept as 16 words per vector instead of being counted away,
+// so that a second column's predicate combines with it where the ballot is made, and what is left is listed or summed at the very end.
+//
+//   alpgpu_select_mask_*         k_select<VB, false, SelMaskArgs> (select_device.hpp): one wavefront per vector, the decode of the selection with its 16
+//                                ballots stored, SET / AND / OR with what the bitmap held.  A vector outside the range, an all-zero vector under AND
+//                                and an all-ones vector under OR cost their 128 bytes of bitmap and nothing of the column.
+//   alpgpu_mask_to_indices       k_mask_count (per-vector popcount) -> launch_select_scan (select_kernels.hip) -> k_mask_emit: three launches
+//                                ordered by kernel boundaries.  A set bit's position = its vector's offset from the prefix sum + the set bits of
+//                                the words before + v_mbcnt of its own word: ascending, and no atomic anywhere.
+//   alpgpu_decode_sum_masked_*   k_select<VB, false, SelSumArgs>: the same decode, each lane adding the values whose bit is set; the order is in
+//                                include/alpgpu.h and belongs to this entry point (the persistent consumer of consume_kernels.hip has its own).
+//
+// HBM traffic per vector: select_mask SET writes 128 bytes beside the selection's count pass; AND / OR read 128 first and read the column only
+// for vectors the bitmap leaves open; mask_to_indices reads 128 + 128 (the second only where a bit is set) and the scan's 12; the masked SUM
+// reads 128 and, where a bit is set, the vector, and writes 8 (+ 4).
+#include "select_device.hpp"
+
+namespace alpgpu {
+
+// counts[v] = set bits of words 16 v .. 16 v + 15: 16 lanes per vector, one word each (a wavefront reads 512 consecutive bytes)
+__global__ __launch_bounds__(256) void k_mask_count(const uint64_t* __restrict__ mask, uint64_t n_vectors, uint64_t wg_off, uint32_t* __restrict__ counts) {
+	const uint64_t t = (wg_off + blockIdx.x) * 256ull + threadIdx.x; // the word
+	const uint64_t v = t >> 4;
+	uint32_t       c = v < n_vectors ? static_cast<uint32_t>(__builtin_popcountll(mask[t])) : 0u;
+	for (int s = 8; s > 0; s >>= 1) { c += __shfl_xor(c, s, 16); }
+	if ((threadIdx.x & 15u) == 0u && v < n_vectors) { counts[v] = c; }
+}
+
+// one wavefront per vector: the indices of its set bits at offsets[v] + rank, below the capacity
+__global__ __launch_bounds__(kSelThreads) void k_mask_emit(const uint64_t* __restrict__ mask, uint64_t n_vectors, uint64_t wg_off, const uint32_t* __restrict__ counts,
+                                                           const uint64_t* __restrict__ offsets, int64_t* __restrict__ d_idx, uint64_t capacity) {
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint64_t v    = (wg_off + blockIdx.x) * kSelWaves + wave;
+	if (v >= n_vectors) { return; }
+	const uint32_t total = counts[v];
+	if (total == 0u) { return; } // a vector without a set bit costs these four bytes
+	const uint64_t out0 = offsets[v];
+	if (out0 >= capacity) { return; }
+	const uint64_t mine   = lane < 16u ? mask[16ull * v + lane] : 0ull;
+	uint32_t       before = 0; // set bits of the words done (wave-uniform)
+	for (uint32_t m = 0; m < 16u; ++m) {
+		const uint64_t w = readlane64(mine, m);
+		const uint64_t j = out0 + before + mbcnt64(w, 0u);
+		if (((w >> lane) & 1ull) && j < capacity) { d_idx[j] = static_cast<int64_t>((v << 10) + 64u * m + lane); }
+		before += static_cast<uint32_t>(__builtin_popcountll(w));
+		if (before >= total || out0 + before >= capacity) { return; }
+	}
+}
+
+// one launch of k_select's mask / sum arm over vectors [v0, v0 + n_range), split only at the grid limit
+template <int VB, class ARGS>
+static int launch_arm(hipStream_t stream, const alpgpu_column* col, uint64_t v0, uint64_t n_range, uint64_t first, uint64_t end, double lo, double hi, const ARGS& args) {
+	const uint64_t n_wg = (n_range + kSelWaves - 1) / kSelWaves;
+	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
+		const uint64_t g = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;
+		hipLaunchKernelGGL((k_select<VB, false, ARGS>), dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc,
+		                   v0, n_range, off, first, end, lo, hi, static_cast<uint32_t*>(nullptr), static_cast<const uint64_t*>(nullptr), static_cast<int64_t*>(nullptr),
+		                   static_cast<void*>(nullptr), 0ull, args);
+		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
+	}
+	return ALPGPU_OK;
+}
+
+// n > 0, first + n <= n_vectors * 1024 and op one of the three (the caller checked).  SET and AND touch every vector of the column (bits outside
+// the range clear), OR only those of the range (bits outside it stay).
+int launch_select_mask(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int op, uint64_t* d_mask, int value_bytes) {
+	const uint64_t    end     = first + n;
+	const uint64_t    v0      = op == kMaskOr ? first >> 10 : 0ull;
+	const uint64_t    n_range = op == kMaskOr ? ((end - 1) >> 10) - v0 + 1 : col->n_vectors;
+	const SelMaskArgs args {d_mask, op};
+	return value_bytes == 8 ? launch_arm<8>(stream, col, v0, n_range, first, end, lo, hi, args) : launch_arm<4>(stream, col, v0, n_range, first, end, lo, hi, args);
+}
+
+// col->n_vectors > 0
+int launch_sum_masked(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts, int value_bytes) {
+	const SelSumArgs args {d_mask, d_sums, d_counts};
+	const uint64_t   end = col->n_vectors << 10;
+	return value_bytes == 8 ? launch_arm<8>(stream, col, 0, col->n_vectors, 0, end, 0.0, 0.0, args) : launch_arm<4>(stream, col, 0, col->n_vectors, 0, end, 0.0, 0.0, args);
+}
+
+// n_vectors > 0; d_scratch: select_scratch_bytes(n_vectors) bytes, 16-byte aligned, laid out as the selection's
+int launch_mask_to_indices(hipStream_t stream, const uint64_t* d_mask, uint64_t n_vectors, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch) {
+	uint64_t* offsets = static_cast<uint64_t*>(d_scratch);
+	uint32_t* counts  = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_scratch) + align16(8ull * n_vectors));
+	uint64_t* levels  = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(counts) + align16(4ull * n_vectors));
+	const uint64_t n_count_wg = (n_vectors + 15) / 16; // 256 words = 16 vectors per workgroup
+	for (uint64_t off = 0; off < n_count_wg; off += kSelMaxGrid) {
+		const uint64_t g = n_count_wg - off < kSelMaxGrid ? n_count_wg - off : kSelMaxGrid;
+		hipLaunchKernelGGL(k_mask_count, dim3(static_cast<unsigned>(g)), dim3(256), 0, stream, d_mask, n_vectors, off, counts);
+		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
+	}
+	const int rc = launch_select_scan(stream, counts, n_vectors, offsets, d_count, levels);
+	if (rc != ALPGPU_OK || capacity == 0) { return rc; }
+	const uint64_t n_wg = (n_vectors + kSelWaves - 1) / kSelWaves;
+	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
+		const uint64_t g = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;
+		hipLaunchKernelGGL(k_mask_emit, dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, d_mask, n_vectors, off, static_cast<const uint32_t*>(counts),
+		                   static_cast<const uint64_t*>(offsets), d_idx, capacity);
+		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
+	}
+	return ALPGPU_OK;
+}
+
+} // namespace alpgpu

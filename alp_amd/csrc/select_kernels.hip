@@ -29,206 +29,12 @@
 // HBM traffic: count reads every vector of the range once (descriptor, packed words, exception record, for ALP_RD the dictionary) and writes
 // 4 bytes; the scan reads them and writes 8; emit reads 4 + 8 bytes per vector and, for vectors with a non-zero count only, the vector again,
 // and writes 8 (+ 8 or 4) bytes per selected value.
-#include <type_traits>
-
-#include "alp_device_f32.hpp"
-#include "lane_field.hpp"
-#include "launch.hpp"
+//
+// k_select itself is in select_device.hpp, which mask_kernels.hip includes too (it instantiates two more arms of the kernel: the ballots kept as
+// a bitmap, and a masked SUM); this file holds the scan, the launches and the scratch layout.
+#include "select_device.hpp"
 
 namespace alpgpu {
-
-constexpr int      kSelWaves   = 4; // wavefronts per workgroup, one vector each (they share nothing)
-constexpr int      kSelThreads = 64 * kSelWaves;
-constexpr uint64_t kSelMaxGrid = 1ull << 30; // workgroups per launch
-constexpr int      kScanBlock  = 1024;       // counts per scan block = threads per scan workgroup
-constexpr uint32_t kSelBatch   = 8;          // steps of a vector whose words are requested together
-
-// EMIT = false: counts[k] = qualifying values of vector v0 + k.  EMIT = true: their indices (and values) at offsets[k] + rank.
-// [first, end) is the selected index range; the launch covers exactly the vectors it touches (v0 = first >> 10, n_range of them).
-// ZONES: empty, or one `const void*` behind the other arguments = the zoned count pass of alpgpu_select_range_zoned_*: zones[v] = {min, max} (one
-// record per vector of the COLUMN, indexed by v, not by v - v0) is read first.  A vector whose zone misses [lo, hi] is counted 0 and one whose
-// zone lies inside it, and which cannot hold a NaN, is counted whole; neither has its packed words or exception record read.  (A trailing
-// parameter pack and not a plain parameter: the unzoned instantiations keep their argument list and with it their instructions.)
-__device__ __forceinline__ const void* zone_records(const void* zones) { return zones; }
-template <int VB, bool EMIT, class... ZONES>
-__global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc* __restrict__ descs, const alpgpu_rowgroup_state* __restrict__ rgs,
-                                                        const uint8_t* __restrict__ packed, const uint8_t* __restrict__ excs, uint64_t v0, uint64_t n_range,
-                                                        uint64_t wg_off, uint64_t first, uint64_t end, double range_lo, double range_hi,
-                                                        uint32_t* __restrict__ counts, const uint64_t* __restrict__ offsets, int64_t* __restrict__ d_idx,
-                                                        void* __restrict__ d_vals, uint64_t capacity, ZONES... zones) {
-	constexpr bool ZONED = sizeof...(ZONES) == 1;
-	static_assert(sizeof...(ZONES) <= 1 && !(ZONED && EMIT), "at most the zone map, and the emit pass reads the counts, not the zones");
-	typedef typename std::conditional<VB == 8, uint64_t, uint32_t>::type U;
-	typedef typename std::conditional<VB == 8, double, float>::type      T;
-	constexpr uint32_t kLanes = VB == 8 ? 16u : 32u; // FastLanes lanes of the value streams
-	constexpr uint32_t kLog   = VB == 8 ? 4u : 5u;
-	__shared__ uint64_t s_exc[kSelWaves][16]; // per wavefront: bit p = value p is an exception
-
-	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-	const uint32_t lane = threadIdx.x & 63u;
-	const uint64_t k    = (wg_off + blockIdx.x) * kSelWaves + wave;
-	if (k >= n_range) { return; }
-	const uint64_t v       = v0 + k;
-	const uint64_t r0      = v << 10;
-	const uint32_t p_begin = first > r0 ? static_cast<uint32_t>(first - r0) : 0u; // the vector's share of [first, end): wave-uniform
-	const uint32_t p_end   = end - r0 < 1024u ? static_cast<uint32_t>(end - r0) : 1024u;
-
-	uint32_t total = 0;
-	uint64_t out0  = 0;
-	if constexpr (EMIT) {
-		total = counts[k];
-		if (total == 0) { return; } // a vector without a qualifying value costs these four bytes
-		out0 = offsets[k];
-		if (out0 >= capacity) { return; }
-		if (d_vals == nullptr && total == p_end - p_begin) { // all of it qualifies and only indices are wanted: nothing to decode
-			for (uint32_t p = p_begin + lane; p < p_end; p += 64u) {
-				const uint64_t j = out0 + (p - p_begin);
-				if (j < capacity) { d_idx[j] = static_cast<int64_t>(r0 + p); }
-			}
-			return;
-		}
-	}
-
-	bool inside = false; // ZONED: every value the zone admits qualifies
-	if constexpr (ZONED) {
-		const T* zone = reinterpret_cast<const T*>(zone_records(zones...)) + 2 * v; // (wave-uniform)
-		const T  z_min = zone[0], z_max = zone[1];
-		const T z_lo = static_cast<T>(range_lo), z_hi = static_cast<T>(range_hi);
-		if (!(z_max >= z_lo && z_min <= z_hi)) { // excluded (a NaN bound excludes every vector): the record is all that was read
-			if (lane == 0u) { counts[k] = 0u; }
-			return;
-		}
-		inside = z_min >= z_lo && z_max <= z_hi;
-	}
-	const alpgpu_vector_desc d     = descs[v];
-	const bool               alp   = d.scheme == ALPGPU_SCHEME_ALP;
-	if constexpr (ZONED) {
-		// contained: only a vector that cannot hold a NaN — ALP without exceptions (a NaN never round-trips through ALP, so it is always an exception)
-		if (inside && alp && d.exc_cnt == 0u) {
-			if (lane == 0u) { counts[k] = p_end - p_begin; }
-			return;
-		}
-	}
-	const uint32_t           bw    = d.bw < 8u * VB ? d.bw : 8u * VB;
-	const uint32_t           cnt   = d.exc_cnt < 1024u ? d.exc_cnt : 1024u;
-	const uint8_t*           rec   = excs + d.exc_off;
-	const U*                 words = reinterpret_cast<const U*>(packed + d.packed_off);
-	const uint16_t*          lefts = reinterpret_cast<const uint16_t*>(packed + d.packed_off + 128ull * d.bw);
-	const U                  base  = static_cast<U>(d.base);
-	// per-vector constants of the two schemes (gather_kernels.hip: value_bits reads the same tables with the same clamps)
-	const uint32_t lbw  = d.lbw < 16u ? d.lbw : 16u;
-	const uint32_t fi   = VB == 8 ? (d.f < 18 ? d.f : 18) : (d.f < 10 ? d.f : 10);
-	const uint32_t ei   = VB == 8 ? (d.e < 20 ? d.e : 20) : (d.e < 10 ? d.e : 10);
-	const RdDict   dict = load_rd_dict(rgs, v, !alp);
-	const T        lo = static_cast<T>(range_lo), hi = static_cast<T>(range_hi);
-	typename std::conditional<VB == 8, int64_t, uint32_t>::type fact;
-	T                                                          frac;
-	if constexpr (VB == 8) {
-		fact = kFactArr[fi];
-		frac = kFracArr[ei];
-	} else {
-		fact = kFactArrF[fi];
-		frac = kFracArrF[ei];
-	}
-
-	if (cnt > 0) { // the exception positions as a mask in index order
-		const uint16_t* pos = reinterpret_cast<const uint16_t*>(rec + (alp ? static_cast<uint64_t>(VB) : 2ull) * d.exc_cnt);
-		if (lane < 16u) { s_exc[wave][lane] = 0ull; }
-		wave_lds_sync();
-		for (uint32_t j = lane; j < cnt; j += 64u) {
-			const uint32_t q = pos[j];
-			if (q < 1024u) { atomicOr(reinterpret_cast<uint32_t*>(&s_exc[wave][0]) + (q >> 5), 1u << (q & 31u)); }
-		}
-		wave_lds_sync();
-	}
-
-	uint32_t before_exc = 0; // exceptions of the steps done
-	uint32_t before_sel = 0; // qualifying values of the steps done (wave-uniform: it comes from ballots)
-	for (uint32_t b = 0; b < 16u; b += kSelBatch) {
-		// every load of kSelBatch steps is requested before the first is used: a step is otherwise its own round trip to memory
-		FieldWords<U>        rw[kSelBatch];
-		FieldWords<uint16_t> lw[kSelBatch];
-#pragma unroll
-		for (uint32_t i = 0; i < kSelBatch; ++i) {
-			rw[i] = FieldWords<U> {0, 0};
-			lw[i] = FieldWords<uint16_t> {0, 0};
-		}
-		if (bw > 0) {
-#pragma unroll
-			for (uint32_t i = 0; i < kSelBatch; ++i) {
-				const uint32_t p = 64u * (b + i) + lane;
-				rw[i]            = load_field_words<U, kLanes>(words + (p & (kLanes - 1u)), p >> kLog, bw);
-			}
-		}
-		if (!alp && lbw > 0) {
-#pragma unroll
-			for (uint32_t i = 0; i < kSelBatch; ++i) { lw[i] = load_field_words<uint16_t, 64>(lefts + lane, b + i, lbw); }
-		}
-		// ... the exceptions' values too (ALP: the value's bits; ALP_RD: its left part): loaded where they are used, each step with an exception in
-		// it would wait for memory once more.  (The ALP_RD loads are still waited for one by one in the generated code, see the head of this file.
-		// A form that avoids it was measured: every lane loads, without the per-lane branch, one loop per scheme.  It takes 98 registers
-		// instead of 81 and cost the mixed and float columns more, +4 % and +8 %, than the ALP_RD column gained, -3 %.)
-		uint64_t em[kSelBatch]; // wave-uniform: bit l = value 64 m + l is an exception
-		U        ev[kSelBatch];
-#pragma unroll
-		for (uint32_t i = 0; i < kSelBatch; ++i) {
-			em[i] = 0ull;
-			ev[i] = 0;
-		}
-		if (cnt > 0) {
-			uint32_t rank0 = before_exc;
-#pragma unroll
-			for (uint32_t i = 0; i < kSelBatch; ++i) {
-				const uint64_t w = s_exc[wave][b + i];
-				const uint32_t w_lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(w))); // (the builtin returns int: no sign extension into the high word)
-				const uint32_t w_hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(w >> 32)));
-				em[i]               = (static_cast<uint64_t>(w_hi) << 32) | w_lo;
-				const uint32_t rank = rank0 + mbcnt64(em[i], 0u);
-				if ((em[i] >> lane) & 1ull) { ev[i] = alp ? reinterpret_cast<const U*>(rec)[rank] : static_cast<U>(reinterpret_cast<const uint16_t*>(rec)[rank]); }
-				rank0 += static_cast<uint32_t>(__builtin_popcountll(em[i]));
-			}
-			before_exc = rank0;
-		}
-#pragma unroll
-		for (uint32_t i = 0; i < kSelBatch; ++i) {
-			const uint32_t m     = b + i;
-			const uint32_t p     = 64u * m + lane;
-			const U        right = extract_field<U>(rw[i], p >> kLog, bw); // ALP: the digit; ALP_RD: the right part
-			const bool     hit   = (em[i] >> lane) & 1ull;
-			U              bits;
-			if (alp) {
-				if constexpr (VB == 8) {
-					bits = static_cast<U>(__double_as_longlong(decode_value(static_cast<int64_t>(right + base), fact, frac)));
-				} else {
-					bits = __float_as_uint(decode_value_f32(static_cast<int32_t>(right + base), fact, frac));
-				}
-				bits = hit ? ev[i] : bits;
-			} else {
-				const uint32_t idx  = extract_field<uint16_t>(lw[i], m, lbw) & 7u;
-				const U        left = hit ? ev[i] : static_cast<U>(((idx < 4u ? dict.lo : dict.hi) >> (16u * (idx & 3u))) & 0xFFFFull);
-				bits                = static_cast<U>((left << bw) | right);
-			}
-			T x;
-			if constexpr (VB == 8) { x = __longlong_as_double(static_cast<long long>(bits)); } else { x = __uint_as_float(bits); }
-			const bool     q   = p >= p_begin && p < p_end && x >= lo && x <= hi; // NaN (value or bound) never qualifies; -0.0 == 0.0
-			const uint64_t sel = ballot64(q);
-			if constexpr (EMIT) {
-				const uint64_t j = out0 + before_sel + mbcnt64(sel, 0u);
-				if (q && j < capacity) {
-					d_idx[j] = static_cast<int64_t>(r0 + p);
-					if (d_vals != nullptr) { reinterpret_cast<U*>(d_vals)[j] = bits; }
-				}
-			}
-			before_sel += static_cast<uint32_t>(__builtin_popcountll(sel));
-		}
-		if constexpr (EMIT) {
-			if (before_sel >= total || out0 + before_sel >= capacity) { return; } // the vector's last qualifying value, or the capacity, is behind us
-		}
-	}
-	if constexpr (!EMIT) {
-		if (lane == 0u) { counts[k] = before_sel; }
-	}
-}
 
 // ---- the scan: out[i] = in[0] + ... + in[i - 1] --------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t wave_sum(uint64_t x) {
@@ -272,7 +78,6 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_apply(const T* in, uint64_t
 	if (total != nullptr && blockIdx.x == gridDim.x - 1 && threadIdx.x == kScanBlock - 1) { *total = before + incl; }
 }
 
-static uint64_t align16(uint64_t x) { return (x + 15ull) & ~15ull; }
 static uint64_t scan_blocks(uint64_t n) { return (n + kScanBlock - 1) / kScanBlock; }
 
 // Scratch of a select over a column of n_vectors: [offsets: u64 per vector][counts: u32 per vector][block sums of every scan level], each

@@ -498,8 +498,86 @@ struct column {
 		}
 		return select_range_with(blob, size, lo, hi, &zones);
 	}
+	// Selection bitmaps (include/alpgpu.h, "selection bitmaps"): the qualify mask of lo <= x <= hi over [0, n_values) as 16 words per vector, bit
+	// r & 63 of word r >> 6 = value index r.  Predicates on columns of equal length combine in one mask (mask_and: the bits of tail padding
+	// clear; mask_or), mask_indices lists what is left and sum_masked sums another column under it.
+	enum mask_op { mask_set = ALPGPU_MASK_SET, mask_and = ALPGPU_MASK_AND, mask_or = ALPGPU_MASK_OR };
+	static std::vector<uint64_t> select_mask(const uint8_t* blob, size_t size, PT lo, PT hi) {
+		std::vector<uint64_t> mask;
+		select_mask_with(blob, size, lo, hi, mask_set, mask, true);
+		return mask;
+	}
+	static void select_mask(const uint8_t* blob, size_t size, PT lo, PT hi, mask_op op, std::vector<uint64_t>& mask) { select_mask_with(blob, size, lo, hi, op, mask, false); }
+	// the set bits as ascending value indices (alpgpu_mask_to_indices)
+	static std::vector<int64_t> mask_indices(const std::vector<uint64_t>& mask) {
+		if (mask.size() % 16 != 0) { throw std::runtime_error("alp::gpu::column::mask_indices: a mask holds 16 words per vector"); }
+		std::vector<int64_t> out;
+		const uint64_t       n_vectors = mask.size() / 16;
+		if (n_vectors == 0) { return out; }
+		device_buffers buf;
+		uint64_t*      d_mask    = static_cast<uint64_t*>(buf.get(mask.size() * sizeof(uint64_t)));
+		uint64_t*      d_count   = static_cast<uint64_t*>(buf.get(sizeof(uint64_t)));
+		void*          d_scratch = buf.get(alpgpu_select_scratch_bytes(n_vectors));
+		check(alpgpu_memcpy_h2d(context(), d_mask, mask.data(), mask.size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d");
+		uint64_t count = 0;
+		check(alpgpu_mask_to_indices(context(), d_mask, n_vectors, nullptr, 0, d_count, d_scratch), "alpgpu_mask_to_indices"); // count first, then allocate exactly
+		check(alpgpu_memcpy_d2h(context(), &count, d_count, sizeof(count)), "alpgpu_memcpy_d2h");
+		if (count == 0) { return out; }
+		int64_t* d_idx = static_cast<int64_t*>(buf.get(count * sizeof(int64_t)));
+		check(alpgpu_mask_to_indices(context(), d_mask, n_vectors, d_idx, count, d_count, d_scratch), "alpgpu_mask_to_indices");
+		out.resize(count);
+		check(alpgpu_memcpy_d2h(context(), out.data(), d_idx, count * sizeof(int64_t)), "alpgpu_memcpy_d2h");
+		return out;
+	}
+	// SUM and COUNT of the column's values whose bit is set (alpgpu_decode_sum_masked_* and alpgpu_tree_sum_f64 over its per-vector sums: the
+	// order include/alpgpu.h documents, so the same blob and mask give the same bits every time)
+	struct masked_sum {
+		double   sum;
+		uint64_t count;
+	};
+	static masked_sum sum_masked(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask) {
+		uploaded_column up(blob, size, "alp::gpu::column::sum_masked");
+		const uint64_t  nv = up.col.n_vectors;
+		if (mask.size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::sum_masked: the mask must hold 16 words per vector"); }
+		masked_sum out {0.0, 0};
+		if (nv == 0) { return out; }
+		uint64_t* d_mask   = static_cast<uint64_t*>(up.get(mask.size() * sizeof(uint64_t)));
+		double*   d_sums   = static_cast<double*>(up.get(nv * sizeof(double)));
+		uint32_t* d_counts = static_cast<uint32_t*>(up.get(nv * sizeof(uint32_t)));
+		double*   d_total  = static_cast<double*>(up.get(sizeof(double)));
+		check(alpgpu_memcpy_h2d(context(), d_mask, mask.data(), mask.size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d");
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_decode_sum_masked_f64(context(), &up.col, d_mask, d_sums, d_counts), "alpgpu_decode_sum_masked_f64");
+		} else {
+			check(alpgpu_decode_sum_masked_f32(context(), &up.col, d_mask, d_sums, d_counts), "alpgpu_decode_sum_masked_f32");
+		}
+		check(alpgpu_tree_sum_f64(context(), d_sums, nv, d_total), "alpgpu_tree_sum_f64");
+		std::vector<uint32_t> counts(nv);
+		check(alpgpu_memcpy_d2h(context(), &out.sum, d_total, sizeof(double)), "alpgpu_memcpy_d2h");
+		check(alpgpu_memcpy_d2h(context(), counts.data(), d_counts, nv * sizeof(uint32_t)), "alpgpu_memcpy_d2h");
+		for (uint32_t c : counts) { out.count += c; }
+		return out;
+	}
 
 private:
+	static void select_mask_with(const uint8_t* blob, size_t size, PT lo, PT hi, mask_op op, std::vector<uint64_t>& mask, bool fresh) {
+		uploaded_column up(blob, size, "alp::gpu::column::select_mask");
+		const uint64_t  words = 16 * up.col.n_vectors;
+		if (fresh) {
+			mask.assign(words, 0);
+		} else if (mask.size() != words) {
+			throw std::runtime_error("alp::gpu::column::select_mask: the mask must hold 16 words per vector");
+		}
+		if (words == 0) { return; }
+		uint64_t* d_mask = static_cast<uint64_t*>(up.get(words * sizeof(uint64_t)));
+		if (op != mask_set) { check(alpgpu_memcpy_h2d(context(), d_mask, mask.data(), words * sizeof(uint64_t)), "alpgpu_memcpy_h2d"); }
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_select_mask_f64(context(), &up.col, 0, up.n_values, lo, hi, op, d_mask), "alpgpu_select_mask_f64");
+		} else {
+			check(alpgpu_select_mask_f32(context(), &up.col, 0, up.n_values, lo, hi, op, d_mask), "alpgpu_select_mask_f32");
+		}
+		check(alpgpu_memcpy_d2h(context(), mask.data(), d_mask, words * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
+	}
 	static void make_zone_map(uploaded_column& up, zone* d_zones) {
 		if constexpr (sizeof(PT) == 8) {
 			check(alpgpu_zone_map_f64(context(), &up.col, d_zones), "alpgpu_zone_map_f64");

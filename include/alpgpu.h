@@ -520,6 +520,57 @@ int alpgpu_select_range_zoned_f64(alpgpu_ctx* ctx, const alpgpu_column* col, con
 int alpgpu_select_range_zoned_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const alpgpu_zone_f32* d_zones, uint64_t first, uint64_t n, float lo, float hi,
                                   int64_t* d_idx, float* d_vals, uint64_t capacity, uint64_t* d_count, void* d_scratch);
 
+/* ---- selection bitmaps -------------------------------------------------------------------------------------------------
+ * The qualify mask of a range predicate, kept instead of counted away: predicates on several columns of equal length combine in it (AND, OR), and
+ * only what is left at the end is listed (alpgpu_mask_to_indices -> alpgpu_gather_*) or summed (alpgpu_decode_sum_masked_*):
+ *   WHERE lo1 <= a <= hi1 AND lo2 <= b <= hi2   select_mask(a, SET), select_mask(b, AND);   SUM(c) WHERE ...: decode_sum_masked(c), tree_sum.
+ * The bitmap of a column is n_vectors * 16 uint64_t words in device memory, caller-owned like every buffer of this ABI and 8-byte aligned (a
+ *   misaligned pointer returns ALPGPU_ERR_INVALID): bit r & 63 of word r >> 6 stands for value index r, the numbering of the random-access section,
+ *   so vector v owns words 16 v .. 16 v + 15 (128 bytes).  It is not part of alpgpu_column and not part of the serialized container.
+ *   alpgpu_select_mask_*        Let q(r) = first <= r < first + n and lo <= x_r <= hi: exactly the predicate of alpgpu_select_range_* (NaN never
+ *                               qualifies, as a value or as a bound; -0.0 == 0.0; lo > hi selects nothing; +-inf are ordinary values and bounds;
+ *                               exceptions patched in, the store decode's arithmetic).  For EVERY value index r of the column:
+ *                                 op = ALPGPU_MASK_SET  bit(r) = q(r): every word of the bitmap is written, what it held does not matter;
+ *                                 op = ALPGPU_MASK_AND  bit(r) &= q(r): bits outside [first, first + n) clear;
+ *                                 op = ALPGPU_MASK_OR   bit(r) |= q(r): bits outside the range keep their value;
+ *                               any other op returns ALPGPU_ERR_INVALID and enqueues nothing.  Cost: one launch, one wavefront per vector.  A vector
+ *                               outside the range is settled from its 128 bytes of bitmap; under AND a vector whose 16 words are all zero, and
+ *                               under OR one whose 16 words are all ones, is not decoded — its descriptor, packed words and exception record are
+ *                               not read — so a second predicate costs in proportion to what the first left open.
+ *                               Range: checked on the host as in alpgpu_select_range_* (first + n past n_vectors * 1024, or overflowing:
+ *                               ALPGPU_ERR_INVALID, nothing enqueued).  n == 0 is valid: SET and AND clear the bitmap, OR enqueues nothing.
+ *                               col->n_vectors == 0 is ALPGPU_OK and launches nothing.  A NULL ctx or col, or a NULL d_mask with n_vectors > 0,
+ *                               returns ALPGPU_ERR_INVALID.
+ *   alpgpu_mask_to_indices      the set bits of a bitmap of n_vectors vectors as ASCENDING value indices: *d_count = their number, also when it
+ *                               exceeds capacity; d_idx[j] for j < min(*d_count, capacity) = the j-th; nothing is written at or behind capacity.
+ *                               capacity == 0 makes it a count (d_idx may be NULL).  d_scratch: alpgpu_select_scratch_bytes(n_vectors) bytes,
+ *                               16-byte aligned, as for the selection.  Three launches ordered by kernel boundaries (per-vector popcount, the
+ *                               selection's prefix sum, emit); positions come from the prefix sum and v_mbcnt ranks, never from an atomic.
+ *                               n_vectors == 0 writes *d_count = 0.  For a bitmap made by alpgpu_select_mask_* with op = SET the result is bit
+ *                               for bit that of alpgpu_select_range_* with the same arguments.
+ *   alpgpu_decode_sum_masked_*  d_sums[v] = the sum of the decoded values of vector v whose bit is set, d_counts[v] (may be NULL) = the number of
+ *                               set bits of the vector (AVG needs nothing else); the values never reach HBM.  A vector whose 16 words are zero
+ *                               gets +0.0 and 0 and is not read.  Summation order (so that the result can be reproduced bit for bit): lane L of
+ *                               64 starts from +0.0 and, for m = 0..15 in that order, adds value 64 m + L if its bit is set and does nothing
+ *                               otherwise (float values widen to double first, exactly); the 64 partials combine by the balanced binary tree over
+ *                               adjacent lanes of alpgpu_decode_sum_* — (0,1), (2,3), ...; six levels.  No multiplication is involved, nothing can
+ *                               contract.  This order belongs to THIS entry point; it is not that of alpgpu_decode_sum_*: a full bitmap gives the
+ *                               same mathematical sum, not necessarily the same bits.  The column's total is alpgpu_tree_sum_f64 over d_sums.  A
+ *                               selected NaN makes its vector's sum a NaN of unspecified payload (bitmaps made by alpgpu_select_mask_* never select
+ *                               one; a caller-made bitmap may).  (tests/test_mask_gpu.py holds the host replica.)
+ * All of them: everything is enqueued on the context's stream and on that stream only, asynchronous, no host synchronisation, no allocation, none
+ *   of what the context remembers about columns is read or written; safe inside a stream capture.  The result is a function of the column, the
+ *   bitmap and the arguments alone.
+ * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector). */
+#define ALPGPU_MASK_SET 0
+#define ALPGPU_MASK_AND 1
+#define ALPGPU_MASK_OR 2
+int alpgpu_select_mask_f64(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int op, uint64_t* d_mask);
+int alpgpu_select_mask_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, float lo, float hi, int op, uint64_t* d_mask);
+int alpgpu_mask_to_indices(alpgpu_ctx* ctx, const uint64_t* d_mask, uint64_t n_vectors, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch);
+int alpgpu_decode_sum_masked_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts);
+int alpgpu_decode_sum_masked_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
