@@ -126,6 +126,7 @@ MASK_SET, MASK_AND, MASK_OR = 0, 1, 2  # ALPGPU_MASK_*
 for _t, _ft in (("f64", C.c_double), ("f32", C.c_float)):
     _sig("alpgpu_select_mask_" + _t, _int, _vp, C.POINTER(CColumn), _u64, _u64, _ft, _ft, _int, _vp)
     _sig("alpgpu_decode_sum_masked_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp)
+    _sig("alpgpu_decode_masked_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp, _u64, _vp, _vp)
 _sig("alpgpu_mask_to_indices", _int, _vp, _vp, _u64, _vp, _u64, _vp, _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -631,7 +632,7 @@ class Context:
         k = min(int(count.item()), int(capacity))
         return (idx[:k], vals[:k]) if values else idx[:k]
 
-    # ---- selection bitmaps (include/alpgpu.h: alpgpu_select_mask_*, alpgpu_mask_to_indices, alpgpu_decode_sum_masked_*) ---
+    # ---- selection bitmaps (include/alpgpu.h: alpgpu_select_mask_*, alpgpu_mask_to_indices, alpgpu_decode_sum_masked_*, alpgpu_decode_masked_*) ---
     _MASK_OPS = {"set": MASK_SET, "and": MASK_AND, "or": MASK_OR}
 
     def _check_mask(self, mask, n_vectors=None):
@@ -718,6 +719,55 @@ class Context:
                 raise ValueError("counts must hold one int32 per vector")
         self._call("decode_sum_masked", col.dtype, C.byref(col.c), _vp(mask.data_ptr()), _vp(out.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None)
         return out
+
+    def decode_masked_into(self, col: "DeviceColumn", mask, vals_out, count_out, idx_out=None, scratch=None):
+        """the raw form of alpgpu_decode_masked_f64 / _f32: the column's values at the set bits of the mask, in ascending index order, into
+        vals_out (the column's value type; its numel() is the capacity, None or empty: a count), their value indices into idx_out (optional,
+        int64, at least as long), their number into count_out (one int64, the full count also beyond the capacity).  Nothing is
+        synchronised and nothing read back; with a scratch given (select_scratch) nothing is allocated either, so the call can be captured
+        into a graph.  The mask is only read."""
+        import torch
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        self._check_mask(mask, col.n_vectors)
+        self._check_tensor(count_out, torch.int64, "count_out")
+        if count_out.numel() < 1:
+            raise ValueError("count_out must hold one int64")
+        capacity = 0
+        if vals_out is not None:
+            self._check_tensor(vals_out, tdt, "vals_out")
+            capacity = vals_out.numel()
+        if idx_out is not None:
+            self._check_tensor(idx_out, torch.int64, "idx_out")
+            if idx_out.numel() < capacity:
+                raise ValueError("idx_out is shorter than vals_out")
+        need = lib.alpgpu_select_scratch_bytes(col.n_vectors)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
+        else:
+            self._check_tensor(scratch, torch.uint8, "scratch")
+            if scratch.numel() < need or scratch.data_ptr() % 16:
+                raise ValueError("scratch must hold alpgpu_select_scratch_bytes(n_vectors) bytes, 16-byte aligned")
+        self._call("decode_masked", col.dtype, C.byref(col.c), _vp(mask.data_ptr()), _vp(vals_out.data_ptr()) if capacity else None,
+                   _vp(idx_out.data_ptr()) if idx_out is not None and capacity else None, capacity, _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
+
+    def decode_masked(self, col: "DeviceColumn", mask, indices: bool = False, capacity: int = None):
+        """the column's values at the set bits of a selection bitmap as a tensor of the column's value type, ascending by index, or
+        (indices, values) with indices=True.  capacity None: the call counts first (one read of the count, which synchronises the stream) and
+        allocates exactly; with a capacity there is no read-back before the projection, one after it to trim the result to
+        min(count, capacity)."""
+        import torch
+        dev = f"cuda:{self.device}"
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        scratch = self.select_scratch(col)
+        if capacity is None:
+            self.decode_masked_into(col, mask, None, count, scratch=scratch)
+            capacity = int(count.item())
+        vals = torch.empty(int(capacity), dtype=tdt, device=dev)
+        idx = torch.empty(int(capacity), dtype=torch.int64, device=dev) if indices else None
+        self.decode_masked_into(col, mask, vals, count, idx, scratch=scratch)
+        k = min(int(count.item()), int(capacity))
+        return (idx[:k], vals[:k]) if indices else vals[:k]
 
     # ---- zone maps (include/alpgpu.h: alpgpu_zone_map_*, alpgpu_zones_minmax_*) ---------------------------------------
     def _check_zones(self, zones, dtype, n_vectors):

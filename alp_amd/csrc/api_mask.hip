@@ -1,6 +1,6 @@
 // api_mask.hip — selection bitmaps of include/alpgpu.h: alpgpu_select_mask_* (a range predicate's qualify mask, set into or combined with a caller's
-// bitmap), alpgpu_mask_to_indices (its set bits as ascending value indices) and alpgpu_decode_sum_masked_* (per-vector sums of the values whose bit is
-// set).  A call is a handful of launches of mask_kernels.hip on the context's stream and nothing else: no host synchronisation, no second stream, no
+// bitmap), alpgpu_mask_to_indices (its set bits as ascending value indices), alpgpu_decode_sum_masked_* (per-vector sums of the values whose bit is
+// set) and alpgpu_decode_masked_* (those values themselves, compacted).  A call is a handful of launches of mask_kernels.hip on the context's stream and nothing else: no host synchronisation, no second stream, no
 // allocation, and none of what the context remembers about columns is read or written.
 #include "host_ctx.hpp"
 
@@ -33,6 +33,25 @@ static int sum_masked(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t*
 	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
 	const int rc = alpgpu::launch_sum_masked(ctx->stream, col, d_mask, d_sums, d_counts, value_bytes);
 	if (rc != ALPGPU_OK) { return fail(rc, "decode_sum_masked launch failed"); }
+	return ALPGPU_OK;
+}
+
+static int decode_masked(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, void* d_vals, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch,
+                         int value_bytes) {
+	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }
+	if (!d_count) { return fail(ALPGPU_ERR_INVALID, "null count"); }
+	if (!d_mask) { return fail(ALPGPU_ERR_INVALID, "null bitmap"); }
+	if (reinterpret_cast<uintptr_t>(d_mask) & 7u) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	if (capacity > 0 && !d_vals) { return fail(ALPGPU_ERR_INVALID, "null value output with a capacity"); }
+	if (col->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
+	if (col->n_vectors == 0) { // no bit at all: the count alone is written
+		ALPGPU_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
+		return ALPGPU_OK;
+	}
+	if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15u)) { return fail(ALPGPU_ERR_INVALID, "scratch is null or not 16-byte aligned"); }
+	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	const int rc = alpgpu::launch_decode_masked(ctx->stream, col, d_mask, d_vals, d_idx, capacity, d_count, d_scratch, value_bytes);
+	if (rc != ALPGPU_OK) { return fail(rc, "decode_masked launch failed"); }
 	return ALPGPU_OK;
 }
 } // extern "C++"
@@ -72,6 +91,17 @@ int alpgpu_decode_sum_masked_f64(alpgpu_ctx* ctx, const alpgpu_column* col, cons
 int alpgpu_decode_sum_masked_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts) {
 	ALPGPU_CHECK_CTX(ctx);
 	return sum_masked(ctx, col, d_mask, d_sums, d_counts, 4);
+}
+
+int alpgpu_decode_masked_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, double* d_vals, int64_t* d_idx, uint64_t capacity, uint64_t* d_count,
+                             void* d_scratch) {
+	ALPGPU_CHECK_CTX(ctx);
+	return decode_masked(ctx, col, d_mask, d_vals, d_idx, capacity, d_count, d_scratch, 8);
+}
+int alpgpu_decode_masked_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, float* d_vals, int64_t* d_idx, uint64_t capacity, uint64_t* d_count,
+                             void* d_scratch) {
+	ALPGPU_CHECK_CTX(ctx);
+	return decode_masked(ctx, col, d_mask, d_vals, d_idx, capacity, d_count, d_scratch, 4);
 }
 
 } // extern "C"

@@ -59,10 +59,13 @@ int launch_select_scan(hipStream_t stream, const uint32_t* d_counts, uint64_t n,
 // mask_kernels.hip: selection bitmaps (16 u64 words per vector, bit r & 63 of word r >> 6 = value index r).  launch_select_mask: bit(r) = / &= / |= q(r),
 // q(r) = first <= r < first + n and lo <= x_r <= hi (n > 0, range and op checked by the caller); launch_mask_to_indices: the set bits as ascending
 // indices up to capacity, *d_count = how many (n_vectors > 0; d_scratch: select_scratch_bytes(n_vectors) bytes); launch_sum_masked: d_sums[v] = the sum of
-// the vector's values whose bit is set, d_counts[v] (nullable) = its set bits (col->n_vectors > 0)
+// the vector's values whose bit is set, d_counts[v] (nullable) = its set bits (col->n_vectors > 0); launch_decode_masked: the values at the set bits,
+// ascending, into d_vals (and their indices into d_idx, nullable) up to capacity, *d_count = how many (col->n_vectors > 0, d_vals non-null when capacity > 0)
 int launch_select_mask(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int op, uint64_t* d_mask, int value_bytes);
 int launch_mask_to_indices(hipStream_t stream, const uint64_t* d_mask, uint64_t n_vectors, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch);
 int launch_sum_masked(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts, int value_bytes);
+int launch_decode_masked(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, void* d_vals, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch,
+                         int value_bytes);
 
 // zone maps (include/alpgpu.h).  decode_kernels.hip / decode_f32_kernels.hip: d_zones[v] = {min, max} of vector v, decoded in registers by the
 // one-wavefront sink kernels (col->n_vectors > 0)

@@ -9,10 +9,15 @@
 //                                the words before + v_mbcnt of its own word: ascending, and no atomic anywhere.
 //   alpgpu_decode_sum_masked_*   k_select<VB, false, SelSumArgs>: the same decode, each lane adding the values whose bit is set; the order is in
 //                                include/alpgpu.h and belongs to this entry point (the persistent consumer of consume_kernels.hip has its own).
+//   alpgpu_decode_masked_*       k_mask_count -> launch_select_scan -> k_select<VB, false, SelTakeArgs>: the projection of a column under a bitmap.
+//                                The emit pass is the selection's with the predicate replaced by a bit test: a vector's values at its set bits,
+//                                compacted at offsets[v] + rank (and their indices beside them, as k_mask_emit writes them).
 //
 // HBM traffic per vector: select_mask SET writes 128 bytes beside the selection's count pass; AND / OR read 128 first and read the column only
 // for vectors the bitmap leaves open; mask_to_indices reads 128 + 128 (the second only where a bit is set) and the scan's 12; the masked SUM
-// reads 128 and, where a bit is set, the vector, and writes 8 (+ 4).
+// reads 128 and, where a bit is set, the vector, and writes 8 (+ 4); the masked projection reads 128 and the scan's 12, then, where a bit is set and
+// the capacity not yet reached, 128 again and the vector (its packed words and exception values only for the halves of the vector that hold a bit),
+// and writes 8 or 4 (+ 8) bytes per selected value.
 #include "select_device.hpp"
 
 namespace alpgpu {
@@ -79,24 +84,59 @@ int launch_sum_masked(hipStream_t stream, const alpgpu_column* col, const uint64
 	return value_bytes == 8 ? launch_arm<8>(stream, col, 0, col->n_vectors, 0, end, 0.0, 0.0, args) : launch_arm<4>(stream, col, 0, col->n_vectors, 0, end, 0.0, 0.0, args);
 }
 
-// n_vectors > 0; d_scratch: select_scratch_bytes(n_vectors) bytes, 16-byte aligned, laid out as the selection's
-int launch_mask_to_indices(hipStream_t stream, const uint64_t* d_mask, uint64_t n_vectors, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch) {
+// the first two phases of mask_to_indices and of the masked projection: counts[v] = the vector's set bits, offsets = their exclusive prefix sum,
+// *d_count = the bitmap's set bits (n_vectors > 0; the scratch laid out as the selection's)
+static int launch_mask_count_scan(hipStream_t stream, const uint64_t* d_mask, uint64_t n_vectors, uint64_t* d_count, void* d_scratch, uint32_t** counts_out, uint64_t** offsets_out) {
 	uint64_t* offsets = static_cast<uint64_t*>(d_scratch);
 	uint32_t* counts  = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_scratch) + align16(8ull * n_vectors));
 	uint64_t* levels  = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(counts) + align16(4ull * n_vectors));
+	*counts_out       = counts;
+	*offsets_out      = offsets;
 	const uint64_t n_count_wg = (n_vectors + 15) / 16; // 256 words = 16 vectors per workgroup
 	for (uint64_t off = 0; off < n_count_wg; off += kSelMaxGrid) {
 		const uint64_t g = n_count_wg - off < kSelMaxGrid ? n_count_wg - off : kSelMaxGrid;
 		hipLaunchKernelGGL(k_mask_count, dim3(static_cast<unsigned>(g)), dim3(256), 0, stream, d_mask, n_vectors, off, counts);
 		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
 	}
-	const int rc = launch_select_scan(stream, counts, n_vectors, offsets, d_count, levels);
+	return launch_select_scan(stream, counts, n_vectors, offsets, d_count, levels);
+}
+
+// n_vectors > 0; d_scratch: select_scratch_bytes(n_vectors) bytes, 16-byte aligned, laid out as the selection's
+int launch_mask_to_indices(hipStream_t stream, const uint64_t* d_mask, uint64_t n_vectors, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch) {
+	uint32_t* counts;
+	uint64_t* offsets;
+	const int rc = launch_mask_count_scan(stream, d_mask, n_vectors, d_count, d_scratch, &counts, &offsets);
 	if (rc != ALPGPU_OK || capacity == 0) { return rc; }
 	const uint64_t n_wg = (n_vectors + kSelWaves - 1) / kSelWaves;
 	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
 		const uint64_t g = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;
 		hipLaunchKernelGGL(k_mask_emit, dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, d_mask, n_vectors, off, static_cast<const uint32_t*>(counts),
 		                   static_cast<const uint64_t*>(offsets), d_idx, capacity);
+		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
+	}
+	return ALPGPU_OK;
+}
+
+// col->n_vectors > 0; d_vals non-null when capacity > 0, d_idx nullable; d_scratch as for launch_mask_to_indices
+int launch_decode_masked(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, void* d_vals, int64_t* d_idx, uint64_t capacity, uint64_t* d_count,
+                         void* d_scratch, int value_bytes) {
+	uint32_t* counts;
+	uint64_t* offsets;
+	const int rc = launch_mask_count_scan(stream, d_mask, col->n_vectors, d_count, d_scratch, &counts, &offsets);
+	if (rc != ALPGPU_OK || capacity == 0) { return rc; }
+	const SelTakeArgs args {d_mask, counts};
+	const uint64_t    n_wg = (col->n_vectors + kSelWaves - 1) / kSelWaves;
+	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
+		const uint64_t g = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;
+		if (value_bytes == 8) {
+			hipLaunchKernelGGL((k_select<8, false, SelTakeArgs>), dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed,
+			                   col->d_exc, 0ull, col->n_vectors, off, 0ull, col->n_vectors << 10, 0.0, 0.0, static_cast<uint32_t*>(nullptr), static_cast<const uint64_t*>(offsets),
+			                   d_idx, d_vals, capacity, args);
+		} else {
+			hipLaunchKernelGGL((k_select<4, false, SelTakeArgs>), dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed,
+			                   col->d_exc, 0ull, col->n_vectors, off, 0ull, col->n_vectors << 10, 0.0, 0.0, static_cast<uint32_t*>(nullptr), static_cast<const uint64_t*>(offsets),
+			                   d_idx, d_vals, capacity, args);
+		}
 		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
 	}
 	return ALPGPU_OK;

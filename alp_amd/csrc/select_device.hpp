@@ -1,5 +1,5 @@
 // select_device.hpp — the one-wavefront decode of a vector that every kernel of the selection family is an arm of: k_select, shared by
-// select_kernels.hip (count, zoned count, emit) and mask_kernels.hip (ballots kept as a bitmap, masked SUM).  The layout of the steps, the
+// select_kernels.hip (count, zoned count, emit) and mask_kernels.hip (ballots kept as a bitmap, masked SUM, masked projection).  The layout of the steps, the
 // exception mask and the arithmetic are described at the head of select_kernels.hip.
 #pragma once
 #include <type_traits>
@@ -23,13 +23,18 @@ inline uint64_t    align16(uint64_t x) { return (x + 15ull) & ~15ull; } // the p
 // record per vector of the COLUMN, indexed by v, not by v - v0) is read first.  A vector whose zone misses [lo, hi] is counted 0 and one whose
 // zone lies inside it, and which cannot hold a NaN, is counted whole; neither has its packed words or exception record read.  (A trailing
 // parameter pack and not a plain parameter: the unzoned instantiations keep their argument list and with it their instructions.)
-// Two more arms take their arguments the same way (mask_kernels.hip; include/alpgpu.h, "selection bitmaps").  In both the launch covers vectors of
+// Three more arms take their arguments the same way (mask_kernels.hip; include/alpgpu.h, "selection bitmaps").  In all the launch covers vectors of
 // the whole column (v0 = 0) and word 16 v + m of the bitmap is step m's ballot: bit `lane` = value index 1024 v + 64 m + lane.
 //   SelMaskArgs  alpgpu_select_mask_*: the 16 ballots of a vector are not counted but kept, lane m < 16 holding step m's, combined with what the
 //                bitmap held (op) and stored as one run of 128 bytes.  A vector outside [first, end), one whose words are all zero under AND and
 //                one whose words are all ones under OR is settled from those 128 bytes: its descriptor is not read.
 //   SelSumArgs   alpgpu_decode_sum_masked_*: no predicate; lane L adds the values 64 m + L whose bit is set, m ascending, from +0.0 (floats widened
 //                first), and the 64 partials combine by wave_tree_sum_f64.  A vector whose words are all zero gets +0.0 and 0 and is not read.
+//   SelTakeArgs  alpgpu_decode_masked_*: no predicate; the emit pass of a selection whose ballots are the bitmap's words.  counts[v] = the vector's
+//                set bits and offsets[v] = the set bits of the vectors before (k_mask_count and the scan ran first); the value at a set bit goes to
+//                d_vals (and its index to d_idx, nullable here) at offsets[v] + the set bits of the words before + those below the lane, under
+//                the capacity.  A vector with counts[v] == 0 costs those four bytes, one at or behind the capacity its offset too; a batch of
+//                kSelBatch steps whose words are all zero requests nothing of the column and only moves the exception rank on.
 constexpr int kMaskSet = ALPGPU_MASK_SET, kMaskAnd = ALPGPU_MASK_AND, kMaskOr = ALPGPU_MASK_OR;
 struct SelMaskArgs {
 	uint64_t* mask;
@@ -40,10 +45,15 @@ struct SelSumArgs {
 	double*         sums;
 	uint32_t*       counts; // nullable
 };
+struct SelTakeArgs {
+	const uint64_t* mask;
+	const uint32_t* counts; // (the kernel's own `counts` is the count pass's output: this arm only reads)
+};
 template <class... ZONES> struct sel_arm { static constexpr int value = 0; };
 template <> struct sel_arm<const void*> { static constexpr int value = 1; };
 template <> struct sel_arm<SelMaskArgs> { static constexpr int value = 2; };
 template <> struct sel_arm<SelSumArgs> { static constexpr int value = 3; };
+template <> struct sel_arm<SelTakeArgs> { static constexpr int value = 4; };
 __device__ __forceinline__ const void* zone_records(const void* zones) { return zones; }
 template <class A> __device__ __forceinline__ const A& arm_args(const A& a) { return a; }
 // lane `idx` (wave-uniform) of a 64-bit value
@@ -59,7 +69,8 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
                                                         uint32_t* __restrict__ counts, const uint64_t* __restrict__ offsets, int64_t* __restrict__ d_idx,
                                                         void* __restrict__ d_vals, uint64_t capacity, ZONES... zones) {
 	constexpr bool ZONED = sel_arm<ZONES...>::value == 1, MASK = sel_arm<ZONES...>::value == 2, SUM = sel_arm<ZONES...>::value == 3;
-	static_assert(sizeof...(ZONES) <= 1 && !((ZONED || MASK || SUM) && EMIT), "at most one arm's arguments, and the emit pass reads the counts and nothing else");
+	constexpr bool TAKE = sel_arm<ZONES...>::value == 4;
+	static_assert(sizeof...(ZONES) <= 1 && !((ZONED || MASK || SUM || TAKE) && EMIT), "at most one arm's arguments, and the emit pass reads the counts and nothing else");
 	typedef typename std::conditional<VB == 8, uint64_t, uint32_t>::type U;
 	typedef typename std::conditional<VB == 8, double, float>::type      T;
 	constexpr uint32_t kLanes = VB == 8 ? 16u : 32u; // FastLanes lanes of the value streams
@@ -91,7 +102,7 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
 		}
 	}
 
-	uint64_t prior = 0; // MASK, SUM: lane m < 16 holds word m of the vector's bitmap as it was found
+	uint64_t prior = 0; // MASK, SUM, TAKE: lane m < 16 holds word m of the vector's bitmap as it was found
 	if constexpr (MASK) {
 		const SelMaskArgs& a       = arm_args(zones...);
 		uint64_t*          mw      = a.mask + 16ull * v;
@@ -121,6 +132,15 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
 			}
 			return;
 		}
+	}
+
+	if constexpr (TAKE) {
+		const SelTakeArgs& a = arm_args(zones...);
+		total                = a.counts[v];
+		if (total == 0) { return; } // a vector without a set bit costs these four bytes
+		out0 = offsets[v];
+		if (out0 >= capacity) { return; } // ... and one at or behind the capacity these eight more: its descriptor is not read
+		prior = lane < 16u ? a.mask[16ull * v + lane] : 0ull; // one read of 128 bytes
 	}
 
 	bool inside = false; // ZONED: every value the zone admits qualifies
@@ -177,10 +197,21 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
 	}
 
 	uint32_t before_exc = 0; // exceptions of the steps done
-	uint32_t before_sel = 0; // qualifying values of the steps done (wave-uniform: it comes from ballots); SUM: set bits of the steps done
+	uint32_t before_sel = 0; // qualifying values of the steps done (wave-uniform: it comes from ballots); SUM, TAKE: set bits of the steps done
 	uint64_t keep       = 0; // MASK: lane m < 16 keeps step m's ballot
 	double   acc        = 0.0; // SUM: this lane's partial
 	for (uint32_t b = 0; b < 16u; b += kSelBatch) {
+		if constexpr (TAKE) {
+			// no bit set in these kSelBatch words: nothing of the column is requested, but the exceptions of the steps passed over still count
+			// towards the rank of those behind them
+			if (ballot64(lane >= b && lane < b + kSelBatch && prior != 0ull) == 0ull) {
+				if (cnt > 0) {
+#pragma unroll
+					for (uint32_t i = 0; i < kSelBatch; ++i) { before_exc += static_cast<uint32_t>(__builtin_popcountll(s_exc[wave][b + i])); } // (every lane reads the same word)
+				}
+				continue;
+			}
+		}
 		// every load of kSelBatch steps is requested before the first is used: a step is otherwise its own round trip to memory
 		FieldWords<U>        rw[kSelBatch];
 		FieldWords<uint16_t> lw[kSelBatch];
@@ -252,6 +283,16 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
 				before_sel += static_cast<uint32_t>(__builtin_popcountll(w));
 				continue;
 			}
+			if constexpr (TAKE) {
+				const uint64_t w = readlane64(prior, m);
+				const uint64_t j = out0 + before_sel + mbcnt64(w, 0u);
+				if (((w >> lane) & 1ull) && j < capacity) { // (lanes of a dense word store side by side)
+					reinterpret_cast<U*>(d_vals)[j] = bits;
+					if (d_idx != nullptr) { d_idx[j] = static_cast<int64_t>(r0 + p); }
+				}
+				before_sel += static_cast<uint32_t>(__builtin_popcountll(w));
+				continue;
+			}
 			const bool     q   = p >= p_begin && p < p_end && x >= lo && x <= hi; // NaN (value or bound) never qualifies; -0.0 == 0.0
 			const uint64_t sel = ballot64(q);
 			if constexpr (MASK) { keep = lane == m ? sel : keep; }
@@ -264,7 +305,7 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
 			}
 			before_sel += static_cast<uint32_t>(__builtin_popcountll(sel));
 		}
-		if constexpr (EMIT) {
+		if constexpr (EMIT || TAKE) {
 			if (before_sel >= total || out0 + before_sel >= capacity) { return; } // the vector's last qualifying value, or the capacity, is behind us
 		}
 	}
@@ -278,7 +319,7 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
 			a.sums[v] = total_sum;
 			if (a.counts != nullptr) { a.counts[v] = before_sel; }
 		}
-	} else if constexpr (!EMIT) {
+	} else if constexpr (!EMIT && !TAKE) {
 		if (lane == 0u) { counts[k] = before_sel; }
 	}
 }

@@ -30,8 +30,8 @@
 // 4 bytes; the scan reads them and writes 8; emit reads 4 + 8 bytes per vector and, for vectors with a non-zero count only, the vector again,
 // and writes 8 (+ 8 or 4) bytes per selected value.
 //
-// k_select itself is in select_device.hpp, which mask_kernels.hip includes too (it instantiates two more arms of the kernel: the ballots kept as
-// a bitmap, and a masked SUM); this file holds the scan, the launches and the scratch layout.
+// k_select itself is in select_device.hpp, which mask_kernels.hip includes too (it instantiates three more arms of the kernel: the ballots kept as
+// a bitmap, a masked SUM and a masked projection); this file holds the scan, the launches and the scratch layout.
 #include "select_device.hpp"
 
 namespace alpgpu {

@@ -500,7 +500,7 @@ struct column {
 	}
 	// Selection bitmaps (include/alpgpu.h, "selection bitmaps"): the qualify mask of lo <= x <= hi over [0, n_values) as 16 words per vector, bit
 	// r & 63 of word r >> 6 = value index r.  Predicates on columns of equal length combine in one mask (mask_and: the bits of tail padding
-	// clear; mask_or), mask_indices lists what is left and sum_masked sums another column under it.
+	// clear; mask_or), mask_indices lists what is left, sum_masked sums another column under it and take_masked projects one.
 	enum mask_op { mask_set = ALPGPU_MASK_SET, mask_and = ALPGPU_MASK_AND, mask_or = ALPGPU_MASK_OR };
 	static std::vector<uint64_t> select_mask(const uint8_t* blob, size_t size, PT lo, PT hi) {
 		std::vector<uint64_t> mask;
@@ -558,8 +558,47 @@ struct column {
 		for (uint32_t c : counts) { out.count += c; }
 		return out;
 	}
+	// The column's values at the set bits of the mask, ascending by index (alpgpu_decode_masked_*): each with the bits decompress gives it.  The
+	// second form also fills `indices` with their value indices (what mask_indices returns).
+	static std::vector<PT> take_masked(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask) { return take_masked_with(blob, size, mask, nullptr); }
+	static std::vector<PT> take_masked(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask, std::vector<int64_t>& indices) {
+		return take_masked_with(blob, size, mask, &indices);
+	}
 
 private:
+	static std::vector<PT> take_masked_with(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask, std::vector<int64_t>* indices) {
+		uploaded_column up(blob, size, "alp::gpu::column::take_masked");
+		const uint64_t  nv = up.col.n_vectors;
+		if (mask.size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::take_masked: the mask must hold 16 words per vector"); }
+		std::vector<PT> out;
+		if (indices) { indices->clear(); }
+		if (nv == 0) { return out; }
+		uint64_t* d_mask    = static_cast<uint64_t*>(up.get(mask.size() * sizeof(uint64_t)));
+		uint64_t* d_count   = static_cast<uint64_t*>(up.get(sizeof(uint64_t)));
+		void*     d_scratch = up.get(alpgpu_select_scratch_bytes(nv));
+		check(alpgpu_memcpy_h2d(context(), d_mask, mask.data(), mask.size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d");
+		uint64_t count = 0;
+		check(decode_masked(&up.col, d_mask, nullptr, nullptr, 0, d_count, d_scratch), "alpgpu_decode_masked"); // count first, then allocate exactly
+		check(alpgpu_memcpy_d2h(context(), &count, d_count, sizeof(count)), "alpgpu_memcpy_d2h");
+		if (count == 0) { return out; }
+		PT*      d_vals = static_cast<PT*>(up.get(count * sizeof(PT)));
+		int64_t* d_idx  = indices ? static_cast<int64_t*>(up.get(count * sizeof(int64_t))) : nullptr;
+		check(decode_masked(&up.col, d_mask, d_vals, d_idx, count, d_count, d_scratch), "alpgpu_decode_masked");
+		out.resize(count);
+		check(alpgpu_memcpy_d2h(context(), out.data(), d_vals, count * sizeof(PT)), "alpgpu_memcpy_d2h");
+		if (indices) {
+			indices->resize(count);
+			check(alpgpu_memcpy_d2h(context(), indices->data(), d_idx, count * sizeof(int64_t)), "alpgpu_memcpy_d2h");
+		}
+		return out;
+	}
+	static int decode_masked(const alpgpu_column* col, const uint64_t* d_mask, PT* d_vals, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch) {
+		if constexpr (sizeof(PT) == 8) {
+			return alpgpu_decode_masked_f64(context(), col, d_mask, reinterpret_cast<double*>(d_vals), d_idx, capacity, d_count, d_scratch);
+		} else {
+			return alpgpu_decode_masked_f32(context(), col, d_mask, reinterpret_cast<float*>(d_vals), d_idx, capacity, d_count, d_scratch);
+		}
+	}
 	static void select_mask_with(const uint8_t* blob, size_t size, PT lo, PT hi, mask_op op, std::vector<uint64_t>& mask, bool fresh) {
 		uploaded_column up(blob, size, "alp::gpu::column::select_mask");
 		const uint64_t  words = 16 * up.col.n_vectors;

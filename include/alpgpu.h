@@ -522,8 +522,9 @@ int alpgpu_select_range_zoned_f32(alpgpu_ctx* ctx, const alpgpu_column* col, con
 
 /* ---- selection bitmaps -------------------------------------------------------------------------------------------------
  * The qualify mask of a range predicate, kept instead of counted away: predicates on several columns of equal length combine in it (AND, OR), and
- * only what is left at the end is listed (alpgpu_mask_to_indices -> alpgpu_gather_*) or summed (alpgpu_decode_sum_masked_*):
- *   WHERE lo1 <= a <= hi1 AND lo2 <= b <= hi2   select_mask(a, SET), select_mask(b, AND);   SUM(c) WHERE ...: decode_sum_masked(c), tree_sum.
+ * only what is left at the end is listed (alpgpu_mask_to_indices), projected (alpgpu_decode_masked_*) or summed (alpgpu_decode_sum_masked_*):
+ *   WHERE lo1 <= a <= hi1 AND lo2 <= b <= hi2   select_mask(a, SET), select_mask(b, AND);   SUM(c) WHERE ...: decode_sum_masked(c), tree_sum;
+ *   SELECT c, d WHERE ...: decode_masked(c), decode_masked(d).
  * The bitmap of a column is n_vectors * 16 uint64_t words in device memory, caller-owned like every buffer of this ABI and 8-byte aligned (a
  *   misaligned pointer returns ALPGPU_ERR_INVALID): bit r & 63 of word r >> 6 stands for value index r, the numbering of the random-access section,
  *   so vector v owns words 16 v .. 16 v + 15 (128 bytes).  It is not part of alpgpu_column and not part of the serialized container.
@@ -558,6 +559,25 @@ int alpgpu_select_range_zoned_f32(alpgpu_ctx* ctx, const alpgpu_column* col, con
  *                               same mathematical sum, not necessarily the same bits.  The column's total is alpgpu_tree_sum_f64 over d_sums.  A
  *                               selected NaN makes its vector's sum a NaN of unspecified payload (bitmaps made by alpgpu_select_mask_* never select
  *                               one; a caller-made bitmap may).  (tests/test_mask_gpu.py holds the host replica.)
+ *  -- masked projection --
+ *   alpgpu_decode_masked_*      the column's values at the set bits of a bitmap, compacted in ascending index order: the projection of
+ *                               SELECT c WHERE ..., one in-register decode of each vector that holds a set bit instead of alpgpu_mask_to_indices and
+ *                               a gather.  d_mask: col->n_vectors * 16 words; every bit is honoured as found, over all n_vectors * 1024 indices
+ *                               (a bitmap built with n = n_values has the tail padding clear); it is read and never written.  Output as
+ *                               alpgpu_select_range_* with d_vals: *d_count = the number of set bits, also when it exceeds capacity; for
+ *                               j < min(*d_count, capacity), d_vals[j] = the value at the j-th set bit, bit for bit what alpgpu_decode_* writes at that
+ *                               index (an exception keeps its bits, -0.0 its sign, a NaN its payload), and d_idx[j] (d_idx may be NULL) = that
+ *                               index, as alpgpu_mask_to_indices returns it.  Nothing is written at or behind capacity, nothing at j >= *d_count.
+ *                               capacity == 0 makes the call a count (d_vals and d_idx may be NULL).  d_scratch: alpgpu_select_scratch_bytes(
+ *                               col->n_vectors) bytes, 16-byte aligned, the selection's layout, contents unspecified afterwards.  Three phases
+ *                               ordered by kernel boundaries: per-vector popcount, the selection's prefix sum, emit (one wavefront per vector);
+ *                               positions come from the prefix sum, the popcount of the words before and v_mbcnt, never from an atomic.  Cost of
+ *                               the emit pass: a vector without a set bit 4 bytes, one at or behind the capacity 12; any other its 128 bytes of
+ *                               bitmap, its descriptor and exception positions, and the packed words and exception values of each half (8 words
+ *                               of bitmap, 512 values) that holds a set bit; it stops behind the vector's last set bit.
+ *                               A NULL ctx, col, d_mask or d_count, a d_mask that is not 8-byte aligned, a NULL d_scratch with n_vectors > 0 and a
+ *                               NULL d_vals with capacity > 0 return ALPGPU_ERR_INVALID before anything is enqueued.  col->n_vectors == 0 writes
+ *                               *d_count = 0 and returns ALPGPU_OK.
  * All of them: everything is enqueued on the context's stream and on that stream only, asynchronous, no host synchronisation, no allocation, none
  *   of what the context remembers about columns is read or written; safe inside a stream capture.  The result is a function of the column, the
  *   bitmap and the arguments alone.
@@ -570,6 +590,10 @@ int alpgpu_select_mask_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t f
 int alpgpu_mask_to_indices(alpgpu_ctx* ctx, const uint64_t* d_mask, uint64_t n_vectors, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch);
 int alpgpu_decode_sum_masked_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts);
 int alpgpu_decode_sum_masked_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts);
+int alpgpu_decode_masked_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, double* d_vals, int64_t* d_idx, uint64_t capacity, uint64_t* d_count,
+                             void* d_scratch);
+int alpgpu_decode_masked_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, float* d_vals, int64_t* d_idx, uint64_t capacity, uint64_t* d_count,
+                             void* d_scratch);
 
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
