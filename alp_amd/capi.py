@@ -128,6 +128,10 @@ for _t, _ft in (("f64", C.c_double), ("f32", C.c_float)):
     _sig("alpgpu_decode_sum_masked_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp)
     _sig("alpgpu_decode_masked_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp, _u64, _vp, _vp)
 _sig("alpgpu_mask_to_indices", _int, _vp, _vp, _u64, _vp, _u64, _vp, _vp)
+CMP_LT, CMP_LE, CMP_GT, CMP_GE, CMP_EQ, CMP_NE = 0, 1, 2, 3, 4, 5  # ALPGPU_CMP_*
+for _t in ("f64", "f32"):
+    _sig("alpgpu_compare_mask_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _u64, _u64, _int, _int, _vp)
+    _sig("alpgpu_decode_dot_masked_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -768,6 +772,58 @@ class Context:
         self.decode_masked_into(col, mask, vals, count, idx, scratch=scratch)
         k = min(int(count.item()), int(capacity))
         return (idx[:k], vals[:k]) if indices else vals[:k]
+
+    # ---- two-column consumers (include/alpgpu.h: alpgpu_compare_mask_*, alpgpu_decode_dot_masked_*) -------------------------
+    _CMP_OPS = {"lt": CMP_LT, "le": CMP_LE, "gt": CMP_GT, "ge": CMP_GE, "eq": CMP_EQ, "ne": CMP_NE}
+
+    @staticmethod
+    def _check_pair(a, b):
+        if a.dtype != b.dtype or a.n_vectors != b.n_vectors:
+            raise ValueError("the two columns must have the same dtype and the same number of vectors")
+
+    def compare_mask(self, a: "DeviceColumn", b: "DeviceColumn", cmp: str = "lt", first: int = 0, n: int = None, op: str = "set", mask=None):
+        """the qualify mask of a_r CMP b_r between two columns of equal length and dtype over the value indices [first, first + n) (n None: to the
+        columns' end) as a selection bitmap.  cmp is "lt", "le", "gt", "ge", "eq" or "ne" with C's meaning (a NaN on either side: only "ne"
+        holds); op and mask as in select_mask.  Returns the mask.  Nothing is synchronised; with a mask given nothing is allocated either
+        (alpgpu_compare_mask_f64 / _f32)."""
+        import torch
+        self._check_pair(a, b)
+        if cmp not in self._CMP_OPS:
+            raise ValueError('cmp must be "lt", "le", "gt", "ge", "eq" or "ne"')
+        if op not in self._MASK_OPS:
+            raise ValueError('op must be "set", "and" or "or"')
+        if mask is None:
+            if op != "set":
+                raise ValueError('op "%s" combines into a mask: pass one' % op)
+            mask = torch.empty(16 * a.n_vectors, dtype=torch.int64, device=f"cuda:{self.device}")
+        else:
+            self._check_mask(mask, a.n_vectors)
+        first = int(first)
+        n = a.n_vectors * VECTOR_SIZE - first if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        self._call("compare_mask", a.dtype, C.byref(a.c), C.byref(b.c), first, n, self._CMP_OPS[cmp], self._MASK_OPS[op], _vp(mask.data_ptr()))
+        return mask
+
+    def decode_dot_masked(self, a: "DeviceColumn", b: "DeviceColumn", mask, out=None, counts=None):
+        """per-vector sums (float64) of a_r * b_r over the set bits of the mask, product and sum rounded separately in the order
+        include/alpgpu.h documents for alpgpu_decode_dot_masked_f64 / _f32; counts (optional, int32, one per vector) receives each vector's
+        number of set bits.  The total is tree_sum(out)."""
+        import torch
+        self._check_pair(a, b)
+        self._check_mask(mask, a.n_vectors)
+        if out is None:
+            out = torch.empty(a.n_vectors, dtype=torch.float64, device=f"cuda:{self.device}")
+        else:
+            self._check_tensor(out, torch.float64, "out")
+            if out.numel() < a.n_vectors:
+                raise ValueError("out must hold one float64 per vector")
+        if counts is not None:
+            self._check_tensor(counts, torch.int32, "counts")
+            if counts.numel() < a.n_vectors:
+                raise ValueError("counts must hold one int32 per vector")
+        self._call("decode_dot_masked", a.dtype, C.byref(a.c), C.byref(b.c), _vp(mask.data_ptr()), _vp(out.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None)
+        return out
 
     # ---- zone maps (include/alpgpu.h: alpgpu_zone_map_*, alpgpu_zones_minmax_*) ---------------------------------------
     def _check_zones(self, zones, dtype, n_vectors):

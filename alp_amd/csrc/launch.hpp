@@ -67,6 +67,12 @@ int launch_sum_masked(hipStream_t stream, const alpgpu_column* col, const uint64
 int launch_decode_masked(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, void* d_vals, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch,
                          int value_bytes);
 
+// pair_kernels.hip: two columns of equal length (a->n_vectors == b->n_vectors > 0; a == b allowed), decoded side by side by one wavefront per
+// vector pair.  launch_compare_mask: bit(r) = / &= / |= q(r), q(r) = first <= r < first + n and a_r CMP b_r (n > 0; range, cmp = ALPGPU_CMP_* and op
+// checked by the caller); launch_dot_masked: d_sums[v] = the sum of a_r * b_r over the vector's set bits, d_counts[v] (nullable) = its set bits
+int launch_compare_mask(hipStream_t stream, const alpgpu_column* a, const alpgpu_column* b, uint64_t first, uint64_t n, int cmp, int op, uint64_t* d_mask, int value_bytes);
+int launch_dot_masked(hipStream_t stream, const alpgpu_column* a, const alpgpu_column* b, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts, int value_bytes);
+
 // zone maps (include/alpgpu.h).  decode_kernels.hip / decode_f32_kernels.hip: d_zones[v] = {min, max} of vector v, decoded in registers by the
 // one-wavefront sink kernels (col->n_vectors > 0)
 int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones);

@@ -558,6 +558,45 @@ struct column {
 		for (uint32_t c : counts) { out.count += c; }
 		return out;
 	}
+	// Two-column consumers (include/alpgpu.h, "two-column consumers"): this column (blob a) against another serialized column of the same type and
+	// the same number of values (blob b; the same blob is allowed).  compare_mask: the qualify mask of a_r CMP b_r over [0, n_values) with C's
+	// comparison (a NaN on either side: only cmp_ne holds), fresh or combined into a mask as select_mask combines; the bits of tail padding
+	// come out clear under mask_set and mask_and.
+	enum compare_op { cmp_lt = ALPGPU_CMP_LT, cmp_le = ALPGPU_CMP_LE, cmp_gt = ALPGPU_CMP_GT, cmp_ge = ALPGPU_CMP_GE, cmp_eq = ALPGPU_CMP_EQ, cmp_ne = ALPGPU_CMP_NE };
+	static std::vector<uint64_t> compare_mask(const uint8_t* blob_a, size_t size_a, const uint8_t* blob_b, size_t size_b, compare_op cmp) {
+		std::vector<uint64_t> mask;
+		compare_mask_with(blob_a, size_a, blob_b, size_b, cmp, mask_set, mask, true);
+		return mask;
+	}
+	static void compare_mask(const uint8_t* blob_a, size_t size_a, const uint8_t* blob_b, size_t size_b, compare_op cmp, mask_op op, std::vector<uint64_t>& mask) {
+		compare_mask_with(blob_a, size_a, blob_b, size_b, cmp, op, mask, false);
+	}
+	// SUM(a * b) and COUNT over the set bits (alpgpu_decode_dot_masked_* and alpgpu_tree_sum_f64 over its per-vector sums: product and sum rounded
+	// separately in the order include/alpgpu.h documents, so the same blobs and mask give the same bits every time)
+	static masked_sum dot_masked(const uint8_t* blob_a, size_t size_a, const uint8_t* blob_b, size_t size_b, const std::vector<uint64_t>& mask) {
+		uploaded_column a(blob_a, size_a, "alp::gpu::column::dot_masked"), b(blob_b, size_b, "alp::gpu::column::dot_masked");
+		const uint64_t  nv = a.col.n_vectors;
+		if (b.col.n_vectors != nv) { throw std::runtime_error("alp::gpu::column::dot_masked: the columns differ in length"); }
+		if (mask.size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::dot_masked: the mask must hold 16 words per vector"); }
+		masked_sum out {0.0, 0};
+		if (nv == 0) { return out; }
+		uint64_t* d_mask   = static_cast<uint64_t*>(a.get(mask.size() * sizeof(uint64_t)));
+		double*   d_sums   = static_cast<double*>(a.get(nv * sizeof(double)));
+		uint32_t* d_counts = static_cast<uint32_t*>(a.get(nv * sizeof(uint32_t)));
+		double*   d_total  = static_cast<double*>(a.get(sizeof(double)));
+		check(alpgpu_memcpy_h2d(context(), d_mask, mask.data(), mask.size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d");
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_decode_dot_masked_f64(context(), &a.col, &b.col, d_mask, d_sums, d_counts), "alpgpu_decode_dot_masked_f64");
+		} else {
+			check(alpgpu_decode_dot_masked_f32(context(), &a.col, &b.col, d_mask, d_sums, d_counts), "alpgpu_decode_dot_masked_f32");
+		}
+		check(alpgpu_tree_sum_f64(context(), d_sums, nv, d_total), "alpgpu_tree_sum_f64");
+		std::vector<uint32_t> counts(nv);
+		check(alpgpu_memcpy_d2h(context(), &out.sum, d_total, sizeof(double)), "alpgpu_memcpy_d2h");
+		check(alpgpu_memcpy_d2h(context(), counts.data(), d_counts, nv * sizeof(uint32_t)), "alpgpu_memcpy_d2h");
+		for (uint32_t c : counts) { out.count += c; }
+		return out;
+	}
 	// The column's values at the set bits of the mask, ascending by index (alpgpu_decode_masked_*): each with the bits decompress gives it.  The
 	// second form also fills `indices` with their value indices (what mask_indices returns).
 	static std::vector<PT> take_masked(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask) { return take_masked_with(blob, size, mask, nullptr); }
@@ -614,6 +653,25 @@ private:
 			check(alpgpu_select_mask_f64(context(), &up.col, 0, up.n_values, lo, hi, op, d_mask), "alpgpu_select_mask_f64");
 		} else {
 			check(alpgpu_select_mask_f32(context(), &up.col, 0, up.n_values, lo, hi, op, d_mask), "alpgpu_select_mask_f32");
+		}
+		check(alpgpu_memcpy_d2h(context(), mask.data(), d_mask, words * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
+	}
+	static void compare_mask_with(const uint8_t* blob_a, size_t size_a, const uint8_t* blob_b, size_t size_b, compare_op cmp, mask_op op, std::vector<uint64_t>& mask, bool fresh) {
+		uploaded_column a(blob_a, size_a, "alp::gpu::column::compare_mask"), b(blob_b, size_b, "alp::gpu::column::compare_mask");
+		if (b.col.n_vectors != a.col.n_vectors || b.n_values != a.n_values) { throw std::runtime_error("alp::gpu::column::compare_mask: the columns differ in length"); }
+		const uint64_t words = 16 * a.col.n_vectors;
+		if (fresh) {
+			mask.assign(words, 0);
+		} else if (mask.size() != words) {
+			throw std::runtime_error("alp::gpu::column::compare_mask: the mask must hold 16 words per vector");
+		}
+		if (words == 0) { return; }
+		uint64_t* d_mask = static_cast<uint64_t*>(a.get(words * sizeof(uint64_t)));
+		if (op != mask_set) { check(alpgpu_memcpy_h2d(context(), d_mask, mask.data(), words * sizeof(uint64_t)), "alpgpu_memcpy_h2d"); }
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_compare_mask_f64(context(), &a.col, &b.col, 0, a.n_values, cmp, op, d_mask), "alpgpu_compare_mask_f64");
+		} else {
+			check(alpgpu_compare_mask_f32(context(), &a.col, &b.col, 0, a.n_values, cmp, op, d_mask), "alpgpu_compare_mask_f32");
 		}
 		check(alpgpu_memcpy_d2h(context(), mask.data(), d_mask, words * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
 	}

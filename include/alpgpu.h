@@ -595,6 +595,49 @@ int alpgpu_decode_masked_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const ui
 int alpgpu_decode_masked_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, float* d_vals, int64_t* d_idx, uint64_t capacity, uint64_t* d_count,
                              void* d_scratch);
 
+/* ---- two-column consumers ----------------------------------------------------------------------------------------------
+ * Two columns a and b of equal length (a->n_vectors == b->n_vectors; both of the entry point's type, mixed f64 / f32 pairs are not offered),
+ * decoded side by side: one wavefront decodes vector v of a AND vector v of b in registers and combines them lane by lane, so that neither
+ * column's values reach HBM.  A predicate between columns, and the aggregate of a product under a bitmap (TPC-H Q6):
+ *   WHERE a < b                         compare_mask(a, b, LT, SET);   WHERE lo <= c <= hi AND a >= b: select_mask(c, SET), compare_mask(a, b, GE, AND);
+ *   SUM(a * b) WHERE ...                select_mask ... ; decode_dot_masked(a, b); tree_sum.
+ * The bitmap is that of the section above (n_vectors * 16 words, 8-byte aligned, bit r & 63 of word r >> 6 = value index r).  a_r and b_r are
+ * the values alpgpu_decode_* writes at index r, exceptions patched in.  a == b (the same column) is allowed.
+ *   alpgpu_compare_mask_*       Let q(r) = first <= r < first + n and a_r CMP b_r, CMP one of ALPGPU_CMP_LT / _LE / _GT / _GE / _EQ / _NE with the
+ *                               meaning of C's <, <=, >, >=, ==, !=: a NaN on either side makes LT, LE, GT, GE and EQ false and NE true;
+ *                               -0.0 == 0.0; +-inf are ordinary values.  op = ALPGPU_MASK_SET / _AND / _OR with exactly the meaning, the range
+ *                               check and the skip rules of alpgpu_select_mask_*: SET writes every word of the bitmap, AND clears the bits
+ *                               outside the range, OR leaves them; a vector outside the range is settled from its 128 bytes of bitmap; under
+ *                               AND a vector whose 16 words are all zero, and under OR one whose 16 words are all ones, is settled the same
+ *                               way — neither column's descriptor, packed words or exception record is read.  n == 0: SET and AND clear the
+ *                               bitmap, OR enqueues nothing.  first + n past n_vectors * 1024, or overflowing: ALPGPU_ERR_INVALID, nothing enqueued.
+ *                               An unknown cmp or op returns ALPGPU_ERR_INVALID and enqueues nothing.
+ *   alpgpu_decode_dot_masked_*  d_sums[v] = the sum, over the set bits of vector v, of a_r * b_r; d_counts[v] (may be NULL) = the number of set
+ *                               bits.  A vector whose 16 words are zero gets +0.0 and 0, and neither column is read for it.  Summation order (so
+ *                               that the result can be reproduced bit for bit): lane L of 64 starts from +0.0 and, for m = 0..15 in that order,
+ *                               if bit 64 m + L is set, forms t = a * b rounded once to double (float values widen to double first, exactly;
+ *                               their product is then exact) and acc = acc + t rounded once — two operations, never a fused multiply-add —
+ *                               and does nothing if the bit is clear; the 64 partials combine by the balanced binary tree over adjacent lanes
+ *                               of alpgpu_decode_sum_* — (0,1), (2,3), ...; six levels.  The column's total is alpgpu_tree_sum_f64 over d_sums.  A
+ *                               selected NaN, or inf * 0, makes its vector's sum a NaN of unspecified payload.  d_mask is read and never
+ *                               written; d_mask and d_sums are required.  (tests/pair_replica.py holds the host replica.)
+ * Both: a->n_vectors != b->n_vectors, a NULL ctx, a or b, a NULL d_mask (or d_sums) with n_vectors > 0 and a d_mask that is not 8-byte aligned
+ *   return ALPGPU_ERR_INVALID before anything is enqueued; n_vectors == 0 is ALPGPU_OK and launches nothing.  One launch, one wavefront per
+ *   vector pair, on the context's stream and on that stream only; asynchronous, no host synchronisation, no allocation, no atomics on results,
+ *   none of what the context remembers about columns is read or written; safe inside a stream capture.  The result is a function of the two
+ *   columns, the bitmap and the arguments alone.
+ * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector), for both columns. */
+#define ALPGPU_CMP_LT 0
+#define ALPGPU_CMP_LE 1
+#define ALPGPU_CMP_GT 2
+#define ALPGPU_CMP_GE 3
+#define ALPGPU_CMP_EQ 4
+#define ALPGPU_CMP_NE 5
+int alpgpu_compare_mask_f64(alpgpu_ctx* ctx, const alpgpu_column* a, const alpgpu_column* b, uint64_t first, uint64_t n, int cmp, int op, uint64_t* d_mask);
+int alpgpu_compare_mask_f32(alpgpu_ctx* ctx, const alpgpu_column* a, const alpgpu_column* b, uint64_t first, uint64_t n, int cmp, int op, uint64_t* d_mask);
+int alpgpu_decode_dot_masked_f64(alpgpu_ctx* ctx, const alpgpu_column* a, const alpgpu_column* b, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts);
+int alpgpu_decode_dot_masked_f32(alpgpu_ctx* ctx, const alpgpu_column* a, const alpgpu_column* b, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
