@@ -132,6 +132,11 @@ CMP_LT, CMP_LE, CMP_GT, CMP_GE, CMP_EQ, CMP_NE = 0, 1, 2, 3, 4, 5  # ALPGPU_CMP_
 for _t in ("f64", "f32"):
     _sig("alpgpu_compare_mask_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _u64, _u64, _int, _int, _vp)
     _sig("alpgpu_decode_dot_masked_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp)
+GROUP_MAX = 16  # ALPGPU_GROUP_MAX
+for _t in ("f64", "f32"):
+    _sig("alpgpu_decode_group_sum_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp)
+_sig("alpgpu_group_totals_scratch_bytes", C.c_size_t, _u64, C.c_uint32)
+_sig("alpgpu_group_totals", _int, _vp, _vp, _vp, _u64, C.c_uint32, _vp, _vp, _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -824,6 +829,82 @@ class Context:
                 raise ValueError("counts must hold one int32 per vector")
         self._call("decode_dot_masked", a.dtype, C.byref(a.c), C.byref(b.c), _vp(mask.data_ptr()), _vp(out.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None)
         return out
+
+    # ---- grouped aggregation (include/alpgpu.h: alpgpu_decode_group_sum_*, alpgpu_group_totals) -----------------------------------
+    def decode_group_sum(self, val: "DeviceColumn", key: "DeviceColumn", mask, lo, hi, out=None, counts=None):
+        """per-group, per-vector sums of val over the set bits of the mask whose key lies in the closed range lo[g] <= k <= hi[g] (select_mask's
+        predicate), every group settled in one pass over the two columns: a [n_groups, n_vectors] float64 tensor, row g bit for bit what
+        decode_sum_masked(val) gives under the mask ANDed with select_mask(key, lo[g], hi[g]).  lo, hi: sequences of 1 .. GROUP_MAX floats of
+        equal length; counts (optional, int32, the same shape) receives the number of values each sum adds.  Every group's total is
+        group_totals(out, counts).  Nothing is synchronised (alpgpu_decode_group_sum_f64 / _f32)."""
+        import torch
+        self._check_pair(val, key)
+        self._check_mask(mask, val.n_vectors)
+        try:
+            lo, hi = [float(t) for t in lo], [float(t) for t in hi]
+        except TypeError:
+            raise ValueError("lo and hi must be sequences of numbers") from None
+        n_groups = len(lo)
+        if len(hi) != n_groups or not 1 <= n_groups <= GROUP_MAX:
+            raise ValueError("lo and hi must hold the same number of bounds, 1 .. %d" % GROUP_MAX)
+        if out is None:
+            out = torch.empty((n_groups, val.n_vectors), dtype=torch.float64, device=f"cuda:{self.device}")
+        else:
+            self._check_tensor(out, torch.float64, "out")
+            if tuple(out.shape) != (n_groups, val.n_vectors):
+                raise ValueError("out must be a [n_groups, n_vectors] float64 tensor")
+        if counts is not None:
+            self._check_tensor(counts, torch.int32, "counts")
+            if tuple(counts.shape) != (n_groups, val.n_vectors):
+                raise ValueError("counts must be a [n_groups, n_vectors] int32 tensor")
+        ft = C.c_double if val.dtype == "f64" else C.c_float
+        self._call("decode_group_sum", val.dtype, C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()), (ft * n_groups)(*lo), (ft * n_groups)(*hi), n_groups, _vp(out.data_ptr()),
+                   _vp(counts.data_ptr()) if counts is not None else None)
+        return out
+
+    def group_totals_scratch(self, n_vectors: int, n_groups: int):
+        """a scratch tensor for group_totals (alpgpu_group_totals_scratch_bytes; torch allocations are at least 16-byte aligned)"""
+        import torch
+        return torch.empty(lib.alpgpu_group_totals_scratch_bytes(int(n_vectors), int(n_groups)), dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    def group_totals(self, sums, counts=None, scratch=None, out=None, counts_out=None):
+        """every group's total of a [n_groups, n_vectors] float64 tensor of per-vector sums, row by row the tree of tree_sum, and (with counts,
+        int32 of the same shape) every group's exact count: (float64[n_groups], int64[n_groups] or None).  With scratch (group_totals_scratch),
+        out and counts_out given nothing is allocated (alpgpu_group_totals)."""
+        import torch
+        self._check_tensor(sums, torch.float64, "sums")
+        if sums.dim() != 2 or not 1 <= sums.shape[0] <= GROUP_MAX:
+            raise ValueError("sums must be a [n_groups, n_vectors] float64 tensor of 1 .. %d groups" % GROUP_MAX)
+        n_groups, n_vectors = int(sums.shape[0]), int(sums.shape[1])
+        if counts is not None:
+            self._check_tensor(counts, torch.int32, "counts")
+            if tuple(counts.shape) != (n_groups, n_vectors):
+                raise ValueError("counts must be a [n_groups, n_vectors] int32 tensor")
+        elif counts_out is not None:
+            raise ValueError("counts_out without counts")
+        need = lib.alpgpu_group_totals_scratch_bytes(n_vectors, n_groups)
+        if scratch is None:
+            scratch = self.group_totals_scratch(n_vectors, n_groups)
+        else:
+            self._check_tensor(scratch, torch.uint8, "scratch")
+            if scratch.numel() < need or scratch.data_ptr() % 16:
+                raise ValueError("scratch must hold group_totals_scratch(n_vectors, n_groups) bytes, 16-byte aligned")
+        if out is None:
+            out = torch.empty(n_groups, dtype=torch.float64, device=f"cuda:{self.device}")
+        else:
+            self._check_tensor(out, torch.float64, "out")
+            if out.numel() != n_groups:
+                raise ValueError("out must hold one float64 per group")
+        if counts is not None:
+            if counts_out is None:
+                counts_out = torch.empty(n_groups, dtype=torch.int64, device=f"cuda:{self.device}")
+            else:
+                self._check_tensor(counts_out, torch.int64, "counts_out")
+                if counts_out.numel() != n_groups:
+                    raise ValueError("counts_out must hold one int64 per group")
+        _check(lib.alpgpu_group_totals(self.h, _vp(sums.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None, n_vectors, n_groups, _vp(out.data_ptr()),
+                                       _vp(counts_out.data_ptr()) if counts is not None else None, _vp(scratch.data_ptr())), "alpgpu_group_totals")
+        return out, counts_out
 
     # ---- zone maps (include/alpgpu.h: alpgpu_zone_map_*, alpgpu_zones_minmax_*) ---------------------------------------
     def _check_zones(self, zones, dtype, n_vectors):

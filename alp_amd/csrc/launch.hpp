@@ -73,6 +73,16 @@ int launch_decode_masked(hipStream_t stream, const alpgpu_column* col, const uin
 int launch_compare_mask(hipStream_t stream, const alpgpu_column* a, const alpgpu_column* b, uint64_t first, uint64_t n, int cmp, int op, uint64_t* d_mask, int value_bytes);
 int launch_dot_masked(hipStream_t stream, const alpgpu_column* a, const alpgpu_column* b, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts, int value_bytes);
 
+// group_kernels.hip: grouped aggregation (val->n_vectors == key->n_vectors > 0; val == key allowed; 1 <= n_groups <= ALPGPU_GROUP_MAX).
+// launch_group_sum: d_sums[g * n_vectors + v] = the sum of val_r over the vector's set bits whose key_r lies in [lo[g], hi[g]] (host arrays, read
+// before the call returns; a float column's bounds are floats widened), d_counts (nullable) their number; launch_group_totals: row g of d_sums
+// [n_groups][n] by launch_tree_sum's tree into d_total_sums[g], row g of d_counts (nullable with d_total_counts) added exactly (n > 0; d_scratch:
+// 32 * n_groups * ceil(n / 1024) bytes, 16-byte aligned, read only when n > 1024)
+int launch_group_sum(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const double* lo, const double* hi, uint32_t n_groups,
+                     double* d_sums, uint32_t* d_counts, int value_bytes);
+int launch_group_totals(hipStream_t stream, const double* d_sums, const uint32_t* d_counts, uint64_t n, uint32_t n_groups, double* d_total_sums, uint64_t* d_total_counts,
+                        void* d_scratch);
+
 // zone maps (include/alpgpu.h).  decode_kernels.hip / decode_f32_kernels.hip: d_zones[v] = {min, max} of vector v, decoded in registers by the
 // one-wavefront sink kernels (col->n_vectors > 0)
 int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones);

@@ -597,6 +597,56 @@ struct column {
 		for (uint32_t c : counts) { out.count += c; }
 		return out;
 	}
+	// Grouped aggregation (include/alpgpu.h, "grouped aggregation"): this column (blob val) summed and counted per vector, under the mask, for the
+	// n_groups closed ranges lo[g] <= k <= hi[g] of a key column of the same type and length (blob key; the same blob is allowed), all in one pass
+	// over the two columns (alpgpu_decode_group_sum_*).  sums and counts (optional) come back as [n_groups][n_vectors], row g bit for bit what
+	// sum_masked's per-vector pass gives under the mask ANDed with select_mask(key, lo[g], hi[g]).  Returns n_vectors.
+	static uint64_t group_sum_masked(const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>& mask, const PT* lo, const PT* hi,
+	                                 uint32_t n_groups, std::vector<double>& sums, std::vector<uint32_t>* counts = nullptr) {
+		if (n_groups == 0 || n_groups > ALPGPU_GROUP_MAX || !lo || !hi) { throw std::runtime_error("alp::gpu::column::group_sum_masked: 1 .. ALPGPU_GROUP_MAX groups with their bounds"); }
+		uploaded_column val(blob_val, size_val, "alp::gpu::column::group_sum_masked"), key(blob_key, size_key, "alp::gpu::column::group_sum_masked");
+		const uint64_t  nv = val.col.n_vectors;
+		if (key.col.n_vectors != nv) { throw std::runtime_error("alp::gpu::column::group_sum_masked: the columns differ in length"); }
+		if (mask.size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::group_sum_masked: the mask must hold 16 words per vector"); }
+		sums.assign(n_groups * nv, 0.0);
+		if (counts) { counts->assign(n_groups * nv, 0); }
+		if (nv == 0) { return nv; }
+		uint64_t* d_mask   = static_cast<uint64_t*>(val.get(mask.size() * sizeof(uint64_t)));
+		double*   d_sums   = static_cast<double*>(val.get(sums.size() * sizeof(double)));
+		uint32_t* d_counts = counts ? static_cast<uint32_t*>(val.get(sums.size() * sizeof(uint32_t))) : nullptr;
+		check(alpgpu_memcpy_h2d(context(), d_mask, mask.data(), mask.size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d");
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_decode_group_sum_f64(context(), &val.col, &key.col, d_mask, lo, hi, n_groups, d_sums, d_counts), "alpgpu_decode_group_sum_f64");
+		} else {
+			check(alpgpu_decode_group_sum_f32(context(), &val.col, &key.col, d_mask, lo, hi, n_groups, d_sums, d_counts), "alpgpu_decode_group_sum_f32");
+		}
+		check(alpgpu_memcpy_d2h(context(), sums.data(), d_sums, sums.size() * sizeof(double)), "alpgpu_memcpy_d2h");
+		if (counts) { check(alpgpu_memcpy_d2h(context(), counts->data(), d_counts, counts->size() * sizeof(uint32_t)), "alpgpu_memcpy_d2h"); }
+		return nv;
+	}
+	// Every group's SUM and COUNT from what group_sum_masked returned (alpgpu_group_totals: each row by the tree of alpgpu_tree_sum_f64, the counts
+	// added exactly; without counts every count is 0)
+	static std::vector<masked_sum> group_totals(const std::vector<double>& sums, const std::vector<uint32_t>* counts, uint64_t n_vectors, uint32_t n_groups) {
+		if (n_groups == 0 || n_groups > ALPGPU_GROUP_MAX || sums.size() != n_groups * n_vectors || (counts && counts->size() != sums.size())) {
+			throw std::runtime_error("alp::gpu::column::group_totals: sums (and counts) must be [n_groups][n_vectors], 1 .. ALPGPU_GROUP_MAX groups");
+		}
+		device_buffers buf;
+		double*        d_sums    = static_cast<double*>(buf.get(sums.size() * sizeof(double)));
+		uint32_t*      d_counts  = counts ? static_cast<uint32_t*>(buf.get(sums.size() * sizeof(uint32_t))) : nullptr;
+		double*        d_totals  = static_cast<double*>(buf.get(n_groups * sizeof(double)));
+		uint64_t*      d_tcounts = counts ? static_cast<uint64_t*>(buf.get(n_groups * sizeof(uint64_t))) : nullptr;
+		void*          d_scratch = buf.get(alpgpu_group_totals_scratch_bytes(n_vectors, n_groups));
+		if (!sums.empty()) { check(alpgpu_memcpy_h2d(context(), d_sums, sums.data(), sums.size() * sizeof(double)), "alpgpu_memcpy_h2d"); }
+		if (counts && !sums.empty()) { check(alpgpu_memcpy_h2d(context(), d_counts, counts->data(), sums.size() * sizeof(uint32_t)), "alpgpu_memcpy_h2d"); }
+		check(alpgpu_group_totals(context(), d_sums, d_counts, n_vectors, n_groups, d_totals, d_tcounts, d_scratch), "alpgpu_group_totals");
+		std::vector<double>   totals(n_groups);
+		std::vector<uint64_t> tcounts(n_groups, 0);
+		check(alpgpu_memcpy_d2h(context(), totals.data(), d_totals, n_groups * sizeof(double)), "alpgpu_memcpy_d2h");
+		if (counts) { check(alpgpu_memcpy_d2h(context(), tcounts.data(), d_tcounts, n_groups * sizeof(uint64_t)), "alpgpu_memcpy_d2h"); }
+		std::vector<masked_sum> out(n_groups);
+		for (uint32_t g = 0; g < n_groups; ++g) { out[g] = masked_sum {totals[g], tcounts[g]}; }
+		return out;
+	}
 	// The column's values at the set bits of the mask, ascending by index (alpgpu_decode_masked_*): each with the bits decompress gives it.  The
 	// second form also fills `indices` with their value indices (what mask_indices returns).
 	static std::vector<PT> take_masked(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask) { return take_masked_with(blob, size, mask, nullptr); }

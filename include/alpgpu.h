@@ -638,6 +638,53 @@ int alpgpu_compare_mask_f32(alpgpu_ctx* ctx, const alpgpu_column* a, const alpgp
 int alpgpu_decode_dot_masked_f64(alpgpu_ctx* ctx, const alpgpu_column* a, const alpgpu_column* b, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts);
 int alpgpu_decode_dot_masked_f32(alpgpu_ctx* ctx, const alpgpu_column* a, const alpgpu_column* b, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts);
 
+/* ---- grouped aggregation -----------------------------------------------------------------------------------------------------------------
+ * SELECT key, SUM(x), COUNT(*) ... WHERE ... GROUP BY key (TPC-H Q1), and the histogram of a column under a predicate: per-group SUM and COUNT
+ * of a value column by closed ranges of a key column, in ONE pass that decodes vector v of both columns in the registers of one wavefront and
+ * settles every group there.  G groups cost two decodes, not the 2 G of G rounds of bitmap copy + select_mask(AND) + decode_sum_masked.
+ *   WHERE ...                           select_mask / compare_mask ... into the bitmap (all ones for no WHERE clause);
+ *   SUM(x), COUNT(*) GROUP BY key       decode_group_sum(val, key, bitmap, lo, hi); group_totals.
+ *   alpgpu_decode_group_sum_*   val and key: two columns of the entry point's type with equal n_vectors; val == key is allowed (a histogram
+ *                               with per-bin sums).  d_mask: the selection bitmap of the sections above (n_vectors * 16 words, 8-byte aligned),
+ *                               required, read and never written.  lo, hi: HOST arrays of n_groups bounds, 1 <= n_groups <= ALPGPU_GROUP_MAX;
+ *                               group g is the closed range lo[g] <= k <= hi[g] with exactly the predicate of alpgpu_select_mask_*: a NaN never
+ *                               qualifies, as a value or as a bound; -0.0 == 0.0; lo > hi selects nothing; +-inf are ordinary.  The arrays are
+ *                               read before the call returns and travel as kernel arguments (at most 256 bytes), so a captured graph keeps the
+ *                               bounds it was captured with.  Groups are independent: they may overlap (a value then counts in each group it
+ *                               falls in), touch or be empty; a discrete key is lo[g] == hi[g]; adjacent histogram bins are the caller's business.
+ *                               Output, group-major: d_sums[g * n_vectors + v] and d_counts[g * n_vectors + v] (d_counts may be NULL); every (g, v)
+ *                               with g < n_groups is written and nothing else.
+ *                               The contract, bit for bit: let M_g be the caller's bitmap ANDed with alpgpu_select_mask_*(key, first = 0,
+ *                               n = n_vectors * 1024, lo[g], hi[g]); row g of d_sums and d_counts is what alpgpu_decode_sum_masked_*(val, M_g)
+ *                               writes.  Summation order: lane L of 64 starts from +0.0; for m = 0..15 in that order it adds value 64 m + L of
+ *                               val (a float widened to double first) if its bit is set and the key there is in range, and does nothing
+ *                               otherwise; the 64 partials combine by the adjacent-lane tree of alpgpu_decode_sum_*.  No multiplication is
+ *                               involved.  A selected NaN in val makes that sum a NaN of unspecified payload.  A vector whose 16 bitmap words
+ *                               are zero gets +0.0 and 0 in every group, and neither column is read for it.  (tests/group_replica.py holds the
+ *                               host replica.)
+ *                               ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx, val, key, lo or hi; n_groups == 0 or
+ *                               > ALPGPU_GROUP_MAX; unequal n_vectors; an implausible n_vectors; with n_vectors > 0 a NULL d_mask or d_sums, a
+ *                               d_mask that is not 8-byte aligned, or columns without descriptors.  n_vectors == 0 is ALPGPU_OK and launches nothing.
+ *   alpgpu_group_totals         d_sums, d_counts: [n_groups][n_vectors] as written above.  d_total_sums[g] is, bit for bit,
+ *                               alpgpu_tree_sum_f64(d_sums + g * n_vectors, n_vectors); d_total_counts[g] is the exact integer sum of row g of
+ *                               d_counts.  d_counts and d_total_counts are NULL together.  d_scratch is the caller's:
+ *                               alpgpu_group_totals_scratch_bytes(n_vectors, n_groups) bytes, 16-byte aligned (it is used, and checked, only
+ *                               when n_vectors > 1024); nothing is allocated and the context's workspace is not used.  No floating-point atomics.
+ *                               n_vectors == 0 writes +0.0 and 0 and looks at neither input (their pointers may be NULL).  A NULL ctx or
+ *                               d_total_sums, n_groups out of range and, with n_vectors > 0, a NULL d_sums and counts without their totals (or
+ *                               the reverse) return ALPGPU_ERR_INVALID before anything is enqueued.
+ * Both run on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation; none of what the context
+ *   remembers about columns is read or written; safe inside a stream capture.  The result is a function of the arguments alone.
+ * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector), for both columns. */
+#define ALPGPU_GROUP_MAX 16
+int alpgpu_decode_group_sum_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const double* lo, const double* hi,
+                                uint32_t n_groups, double* d_sums, uint32_t* d_counts);
+int alpgpu_decode_group_sum_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const float* lo, const float* hi,
+                                uint32_t n_groups, double* d_sums, uint32_t* d_counts);
+size_t alpgpu_group_totals_scratch_bytes(uint64_t n_vectors, uint32_t n_groups);
+int    alpgpu_group_totals(alpgpu_ctx* ctx, const double* d_sums, const uint32_t* d_counts, uint64_t n_vectors, uint32_t n_groups, double* d_total_sums,
+                           uint64_t* d_total_counts, void* d_scratch);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
