@@ -137,6 +137,10 @@ for _t in ("f64", "f32"):
     _sig("alpgpu_decode_group_sum_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp)
 _sig("alpgpu_group_totals_scratch_bytes", C.c_size_t, _u64, C.c_uint32)
 _sig("alpgpu_group_totals", _int, _vp, _vp, _vp, _u64, C.c_uint32, _vp, _vp, _vp)
+for _t in ("f64", "f32"):
+    _sig("alpgpu_decode_minmax_masked_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp)
+    _sig("alpgpu_decode_group_minmax_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp)
+    _sig("alpgpu_group_minmax_totals_" + _t, _int, _vp, _vp, _u64, C.c_uint32, _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -905,6 +909,77 @@ class Context:
         _check(lib.alpgpu_group_totals(self.h, _vp(sums.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None, n_vectors, n_groups, _vp(out.data_ptr()),
                                        _vp(counts_out.data_ptr()) if counts is not None else None, _vp(scratch.data_ptr())), "alpgpu_group_totals")
         return out, counts_out
+
+    # ---- masked and grouped MIN / MAX (include/alpgpu.h: alpgpu_decode_minmax_masked_*, alpgpu_decode_group_minmax_*, alpgpu_group_minmax_totals_*) ---
+    def decode_minmax_masked(self, col: "DeviceColumn", mask, out=None, counts=None):
+        """per-vector records {min, max} over the decoded values whose bit is set in the mask: a [n_vectors, 2] tensor of the column's value type
+        with the rules of zone_map (NaNs ignored, -0.0 < +0.0, {+inf, -inf} when nothing selected is a number); counts (optional, int32, one per
+        vector) receives each vector's number of set bits.  The column's MIN / MAX is column_minmax(out).  The records are narrower than the
+        vectors' intervals: not a zone map for select_range.  Nothing is synchronised (alpgpu_decode_minmax_masked_f64 / _f32)."""
+        import torch
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        self._check_mask(mask, col.n_vectors)
+        if out is None:
+            out = torch.empty((col.n_vectors, 2), dtype=tdt, device=f"cuda:{self.device}")
+        else:
+            self._check_zones(out, tdt, col.n_vectors)
+        if counts is not None:
+            self._check_tensor(counts, torch.int32, "counts")
+            if counts.numel() < col.n_vectors:
+                raise ValueError("counts must hold one int32 per vector")
+        self._call("decode_minmax_masked", col.dtype, C.byref(col.c), _vp(mask.data_ptr()), _vp(out.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None)
+        return out
+
+    def decode_group_minmax(self, val: "DeviceColumn", key: "DeviceColumn", mask, lo, hi, out=None, counts=None):
+        """per-group, per-vector records {min, max} of val over the set bits of the mask whose key lies in the closed range lo[g] <= k <= hi[g]
+        (select_mask's predicate), every group settled in one pass over the two columns: a [n_groups, n_vectors, 2] tensor of the columns' value
+        type, row g bit for bit what decode_minmax_masked(val) gives under the mask ANDed with select_mask(key, lo[g], hi[g]).  lo, hi: sequences
+        of 1 .. GROUP_MAX floats of equal length; counts (optional, int32 [n_groups, n_vectors]) receives what decode_group_sum counts.  Every
+        group's MIN / MAX is group_minmax_totals(out).  Nothing is synchronised (alpgpu_decode_group_minmax_f64 / _f32)."""
+        import torch
+        self._check_pair(val, key)
+        self._check_mask(mask, val.n_vectors)
+        try:
+            lo, hi = [float(t) for t in lo], [float(t) for t in hi]
+        except TypeError:
+            raise ValueError("lo and hi must be sequences of numbers") from None
+        n_groups = len(lo)
+        if len(hi) != n_groups or not 1 <= n_groups <= GROUP_MAX:
+            raise ValueError("lo and hi must hold the same number of bounds, 1 .. %d" % GROUP_MAX)
+        tdt = torch.float64 if val.dtype == "f64" else torch.float32
+        if out is None:
+            out = torch.empty((n_groups, val.n_vectors, 2), dtype=tdt, device=f"cuda:{self.device}")
+        else:
+            self._check_tensor(out, tdt, "out")
+            if tuple(out.shape) != (n_groups, val.n_vectors, 2) or out.data_ptr() % (2 * out.element_size()):
+                raise ValueError("out must be a [n_groups, n_vectors, 2] tensor of the columns' value type, aligned to its records")
+        if counts is not None:
+            self._check_tensor(counts, torch.int32, "counts")
+            if tuple(counts.shape) != (n_groups, val.n_vectors):
+                raise ValueError("counts must be a [n_groups, n_vectors] int32 tensor")
+        ft = C.c_double if val.dtype == "f64" else C.c_float
+        self._call("decode_group_minmax", val.dtype, C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()), (ft * n_groups)(*lo), (ft * n_groups)(*hi), n_groups,
+                   _vp(out.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None)
+        return out
+
+    def group_minmax_totals(self, zones, out=None):
+        """every group's {min, max} of a [n_groups, n_vectors, 2] tensor of records: a [n_groups, 2] tensor, row g what column_minmax(zones[g])
+        gives; {+inf, -inf} for n_vectors == 0.  No scratch (alpgpu_group_minmax_totals_f64 / _f32)."""
+        import torch
+        if not isinstance(zones, torch.Tensor) or zones.dtype not in (torch.float64, torch.float32):
+            raise ValueError("zones must be a float64 or float32 tensor")
+        self._check_tensor(zones, zones.dtype, "zones")
+        if zones.dim() != 3 or zones.shape[2] != 2 or not 1 <= zones.shape[0] <= GROUP_MAX or zones.data_ptr() % (2 * zones.element_size()):
+            raise ValueError("zones must be a [n_groups, n_vectors, 2] tensor of 1 .. %d groups, aligned to its records" % GROUP_MAX)
+        n_groups, n_vectors = int(zones.shape[0]), int(zones.shape[1])
+        if out is None:
+            out = torch.empty((n_groups, 2), dtype=zones.dtype, device=zones.device)
+        else:
+            self._check_tensor(out, zones.dtype, "out")
+            if tuple(out.shape) != (n_groups, 2):
+                raise ValueError("out must be a [n_groups, 2] tensor of the records' type")
+        self._call("group_minmax_totals", self._sfx(zones), _vp(zones.data_ptr()) if n_vectors else None, n_vectors, n_groups, _vp(out.data_ptr()))
+        return out
 
     # ---- zone maps (include/alpgpu.h: alpgpu_zone_map_*, alpgpu_zones_minmax_*) ---------------------------------------
     def _check_zones(self, zones, dtype, n_vectors):

@@ -83,6 +83,16 @@ int launch_group_sum(hipStream_t stream, const alpgpu_column* val, const alpgpu_
 int launch_group_totals(hipStream_t stream, const double* d_sums, const uint32_t* d_counts, uint64_t n, uint32_t n_groups, double* d_total_sums, uint64_t* d_total_counts,
                         void* d_scratch);
 
+// minmax_kernels.hip: masked and grouped MIN / MAX; value_bytes 8 or 4, d_zones records {min, max} of that type.  launch_minmax_masked:
+// d_zones[v] = the record of the vector's values whose bit is set, d_counts[v] (nullable) = its set bits (col->n_vectors > 0);
+// launch_group_minmax: the arguments of launch_group_sum, d_zones[g * n_vectors + v] = the record of val_r over the vector's set bits whose key_r
+// lies in [lo[g], hi[g]], d_counts (nullable) their number; launch_group_minmax_totals: d_minmax[2 g], d_minmax[2 g + 1] = the reduction of row g
+// of d_zones [n_groups][n] (n >= 0; no scratch)
+int launch_minmax_masked(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, void* d_zones, uint32_t* d_counts, int value_bytes);
+int launch_group_minmax(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const double* lo, const double* hi, uint32_t n_groups,
+                        void* d_zones, uint32_t* d_counts, int value_bytes);
+int launch_group_minmax_totals(hipStream_t stream, const void* d_zones, uint64_t n, uint32_t n_groups, void* d_minmax, int value_bytes);
+
 // zone maps (include/alpgpu.h).  decode_kernels.hip / decode_f32_kernels.hip: d_zones[v] = {min, max} of vector v, decoded in registers by the
 // one-wavefront sink kernels (col->n_vectors > 0)
 int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones);

@@ -1,5 +1,6 @@
 // wave_minmax.hpp — wavefront-wide minimum and maximum in registers (gfx950): the reduction the encoders use for a vector's value range and the
-// zone-map kernels (decode_kernels.hip, decode_f32_kernels.hip, zone_kernels.hip) for a vector's record.
+// zone-map kernels (decode_kernels.hip, decode_f32_kernels.hip, zone_kernels.hip) and the masked MIN / MAX (minmax_device.hpp) for a vector's
+// record; and what the reductions of records share (zone_kernels.hip, minmax_kernels.hip): the atomics that join a result in the records' order.
 #pragma once
 #include "alp_device.hpp"
 
@@ -97,6 +98,38 @@ __device__ __forceinline__ void minmax_take(float& mn, float& mx, float x) {
 	const float q = fmax_num_f32(x, x);
 	mn            = fmin_num_f32(mn, q);
 	mx            = fmax_num_f32(mx, q);
+}
+
+// ---- either precision -------------------------------------------------------------------------------------------------------------------------
+template <class T>
+__device__ __forceinline__ void wave_minmax(T& mn, T& mx) {
+	if constexpr (sizeof(T) == 8) { wave_minmax_f64(mn, mx); } else { wave_minmax_f32(mn, mx); }
+}
+template <class T>
+__device__ __forceinline__ T pos_inf() {
+	if constexpr (sizeof(T) == 8) { return __builtin_inf(); } else { return __builtin_inff(); }
+}
+
+// *addr = min(*addr, x) / max(*addr, x) in the records' order; x is not a NaN, *addr holds value bits
+template <class T>
+__device__ __forceinline__ void atomic_min_value(T* addr, T x) {
+	if constexpr (sizeof(T) == 8) {
+		const long long b = __double_as_longlong(x);
+		if (b >= 0) { atomicMin(reinterpret_cast<long long*>(addr), b); } else { atomicMax(reinterpret_cast<unsigned long long*>(addr), static_cast<unsigned long long>(b)); }
+	} else {
+		const int b = static_cast<int>(__float_as_uint(x));
+		if (b >= 0) { atomicMin(reinterpret_cast<int*>(addr), b); } else { atomicMax(reinterpret_cast<unsigned int*>(addr), static_cast<unsigned int>(b)); }
+	}
+}
+template <class T>
+__device__ __forceinline__ void atomic_max_value(T* addr, T x) {
+	if constexpr (sizeof(T) == 8) {
+		const long long b = __double_as_longlong(x);
+		if (b >= 0) { atomicMax(reinterpret_cast<long long*>(addr), b); } else { atomicMin(reinterpret_cast<unsigned long long*>(addr), static_cast<unsigned long long>(b)); }
+	} else {
+		const int b = static_cast<int>(__float_as_uint(x));
+		if (b >= 0) { atomicMax(reinterpret_cast<int*>(addr), b); } else { atomicMin(reinterpret_cast<unsigned int*>(addr), static_cast<unsigned int>(b)); }
+	}
 }
 
 } // namespace alpgpu

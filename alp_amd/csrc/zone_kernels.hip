@@ -26,15 +26,6 @@ constexpr uint64_t kZoneMaxGrid = 1ull << 30;
 constexpr unsigned kReduceGrid  = 2048; // workgroups of the reduction at most: two atomics each
 
 template <class T>
-__device__ __forceinline__ void wave_minmax(T& mn, T& mx) {
-	if constexpr (sizeof(T) == 8) { wave_minmax_f64(mn, mx); } else { wave_minmax_f32(mn, mx); }
-}
-template <class T>
-__device__ __forceinline__ T pos_inf() {
-	if constexpr (sizeof(T) == 8) { return __builtin_inf(); } else { return __builtin_inff(); }
-}
-
-template <class T>
 __global__ __launch_bounds__(kZoneThreads) void k_zone_of_values(const T* __restrict__ in, uint64_t n_vectors, uint64_t wg_off, T* __restrict__ zones) {
 	typedef T V16 __attribute__((ext_vector_type(16 / sizeof(T))));
 	constexpr int kLoads = 1024 * sizeof(T) / (64 * 16);
@@ -63,28 +54,6 @@ template <class T>
 __global__ void k_zones_reset(T* __restrict__ d_minmax) {
 	d_minmax[0] = pos_inf<T>();
 	d_minmax[1] = -pos_inf<T>();
-}
-
-// *addr = min(*addr, x) / max(*addr, x) in the records' order; x is not a NaN, *addr holds value bits
-template <class T>
-__device__ __forceinline__ void atomic_min_value(T* addr, T x) {
-	if constexpr (sizeof(T) == 8) {
-		const long long b = __double_as_longlong(x);
-		if (b >= 0) { atomicMin(reinterpret_cast<long long*>(addr), b); } else { atomicMax(reinterpret_cast<unsigned long long*>(addr), static_cast<unsigned long long>(b)); }
-	} else {
-		const int b = static_cast<int>(__float_as_uint(x));
-		if (b >= 0) { atomicMin(reinterpret_cast<int*>(addr), b); } else { atomicMax(reinterpret_cast<unsigned int*>(addr), static_cast<unsigned int>(b)); }
-	}
-}
-template <class T>
-__device__ __forceinline__ void atomic_max_value(T* addr, T x) {
-	if constexpr (sizeof(T) == 8) {
-		const long long b = __double_as_longlong(x);
-		if (b >= 0) { atomicMax(reinterpret_cast<long long*>(addr), b); } else { atomicMin(reinterpret_cast<unsigned long long*>(addr), static_cast<unsigned long long>(b)); }
-	} else {
-		const int b = static_cast<int>(__float_as_uint(x));
-		if (b >= 0) { atomicMax(reinterpret_cast<int*>(addr), b); } else { atomicMin(reinterpret_cast<unsigned int*>(addr), static_cast<unsigned int>(b)); }
-	}
 }
 
 // d_minmax was reset by k_zones_reset in front of this launch

@@ -647,6 +647,72 @@ struct column {
 		for (uint32_t g = 0; g < n_groups; ++g) { out[g] = masked_sum {totals[g], tcounts[g]}; }
 		return out;
 	}
+	// Masked and grouped MIN / MAX (include/alpgpu.h, "masked and grouped MIN / MAX").  minmax_masked: one record per vector over the values whose
+	// bit is set (alpgpu_decode_minmax_masked_*), with the rules of zone_map — NaNs ignored, -0.0 below +0.0, {+inf, -inf} when nothing selected is
+	// a number — and, optionally, each vector's number of set bits.  The records are narrower than the vectors' intervals: not for select_range.
+	static std::vector<zone> minmax_masked(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask, std::vector<uint32_t>* counts = nullptr) {
+		uploaded_column up(blob, size, "alp::gpu::column::minmax_masked");
+		const uint64_t  nv = up.col.n_vectors;
+		if (mask.size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::minmax_masked: the mask must hold 16 words per vector"); }
+		std::vector<zone> out(nv);
+		if (counts) { counts->assign(nv, 0); }
+		if (nv == 0) { return out; }
+		uint64_t* d_mask   = static_cast<uint64_t*>(up.get(mask.size() * sizeof(uint64_t)));
+		zone*     d_zones  = static_cast<zone*>(up.get(nv * sizeof(zone)));
+		uint32_t* d_counts = counts ? static_cast<uint32_t*>(up.get(nv * sizeof(uint32_t))) : nullptr;
+		check(alpgpu_memcpy_h2d(context(), d_mask, mask.data(), mask.size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d");
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_decode_minmax_masked_f64(context(), &up.col, d_mask, d_zones, d_counts), "alpgpu_decode_minmax_masked_f64");
+		} else {
+			check(alpgpu_decode_minmax_masked_f32(context(), &up.col, d_mask, d_zones, d_counts), "alpgpu_decode_minmax_masked_f32");
+		}
+		check(alpgpu_memcpy_d2h(context(), out.data(), d_zones, nv * sizeof(zone)), "alpgpu_memcpy_d2h");
+		if (counts) { check(alpgpu_memcpy_d2h(context(), counts->data(), d_counts, nv * sizeof(uint32_t)), "alpgpu_memcpy_d2h"); }
+		return out;
+	}
+	// group_minmax_masked: group_sum_masked's arguments; zones and counts (optional) come back as [n_groups][n_vectors], row g bit for bit what
+	// minmax_masked gives under the mask ANDed with select_mask(key, lo[g], hi[g]) (alpgpu_decode_group_minmax_*).  Returns n_vectors.
+	static uint64_t group_minmax_masked(const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>& mask, const PT* lo, const PT* hi,
+	                                    uint32_t n_groups, std::vector<zone>& zones, std::vector<uint32_t>* counts = nullptr) {
+		if (n_groups == 0 || n_groups > ALPGPU_GROUP_MAX || !lo || !hi) { throw std::runtime_error("alp::gpu::column::group_minmax_masked: 1 .. ALPGPU_GROUP_MAX groups with their bounds"); }
+		uploaded_column val(blob_val, size_val, "alp::gpu::column::group_minmax_masked"), key(blob_key, size_key, "alp::gpu::column::group_minmax_masked");
+		const uint64_t  nv = val.col.n_vectors;
+		if (key.col.n_vectors != nv) { throw std::runtime_error("alp::gpu::column::group_minmax_masked: the columns differ in length"); }
+		if (mask.size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::group_minmax_masked: the mask must hold 16 words per vector"); }
+		zones.assign(n_groups * nv, zone {});
+		if (counts) { counts->assign(n_groups * nv, 0); }
+		if (nv == 0) { return nv; }
+		uint64_t* d_mask   = static_cast<uint64_t*>(val.get(mask.size() * sizeof(uint64_t)));
+		zone*     d_zones  = static_cast<zone*>(val.get(zones.size() * sizeof(zone)));
+		uint32_t* d_counts = counts ? static_cast<uint32_t*>(val.get(zones.size() * sizeof(uint32_t))) : nullptr;
+		check(alpgpu_memcpy_h2d(context(), d_mask, mask.data(), mask.size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d");
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_decode_group_minmax_f64(context(), &val.col, &key.col, d_mask, lo, hi, n_groups, d_zones, d_counts), "alpgpu_decode_group_minmax_f64");
+		} else {
+			check(alpgpu_decode_group_minmax_f32(context(), &val.col, &key.col, d_mask, lo, hi, n_groups, d_zones, d_counts), "alpgpu_decode_group_minmax_f32");
+		}
+		check(alpgpu_memcpy_d2h(context(), zones.data(), d_zones, zones.size() * sizeof(zone)), "alpgpu_memcpy_d2h");
+		if (counts) { check(alpgpu_memcpy_d2h(context(), counts->data(), d_counts, counts->size() * sizeof(uint32_t)), "alpgpu_memcpy_d2h"); }
+		return nv;
+	}
+	// Every group's {min, max} from what group_minmax_masked returned (alpgpu_group_minmax_totals_*); {+inf, -inf} for n_vectors == 0
+	static std::vector<zone> group_minmax_totals(const std::vector<zone>& zones, uint64_t n_vectors, uint32_t n_groups) {
+		if (n_groups == 0 || n_groups > ALPGPU_GROUP_MAX || zones.size() != n_groups * n_vectors) {
+			throw std::runtime_error("alp::gpu::column::group_minmax_totals: zones must be [n_groups][n_vectors], 1 .. ALPGPU_GROUP_MAX groups");
+		}
+		device_buffers buf;
+		zone*          d_zones  = static_cast<zone*>(buf.get(zones.size() * sizeof(zone)));
+		zone*          d_totals = static_cast<zone*>(buf.get(n_groups * sizeof(zone)));
+		if (!zones.empty()) { check(alpgpu_memcpy_h2d(context(), d_zones, zones.data(), zones.size() * sizeof(zone)), "alpgpu_memcpy_h2d"); }
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_group_minmax_totals_f64(context(), d_zones, n_vectors, n_groups, reinterpret_cast<double*>(d_totals)), "alpgpu_group_minmax_totals_f64");
+		} else {
+			check(alpgpu_group_minmax_totals_f32(context(), d_zones, n_vectors, n_groups, reinterpret_cast<float*>(d_totals)), "alpgpu_group_minmax_totals_f32");
+		}
+		std::vector<zone> out(n_groups);
+		check(alpgpu_memcpy_d2h(context(), out.data(), d_totals, n_groups * sizeof(zone)), "alpgpu_memcpy_d2h");
+		return out;
+	}
 	// The column's values at the set bits of the mask, ascending by index (alpgpu_decode_masked_*): each with the bits decompress gives it.  The
 	// second form also fills `indices` with their value indices (what mask_indices returns).
 	static std::vector<PT> take_masked(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask) { return take_masked_with(blob, size, mask, nullptr); }

@@ -685,6 +685,55 @@ size_t alpgpu_group_totals_scratch_bytes(uint64_t n_vectors, uint32_t n_groups);
 int    alpgpu_group_totals(alpgpu_ctx* ctx, const double* d_sums, const uint32_t* d_counts, uint64_t n_vectors, uint32_t n_groups, double* d_total_sums,
                            uint64_t* d_total_counts, void* d_scratch);
 
+/* ---- masked and grouped MIN / MAX --------------------------------------------------------------------------------------------------------
+ * SELECT MIN(x), MAX(x) ... WHERE ..., and SELECT key, MIN(x), MAX(x), COUNT(*) ... WHERE ... GROUP BY key (TPC-H Q2, Q15): the two aggregates
+ * the sections above leave out, computed like their sums — each vector decoded in the registers of one wavefront, no value reaching HBM.
+ *   WHERE ...                           select_mask / compare_mask ... into the bitmap (all ones for no WHERE clause);
+ *   MIN(x), MAX(x)                      decode_minmax_masked(x, bitmap); zones_minmax.
+ *   MIN(x), MAX(x) GROUP BY key         decode_group_minmax(x, key, bitmap, lo, hi); group_minmax_totals.
+ * The records are alpgpu_zone_f64 / alpgpu_zone_f32 of the zone-map section, with its alignment (16 / 8 bytes; a misaligned array returns
+ * ALPGPU_ERR_INVALID) and its rules, bit for bit, over the SELECTED values: NaNs, quiet and signalling, are ignored; +-inf are ordinary values;
+ * -0.0 < +0.0; {+inf, -inf} when no selected value is a number.  A float column gives float records: nothing widens.  Minimum and maximum are
+ * exactly associative and commutative, so every result here is a function of the inputs alone and there is no order to document.
+ * These records are NOT a zone map for alpgpu_select_range_zoned_*: they are narrower than the vector's true interval.
+ *   alpgpu_decode_minmax_masked_*   d_zones[v] = {min, max} over the decoded values of vector v whose bit is set in d_mask (col->n_vectors * 16
+ *                                   words, 8-byte aligned; every bit honoured as found; read and never written).  d_counts[v] (may be NULL) = the
+ *                                   number of set bits of the vector, selected NaNs included, exactly as alpgpu_decode_sum_masked_* counts them.  A
+ *                                   vector whose 16 words are zero gets {+inf, -inf} and 0, and the column is not read for it.  Under a full bitmap
+ *                                   the records are bit for bit those of alpgpu_zone_map_*.  The column's MIN / MAX is alpgpu_zones_minmax_* over
+ *                                   the records.
+ *                                   ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx or col, a d_mask that is not 8-byte aligned,
+ *                                   misaligned records and, with n_vectors > 0, a NULL d_mask or d_zones, an implausible n_vectors or a column
+ *                                   without descriptors.  col->n_vectors == 0 is ALPGPU_OK and launches nothing.
+ *   alpgpu_decode_group_minmax_*    The arguments of alpgpu_decode_group_sum_* with the same meaning: val and key of the entry point's type with
+ *                                   equal n_vectors (val == key allowed); lo, hi HOST arrays of n_groups bounds, 1 <= n_groups <= ALPGPU_GROUP_MAX,
+ *                                   read before the call returns and passed as kernel arguments; group g is lo[g] <= k <= hi[g] with the predicate
+ *                                   of alpgpu_select_mask_* (a NaN never qualifies, as a key or as a bound; -0.0 == 0.0; lo > hi selects nothing);
+ *                                   groups may overlap, touch or be empty.  Output, group-major: d_zones[g * n_vectors + v] and
+ *                                   d_counts[g * n_vectors + v] (d_counts may be NULL); every (g, v) with g < n_groups is written and nothing else.
+ *                                   The contract, bit for bit: let M_g be the caller's bitmap ANDed with alpgpu_select_mask_*(key, first = 0,
+ *                                   n = n_vectors * 1024, lo[g], hi[g]); row g of d_zones is what alpgpu_decode_minmax_masked_*(val, M_g) writes, and
+ *                                   row g of d_counts what alpgpu_decode_group_sum_* writes.  A vector whose 16 bitmap words are zero gets
+ *                                   {+inf, -inf} and 0 in every row, and neither column is read for it.
+ *                                   ALPGPU_ERR_INVALID before anything is enqueued: as alpgpu_decode_group_sum_*, and misaligned records.
+ *                                   n_vectors == 0 is ALPGPU_OK and launches nothing.
+ *   alpgpu_group_minmax_totals_*    d_zones: [n_groups][n_vectors] as written above.  d_minmax[2 g], d_minmax[2 g + 1] (device memory, 2 * n_groups
+ *                                   values) are what alpgpu_zones_minmax_*(d_zones + g * n_vectors, n_vectors) writes: one call serves all groups.
+ *                                   n_vectors == 0 writes {+inf, -inf} for every group (that write is still enqueued; d_zones may be NULL).  No
+ *                                   scratch.  A NULL ctx or d_minmax, n_groups out of range, misaligned pointers and, with n_vectors > 0, a NULL
+ *                                   d_zones return ALPGPU_ERR_INVALID before anything is enqueued.
+ * All run on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation; none of what the context
+ *   remembers about columns is read or written; safe inside a stream capture.  (tests/minmax_replica.py holds the host replica.)
+ * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector), for every column. */
+int alpgpu_decode_minmax_masked_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, alpgpu_zone_f64* d_zones, uint32_t* d_counts);
+int alpgpu_decode_minmax_masked_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, alpgpu_zone_f32* d_zones, uint32_t* d_counts);
+int alpgpu_decode_group_minmax_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const double* lo, const double* hi,
+                                   uint32_t n_groups, alpgpu_zone_f64* d_zones, uint32_t* d_counts);
+int alpgpu_decode_group_minmax_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const float* lo, const float* hi,
+                                   uint32_t n_groups, alpgpu_zone_f32* d_zones, uint32_t* d_counts);
+int alpgpu_group_minmax_totals_f64(alpgpu_ctx* ctx, const alpgpu_zone_f64* d_zones, uint64_t n_vectors, uint32_t n_groups, double* d_minmax);
+int alpgpu_group_minmax_totals_f32(alpgpu_ctx* ctx, const alpgpu_zone_f32* d_zones, uint64_t n_vectors, uint32_t n_groups, float* d_minmax);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
