@@ -141,6 +141,9 @@ for _t in ("f64", "f32"):
     _sig("alpgpu_decode_minmax_masked_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp)
     _sig("alpgpu_decode_group_minmax_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp)
     _sig("alpgpu_group_minmax_totals_" + _t, _int, _vp, _vp, _u64, C.c_uint32, _vp)
+for _t in ("f64", "f32"):
+    _sig("alpgpu_select_in_mask_" + _t, _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp, _u64, _int, _vp, _int, _vp)
+_sig("alpgpu_in_list_lds_max", C.c_size_t, _int)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -980,6 +983,56 @@ class Context:
                 raise ValueError("out must be a [n_groups, 2] tensor of the records' type")
         self._call("group_minmax_totals", self._sfx(zones), _vp(zones.data_ptr()) if n_vectors else None, n_vectors, n_groups, _vp(out.data_ptr()))
         return out
+
+    # ---- set membership (include/alpgpu.h: alpgpu_select_in_mask_*, alpgpu_in_list_lds_max) ---------------------------------
+    @staticmethod
+    def in_list_lds_max(dtype) -> int:
+        """the longest list select_in_mask holds whole in LDS: dtype is "f64" / "f32", a torch or numpy float64 / float32 type; 0 for anything else"""
+        name = str(dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
+        return int(lib.alpgpu_in_list_lds_max({"f64": 8, "float64": 8, "f32": 4, "float32": 4}.get(name, 0)))
+
+    def select_in_mask(self, col: "DeviceColumn", values, first: int = 0, n: int = None, negate: bool = False, zones=None, op: str = "set", mask=None, sorted: bool = False):
+        """the qualify mask of `x IN (values)` — negate: `x NOT IN (values)`, which a NaN satisfies — over the value indices [first, first + n) as a
+        selection bitmap, set or combined as select_mask does it.  A value is a member iff some element == it: -0.0 matches +0.0, a NaN never
+        matches.  values: a device tensor, host tensor, sequence or numpy array of the column's type; it is brought into list form by torch.sort on
+        the device (nothing dropped or deduplicated: NaNs sort last and are inert); sorted=True skips that for a caller who guarantees the
+        order.  zones (zone_map(col)): the same bytes, vectors whose record holds no element are not decoded.  Returns the mask.  Nothing is
+        synchronised; with a mask and a sorted device tensor given nothing is allocated either (alpgpu_select_in_mask_f64 / _f32)."""
+        import torch
+        if op not in self._MASK_OPS:
+            raise ValueError('op must be "set", "and" or "or"')
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        dev = f"cuda:{self.device}"
+        if isinstance(values, np.ndarray):
+            if values.dtype != (np.float64 if col.dtype == "f64" else np.float32):
+                raise ValueError("values must be of the column's type (%s)" % col.dtype)
+            values = torch.from_numpy(np.ascontiguousarray(values))
+        elif not isinstance(values, torch.Tensor):
+            values = torch.tensor(list(values), dtype=tdt)
+        if values.dtype != tdt:
+            raise ValueError("values must be of the column's type (%s)" % col.dtype)
+        if values.dim() != 1:
+            raise ValueError("values must be one-dimensional")
+        if values.is_cuda and values.device.index != self.device:
+            raise ValueError("values must be on the host or on cuda:%d" % self.device)
+        if zones is not None:
+            self._check_zones(zones, tdt, col.n_vectors)
+        if mask is None:
+            if op != "set":
+                raise ValueError('op "%s" combines into a mask: pass one' % op)
+        else:
+            self._check_mask(mask, col.n_vectors)
+        first = int(first)
+        n = col.n_vectors * VECTOR_SIZE - first if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        if mask is None:
+            mask = torch.empty(16 * col.n_vectors, dtype=torch.int64, device=dev)
+        lst = values if values.is_cuda else values.to(dev)
+        lst = lst.contiguous() if sorted else torch.sort(lst).values
+        self._call("select_in_mask", col.dtype, C.byref(col.c), first, n, _vp(lst.data_ptr()) if lst.numel() else None, lst.numel(), 1 if negate else 0,
+                   _vp(zones.data_ptr()) if zones is not None else None, self._MASK_OPS[op], _vp(mask.data_ptr()))
+        return mask
 
     # ---- zone maps (include/alpgpu.h: alpgpu_zone_map_*, alpgpu_zones_minmax_*) ---------------------------------------
     def _check_zones(self, zones, dtype, n_vectors):

@@ -1,0 +1,272 @@
+// in_list_kernels.hip — set membership (include/alpgpu.h, "set membership": alpgpu_select_in_mask_*): `x IN (list)` on a compressed column into a
+// selection bitmap.
+//
+//   k_in_list<VB, GLOBAL>   persistent workgroups of kInWaves wavefronts.  The workgroup stages the sorted list (or, GLOBAL, every stride-th element
+//                           of it: the pivots) into 32 KiB of static LDS, passes ONE workgroup barrier and only then walks vectors
+//                           v = wave_id, wave_id + n_waves, ...: every early-out of the skip rules sits behind that barrier.  A vector is decoded in
+//                           registers by PairVec / PairBatch (pair_device.hpp: the steps, batches, exception mask and clamps of k_pair and k_group);
+//                           the kPairBatch values of a batch search together, so that their LDS (and global) probes overlap.  The ballot of step m
+//                           is kept in lane m, combined with the prior words and stored as one run of 128 bytes, as the MASK arm of k_select does.
+//   the search              a branch-free lower bound, every step wave-uniform in its length: ceil(log2(n + 1)) probes of the LDS words
+//                           [i0, i1), then, GLOBAL, ceil(log2(stride)) probes of the list itself on the slice between two pivots (stride - 1
+//                           elements at most; elements behind the slice's end count as "not less"), then one ==.  Every probe index is clamped to
+//                           the words staged and to the list: an unsorted list gives unspecified bits and reads nothing else.
+//   zones                   a vector's record {min, max} is searched twice by the whole wavefront (the same routine, every lane the same probes):
+//                           j0 = the first element >= min, j1 = the first element > max.  j1 <= j0: no element lies in the record and the vector is
+//                           settled from its 128 bytes of bitmap; else the per-value search runs over [j0, j1) only.
+//
+// HBM traffic per vector: the bitmap's 128 bytes and, unless they (or the zone record) settle the vector, its descriptor, packed words and exception
+// record; the list once per workgroup.  One launch of at most 4 workgroups per CU (what 33 KiB of LDS each allow), whatever the column's length.
+//
+// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; launch bounds 512 = 2 wavefronts per SIMD and workgroup):
+//   k_in_list<8, false>   83 VGPRs, 33792 B LDS, 5 waves per SIMD, no scratch
+//   k_in_list<8, true>    79 VGPRs, 33792 B LDS, 6 waves per SIMD, no scratch
+//   k_in_list<4, false>   75 VGPRs, 33792 B LDS, 6 waves per SIMD, no scratch
+//   k_in_list<4, true>    71 VGPRs, 33792 B LDS, 7 waves per SIMD, no scratch
+#include "pair_device.hpp"
+
+namespace alpgpu {
+
+constexpr int      kInWaves    = 8; // wavefronts per workgroup: they share the staged list and nothing else
+constexpr int      kInThreads  = 64 * kInWaves;
+constexpr uint32_t kInLdsBytes = 32768; // of list per workgroup: 4096 doubles or 8192 floats; with the exception masks 33 KiB, four workgroups per CU
+constexpr int      kInWgPerCu  = 4;
+
+struct InArgs {
+	uint64_t    v0, n_range; // the launch covers vectors v0 + [0, n_range)
+	uint64_t    first, end;  // the selected index range
+	uint64_t*   mask;        // combined and stored
+	const void* list;        // n_list sorted elements of the column's type
+	const void* zones;       // nullable: one record {min, max} per vector of the COLUMN
+	uint32_t    n_list;      // <= 2^31 - 1
+	uint32_t    stride;      // LDS word i = list[i * stride]; 1 unless GLOBAL
+	uint32_t    n_piv;       // LDS words staged: ceil(n_list / stride) <= kInLdsBytes / VB
+	int         op;          // kMaskSet / kMaskAnd / kMaskOr
+	int         negate;
+};
+
+// NB searches side by side over the list's elements [j0, j1) (wave-uniform, j0 <= j1 <= n_list, n_list > 0): out[i] = j0 + the number of elements e
+// of them with e < x[i] (bit i of `upper` set: e <= x[i]) if the list is sorted, in [j0, j1] whatever it holds.  A NaN element is never less, so
+// that NaNs sorted last end the list; a NaN x gives j0.
+template <int VB, bool GLOBAL, uint32_t NB>
+__device__ __forceinline__ void in_list_search(const typename PairVec<VB>::T* s_list, const typename PairVec<VB>::T* list, const InArgs& g, uint32_t j0, uint32_t j1,
+                                               const typename PairVec<VB>::T (&x)[NB], uint32_t upper, uint32_t (&out)[NB]) {
+	typedef typename PairVec<VB>::T T;
+	const uint32_t stride = GLOBAL ? g.stride : 1u;
+	const uint32_t i0 = GLOBAL ? (j0 + stride - 1u) / stride : j0, i1 = GLOBAL ? (j1 + stride - 1u) / stride : j1; // the LDS words whose elements lie in [j0, j1)
+	const uint32_t last_word = g.n_piv - 1u, last_elem = g.n_list - 1u;
+	uint32_t       base[NB];
+#pragma unroll
+	for (uint32_t i = 0; i < NB; ++i) { base[i] = i0; }
+	uint32_t n = i1 - i0; // wave-uniform: every lane and every one of the NB searches takes the same steps
+	while (n > 1u) {
+		const uint32_t half = n >> 1;
+		T              e[NB];
+#pragma unroll
+		for (uint32_t i = 0; i < NB; ++i) {
+			const uint32_t at = base[i] + half - 1u;
+			e[i]              = s_list[at < last_word ? at : last_word];
+		}
+#pragma unroll
+		for (uint32_t i = 0; i < NB; ++i) { base[i] += (((upper >> i) & 1u) ? e[i] <= x[i] : e[i] < x[i]) ? half : 0u; }
+		n -= half;
+	}
+	if (n == 1u) {
+		T e[NB];
+#pragma unroll
+		for (uint32_t i = 0; i < NB; ++i) { e[i] = s_list[base[i] < last_word ? base[i] : last_word]; }
+#pragma unroll
+		for (uint32_t i = 0; i < NB; ++i) { base[i] += (((upper >> i) & 1u) ? e[i] <= x[i] : e[i] < x[i]) ? 1u : 0u; }
+	}
+	if constexpr (!GLOBAL) {
+#pragma unroll
+		for (uint32_t i = 0; i < NB; ++i) { out[i] = base[i]; }
+	} else {
+		// base = p in [i0, i1]: word p - 1 is less (or p == i0) and word p is not (or p == i1), so the bound lies in the list's slice
+		// [lo, hi], hi - lo <= stride - 1.  The same steps over a window of stride - 1 elements from lo on, those at or behind hi never less.
+		uint32_t lo[NB], hi[NB];
+#pragma unroll
+		for (uint32_t i = 0; i < NB; ++i) {
+			const uint32_t p = base[i];
+			lo[i]            = p == i0 ? j0 : (p - 1u) * stride + 1u;
+			hi[i]            = p * stride < j1 ? p * stride : j1;
+		}
+		n = stride - 1u;
+		while (n > 1u) {
+			const uint32_t half = n >> 1;
+			T              e[NB];
+#pragma unroll
+			for (uint32_t i = 0; i < NB; ++i) {
+				const uint32_t at = lo[i] + half - 1u;
+				e[i]              = list[at < last_elem ? at : last_elem];
+			}
+#pragma unroll
+			for (uint32_t i = 0; i < NB; ++i) {
+				const uint32_t at = lo[i] + half - 1u;
+				lo[i] += (at < hi[i] && (((upper >> i) & 1u) ? e[i] <= x[i] : e[i] < x[i])) ? half : 0u;
+			}
+			n -= half;
+		}
+		if (n == 1u) {
+			T e[NB];
+#pragma unroll
+			for (uint32_t i = 0; i < NB; ++i) { e[i] = list[lo[i] < last_elem ? lo[i] : last_elem]; }
+#pragma unroll
+			for (uint32_t i = 0; i < NB; ++i) { lo[i] += (lo[i] < hi[i] && (((upper >> i) & 1u) ? e[i] <= x[i] : e[i] < x[i])) ? 1u : 0u; }
+		}
+#pragma unroll
+		for (uint32_t i = 0; i < NB; ++i) { out[i] = lo[i]; }
+	}
+}
+
+// word m (= lane, < 16) of a vector's bitmap with the bits of the positions [p_begin, p_end) set
+__device__ __forceinline__ uint64_t in_list_range_word(uint32_t lane, uint32_t p_begin, uint32_t p_end) {
+	const uint32_t w0 = 64u * lane;
+	const uint32_t lo = p_begin > w0 ? p_begin : w0, hi = p_end < w0 + 64u ? p_end : w0 + 64u;
+	if (hi <= lo) { return 0ull; }
+	const uint64_t run = hi - lo == 64u ? ~0ull : (1ull << (hi - lo)) - 1ull;
+	return run << (lo - w0);
+}
+
+template <int VB, bool GLOBAL>
+__global__ __launch_bounds__(kInThreads) void k_in_list(const PairColumn c, const InArgs g) {
+	typedef typename PairVec<VB>::T T;
+	__shared__ T        s_list[kInLdsBytes / VB];
+	__shared__ uint64_t s_exc[kInWaves][16]; // per wavefront: bit p = value p is an exception
+
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const uint32_t lane = threadIdx.x & 63u;
+	const T*       list = static_cast<const T*>(g.list);
+
+	// 0. the list (GLOBAL: its pivots) into LDS, once per workgroup; the one workgroup barrier of the kernel
+	for (uint32_t i = threadIdx.x; i < g.n_piv; i += kInThreads) {
+		const uint64_t at = static_cast<uint64_t>(i) * (GLOBAL ? g.stride : 1u);
+		s_list[i]         = list[at < g.n_list ? at : g.n_list - 1u]; // (n_piv > 0 only with n_list > 0)
+	}
+	__syncthreads();
+
+	const uint64_t n_waves = static_cast<uint64_t>(gridDim.x) * kInWaves;
+	for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kInWaves + wave; k < g.n_range; k += n_waves) {
+		const uint64_t v  = g.v0 + k;
+		const uint64_t r0 = v << 10;
+		uint64_t*      mw = g.mask + 16ull * v;
+
+		// 1. the vector's 128 bytes of bitmap, lane m < 16 holding word m, and what they settle without the column (the rules of k_select's MASK arm)
+		uint64_t   prior   = 0;
+		const bool outside = r0 >= g.end || r0 + 1024u <= g.first; // no value of the vector is in the range: q is false throughout
+		if (g.op == kMaskSet) {
+			if (outside) {
+				if (lane < 16u) { mw[lane] = 0ull; }
+				continue;
+			}
+		} else {
+			const uint64_t neutral = g.op == kMaskAnd ? 0ull : ~0ull; // the word that q cannot change
+			prior                  = lane < 16u ? mw[lane] : neutral;
+			if (ballot64(prior != neutral) == 0ull) { continue; } // AND of all zeros, OR of all ones: these 128 bytes were all that was read
+			if (outside) {
+				if (g.op == kMaskAnd && lane < 16u) { mw[lane] = 0ull; }
+				continue;
+			}
+		}
+		const uint32_t p_begin = g.first > r0 ? static_cast<uint32_t>(g.first - r0) : 0u; // the vector's share of [first, end): wave-uniform
+		const uint32_t p_end   = g.end - r0 < 1024u ? static_cast<uint32_t>(g.end - r0) : 1024u;
+
+		// 2. the part [j0, j1) of the list that the vector's zone record admits: all of it without a record or with a NaN bound
+		uint32_t j0 = 0u, j1 = g.n_list;
+		if (g.zones != nullptr && g.n_list > 0u) {
+			const T* zone = static_cast<const T*>(g.zones) + 2 * v; // (wave-uniform)
+			const T  z[2] = {zone[0], zone[1]};
+			if (z[0] == z[0] && z[1] == z[1]) {
+				uint32_t j[2];
+				in_list_search<VB, GLOBAL, 2>(s_list, list, g, 0u, g.n_list, z, 2u, j); // the first element >= min, the first element > max
+				j0 = __builtin_amdgcn_readfirstlane(j[0]);
+				j1 = __builtin_amdgcn_readfirstlane(j[1]);
+			}
+		}
+		if (j1 <= j0) { // no element can be a member here (an empty list included): the descriptor is not read
+			const uint64_t q = g.negate ? in_list_range_word(lane, p_begin, p_end) : 0ull;
+			if (lane < 16u && !(g.op == kMaskOr && !g.negate)) { mw[lane] = g.op == kMaskAnd ? (prior & q) : g.op == kMaskOr ? (prior | q) : q; }
+			continue;
+		}
+
+		// 3. the descriptor, the dictionary and the exception mask
+		const PairVec<VB> V = pair_vec_load<VB>(c, v);
+		if (V.cnt > 0) {
+			if (lane < 16u) { s_exc[wave][lane] = 0ull; }
+			wave_lds_sync();
+			pair_mark_exceptions<VB>(V, s_exc[wave], lane);
+			wave_lds_sync();
+		}
+
+		uint32_t before_exc = 0; // exceptions of the steps done
+		uint64_t keep       = 0; // lane m < 16 keeps step m's ballot
+		for (uint32_t b = 0; b < 16u; b += kPairBatch) {
+			// 4. every load of kPairBatch steps is requested before the first is used
+			PairBatch<VB> R;
+			pair_request<VB>(V, s_exc[wave], b, lane, before_exc, R);
+			T x[kPairBatch];
+#pragma unroll
+			for (uint32_t i = 0; i < kPairBatch; ++i) { x[i] = pair_value<VB>(V, R, b, i, lane); }
+			// 5. the batch's lower bounds, searched together, then one == each: -0.0 == 0.0; a NaN (value or element) is never a member
+			uint32_t at[kPairBatch];
+			in_list_search<VB, GLOBAL, kPairBatch>(s_list, list, g, j0, j1, x, 0u, at);
+			T e[kPairBatch];
+#pragma unroll
+			for (uint32_t i = 0; i < kPairBatch; ++i) {
+				if constexpr (GLOBAL) {
+					e[i] = list[at[i] < g.n_list - 1u ? at[i] : g.n_list - 1u];
+				} else {
+					e[i] = s_list[at[i] < g.n_piv - 1u ? at[i] : g.n_piv - 1u];
+				}
+			}
+#pragma unroll
+			for (uint32_t i = 0; i < kPairBatch; ++i) {
+				const uint32_t m      = b + i;
+				const uint32_t p      = 64u * m + lane;
+				const bool     member = at[i] < j1 && e[i] == x[i];
+				const uint64_t sel    = ballot64(p - p_begin < p_end - p_begin && member != (g.negate != 0)); // p_begin <= p < p_end
+				keep                  = lane == m ? sel : keep;
+			}
+		}
+		if (lane < 16u) { mw[lane] = g.op == kMaskAnd ? (prior & keep) : g.op == kMaskOr ? (prior | keep) : keep; } // one run of 128 bytes
+	}
+}
+
+size_t in_list_lds_max(int value_bytes) { return value_bytes == 8 || value_bytes == 4 ? kInLdsBytes / static_cast<uint32_t>(value_bytes) : 0u; }
+
+template <int VB>
+static int launch_in_list_vb(hipStream_t stream, const PairColumn& c, const InArgs& args, unsigned grid) {
+	if (args.stride > 1u) {
+		hipLaunchKernelGGL((k_in_list<VB, true>), dim3(grid), dim3(kInThreads), 0, stream, c, args);
+	} else {
+		hipLaunchKernelGGL((k_in_list<VB, false>), dim3(grid), dim3(kInThreads), 0, stream, c, args);
+	}
+	return hipGetLastError() != hipSuccess ? ALPGPU_ERR_HIP : ALPGPU_OK;
+}
+
+// col->n_vectors > 0, n > 0, n_list <= 2^31 - 1; range, op and alignments checked by the caller
+int launch_select_in_mask(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const void* d_list, uint64_t n_list, int negate, const void* d_zones, int op,
+                          uint64_t* d_mask, int value_bytes, int n_cus) {
+	const uint64_t end     = first + n;
+	const uint64_t lds_max = in_list_lds_max(value_bytes);
+	InArgs         args {};
+	args.v0      = op == kMaskOr ? first >> 10 : 0ull; // SET and AND cover every vector, OR those of the range
+	args.n_range = op == kMaskOr ? ((end - 1) >> 10) - args.v0 + 1 : col->n_vectors;
+	args.first   = first;
+	args.end     = end;
+	args.mask    = d_mask;
+	args.list    = d_list;
+	args.zones   = d_zones;
+	args.n_list  = static_cast<uint32_t>(n_list);
+	args.stride  = n_list > lds_max ? static_cast<uint32_t>((n_list + lds_max - 1) / lds_max) : 1u;
+	args.n_piv   = static_cast<uint32_t>((n_list + args.stride - 1) / args.stride);
+	args.op      = op;
+	args.negate  = negate != 0;
+	const uint64_t   n_wg     = (args.n_range + kInWaves - 1) / kInWaves;
+	const uint64_t   resident = static_cast<uint64_t>(n_cus > 0 ? n_cus : 1) * kInWgPerCu; // the grid is sized to the device: a workgroup stages the list once
+	const PairColumn c {col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc};
+	const unsigned   grid = static_cast<unsigned>(n_wg < resident ? n_wg : resident);
+	return value_bytes == 8 ? launch_in_list_vb<8>(stream, c, args, grid) : launch_in_list_vb<4>(stream, c, args, grid);
+}
+
+} // namespace alpgpu

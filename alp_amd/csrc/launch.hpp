@@ -93,6 +93,14 @@ int launch_group_minmax(hipStream_t stream, const alpgpu_column* val, const alpg
                         void* d_zones, uint32_t* d_counts, int value_bytes);
 int launch_group_minmax_totals(hipStream_t stream, const void* d_zones, uint64_t n, uint32_t n_groups, void* d_minmax, int value_bytes);
 
+// in_list_kernels.hip: set membership.  launch_select_in_mask: bit(r) = / &= / |= q(r), q(r) = first <= r < first + n and ((some j < n_list has
+// d_list[j] == x_r) != negate) (n > 0; range, op, n_list <= 2^31 - 1 and the alignments checked by the caller; d_list sorted, device memory of the
+// column's type, NULL with n_list == 0; d_zones nullable: the column's zone map); one launch of persistent workgroups, at most four per CU.
+// in_list_lds_max: the longest list the kernel holds whole in LDS (value_bytes 8 or 4; else 0)
+size_t in_list_lds_max(int value_bytes);
+int launch_select_in_mask(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const void* d_list, uint64_t n_list, int negate, const void* d_zones, int op,
+                          uint64_t* d_mask, int value_bytes, int n_cus);
+
 // zone maps (include/alpgpu.h).  decode_kernels.hip / decode_f32_kernels.hip: d_zones[v] = {min, max} of vector v, decoded in registers by the
 // one-wavefront sink kernels (col->n_vectors > 0)
 int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones);

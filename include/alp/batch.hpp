@@ -15,6 +15,7 @@
 // functions in a loop (tests/cpp/batch_test.cpp checks that on the GPU).  ALP_RD rowgroups have ::encode_rd / ::decode_rd.
 #ifndef ALP_BATCH_HPP
 #define ALP_BATCH_HPP
+#include <algorithm>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -713,6 +714,17 @@ struct column {
 		check(alpgpu_memcpy_d2h(context(), out.data(), d_totals, n_groups * sizeof(zone)), "alpgpu_memcpy_d2h");
 		return out;
 	}
+	// Set membership (include/alpgpu.h, "set membership"): the mask of `x IN (values)` over [0, n_values) — with negate, of `x NOT IN (values)`, which a
+	// NaN value satisfies — fresh, or combined into a mask as select_mask combines.  member(x): some element == x (-0.0 == 0.0, a NaN never).  The
+	// values are sorted here, on the host (NaNs last, nothing dropped), as alpgpu_select_in_mask_* wants its list.
+	static std::vector<uint64_t> select_in_mask(const uint8_t* blob, size_t size, const std::vector<PT>& values, bool negate = false) {
+		std::vector<uint64_t> mask;
+		select_in_mask_with(blob, size, values, negate, mask_set, mask, true);
+		return mask;
+	}
+	static void select_in_mask(const uint8_t* blob, size_t size, const std::vector<PT>& values, bool negate, mask_op op, std::vector<uint64_t>& mask) {
+		select_in_mask_with(blob, size, values, negate, op, mask, false);
+	}
 	// The column's values at the set bits of the mask, ascending by index (alpgpu_decode_masked_*): each with the bits decompress gives it.  The
 	// second form also fills `indices` with their value indices (what mask_indices returns).
 	static std::vector<PT> take_masked(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask) { return take_masked_with(blob, size, mask, nullptr); }
@@ -769,6 +781,28 @@ private:
 			check(alpgpu_select_mask_f64(context(), &up.col, 0, up.n_values, lo, hi, op, d_mask), "alpgpu_select_mask_f64");
 		} else {
 			check(alpgpu_select_mask_f32(context(), &up.col, 0, up.n_values, lo, hi, op, d_mask), "alpgpu_select_mask_f32");
+		}
+		check(alpgpu_memcpy_d2h(context(), mask.data(), d_mask, words * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
+	}
+	static void select_in_mask_with(const uint8_t* blob, size_t size, const std::vector<PT>& values, bool negate, mask_op op, std::vector<uint64_t>& mask, bool fresh) {
+		uploaded_column up(blob, size, "alp::gpu::column::select_in_mask");
+		const uint64_t  words = 16 * up.col.n_vectors;
+		if (fresh) {
+			mask.assign(words, 0);
+		} else if (mask.size() != words) {
+			throw std::runtime_error("alp::gpu::column::select_in_mask: the mask must hold 16 words per vector");
+		}
+		if (words == 0) { return; }
+		std::vector<PT> list(values);
+		std::sort(list.begin(), list.end(), [](PT a, PT b) { return b != b ? a == a : a < b; }); // ascending by <, NaNs last
+		uint64_t* d_mask = static_cast<uint64_t*>(up.get(words * sizeof(uint64_t)));
+		PT*       d_list = list.empty() ? nullptr : static_cast<PT*>(up.get(list.size() * sizeof(PT)));
+		if (op != mask_set) { check(alpgpu_memcpy_h2d(context(), d_mask, mask.data(), words * sizeof(uint64_t)), "alpgpu_memcpy_h2d"); }
+		if (d_list) { check(alpgpu_memcpy_h2d(context(), d_list, list.data(), list.size() * sizeof(PT)), "alpgpu_memcpy_h2d"); }
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_select_in_mask_f64(context(), &up.col, 0, up.n_values, reinterpret_cast<const double*>(d_list), list.size(), negate ? 1 : 0, nullptr, op, d_mask), "alpgpu_select_in_mask_f64");
+		} else {
+			check(alpgpu_select_in_mask_f32(context(), &up.col, 0, up.n_values, reinterpret_cast<const float*>(d_list), list.size(), negate ? 1 : 0, nullptr, op, d_mask), "alpgpu_select_in_mask_f32");
 		}
 		check(alpgpu_memcpy_d2h(context(), mask.data(), d_mask, words * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
 	}

@@ -734,6 +734,52 @@ int alpgpu_decode_group_minmax_f32(alpgpu_ctx* ctx, const alpgpu_column* val, co
 int alpgpu_group_minmax_totals_f64(alpgpu_ctx* ctx, const alpgpu_zone_f64* d_zones, uint64_t n_vectors, uint32_t n_groups, double* d_minmax);
 int alpgpu_group_minmax_totals_f32(alpgpu_ctx* ctx, const alpgpu_zone_f32* d_zones, uint64_t n_vectors, uint32_t n_groups, float* d_minmax);
 
+/* ---- set membership -------------------------------------------------------------------------------------------------------------------------
+ * `x IN (list)` on a compressed column into a selection bitmap: the predicate against a SET of values that the range and the two-column predicates
+ * above cannot express (TPC-H Q12, Q16, Q19, Q22), and the probe side of a semi-join WHERE key IN (SELECT key FROM other WHERE ...), whose build
+ * side is what alpgpu_decode_masked_* of the other column hands back, sorted:
+ *   WHERE mode IN (3, 5)                        select_in_mask(mode, list, SET);   ... AND lo <= c <= hi: select_mask(c, AND);
+ *   WHERE key IN (SELECT key FROM o WHERE ...)  select_mask(o.c ...); decode_masked(o.key, bitmap); sort; select_in_mask(key, list, AND or SET).
+ * It belongs to the selection-bitmap family: the bitmap, op, first and n are those of alpgpu_select_mask_*.
+ *   alpgpu_select_in_mask_*     member(x) is true iff some j < n_list has d_list[j] == x under C's ==: -0.0 and +0.0 match each other, a NaN (value
+ *                               or list element) never matches, +-inf are ordinary.  q(r) = first <= r < first + n && (member(x_r) != (negate != 0)),
+ *                               so under negate a NaN value inside the range qualifies: it is not a member.  x_r is, bit for bit, what
+ *                               alpgpu_decode_* writes at r, exceptions patched in.  op, first and n have exactly the meaning, the host-side range
+ *                               check and the n == 0 behaviour of alpgpu_select_mask_*, and the skip rules are the same: a vector outside the
+ *                               range, one that is all-zero under AND and one that is all-ones under OR costs its 128 bytes of bitmap and nothing
+ *                               of the column.  SET and AND cover every vector, OR only those of the range.
+ *                               d_list: n_list elements of the column's type in DEVICE memory, aligned to the element, read when the kernel runs
+ *                               (a captured graph sees the list's contents at replay; n_list and the pointers are fixed at capture).  It must be
+ *                               sorted as numpy.sort sorts: ascending by <, -0.0 and +0.0 in either order, duplicates allowed, NaNs, if any, last.
+ *                               A list that is not sorted gives unspecified bits and never a read outside d_list[0 .. n_list) nor a write outside
+ *                               the bitmap: every probe index is clamped.  n_list == 0 is valid (d_list may be NULL): nothing is a member.
+ *                               n_list > 2^31 - 1 returns ALPGPU_ERR_INVALID.
+ *                               d_zones (may be NULL): the column's zone map, one record per vector (alpgpu_zone_map_*; 16 / 8 bytes aligned).  A
+ *                               vector whose [min, max] holds no list element — the first element >= min is > max, or there is none — is settled
+ *                               without reading its descriptor, packed words or exception record: as "nothing qualifies" without negate, as
+ *                               "every index of its share of [first, first + n) qualifies" with it (NaNs included: they qualify anyway).  For a
+ *                               vector that is decoded, the two searches that made the check give the part [j0, j1) of the list that can match,
+ *                               and the per-value search runs over that part only.  The contract is that of alpgpu_select_range_zoned_*: any zone
+ *                               map that contains the vectors' true intervals gives the bytes of the call without zones.  Records are read as
+ *                               found; a NaN bound means "decode the vector".
+ *                               Cost: one launch of persistent workgroups, sized to the device and not to the column.  A workgroup stages the
+ *                               list into LDS once; a list of up to alpgpu_in_list_lds_max(value bytes) elements sits there whole and a value
+ *                               costs ceil(log2(n_list + 1)) LDS probes and one ==; a longer one leaves every ceil(n_list / lds_max)-th element
+ *                               there and the last ceil(log2(stride)) probes of each search read the list itself (L2-resident up to a few MiB).
+ *                               ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx or col, a NULL d_mask (with n_vectors > 0) or one not
+ *                               8-byte aligned, a NULL d_list with n_list > 0, a misaligned d_list or d_zones, an unknown op, a range past the
+ *                               end.  col->n_vectors == 0 is ALPGPU_OK and launches nothing.
+ *   alpgpu_in_list_lds_max      the longest list the kernel holds whole in LDS, for value_bytes 8 (4096) and 4 (8192); 0 for anything else.
+ * The call runs on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no state kept, no atomics on
+ *   results; none of what the context remembers about columns (the decode plans) is read or written; safe inside a stream capture.  The result is a
+ *   function of the column, the list, the prior bitmap and the arguments alone.  (tests/in_list_replica.py holds the host replica.)
+ * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector). */
+int    alpgpu_select_in_mask_f64(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const double* d_list, uint64_t n_list, int negate,
+                                 const alpgpu_zone_f64* d_zones, int op, uint64_t* d_mask);
+int    alpgpu_select_in_mask_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const float* d_list, uint64_t n_list, int negate,
+                                 const alpgpu_zone_f32* d_zones, int op, uint64_t* d_mask);
+size_t alpgpu_in_list_lds_max(int value_bytes);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
