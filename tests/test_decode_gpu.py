@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import datagen
+import double_rows as dr
 import golden_io
 import layout
 
@@ -63,21 +64,16 @@ def test_falp_every_bit_width_class(ctx, oracle, bw):
     wrap-around base and exceptions at random positions; oracle falp+patch is the expectation."""
     rng = np.random.default_rng(1000 + bw)
     n = 37
-    enc = dict(scheme=np.full(n, 2, np.uint8), e=np.zeros(n, np.uint8), f=np.zeros(n, np.uint8), bw=np.full(n, bw, np.uint8),
-               lbw=np.zeros(n, np.uint8), base=rng.integers(-2**62, 2**62, n), exc_cnt=np.zeros(n, np.uint16),
-               packed=np.zeros((n, 1024), np.int64), packed_left=np.zeros((n, 1024), np.uint16),
-               exc=np.zeros((n, 1024), np.float64), pos=np.zeros((n, 1024), np.uint16), dict=np.zeros((1, 8), np.uint16),
-               dict_size=np.zeros(1, np.uint8), k=np.ones(1, np.uint8), combos=np.zeros((1, 10), np.int32))
+    enc = dr.empty_encoding(n)
+    enc["bw"][:] = bw
+    enc["base"][:] = rng.integers(-2**62, 2**62, n)
     for v in range(n):
         e = int(rng.integers(0, 19)); f = int(rng.integers(0, e + 1))
         enc["e"][v], enc["f"][v] = e, f
         words = rng.integers(-2**63, 2**63 - 1, 16 * bw, dtype=np.int64)
         enc["packed"][v, :16 * bw] = words
         c = int(rng.choice([0, 1, 5, 64, 129, 1024]))
-        pos = np.sort(rng.choice(1024, c, replace=False)).astype(np.uint16)
-        enc["exc_cnt"][v] = c
-        enc["pos"][v, :c] = pos
-        enc["exc"][v, :c] = rng.integers(0, 2**64, c, dtype=np.uint64).view(np.float64)  # arbitrary bit patterns incl. NaN payloads
+        dr.set_random_exceptions(enc, v, np.sort(rng.choice(1024, c, replace=False)), rng)  # arbitrary bit patterns incl. NaN payloads
     want = oracle.decode_column(enc)
     got = gpu_decode(ctx, enc)
     assert np.array_equal(got.view(np.uint64), want.view(np.uint64))
@@ -125,32 +121,7 @@ def test_residency_pad_does_not_change_results(ctx, oracle, pad_kib):
         ctx.set_option(capi.OPT_DECODE_VECTORS_PER_WG, 0)
 
 
-def _alp_vectors_with_exception_counts(rng, counts, bw, placement="random"):
-    """hand-built ALP vectors (random packed words) with the given exception counts; placement: random / front (all in the first quarter) /
-    edges (quarter boundaries first: 0, 255, 256, 511, 512, 767, 768, 1023)"""
-    n = len(counts)
-    enc = dict(scheme=np.full(n, 2, np.uint8), e=np.zeros(n, np.uint8), f=np.zeros(n, np.uint8), bw=np.full(n, bw, np.uint8),
-               lbw=np.zeros(n, np.uint8), base=rng.integers(-2**40, 2**40, n), exc_cnt=np.zeros(n, np.uint16),
-               packed=np.zeros((n, 1024), np.int64), packed_left=np.zeros((n, 1024), np.uint16),
-               exc=np.zeros((n, 1024), np.float64), pos=np.zeros((n, 1024), np.uint16), dict=np.zeros((1, 8), np.uint16),
-               dict_size=np.zeros(1, np.uint8), k=np.ones(1, np.uint8), combos=np.zeros((1, 10), np.int32))
-    edges = np.array([0, 255, 256, 511, 512, 767, 768, 1023])
-    for v, c in enumerate(counts):
-        e = int(rng.integers(0, 19)); f = int(rng.integers(0, e + 1))
-        enc["e"][v], enc["f"][v] = e, f
-        enc["packed"][v, :16 * bw] = rng.integers(-2**63, 2**63 - 1, 16 * bw, dtype=np.int64)
-        if placement == "front":
-            pos = np.sort(rng.choice(256, min(c, 256), replace=False))
-            c = len(pos)
-        elif placement == "edges":
-            rest = np.setdiff1d(np.arange(1024), edges)
-            pos = np.sort(np.concatenate([edges[:min(c, 8)], rng.choice(rest, max(c - 8, 0), replace=False)]))
-        else:
-            pos = np.sort(rng.choice(1024, c, replace=False))
-        enc["exc_cnt"][v] = c
-        enc["pos"][v, :c] = pos.astype(np.uint16)
-        enc["exc"][v, :c] = rng.integers(0, 2**64, c, dtype=np.uint64).view(np.float64)  # arbitrary bit patterns incl. NaN payloads
-    return enc
+_alp_vectors_with_exception_counts = dr.alp_vectors_with_exception_counts
 
 
 @pytest.mark.parametrize("placement", ["random", "front", "edges"])
@@ -223,8 +194,7 @@ def test_shortcut_arithmetic_at_every_width(ctx, oracle, exceptions):
     zero and at the shortcut's bound for the factor; random packed words; every launch shape; against the oracle's falp + patch"""
     from alp_amd import capi
     rng = np.random.default_rng(4242 + exceptions)
-    bound = [2251799813685247, 2251799813685247, 2251799813685247, 2251799813685247, 922337203685477, 92233720368547, 9223372036854, 922337203685, 92233720368,
-             9223372036, 922337203, 92233720, 9223372, 922337, 92233, 9223, 922, 92, 9]
+    bound = dr.SHORTCUT_BOUND
     rows = []
     for bw in range(0, 53):
         for f in (0, 2, 6, 11, 14, 18):
@@ -236,17 +206,12 @@ def test_shortcut_arithmetic_at_every_width(ctx, oracle, exceptions):
                     continue
                 rows.append((bw, f, min(18, f + int(rng.integers(0, 3))), base))
     n = len(rows)
-    enc = dict(scheme=np.full(n, 2, np.uint8), e=np.array([r[2] for r in rows], np.uint8), f=np.array([r[1] for r in rows], np.uint8),
-               bw=np.array([r[0] for r in rows], np.uint8), lbw=np.zeros(n, np.uint8), base=np.array([r[3] for r in rows], np.int64), exc_cnt=np.zeros(n, np.uint16),
-               packed=np.zeros((n, 1024), np.int64), packed_left=np.zeros((n, 1024), np.uint16), exc=np.zeros((n, 1024), np.float64), pos=np.zeros((n, 1024), np.uint16),
-               dict=np.zeros(((n + 99) // 100, 8), np.uint16), dict_size=np.zeros((n + 99) // 100, np.uint8), k=np.ones((n + 99) // 100, np.uint8),
-               combos=np.zeros(((n + 99) // 100, 10), np.int32))
+    enc = dr.empty_encoding(n)
+    enc["bw"][:], enc["f"][:], enc["e"][:], enc["base"][:] = [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows], [r[3] for r in rows]
     for v, (bw, f, e, base) in enumerate(rows):
         enc["packed"][v, :16 * bw] = rng.integers(-2**63, 2**63 - 1, 16 * bw, dtype=np.int64)
         c = exceptions if exceptions < 200 else int(rng.integers(129, 400))
-        enc["exc_cnt"][v] = c
-        enc["pos"][v, :c] = np.sort(rng.choice(1024, c, replace=False)).astype(np.uint16)
-        enc["exc"][v, :c] = rng.integers(0, 2**64, c, dtype=np.uint64).view(np.float64)
+        dr.set_random_exceptions(enc, v, np.sort(rng.choice(1024, c, replace=False)), rng)
     want = oracle.decode_column(enc)
     try:
         for vpw in (0, 1, 2):
