@@ -1,6 +1,7 @@
 """Hand-built double (64-bit) encodings in the checkers' fixed-stride layout (the dict oracle/pyoracle.py's Oracle.encode_column returns): the 64-bit sibling
 of float_rows.py.  Every packed width 0..64 under factors across the table, bases on the bounds of the store decode's conversion shortcut and at both ends of
-int64, exception records on both sides of every staging limit, and every ALP_RD cut 48..63 with a dictionary of its own.  numpy only: the CPU tests import this
+int64, exception records on both sides of every staging limit, and every ALP_RD cut 48..63 with a dictionary of its own; arm_rows adds the ALP vectors that sit on
+both sides of every per-vector decision of the store decode and the sinks, interleave an order in which narrow and wide vectors are neighbours.  numpy only: the CPU tests import this
 module, so nothing here may need the built library (tests/layout.py and alp_amd.capi do).  The pieces tests/test_decode_gpu.py builds its vectors from
 (empty_encoding, SHORTCUT_BOUND, set_random_exceptions, alp_vectors_with_exception_counts) live here too."""
 import numpy as np
@@ -187,6 +188,102 @@ def alp_rows(seed=15):
     for r in range(n // ROWGROUP):
         enc["combos"][r, :2] = enc["e"][r * ROWGROUP], enc["f"][r * ROWGROUP]
     return enc
+
+
+# ---- ALP rows for the per-vector arms of the store decode and the sinks ---------------------------------------------------------------------------------
+ARM_EXC_COUNTS = (0, 1, 48, 49, 102, 103, 128, 129, 255, 256, 257, 1024)  # both sides of: any exception at all, the sink's LDS stage (48), the pipelined consumer's
+#                                                                           1-KiB record (102), the store decode's stage of 128 and the 256-entry one, and everything
+ARM_EDGE_WIDTHS = (28, 29, 32, 33, 50, 51, 56, 57, 63, 64)               # the sink's stage (28 | 29), the 32-bit unpack (32 | 33), the shortcut (50 | 51), the ring (56 | 57), the ends
+
+
+def shortcut_factors(bw):
+    """the factors of FACTORS under which a vector of this width can take the shortcut: some base fits the width between the two bounds"""
+    return [f for f in FACTORS if bw <= SHORTCUT_MAX_BW and (1 << bw) - 1 <= 2 * SHORTCUT_BOUND[f]]
+
+
+def arm_rows(seed=17):
+    """ALP vectors that populate every (arithmetic arm, exception arm) pair of decode_kernels.hip and consume_kernels.hip, built like alp_rows (random words with both
+    extreme digits, exception values mostly finite with specials in every fourth row, ascending positions, random rows up to whole rowgroups):
+      * every width 0..50 on the SHORTCUT route with every count of ARM_EXC_COUNTS, under the factors that admit the width in turn, the base on the lower bound, on the
+        upper bound (base + mask == bound) and inside, in turn and out of step with the counts;
+      * every width of ARM_EDGE_WIDTHS on the LITERAL route with every count of ARM_EXC_COUNTS: bases one step outside either bound, one whose base + mask wraps int64,
+        one beside INT64_MIN and a random one, each checked to fail the rule."""
+    rng = np.random.default_rng(seed)
+    rows = []  # (bw, f, base, exception count)
+    for bw in range(SHORTCUT_MAX_BW + 1):
+        mask, factors = (1 << bw) - 1, shortcut_factors(bw)
+        for i, cnt in enumerate(ARM_EXC_COUNTS):
+            f = factors[(i + bw) % len(factors)]
+            kind = (i + i // 3 + bw) % 3
+            if kind == 2 and 2 * SHORTCUT_BOUND[f] - mask < 2:  # no base strictly inside under this factor: the widest bounds have one
+                f = 0
+            bnd = SHORTCUT_BOUND[f]
+            base = (-bnd, bnd - mask, int(rng.integers(-bnd + 1, bnd - mask)) if kind == 2 else 0)[kind]
+            assert shortcut_applies(bw, f, base)
+            rows.append((bw, f, base, cnt))
+    for bw in ARM_EDGE_WIDTHS:
+        mask = (1 << bw) - 1
+        for i, cnt in enumerate(ARM_EXC_COUNTS):
+            f = FACTORS[(i + bw) % len(FACTORS)]
+            bnd = SHORTCUT_BOUND[f]
+            bases = [b for b in (-bnd - 1, bnd - mask + 1, INT64_MAX - mask // 2, INT64_MIN + 1, int(rng.integers(INT64_MIN, INT64_MAX, endpoint=True)), 0, -1)
+                     if INT64_MIN <= b <= INT64_MAX and not shortcut_applies(bw, f, b)]
+            rows.append((bw, f, bases[(i + i // 5) % len(bases)], cnt))
+    n = (len(rows) + ROWGROUP - 1) // ROWGROUP * ROWGROUP
+    while len(rows) < n:
+        rows.append((int(rng.integers(0, 65)), FACTORS[int(rng.integers(0, len(FACTORS)))], int(rng.integers(INT64_MIN, INT64_MAX, endpoint=True)),
+                     ARM_EXC_COUNTS[int(rng.integers(0, len(ARM_EXC_COUNTS)))]))
+    enc = empty_encoding(n)
+    for v, (bw, f, base, cnt) in enumerate(rows):
+        enc["bw"][v], enc["f"][v], enc["base"][v] = bw, f, base
+        enc["e"][v] = f + v % (min(18, f + 2) - f + 1)
+        enc["packed"][v, :16 * bw] = random_words(rng, bw)
+        set_exceptions(enc, v, cnt, exception_bits(rng, cnt, finite=v % 4 != 0), rng)
+    for r in range(n // ROWGROUP):
+        enc["combos"][r, :2] = enc["e"][r * ROWGROUP], enc["f"][r * ROWGROUP]
+    return enc
+
+
+def interleave(enc, seed=18):
+    """-> (encoding, order): the vectors of an encoding of ALP rowgroups followed by ALP_RD rowgroups in an order in which narrow and wide vectors are neighbours.  The
+    ALP vectors are permuted freely (take_vectors): one of at most 32 packed bits, then one wider, every fourth time two wider ones, so that wide follows narrow, narrow
+    follows wide and wide follows wide; what is left of either kind closes the ALP part.  The ALP_RD rowgroups move as whole rowgroups with their dictionaries, one behind
+    each ALP rowgroup while both last.  Vector i of the result is vector order[i] of `enc`."""
+    rng = np.random.default_rng(seed)
+    n = enc["scheme"].size
+    assert n % ROWGROUP == 0
+    n_alp = int((enc["scheme"] == SCHEME_ALP).sum())
+    assert n_alp % ROWGROUP == 0 and (enc["scheme"][:n_alp] == SCHEME_ALP).all() and (enc["scheme"][n_alp:] == SCHEME_ALP_RD).all()
+    narrow, wide = rng.permutation(np.nonzero(enc["bw"][:n_alp] <= 32)[0]), rng.permutation(np.nonzero(enc["bw"][:n_alp] > 32)[0])
+    alp_order, i, j, step = [], 0, 0, 0
+    while i < narrow.size or j < wide.size:
+        alp_order += narrow[i:i + 1].tolist()
+        take = 2 if step % 4 == 3 else 1
+        alp_order += wide[j:j + take].tolist()
+        i, j, step = i + 1, j + take, step + 1
+    alp_order = np.array(alp_order, np.int64)
+    assert np.array_equal(np.sort(alp_order), np.arange(n_alp))
+    n_alp_rg, n_rd_rg = n_alp // ROWGROUP, (n - n_alp) // ROWGROUP
+    order, source = [], []  # source: the rowgroup of `enc` an ALP_RD rowgroup of the result is, -1 for an ALP rowgroup
+    for g in range(max(n_alp_rg, n_rd_rg)):
+        if g < n_alp_rg:
+            order.append(alp_order[g * ROWGROUP:(g + 1) * ROWGROUP])
+            source.append(-1)
+        if g < n_rd_rg:
+            order.append(n_alp + g * ROWGROUP + np.arange(ROWGROUP))
+            source.append(n_alp_rg + g)
+    order = np.concatenate(order)
+    out = take_vectors(enc, order)
+    for k in ("dict", "dict_size", "k", "combos"):  # (an ALP rowgroup's as empty_encoding has them: zeros, k = 1)
+        out[k] = np.zeros((n // ROWGROUP,) + enc[k].shape[1:], enc[k].dtype)
+    out["k"][:] = 1
+    for g, s in enumerate(source):
+        if s >= 0:
+            for k in ("dict", "dict_size", "k", "combos"):
+                out[k][g] = enc[k][s]
+        else:
+            out["combos"][g, :2] = out["e"][g * ROWGROUP], out["f"][g * ROWGROUP]
+    return out, order
 
 
 # ---- ALP_RD rows ------------------------------------------------------------------------------------------------------------------------------------
