@@ -144,6 +144,10 @@ for _t in ("f64", "f32"):
 for _t in ("f64", "f32"):
     _sig("alpgpu_select_in_mask_" + _t, _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp, _u64, _int, _vp, _int, _vp)
 _sig("alpgpu_in_list_lds_max", C.c_size_t, _int)
+TOP_K_MAX = 1024  # ALPGPU_TOP_K_MAX
+_sig("alpgpu_top_k_scratch_bytes", _u64, _u64, _u64)
+for _t in ("f64", "f32"):
+    _sig("alpgpu_top_k_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _u64, _int, _vp, _vp, _vp, _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -1033,6 +1037,72 @@ class Context:
         self._call("select_in_mask", col.dtype, C.byref(col.c), first, n, _vp(lst.data_ptr()) if lst.numel() else None, lst.numel(), 1 if negate else 0,
                    _vp(zones.data_ptr()) if zones is not None else None, self._MASK_OPS[op], _vp(mask.data_ptr()))
         return mask
+
+    # ---- top-k (include/alpgpu.h: alpgpu_top_k_scratch_bytes, alpgpu_top_k_*) ---------------------------------------------
+    @staticmethod
+    def _check_k(k):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) <= TOP_K_MAX:
+            raise ValueError("k must be an integer in 0 .. %d" % TOP_K_MAX)
+        return int(k)
+
+    def top_k_scratch(self, col: "DeviceColumn", k: int):
+        """a scratch tensor for top_k_into on this column with this k or a smaller one (alpgpu_top_k_scratch_bytes; torch allocations are at least
+        16-byte aligned)"""
+        import torch
+        return torch.empty(lib.alpgpu_top_k_scratch_bytes(col.n_vectors, self._check_k(k)), dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    def top_k_into(self, col: "DeviceColumn", mask, k: int, vals_out, count_out, idx_out=None, largest: bool = True, records=None, scratch=None):
+        """the raw form of alpgpu_top_k_f64 / _f32: the k largest (largest=False: smallest) values among the set bits of the mask that are no NaNs,
+        in the order include/alpgpu.h defines (-0.0 below +0.0, equal bit patterns by ascending index), into vals_out (the column's value type, at
+        least k long), their value indices into idx_out (optional, int64, at least k long), their number min(k, selected values that are no
+        NaNs) into count_out (one int64).  Nothing is written behind the count.  records: the EXACT masked records of the column under this mask
+        (decode_minmax_masked, or zone_map under a mask of every real value): the first decode pass is skipped; anything else there gives an
+        unspecified selection.  Nothing is synchronised and nothing read back; with a scratch given (top_k_scratch) nothing is allocated
+        either, so the call can be captured into a graph.  The mask is only read."""
+        import torch
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        k = self._check_k(k)
+        self._check_mask(mask, col.n_vectors)
+        self._check_tensor(count_out, torch.int64, "count_out")
+        if count_out.numel() < 1:
+            raise ValueError("count_out must hold one int64")
+        self._check_tensor(vals_out, tdt, "vals_out")
+        if vals_out.numel() < k:
+            raise ValueError("vals_out must hold k values")
+        if idx_out is not None:
+            self._check_tensor(idx_out, torch.int64, "idx_out")
+            if idx_out.numel() < k:
+                raise ValueError("idx_out must hold k indices")
+        if records is not None:
+            self._check_zones(records, tdt, col.n_vectors)
+            if records.data_ptr() % 16:
+                raise ValueError("records must be 16-byte aligned")
+        need = lib.alpgpu_top_k_scratch_bytes(col.n_vectors, k)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
+        else:
+            self._check_tensor(scratch, torch.uint8, "scratch")
+            if scratch.numel() < need or scratch.data_ptr() % 16:
+                raise ValueError("scratch must hold alpgpu_top_k_scratch_bytes(n_vectors, k) bytes, 16-byte aligned")
+        # (a tensor without elements has no address: the library wants one even where it writes nothing)
+        self._call("top_k", col.dtype, C.byref(col.c), _vp(mask.data_ptr()) if mask.numel() else _vp(scratch.data_ptr()), _vp(records.data_ptr()) if records is not None else None, k,
+                   1 if largest else 0, _vp(vals_out.data_ptr()) if vals_out.numel() else _vp(scratch.data_ptr()), _vp(idx_out.data_ptr()) if idx_out is not None and idx_out.numel() else None,
+                   _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
+
+    def top_k(self, col: "DeviceColumn", mask, k: int, largest: bool = True, records=None, indices: bool = True):
+        """(values, indices) — values alone with indices=False — of the k largest (largest=False: smallest) values among the set bits of the mask,
+        NaNs left out, largest (smallest) first, equal bit patterns by ascending index; trimmed to min(k, how many there are).  One read of the
+        count, which synchronises the stream."""
+        import torch
+        dev = f"cuda:{self.device}"
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        k = self._check_k(k)
+        vals = torch.empty(k, dtype=tdt, device=dev)
+        idx = torch.empty(k, dtype=torch.int64, device=dev) if indices else None
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        self.top_k_into(col, mask, k, vals, count, idx, largest=largest, records=records)
+        n = min(int(count.item()), k)
+        return (vals[:n], idx[:n]) if indices else vals[:n]
 
     # ---- zone maps (include/alpgpu.h: alpgpu_zone_map_*, alpgpu_zones_minmax_*) ---------------------------------------
     def _check_zones(self, zones, dtype, n_vectors):

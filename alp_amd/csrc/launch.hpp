@@ -93,6 +93,30 @@ int launch_group_minmax(hipStream_t stream, const alpgpu_column* val, const alpg
                         void* d_zones, uint32_t* d_counts, int value_bytes);
 int launch_group_minmax_totals(hipStream_t stream, const void* d_zones, uint64_t n, uint32_t n_groups, void* d_minmax, int value_bytes);
 
+// top_k_kernels.hip: ORDER BY x [DESC] LIMIT k under a bitmap.  top_k_layout: where the pieces of the caller's scratch lie (byte offsets, each a
+// multiple of 16) and their total; false when n_vectors or k is more than the call accepts.  launch_top_k: col->n_vectors in 1 .. 2^32 - 1,
+// 1 <= k <= ALPGPU_TOP_K_MAX, d_records nullable (then launch_minmax_masked writes them into the scratch), d_idx nullable; value_bytes 8 or 4.
+// Memset, records, a histogram and a pick per digit of the vector level, the candidates, the same per digit of the element level, the filter, the sort.
+struct TopKLayout {
+	uint64_t records, counts, cand, stage, bins, state, total;
+	uint64_t cand_capacity; // candidates: min(k, n_vectors) * 1024
+};
+inline bool top_k_layout(uint64_t n_vectors, uint64_t k, TopKLayout& L) {
+	if (k > ALPGPU_TOP_K_MAX || n_vectors > 0xFFFFFFFFull) { return false; }
+	const auto up16   = [](uint64_t x) { return (x + 15ull) & ~15ull; };
+	L.cand_capacity   = (k < n_vectors ? k : n_vectors) * 1024ull;
+	L.records         = 0;
+	L.counts          = L.records + 16ull * n_vectors;
+	L.cand            = L.counts + up16(4ull * n_vectors);
+	L.stage           = L.cand + 16ull * L.cand_capacity;
+	L.bins            = L.stage + 16ull * ALPGPU_TOP_K_MAX;
+	L.state           = L.bins + 2ull * 16ull * 256ull * sizeof(uint32_t); // two levels of at most 16 passes
+	L.total           = L.state + 64ull;
+	return true;
+}
+int launch_top_k(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, const void* d_records, uint32_t k, int largest, void* d_vals, int64_t* d_idx,
+                 uint64_t* d_count, void* d_scratch, int value_bytes);
+
 // in_list_kernels.hip: set membership.  launch_select_in_mask: bit(r) = / &= / |= q(r), q(r) = first <= r < first + n and ((some j < n_list has
 // d_list[j] == x_r) != negate) (n > 0; range, op, n_list <= 2^31 - 1 and the alignments checked by the caller; d_list sorted, device memory of the
 // column's type, NULL with n_list == 0; d_zones nullable: the column's zone map); one launch of persistent workgroups, at most four per CU.

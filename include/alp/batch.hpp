@@ -671,6 +671,47 @@ struct column {
 		if (counts) { check(alpgpu_memcpy_d2h(context(), counts->data(), d_counts, nv * sizeof(uint32_t)), "alpgpu_memcpy_d2h"); }
 		return out;
 	}
+	// Top-k (include/alpgpu.h, "top-k"): ORDER BY x [DESC] LIMIT k over the values whose bit is set (alpgpu_top_k_*).  values[j], indices[j] are the
+	// j-th element, the largest (largest = false: the smallest) first; NaNs are left out, -0.0 lies below +0.0, equal bit patterns come by ascending
+	// index, and each value has the bits decompress gives it.  Both vectors are min(k, selected values that are no NaNs) long; k <= ALPGPU_TOP_K_MAX.
+	// records (optional): the EXACT masked records of this column under this mask, as minmax_masked returns them — the call then skips its first
+	// decode pass; any other records give an unspecified selection.
+	struct top_k_result {
+		std::vector<PT>      values;
+		std::vector<int64_t> indices;
+	};
+	static top_k_result top_k(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask, uint64_t k, bool largest = true, const std::vector<zone>* records = nullptr) {
+		uploaded_column up(blob, size, "alp::gpu::column::top_k");
+		const uint64_t  nv = up.col.n_vectors;
+		if (mask.size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::top_k: the mask must hold 16 words per vector"); }
+		if (k > ALPGPU_TOP_K_MAX) { throw std::runtime_error("alp::gpu::column::top_k: k must not be more than ALPGPU_TOP_K_MAX"); }
+		if (records && records->size() != nv) { throw std::runtime_error("alp::gpu::column::top_k: one record per vector"); }
+		top_k_result out;
+		if (nv == 0 || k == 0) { return out; }
+		uint64_t* d_mask    = static_cast<uint64_t*>(up.get(mask.size() * sizeof(uint64_t)));
+		zone*     d_records = records ? static_cast<zone*>(up.get(nv * sizeof(zone))) : nullptr;
+		PT*       d_vals    = static_cast<PT*>(up.get(k * sizeof(PT)));
+		int64_t*  d_idx     = static_cast<int64_t*>(up.get(k * sizeof(int64_t)));
+		uint64_t* d_count   = static_cast<uint64_t*>(up.get(sizeof(uint64_t)));
+		void*     d_scratch = up.get(alpgpu_top_k_scratch_bytes(nv, k));
+		check(alpgpu_memcpy_h2d(context(), d_mask, mask.data(), mask.size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d");
+		if (records) { check(alpgpu_memcpy_h2d(context(), d_records, records->data(), nv * sizeof(zone)), "alpgpu_memcpy_h2d"); }
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_top_k_f64(context(), &up.col, d_mask, d_records, k, largest ? 1 : 0, reinterpret_cast<double*>(d_vals), d_idx, d_count, d_scratch), "alpgpu_top_k_f64");
+		} else {
+			check(alpgpu_top_k_f32(context(), &up.col, d_mask, d_records, k, largest ? 1 : 0, reinterpret_cast<float*>(d_vals), d_idx, d_count, d_scratch), "alpgpu_top_k_f32");
+		}
+		uint64_t count = 0;
+		check(alpgpu_memcpy_d2h(context(), &count, d_count, sizeof(count)), "alpgpu_memcpy_d2h");
+		if (count > k) { throw std::runtime_error("alp::gpu::column::top_k: the count exceeds k"); }
+		out.values.resize(count);
+		out.indices.resize(count);
+		if (count > 0) {
+			check(alpgpu_memcpy_d2h(context(), out.values.data(), d_vals, count * sizeof(PT)), "alpgpu_memcpy_d2h");
+			check(alpgpu_memcpy_d2h(context(), out.indices.data(), d_idx, count * sizeof(int64_t)), "alpgpu_memcpy_d2h");
+		}
+		return out;
+	}
 	// group_minmax_masked: group_sum_masked's arguments; zones and counts (optional) come back as [n_groups][n_vectors], row g bit for bit what
 	// minmax_masked gives under the mask ANDed with select_mask(key, lo[g], hi[g]) (alpgpu_decode_group_minmax_*).  Returns n_vectors.
 	static uint64_t group_minmax_masked(const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>& mask, const PT* lo, const PT* hi,

@@ -780,6 +780,57 @@ int    alpgpu_select_in_mask_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint
                                  const alpgpu_zone_f32* d_zones, int op, uint64_t* d_mask);
 size_t alpgpu_in_list_lds_max(int value_bytes);
 
+/* ---- top-k -----------------------------------------------------------------------------------------------------------------------------------
+ * SELECT x ... WHERE ... ORDER BY x [DESC] LIMIT k (TPC-H Q2, Q3, Q10, Q18, Q21; "the 100 largest readings where ..."): the k largest or smallest
+ * selected values of a compressed column and their indices, no value reaching HBM but the candidates of at most k vectors.
+ *   WHERE ...                           select_mask / compare_mask / select_in_mask ... into the bitmap (all ones for no WHERE clause);
+ *   ORDER BY x DESC LIMIT k             top_k(x, bitmap, k, largest = 1).
+ * THE ORDER is the zone records' order made total:
+ *   - NaNs are never returned, quiet or signalling, in an exception record as in packed words;
+ *   - -inf < ... < -0.0 < +0.0 < ... < +inf: the two zeros are distinct and ordered;
+ *   - equal bit patterns are ordered by ascending value index.
+ *   As an integer: okey(x) = bits ^ (sign ? all-ones : sign-bit), an unsigned monotone bijection on the bits of the values that are not NaNs.  An
+ *   element's composite key is (okey(x), ~index) for `largest` and (~okey(x), ~index) for smallest; no two elements of a column share one, so every
+ *   step of the call is exact and free of ties, and the value's bits are recovered from the key.
+ *   alpgpu_top_k_*              *d_count = min(k, number of set bits whose value is not a NaN).  For j < *d_count, d_vals[j] / d_idx[j] (d_idx may be
+ *                               NULL) are the j-th element in descending composite order: with largest != 0 the largest value first, otherwise the
+ *                               smallest first, equal bit patterns by ascending index.  d_vals[j] is bit for bit what alpgpu_decode_* writes at
+ *                               d_idx[j]: a -0.0 keeps its sign, an exception its bits.  Nothing is written at j >= *d_count.  The result is a
+ *                               function of the column, the bitmap, k and largest alone, not of launch shapes or of the order in which wavefronts
+ *                               arrive.
+ *                               d_mask: a selection bitmap of col->n_vectors * 16 words, 8-byte aligned, required, read and never written; the
+ *                               caller excludes the tail padding by it, as with alpgpu_decode_masked_*.
+ *                               d_records (may be NULL; 16-byte aligned): the EXACT masked records of this column under this bitmap — what
+ *                               alpgpu_decode_minmax_masked_* writes, or, under a bitmap that selects every real value, what alpgpu_zone_map_*
+ *                               writes.  With them the first decode pass is skipped; with NULL the call computes them into the scratch.  Records
+ *                               that are not those give an UNSPECIFIED selection: unlike alpgpu_select_range_zoned_*, widened records are NOT
+ *                               enough, because the vectors to decode are chosen by the k-th largest ATTAINED maximum (minimum).  Even then the
+ *                               call writes at most k entries and reads and writes nothing out of bounds: the vectors it decodes are chosen by the
+ *                               composite key (record, ~vector), so there are at most k of them whatever the records say.
+ *                               Cost: without records one pass of alpgpu_decode_minmax_masked_*; then a histogram and a pick launch per byte of
+ *                               the keys over the records (16 bytes per vector each), the decode of at most k vectors, the same over at most
+ *                               min(k, n_vectors) * 1024 candidates, and one workgroup that sorts the k results.
+ *                               k == 0 or col->n_vectors == 0: ALPGPU_OK and *d_count = 0 (that one write is still enqueued).
+ *                               ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx, col, d_count, d_vals, d_mask or d_scratch;
+ *                               k > ALPGPU_TOP_K_MAX; d_records or d_scratch not 16-byte aligned, d_mask, d_count or d_idx not 8-byte aligned,
+ *                               d_vals not aligned to its type; n_vectors >= 2^32 or, with n_vectors > 0, a column without descriptors.
+ *   alpgpu_top_k_scratch_bytes  the scratch of a call: caller-owned device memory, 16-byte aligned; what it holds before does not matter and what it
+ *                               holds after is unspecified.  It covers the records and counts (20 bytes per vector, also when d_records is given:
+ *                               one formula), min(k, n_vectors) * 1024 candidates of 16 bytes, ALPGPU_TOP_K_MAX staging slots, the histogram bins
+ *                               and the device-side state.  Never 0, monotone in both arguments; UINT64_MAX for k > ALPGPU_TOP_K_MAX and for
+ *                               n_vectors >= 2^32.
+ * Contract as for the masked MIN / MAX section: everything is enqueued on the context's stream and on that stream only: asynchronous, no host
+ *   synchronisation, no allocation; none of what the context remembers about columns is read or written; safe inside a stream capture (a replay
+ *   sees the bitmap's, the records' and the column's contents of that time; k, largest and the pointers are fixed at capture).  All counts live in
+ *   device memory, every grid is fixed on the host and no workgroup waits for another.  (tests/top_k_replica.py holds the host replica.)
+ * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector). */
+#define ALPGPU_TOP_K_MAX 1024
+uint64_t alpgpu_top_k_scratch_bytes(uint64_t n_vectors, uint64_t k);
+int alpgpu_top_k_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const alpgpu_zone_f64* d_records, uint64_t k, int largest, double* d_vals, int64_t* d_idx,
+                     uint64_t* d_count, void* d_scratch);
+int alpgpu_top_k_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const alpgpu_zone_f32* d_records, uint64_t k, int largest, float* d_vals, int64_t* d_idx,
+                     uint64_t* d_count, void* d_scratch);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
