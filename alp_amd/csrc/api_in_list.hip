@@ -4,8 +4,6 @@
 #include "host_ctx.hpp"
 
 extern "C++" {
-static bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) != 0; }
-
 // op, first, n: the checks and the n == 0 behaviour of alpgpu_select_mask_* (api_mask.hip: select_mask)
 static int select_in_mask(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const void* d_list, uint64_t n_list, int negate, const void* d_zones, int op,
                           uint64_t* d_mask, int value_bytes) {

@@ -6,13 +6,10 @@
 #include "host_ctx.hpp"
 
 extern "C++" {
-// a record array is aligned to its records (16 / 8 bytes: the kernels store and load a record at once)
-static bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) != 0; }
-
 static int minmax_masked(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, void* d_zones, uint32_t* d_counts, int value_bytes) {
 	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }
 	if (misaligned(d_mask, 8u)) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
-	if (misaligned(d_zones, 2u * value_bytes)) { return fail(ALPGPU_ERR_INVALID, "records are not aligned to their size"); }
+	if (misaligned(d_zones, 2u * value_bytes)) { return fail(ALPGPU_ERR_INVALID, "records are not aligned to their size"); } // (16 / 8 bytes: the kernels store and load a record at once)
 	if (col->n_vectors == 0) { return ALPGPU_OK; }
 	if (!d_mask || !d_zones) { return fail(ALPGPU_ERR_INVALID, "null bitmap or records"); }
 	if (col->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }

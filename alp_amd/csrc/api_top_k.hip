@@ -5,8 +5,6 @@
 #include "host_ctx.hpp"
 
 extern "C++" {
-static bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) != 0; }
-
 static int top_k(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const void* d_records, uint64_t k, int largest, void* d_vals, int64_t* d_idx, uint64_t* d_count,
                  void* d_scratch, int value_bytes) {
 	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }

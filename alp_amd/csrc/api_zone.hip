@@ -5,8 +5,8 @@
 #include "host_ctx.hpp"
 
 extern "C++" {
-// a zone array is aligned to its records (16 / 8 bytes: the kernels store and load a record at once), the raw values to the 16 bytes of a load
-static bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) != 0; }
+// (every misaligned() below: a zone array is aligned to its records, 16 / 8 bytes, because the kernels store and load a record at once, and the raw
+// values to the 16 bytes of a load)
 static int zone_map(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_zones, int value_bytes) {
 	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }
 	if (col->n_vectors == 0) { return ALPGPU_OK; }

@@ -1,16 +1,16 @@
-// group_device.hpp — grouped aggregation (include/alpgpu.h, "grouped aggregation": alpgpu_decode_group_sum_*): k_group, a third consumer of the
-// side-by-side decode of pair_device.hpp.  Vector v of the VALUE column and vector v of the KEY column are decoded in registers exactly as k_pair
-// decodes its pair (PairVec, pair_request, pair_value: the same steps, batches, exception masks and clamps); every group's range predicate on the
-// key is then settled in that one pass, so that SUM and COUNT of G groups cost two decodes and not 2 G.  k_pair and k_select are left as they are.
+// group_device.hpp — grouped aggregation (include/alpgpu.h, "grouped aggregation": alpgpu_decode_group_sum_*): k_group.  Vector v of the VALUE
+// column and vector v of the KEY column are decoded in registers side by side (register_decode.hpp: kStepBatch steps of both at a time, as k_pair
+// decodes its pair); every group's range predicate on the key is then settled in that one pass, so that SUM and COUNT of G groups cost two
+// decodes and not 2 G.
 #pragma once
-#include "pair_device.hpp"
+#include "register_decode.hpp"
 
 namespace alpgpu {
 
 // the groups' closed ranges in the key's own type: kernel arguments, wave-uniform.  The host pads the tier's unused groups with lo > hi.
 template <int VB, int GT>
 struct GroupBounds {
-	typename PairVec<VB>::T lo[GT], hi[GT];
+	typename DecodeVec<VB>::T lo[GT], hi[GT];
 };
 struct GroupArgs {
 	uint64_t        n_vectors, wg_off; // the launch covers the whole column, this grid from workgroup wg_off on
@@ -24,7 +24,7 @@ struct GroupArgs {
 // full unrolling and never an indexed array.  Row g of the output is, bit for bit, what alpgpu_decode_sum_masked_* writes under the bitmap ANDed
 // with alpgpu_select_mask_*(key, lo[g], hi[g]): the same lanes, the same m ascending, `acc + x` only where the value is selected, the same tree.
 template <int VB, int GT>
-__global__ __launch_bounds__(kSelThreads) void k_group(const PairColumn cv, const PairColumn ck, const GroupArgs g, const GroupBounds<VB, GT> r) {
+__global__ __launch_bounds__(kSelThreads) void k_group(const ColumnStreams cv, const ColumnStreams ck, const GroupArgs g, const GroupBounds<VB, GT> r) {
 	__shared__ uint64_t s_exc[kSelWaves][2][16]; // per wavefront and column: bit p = value p is an exception
 
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -33,8 +33,8 @@ __global__ __launch_bounds__(kSelThreads) void k_group(const PairColumn cv, cons
 	if (v >= g.n_vectors) { return; }
 
 	// 1. the vector's 128 bytes of bitmap, lane m < 16 holding word m; without a set bit every group gets +0.0 and 0 and neither column is read
-	const uint64_t prior = lane < 16u ? g.mask[16ull * v + lane] : 0ull;
-	if (ballot64(prior != 0ull) == 0ull) {
+	uint64_t prior;
+	if (!bitmap_words(g.mask, v, lane, prior)) {
 		if (lane < g.n_groups) {
 			g.sums[static_cast<uint64_t>(lane) * g.n_vectors + v] = 0.0;
 			if (g.counts != nullptr) { g.counts[static_cast<uint64_t>(lane) * g.n_vectors + v] = 0u; }
@@ -43,15 +43,9 @@ __global__ __launch_bounds__(kSelThreads) void k_group(const PairColumn cv, cons
 	}
 
 	// 2. both descriptors and dictionaries, 3. both exception masks
-	const PairVec<VB> A = pair_vec_load<VB>(cv, v);
-	const PairVec<VB> B = pair_vec_load<VB>(ck, v);
-	if ((A.cnt | B.cnt) > 0) {
-		if (lane < 32u) { s_exc[wave][lane >> 4][lane & 15u] = 0ull; }
-		wave_lds_sync();
-		pair_mark_exceptions<VB>(A, s_exc[wave][0], lane);
-		pair_mark_exceptions<VB>(B, s_exc[wave][1], lane);
-		wave_lds_sync();
-	}
+	const DecodeVec<VB> A = decode_vec_load<VB>(cv, v);
+	const DecodeVec<VB> B = decode_vec_load<VB>(ck, v);
+	exception_masks(A, B, s_exc, wave, lane);
 
 	uint32_t exc_a = 0, exc_b = 0; // exceptions of the steps done
 	double   acc[GT];              // this lane's partial of every group
@@ -61,19 +55,19 @@ __global__ __launch_bounds__(kSelThreads) void k_group(const PairColumn cv, cons
 		acc[j] = 0.0;
 		n[j]   = 0u;
 	}
-	for (uint32_t b = 0; b < 16u; b += kPairBatch) {
-		// 4. every load of kPairBatch steps of BOTH vectors is requested before the first is used
-		PairBatch<VB> Ra, Rb;
-		pair_request<VB>(A, s_exc[wave][0], b, lane, exc_a, Ra);
-		pair_request<VB>(B, s_exc[wave][1], b, lane, exc_b, Rb);
+	for (uint32_t b = 0; b < 16u; b += kStepBatch) {
+		// 4. every load of kStepBatch steps of BOTH vectors is requested before the first is used
+		StepBatch<VB, kStepBatch> Ra, Rb;
+		step_request(A, s_exc[wave][0], b, lane, exc_a, Ra);
+		step_request(B, s_exc[wave][1], b, lane, exc_b, Rb);
 		// 5. the batch's values and their keys
-		double                  x[kPairBatch];
-		typename PairVec<VB>::T k[kPairBatch];
-		bool                    bit[kPairBatch];
+		double                    x[kStepBatch];
+		typename DecodeVec<VB>::T k[kStepBatch];
+		bool                      bit[kStepBatch];
 #pragma unroll
-		for (uint32_t i = 0; i < kPairBatch; ++i) {
-			x[i]   = static_cast<double>(pair_value<VB>(A, Ra, b, i, lane));
-			k[i]   = pair_value<VB>(B, Rb, b, i, lane);
+		for (uint32_t i = 0; i < kStepBatch; ++i) {
+			x[i]   = static_cast<double>(step_value(A, Ra, b, i, lane));
+			k[i]   = step_value(B, Rb, b, i, lane);
 			bit[i] = (readlane64(prior, b + i) >> lane) & 1ull;
 		}
 		// 6. every group, its bounds fetched once for the batch's steps (m ascending within the group: the documented order): NaN (key or bound)
@@ -81,7 +75,7 @@ __global__ __launch_bounds__(kSelThreads) void k_group(const PairColumn cv, cons
 #pragma unroll
 		for (int j = 0; j < GT; ++j) {
 #pragma unroll
-			for (uint32_t i = 0; i < kPairBatch; ++i) {
+			for (uint32_t i = 0; i < kStepBatch; ++i) {
 				const bool q = bit[i] && k[i] >= r.lo[j] && k[i] <= r.hi[j];
 				acc[j]       = q ? acc[j] + x[i] : acc[j]; // (an addition alone: nothing to contract)
 				n[j] += static_cast<uint32_t>(__builtin_popcountll(ballot64(q)));

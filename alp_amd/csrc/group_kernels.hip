@@ -10,18 +10,19 @@
 // HBM traffic per vector: the bitmap's 128 bytes and, unless they settle the vector, both vectors' descriptors, packed words and exception
 // records; 8 (+ 4) bytes written per group.  One launch, split only at the grid limit.
 #include "group_device.hpp"
+#include "launch.hpp"
 
 namespace alpgpu {
 
 template <int VB, int GT>
 static int launch_group_tier(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, GroupArgs args, const double* lo, const double* hi) {
-	typedef typename PairVec<VB>::T T;
+	typedef typename DecodeVec<VB>::T T;
 	GroupBounds<VB, GT>             r;
 	for (uint32_t j = 0; j < static_cast<uint32_t>(GT); ++j) { // (a float entry point's bounds are floats: they pass through double unchanged)
 		r.lo[j] = j < args.n_groups ? static_cast<T>(lo[j]) : static_cast<T>(1);
 		r.hi[j] = j < args.n_groups ? static_cast<T>(hi[j]) : static_cast<T>(0);
 	}
-	const PairColumn cv {val->d_vectors, val->d_rowgroups, val->d_packed, val->d_exc}, ck {key->d_vectors, key->d_rowgroups, key->d_packed, key->d_exc};
+	const ColumnStreams cv = column_streams(val), ck = column_streams(key);
 	const uint64_t   n_wg = (args.n_vectors + kSelWaves - 1) / kSelWaves;
 	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
 		const uint64_t n = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;

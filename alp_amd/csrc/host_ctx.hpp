@@ -132,3 +132,5 @@ ALPGPU_INTERNAL int  validate_blob_header(const void* h_blob, uint64_t size, uin
 ALPGPU_INTERNAL int  validate_blob_vectors(const void* h_blob, const alpgpu_blob_header& h, uint64_t value_bytes, uint64_t v_begin, uint64_t v_end, const uint64_t* window = nullptr);
 } // extern "C"
 inline uint64_t align8(uint64_t x) { return (x + 7ull) & ~7ull; }
+// p does not lie on a multiple of `bytes` (a power of two); a null pointer never is misaligned
+inline bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) != 0; }

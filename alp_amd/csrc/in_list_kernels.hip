@@ -4,9 +4,9 @@
 //   k_in_list<VB, GLOBAL>   persistent workgroups of kInWaves wavefronts.  The workgroup stages the sorted list (or, GLOBAL, every stride-th element
 //                           of it: the pivots) into 32 KiB of static LDS, passes ONE workgroup barrier and only then walks vectors
 //                           v = wave_id, wave_id + n_waves, ...: every early-out of the skip rules sits behind that barrier.  A vector is decoded in
-//                           registers by PairVec / PairBatch (pair_device.hpp: the steps, batches, exception mask and clamps of k_pair and k_group);
-//                           the kPairBatch values of a batch search together, so that their LDS (and global) probes overlap.  The ballot of step m
-//                           is kept in lane m, combined with the prior words and stored as one run of 128 bytes, as the MASK arm of k_select does.
+//                           registers by register_decode.hpp in batches of kStepBatch steps, whose values search together, so that their LDS
+//                           (and global) probes overlap.  The ballot of step m is kept in lane m, combined with the prior words and stored as
+//                           one run of 128 bytes, as the MASK arm of k_select does.
 //   the search              a branch-free lower bound, every step wave-uniform in its length: ceil(log2(n + 1)) probes of the LDS words
 //                           [i0, i1), then, GLOBAL, ceil(log2(stride)) probes of the list itself on the slice between two pivots (stride - 1
 //                           elements at most; elements behind the slice's end count as "not less"), then one ==.  Every probe index is clamped to
@@ -23,7 +23,8 @@
 //   k_in_list<8, true>    79 VGPRs, 33792 B LDS, 6 waves per SIMD, no scratch
 //   k_in_list<4, false>   75 VGPRs, 33792 B LDS, 6 waves per SIMD, no scratch
 //   k_in_list<4, true>    71 VGPRs, 33792 B LDS, 7 waves per SIMD, no scratch
-#include "pair_device.hpp"
+#include "launch.hpp"
+#include "register_decode.hpp"
 
 namespace alpgpu {
 
@@ -49,9 +50,9 @@ struct InArgs {
 // of them with e < x[i] (bit i of `upper` set: e <= x[i]) if the list is sorted, in [j0, j1] whatever it holds.  A NaN element is never less, so
 // that NaNs sorted last end the list; a NaN x gives j0.
 template <int VB, bool GLOBAL, uint32_t NB>
-__device__ __forceinline__ void in_list_search(const typename PairVec<VB>::T* s_list, const typename PairVec<VB>::T* list, const InArgs& g, uint32_t j0, uint32_t j1,
-                                               const typename PairVec<VB>::T (&x)[NB], uint32_t upper, uint32_t (&out)[NB]) {
-	typedef typename PairVec<VB>::T T;
+__device__ __forceinline__ void in_list_search(const typename DecodeVec<VB>::T* s_list, const typename DecodeVec<VB>::T* list, const InArgs& g, uint32_t j0, uint32_t j1,
+                                               const typename DecodeVec<VB>::T (&x)[NB], uint32_t upper, uint32_t (&out)[NB]) {
+	typedef typename DecodeVec<VB>::T T;
 	const uint32_t stride = GLOBAL ? g.stride : 1u;
 	const uint32_t i0 = GLOBAL ? (j0 + stride - 1u) / stride : j0, i1 = GLOBAL ? (j1 + stride - 1u) / stride : j1; // the LDS words whose elements lie in [j0, j1)
 	const uint32_t last_word = g.n_piv - 1u, last_elem = g.n_list - 1u;
@@ -129,8 +130,8 @@ __device__ __forceinline__ uint64_t in_list_range_word(uint32_t lane, uint32_t p
 }
 
 template <int VB, bool GLOBAL>
-__global__ __launch_bounds__(kInThreads) void k_in_list(const PairColumn c, const InArgs g) {
-	typedef typename PairVec<VB>::T T;
+__global__ __launch_bounds__(kInThreads) void k_in_list(const ColumnStreams c, const InArgs g) {
+	typedef typename DecodeVec<VB>::T T;
 	__shared__ T        s_list[kInLdsBytes / VB];
 	__shared__ uint64_t s_exc[kInWaves][16]; // per wavefront: bit p = value p is an exception
 
@@ -151,7 +152,8 @@ __global__ __launch_bounds__(kInThreads) void k_in_list(const PairColumn c, cons
 		const uint64_t r0 = v << 10;
 		uint64_t*      mw = g.mask + 16ull * v;
 
-		// 1. the vector's 128 bytes of bitmap, lane m < 16 holding word m, and what they settle without the column (the rules of k_select's MASK arm)
+		// 1. the vector's 128 bytes of bitmap, lane m < 16 holding word m, and what they settle without the column
+		// (the rules of k_select's MASK arm; written out in each of the three kernels that write a bitmap: the note at the end of register_decode.hpp)
 		uint64_t   prior   = 0;
 		const bool outside = r0 >= g.end || r0 + 1024u <= g.first; // no value of the vector is in the range: q is false throughout
 		if (g.op == kMaskSet) {
@@ -168,8 +170,8 @@ __global__ __launch_bounds__(kInThreads) void k_in_list(const PairColumn c, cons
 				continue;
 			}
 		}
-		const uint32_t p_begin = g.first > r0 ? static_cast<uint32_t>(g.first - r0) : 0u; // the vector's share of [first, end): wave-uniform
-		const uint32_t p_end   = g.end - r0 < 1024u ? static_cast<uint32_t>(g.end - r0) : 1024u;
+		uint32_t p_begin, p_end;
+		range_share(g.first, g.end, r0, p_begin, p_end);
 
 		// 2. the part [j0, j1) of the list that the vector's zone record admits: all of it without a record or with a NaN bound
 		uint32_t j0 = 0u, j1 = g.n_list;
@@ -190,29 +192,24 @@ __global__ __launch_bounds__(kInThreads) void k_in_list(const PairColumn c, cons
 		}
 
 		// 3. the descriptor, the dictionary and the exception mask
-		const PairVec<VB> V = pair_vec_load<VB>(c, v);
-		if (V.cnt > 0) {
-			if (lane < 16u) { s_exc[wave][lane] = 0ull; }
-			wave_lds_sync();
-			pair_mark_exceptions<VB>(V, s_exc[wave], lane);
-			wave_lds_sync();
-		}
+		const DecodeVec<VB> V = decode_vec_load<VB>(c, v);
+		exception_mask(V, s_exc, wave, lane);
 
 		uint32_t before_exc = 0; // exceptions of the steps done
 		uint64_t keep       = 0; // lane m < 16 keeps step m's ballot
-		for (uint32_t b = 0; b < 16u; b += kPairBatch) {
-			// 4. every load of kPairBatch steps is requested before the first is used
-			PairBatch<VB> R;
-			pair_request<VB>(V, s_exc[wave], b, lane, before_exc, R);
-			T x[kPairBatch];
+		for (uint32_t b = 0; b < 16u; b += kStepBatch) {
+			// 4. every load of kStepBatch steps is requested before the first is used
+			StepBatch<VB, kStepBatch> R;
+			step_request(V, s_exc[wave], b, lane, before_exc, R);
+			T x[kStepBatch];
 #pragma unroll
-			for (uint32_t i = 0; i < kPairBatch; ++i) { x[i] = pair_value<VB>(V, R, b, i, lane); }
+			for (uint32_t i = 0; i < kStepBatch; ++i) { x[i] = step_value(V, R, b, i, lane); }
 			// 5. the batch's lower bounds, searched together, then one == each: -0.0 == 0.0; a NaN (value or element) is never a member
-			uint32_t at[kPairBatch];
-			in_list_search<VB, GLOBAL, kPairBatch>(s_list, list, g, j0, j1, x, 0u, at);
-			T e[kPairBatch];
+			uint32_t at[kStepBatch];
+			in_list_search<VB, GLOBAL, kStepBatch>(s_list, list, g, j0, j1, x, 0u, at);
+			T e[kStepBatch];
 #pragma unroll
-			for (uint32_t i = 0; i < kPairBatch; ++i) {
+			for (uint32_t i = 0; i < kStepBatch; ++i) {
 				if constexpr (GLOBAL) {
 					e[i] = list[at[i] < g.n_list - 1u ? at[i] : g.n_list - 1u];
 				} else {
@@ -220,7 +217,7 @@ __global__ __launch_bounds__(kInThreads) void k_in_list(const PairColumn c, cons
 				}
 			}
 #pragma unroll
-			for (uint32_t i = 0; i < kPairBatch; ++i) {
+			for (uint32_t i = 0; i < kStepBatch; ++i) {
 				const uint32_t m      = b + i;
 				const uint32_t p      = 64u * m + lane;
 				const bool     member = at[i] < j1 && e[i] == x[i];
@@ -235,7 +232,7 @@ __global__ __launch_bounds__(kInThreads) void k_in_list(const PairColumn c, cons
 size_t in_list_lds_max(int value_bytes) { return value_bytes == 8 || value_bytes == 4 ? kInLdsBytes / static_cast<uint32_t>(value_bytes) : 0u; }
 
 template <int VB>
-static int launch_in_list_vb(hipStream_t stream, const PairColumn& c, const InArgs& args, unsigned grid) {
+static int launch_in_list_vb(hipStream_t stream, const ColumnStreams& c, const InArgs& args, unsigned grid) {
 	if (args.stride > 1u) {
 		hipLaunchKernelGGL((k_in_list<VB, true>), dim3(grid), dim3(kInThreads), 0, stream, c, args);
 	} else {
@@ -264,7 +261,7 @@ int launch_select_in_mask(hipStream_t stream, const alpgpu_column* col, uint64_t
 	args.negate  = negate != 0;
 	const uint64_t   n_wg     = (args.n_range + kInWaves - 1) / kInWaves;
 	const uint64_t   resident = static_cast<uint64_t>(n_cus > 0 ? n_cus : 1) * kInWgPerCu; // the grid is sized to the device: a workgroup stages the list once
-	const PairColumn c {col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc};
+	const ColumnStreams c = column_streams(col);
 	const unsigned   grid = static_cast<unsigned>(n_wg < resident ? n_wg : resident);
 	return value_bytes == 8 ? launch_in_list_vb<8>(stream, c, args, grid) : launch_in_list_vb<4>(stream, c, args, grid);
 }

@@ -1,11 +1,11 @@
 // minmax_device.hpp — masked and grouped MIN / MAX (include/alpgpu.h, "masked and grouped MIN / MAX": alpgpu_decode_minmax_masked_*,
-// alpgpu_decode_group_minmax_*): k_minmax_masked and k_group_minmax, two more consumers of the in-register decode of pair_device.hpp (PairVec,
-// pair_request, pair_value: the same steps, batches, exception masks and clamps).  What they write are zone records (wave_minmax.hpp: NaNs
-// ignored, -0.0 < +0.0, {+inf, -inf} for nothing) over the SELECTED values of a vector.  Minimum and maximum are exactly associative and
-// commutative, so a record is a function of the selected values alone and no order needs documenting.  k_select, k_pair and k_group are left
-// as they are.
+// alpgpu_decode_group_minmax_*): k_minmax_masked and k_group_minmax, on the in-register decode of register_decode.hpp in batches of kStepBatch
+// steps.  What they write are zone records (wave_minmax.hpp: NaNs ignored, -0.0 < +0.0, {+inf, -inf} for nothing) over the SELECTED values of
+// a vector.  Minimum and maximum are exactly associative and commutative, so a record is a function of the selected values alone and no order
+// needs documenting.
 #pragma once
-#include "group_device.hpp"
+#include "group_device.hpp" // GroupBounds
+#include "register_decode.hpp"
 #include "wave_minmax.hpp"
 
 namespace alpgpu {
@@ -41,8 +41,8 @@ __device__ __forceinline__ void zone_store(void* zones, uint64_t i, T mn, T mx) 
 
 // One wavefront per vector, four per workgroup, sharing nothing.  Under a full bitmap the record is that of alpgpu_zone_map_*.
 template <int VB>
-__global__ __launch_bounds__(kSelThreads) void k_minmax_masked(const PairColumn c, const MinmaxArgs g) {
-	typedef typename PairVec<VB>::T T;
+__global__ __launch_bounds__(kSelThreads) void k_minmax_masked(const ColumnStreams c, const MinmaxArgs g) {
+	typedef typename DecodeVec<VB>::T T;
 	__shared__ uint64_t             s_exc[kSelWaves][16]; // per wavefront: bit p = value p is an exception
 
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -51,8 +51,8 @@ __global__ __launch_bounds__(kSelThreads) void k_minmax_masked(const PairColumn 
 	if (v >= g.n_vectors) { return; }
 
 	// 1. the vector's 128 bytes of bitmap, lane m < 16 holding word m; without a set bit the record is empty and the column is not read
-	const uint64_t prior = lane < 16u ? g.mask[16ull * v + lane] : 0ull;
-	if (ballot64(prior != 0ull) == 0ull) {
+	uint64_t prior;
+	if (!bitmap_words(g.mask, v, lane, prior)) {
 		if (lane == 0u) {
 			zone_store<T>(g.zones, v, pos_inf<T>(), -pos_inf<T>());
 			if (g.counts != nullptr) { g.counts[v] = 0u; }
@@ -61,25 +61,20 @@ __global__ __launch_bounds__(kSelThreads) void k_minmax_masked(const PairColumn 
 	}
 
 	// 2. the descriptor and dictionary, 3. the exception mask
-	const PairVec<VB> A = pair_vec_load<VB>(c, v);
-	if (A.cnt > 0) {
-		if (lane < 16u) { s_exc[wave][lane] = 0ull; }
-		wave_lds_sync();
-		pair_mark_exceptions<VB>(A, s_exc[wave], lane);
-		wave_lds_sync();
-	}
+	const DecodeVec<VB> A = decode_vec_load<VB>(c, v);
+	exception_mask(A, s_exc, wave, lane);
 
 	uint32_t exc_a = 0; // exceptions of the steps done
 	uint32_t n_set = 0; // set bits of the steps done
 	T        mn = pos_inf<T>(), mx = -pos_inf<T>();
-	for (uint32_t b = 0; b < 16u; b += kPairBatch) {
-		// 4. every load of kPairBatch steps is requested before the first is used
-		PairBatch<VB> Ra;
-		pair_request<VB>(A, s_exc[wave], b, lane, exc_a, Ra);
+	for (uint32_t b = 0; b < 16u; b += kStepBatch) {
+		// 4. every load of kStepBatch steps is requested before the first is used
+		StepBatch<VB, kStepBatch> Ra;
+		step_request(A, s_exc[wave], b, lane, exc_a, Ra);
 #pragma unroll
-		for (uint32_t i = 0; i < kPairBatch; ++i) {
+		for (uint32_t i = 0; i < kStepBatch; ++i) {
 			// 5. the value, taken or skipped by its bit: selected NaNs are counted and ignored
-			const T        q = minmax_canonical(pair_value<VB>(A, Ra, b, i, lane));
+			const T        q = minmax_canonical(step_value(A, Ra, b, i, lane));
 			const uint64_t w = readlane64(prior, b + i);
 			minmax_feed(mn, mx, (w >> lane) & 1ull ? q : minmax_skip<T>());
 			n_set += static_cast<uint32_t>(__builtin_popcountll(w));
@@ -97,8 +92,8 @@ __global__ __launch_bounds__(kSelThreads) void k_minmax_masked(const PairColumn 
 // and never an indexed array.  Row g of the output is what k_minmax_masked writes under the bitmap ANDed with
 // alpgpu_select_mask_*(key, lo[g], hi[g]), and its counts are k_group's.
 template <int VB, int GT>
-__global__ __launch_bounds__(kSelThreads) void k_group_minmax(const PairColumn cv, const PairColumn ck, const MinmaxArgs g, const GroupBounds<VB, GT> r) {
-	typedef typename PairVec<VB>::T T;
+__global__ __launch_bounds__(kSelThreads) void k_group_minmax(const ColumnStreams cv, const ColumnStreams ck, const MinmaxArgs g, const GroupBounds<VB, GT> r) {
+	typedef typename DecodeVec<VB>::T T;
 	__shared__ uint64_t             s_exc[kSelWaves][2][16]; // per wavefront and column: bit p = value p is an exception
 
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -107,8 +102,8 @@ __global__ __launch_bounds__(kSelThreads) void k_group_minmax(const PairColumn c
 	if (v >= g.n_vectors) { return; }
 
 	// 1. the vector's 128 bytes of bitmap; without a set bit every group's record is empty and neither column is read
-	const uint64_t prior = lane < 16u ? g.mask[16ull * v + lane] : 0ull;
-	if (ballot64(prior != 0ull) == 0ull) {
+	uint64_t prior;
+	if (!bitmap_words(g.mask, v, lane, prior)) {
 		if (lane < g.n_groups) {
 			zone_store<T>(g.zones, static_cast<uint64_t>(lane) * g.n_vectors + v, pos_inf<T>(), -pos_inf<T>());
 			if (g.counts != nullptr) { g.counts[static_cast<uint64_t>(lane) * g.n_vectors + v] = 0u; }
@@ -117,15 +112,9 @@ __global__ __launch_bounds__(kSelThreads) void k_group_minmax(const PairColumn c
 	}
 
 	// 2. both descriptors and dictionaries, 3. both exception masks
-	const PairVec<VB> A = pair_vec_load<VB>(cv, v);
-	const PairVec<VB> B = pair_vec_load<VB>(ck, v);
-	if ((A.cnt | B.cnt) > 0) {
-		if (lane < 32u) { s_exc[wave][lane >> 4][lane & 15u] = 0ull; }
-		wave_lds_sync();
-		pair_mark_exceptions<VB>(A, s_exc[wave][0], lane);
-		pair_mark_exceptions<VB>(B, s_exc[wave][1], lane);
-		wave_lds_sync();
-	}
+	const DecodeVec<VB> A = decode_vec_load<VB>(cv, v);
+	const DecodeVec<VB> B = decode_vec_load<VB>(ck, v);
+	exception_masks(A, B, s_exc, wave, lane);
 
 	uint32_t exc_a = 0, exc_b = 0; // exceptions of the steps done
 	T        mn[GT], mx[GT];       // this lane's candidates of every group
@@ -136,18 +125,18 @@ __global__ __launch_bounds__(kSelThreads) void k_group_minmax(const PairColumn c
 		mx[j] = -pos_inf<T>();
 		n[j]  = 0u;
 	}
-	for (uint32_t b = 0; b < 16u; b += kPairBatch) {
-		// 4. every load of kPairBatch steps of BOTH vectors is requested before the first is used
-		PairBatch<VB> Ra, Rb;
-		pair_request<VB>(A, s_exc[wave][0], b, lane, exc_a, Ra);
-		pair_request<VB>(B, s_exc[wave][1], b, lane, exc_b, Rb);
+	for (uint32_t b = 0; b < 16u; b += kStepBatch) {
+		// 4. every load of kStepBatch steps of BOTH vectors is requested before the first is used
+		StepBatch<VB, kStepBatch> Ra, Rb;
+		step_request(A, s_exc[wave][0], b, lane, exc_a, Ra);
+		step_request(B, s_exc[wave][1], b, lane, exc_b, Rb);
 		// 5. the batch's values, canonical once, and their keys
-		T    q[kPairBatch], k[kPairBatch];
-		bool bit[kPairBatch];
+		T    q[kStepBatch], k[kStepBatch];
+		bool bit[kStepBatch];
 #pragma unroll
-		for (uint32_t i = 0; i < kPairBatch; ++i) {
-			q[i]   = minmax_canonical(pair_value<VB>(A, Ra, b, i, lane));
-			k[i]   = pair_value<VB>(B, Rb, b, i, lane);
+		for (uint32_t i = 0; i < kStepBatch; ++i) {
+			q[i]   = minmax_canonical(step_value(A, Ra, b, i, lane));
+			k[i]   = step_value(B, Rb, b, i, lane);
 			bit[i] = (readlane64(prior, b + i) >> lane) & 1ull;
 		}
 		// 6. every group (select_mask's predicate: a NaN key or bound never qualifies; -0.0 == 0.0; lo > hi selects nothing): an unselected value
@@ -155,7 +144,7 @@ __global__ __launch_bounds__(kSelThreads) void k_group_minmax(const PairColumn c
 #pragma unroll
 		for (int j = 0; j < GT; ++j) {
 #pragma unroll
-			for (uint32_t i = 0; i < kPairBatch; ++i) {
+			for (uint32_t i = 0; i < kStepBatch; ++i) {
 				const bool sel = bit[i] && k[i] >= r.lo[j] && k[i] <= r.hi[j];
 				minmax_feed(mn[j], mx[j], sel ? q[i] : minmax_skip<T>());
 				n[j] += static_cast<uint32_t>(__builtin_popcountll(ballot64(sel)));

@@ -10,6 +10,7 @@
 //
 // HBM traffic per vector: the bitmap's 128 bytes and, unless they settle the vector, the descriptors, packed words and exception records of the
 // column (grouped: of both columns); 16 or 8 (+ 4) bytes written per group.  One launch, split only at the grid limit.
+#include "launch.hpp"
 #include "minmax_device.hpp"
 
 namespace alpgpu {
@@ -31,7 +32,7 @@ int launch_minmax_masked(hipStream_t stream, const alpgpu_column* col, const uin
 	args.mask      = d_mask;
 	args.zones     = d_zones;
 	args.counts    = d_counts;
-	const PairColumn c {col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc};
+	const ColumnStreams c = column_streams(col);
 	return launch_minmax_chunks(args.n_vectors, [&](dim3 grid, uint64_t off) {
 		args.wg_off = off;
 		if (value_bytes == 8) {
@@ -44,13 +45,13 @@ int launch_minmax_masked(hipStream_t stream, const alpgpu_column* col, const uin
 
 template <int VB, int GT>
 static int launch_group_minmax_tier(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, MinmaxArgs args, const double* lo, const double* hi) {
-	typedef typename PairVec<VB>::T T;
+	typedef typename DecodeVec<VB>::T T;
 	GroupBounds<VB, GT>             r;
 	for (uint32_t j = 0; j < static_cast<uint32_t>(GT); ++j) { // (a float entry point's bounds are floats: they pass through double unchanged)
 		r.lo[j] = j < args.n_groups ? static_cast<T>(lo[j]) : static_cast<T>(1);
 		r.hi[j] = j < args.n_groups ? static_cast<T>(hi[j]) : static_cast<T>(0);
 	}
-	const PairColumn cv {val->d_vectors, val->d_rowgroups, val->d_packed, val->d_exc}, ck {key->d_vectors, key->d_rowgroups, key->d_packed, key->d_exc};
+	const ColumnStreams cv = column_streams(val), ck = column_streams(key);
 	return launch_minmax_chunks(args.n_vectors, [&](dim3 grid, uint64_t off) {
 		args.wg_off = off;
 		hipLaunchKernelGGL((k_group_minmax<VB, GT>), grid, dim3(kSelThreads), 0, stream, cv, ck, args, r);

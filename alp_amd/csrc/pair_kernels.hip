@@ -9,13 +9,14 @@
 //
 // HBM traffic per vector: the bitmap's 128 bytes (compare SET writes them without reading), and, unless they settle the vector, both vectors'
 // descriptors, packed words and exception records; the dot writes 8 (+ 4) bytes.  One launch each, split only at the grid limit.
+#include "launch.hpp"
 #include "pair_device.hpp"
 
 namespace alpgpu {
 
 template <int VB, int ARM>
 static int launch_pair(hipStream_t stream, const alpgpu_column* a, const alpgpu_column* b, PairArgs args) {
-	const PairColumn ca {a->d_vectors, a->d_rowgroups, a->d_packed, a->d_exc}, cb {b->d_vectors, b->d_rowgroups, b->d_packed, b->d_exc};
+	const ColumnStreams ca = column_streams(a), cb = column_streams(b);
 	const uint64_t   n_wg = (args.n_range + kSelWaves - 1) / kSelWaves;
 	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
 		const uint64_t g = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;

@@ -1,20 +1,15 @@
-// select_device.hpp — the one-wavefront decode of a vector that every kernel of the selection family is an arm of: k_select, shared by
-// select_kernels.hip (count, zoned count, emit) and mask_kernels.hip (ballots kept as a bitmap, masked SUM, masked projection).  The layout of the steps, the
-// exception mask and the arithmetic are described at the head of select_kernels.hip.
+// select_device.hpp — k_select, the kernel that every entry point of range selection and of the single-column bitmaps is an arm of: shared by
+// select_kernels.hip (count, zoned count, emit) and mask_kernels.hip (ballots kept as a bitmap, masked SUM, masked projection).  The decode of the
+// vector is register_decode.hpp's, in batches of kSelBatch = 8 steps; what is here are the arms: their prologues and early exits, the predicate and
+// the epilogues.  Only those two files include this header and compile the kernel.
 #pragma once
-#include <type_traits>
-
-#include "alp_device_f32.hpp"
-#include "lane_field.hpp"
 #include "launch.hpp"
+#include "register_decode.hpp"
 
 namespace alpgpu {
 
-constexpr int      kSelWaves   = 4; // wavefronts per workgroup, one vector each (they share nothing)
-constexpr int      kSelThreads = 64 * kSelWaves;
-constexpr uint64_t kSelMaxGrid = 1ull << 30; // workgroups per launch
-constexpr int      kScanBlock  = 1024;       // counts per scan block = threads per scan workgroup
-constexpr uint32_t kSelBatch   = 8;          // steps of a vector whose words are requested together
+constexpr int      kScanBlock = 1024; // counts per scan block = threads per scan workgroup
+constexpr uint32_t kSelBatch  = 8;    // steps of a vector whose words are requested together
 inline uint64_t    align16(uint64_t x) { return (x + 15ull) & ~15ull; } // the parts of the scratch (select_scratch_bytes) begin on 16 bytes
 
 // EMIT = false: counts[k] = qualifying values of vector v0 + k.  EMIT = true: their indices (and values) at offsets[k] + rank.
@@ -35,7 +30,6 @@ inline uint64_t    align16(uint64_t x) { return (x + 15ull) & ~15ull; } // the p
 //                d_vals (and its index to d_idx, nullable here) at offsets[v] + the set bits of the words before + those below the lane, under
 //                the capacity.  A vector with counts[v] == 0 costs those four bytes, one at or behind the capacity its offset too; a batch of
 //                kSelBatch steps whose words are all zero requests nothing of the column and only moves the exception rank on.
-constexpr int kMaskSet = ALPGPU_MASK_SET, kMaskAnd = ALPGPU_MASK_AND, kMaskOr = ALPGPU_MASK_OR;
 struct SelMaskArgs {
 	uint64_t* mask;
 	int       op;
@@ -56,12 +50,6 @@ template <> struct sel_arm<SelSumArgs> { static constexpr int value = 3; };
 template <> struct sel_arm<SelTakeArgs> { static constexpr int value = 4; };
 __device__ __forceinline__ const void* zone_records(const void* zones) { return zones; }
 template <class A> __device__ __forceinline__ const A& arm_args(const A& a) { return a; }
-// lane `idx` (wave-uniform) of a 64-bit value
-__device__ __forceinline__ uint64_t readlane64(uint64_t x, uint32_t idx) {
-	const uint32_t l = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<uint32_t>(x), idx));
-	const uint32_t h = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<uint32_t>(x >> 32), idx));
-	return (static_cast<uint64_t>(h) << 32) | l;
-}
 template <int VB, bool EMIT, class... ZONES>
 __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc* __restrict__ descs, const alpgpu_rowgroup_state* __restrict__ rgs,
                                                         const uint8_t* __restrict__ packed, const uint8_t* __restrict__ excs, uint64_t v0, uint64_t n_range,
@@ -71,20 +59,18 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
 	constexpr bool ZONED = sel_arm<ZONES...>::value == 1, MASK = sel_arm<ZONES...>::value == 2, SUM = sel_arm<ZONES...>::value == 3;
 	constexpr bool TAKE = sel_arm<ZONES...>::value == 4;
 	static_assert(sizeof...(ZONES) <= 1 && !((ZONED || MASK || SUM || TAKE) && EMIT), "at most one arm's arguments, and the emit pass reads the counts and nothing else");
-	typedef typename std::conditional<VB == 8, uint64_t, uint32_t>::type U;
-	typedef typename std::conditional<VB == 8, double, float>::type      T;
-	constexpr uint32_t kLanes = VB == 8 ? 16u : 32u; // FastLanes lanes of the value streams
-	constexpr uint32_t kLog   = VB == 8 ? 4u : 5u;
+	typedef typename DecodeVec<VB>::U U;
+	typedef typename DecodeVec<VB>::T T;
 	__shared__ uint64_t s_exc[kSelWaves][16]; // per wavefront: bit p = value p is an exception
 
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint64_t k    = (wg_off + blockIdx.x) * kSelWaves + wave;
 	if (k >= n_range) { return; }
-	const uint64_t v       = v0 + k;
-	const uint64_t r0      = v << 10;
-	const uint32_t p_begin = first > r0 ? static_cast<uint32_t>(first - r0) : 0u; // the vector's share of [first, end): wave-uniform
-	const uint32_t p_end   = end - r0 < 1024u ? static_cast<uint32_t>(end - r0) : 1024u;
+	const uint64_t v  = v0 + k;
+	const uint64_t r0 = v << 10;
+	uint32_t       p_begin, p_end; // (what they hold for a vector outside the range is not used: the MASK arm settles such a vector first)
+	range_share(first, end, r0, p_begin, p_end);
 
 	uint32_t total = 0;
 	uint64_t out0  = 0;
@@ -104,9 +90,10 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
 
 	uint64_t prior = 0; // MASK, SUM, TAKE: lane m < 16 holds word m of the vector's bitmap as it was found
 	if constexpr (MASK) {
-		const SelMaskArgs& a       = arm_args(zones...);
-		uint64_t*          mw      = a.mask + 16ull * v;
-		const bool         outside = r0 >= end || r0 + 1024u <= first; // no value of the vector is in the range: q is false throughout
+		const SelMaskArgs& a  = arm_args(zones...);
+		uint64_t*          mw = a.mask + 16ull * v;
+		// (written out in each of the three kernels that write a bitmap, and not a helper: the note at the end of register_decode.hpp)
+		const bool outside = r0 >= end || r0 + 1024u <= first; // no value of the vector is in the range: q is false throughout
 		if (a.op == kMaskSet) {
 			if (outside) {
 				if (lane < 16u) { mw[lane] = 0ull; }
@@ -124,8 +111,7 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
 	}
 	if constexpr (SUM) {
 		const SelSumArgs& a = arm_args(zones...);
-		prior               = lane < 16u ? a.mask[16ull * v + lane] : 0ull;
-		if (ballot64(prior != 0ull) == 0ull) {
+		if (!bitmap_words(a.mask, v, lane, prior)) {
 			if (lane == 0u) {
 				a.sums[v] = 0.0;
 				if (a.counts != nullptr) { a.counts[v] = 0u; }
@@ -154,47 +140,16 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
 		}
 		inside = z_min >= z_lo && z_max <= z_hi;
 	}
-	const alpgpu_vector_desc d     = descs[v];
-	const bool               alp   = d.scheme == ALPGPU_SCHEME_ALP;
+	const DecodeVec<VB> V = decode_vec_load<VB>(ColumnStreams {descs, rgs, packed, excs}, v);
 	if constexpr (ZONED) {
 		// contained: only a vector that cannot hold a NaN — ALP without exceptions (a NaN never round-trips through ALP, so it is always an exception)
-		if (inside && alp && d.exc_cnt == 0u) {
+		if (inside && V.alp && V.cnt == 0u) {
 			if (lane == 0u) { counts[k] = p_end - p_begin; }
 			return;
 		}
 	}
-	const uint32_t           bw    = d.bw < 8u * VB ? d.bw : 8u * VB;
-	const uint32_t           cnt   = d.exc_cnt < 1024u ? d.exc_cnt : 1024u;
-	const uint8_t*           rec   = excs + d.exc_off;
-	const U*                 words = reinterpret_cast<const U*>(packed + d.packed_off);
-	const uint16_t*          lefts = reinterpret_cast<const uint16_t*>(packed + d.packed_off + 128ull * d.bw);
-	const U                  base  = static_cast<U>(d.base);
-	// per-vector constants of the two schemes (gather_kernels.hip: value_bits reads the same tables with the same clamps)
-	const uint32_t lbw  = d.lbw < 16u ? d.lbw : 16u;
-	const uint32_t fi   = VB == 8 ? (d.f < 18 ? d.f : 18) : (d.f < 10 ? d.f : 10);
-	const uint32_t ei   = VB == 8 ? (d.e < 20 ? d.e : 20) : (d.e < 10 ? d.e : 10);
-	const RdDict   dict = load_rd_dict(rgs, v, !alp);
-	const T        lo = static_cast<T>(range_lo), hi = static_cast<T>(range_hi);
-	typename std::conditional<VB == 8, int64_t, uint32_t>::type fact;
-	T                                                          frac;
-	if constexpr (VB == 8) {
-		fact = kFactArr[fi];
-		frac = kFracArr[ei];
-	} else {
-		fact = kFactArrF[fi];
-		frac = kFracArrF[ei];
-	}
-
-	if (cnt > 0) { // the exception positions as a mask in index order
-		const uint16_t* pos = reinterpret_cast<const uint16_t*>(rec + (alp ? static_cast<uint64_t>(VB) : 2ull) * d.exc_cnt);
-		if (lane < 16u) { s_exc[wave][lane] = 0ull; }
-		wave_lds_sync();
-		for (uint32_t j = lane; j < cnt; j += 64u) {
-			const uint32_t q = pos[j];
-			if (q < 1024u) { atomicOr(reinterpret_cast<uint32_t*>(&s_exc[wave][0]) + (q >> 5), 1u << (q & 31u)); }
-		}
-		wave_lds_sync();
-	}
+	const T lo = static_cast<T>(range_lo), hi = static_cast<T>(range_hi);
+	exception_mask(V, s_exc, wave, lane);
 
 	uint32_t before_exc = 0; // exceptions of the steps done
 	uint32_t before_sel = 0; // qualifying values of the steps done (wave-uniform: it comes from ballots); SUM, TAKE: set bits of the steps done
@@ -205,78 +160,21 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const alpgpu_vector_desc
 			// no bit set in these kSelBatch words: nothing of the column is requested, but the exceptions of the steps passed over still count
 			// towards the rank of those behind them
 			if (ballot64(lane >= b && lane < b + kSelBatch && prior != 0ull) == 0ull) {
-				if (cnt > 0) {
+				if (V.cnt > 0) {
 #pragma unroll
 					for (uint32_t i = 0; i < kSelBatch; ++i) { before_exc += static_cast<uint32_t>(__builtin_popcountll(s_exc[wave][b + i])); } // (every lane reads the same word)
 				}
 				continue;
 			}
 		}
-		// every load of kSelBatch steps is requested before the first is used: a step is otherwise its own round trip to memory
-		FieldWords<U>        rw[kSelBatch];
-		FieldWords<uint16_t> lw[kSelBatch];
+		StepBatch<VB, kSelBatch> R;
+		step_request(V, s_exc[wave], b, lane, before_exc, R);
 #pragma unroll
 		for (uint32_t i = 0; i < kSelBatch; ++i) {
-			rw[i] = FieldWords<U> {0, 0};
-			lw[i] = FieldWords<uint16_t> {0, 0};
-		}
-		if (bw > 0) {
-#pragma unroll
-			for (uint32_t i = 0; i < kSelBatch; ++i) {
-				const uint32_t p = 64u * (b + i) + lane;
-				rw[i]            = load_field_words<U, kLanes>(words + (p & (kLanes - 1u)), p >> kLog, bw);
-			}
-		}
-		if (!alp && lbw > 0) {
-#pragma unroll
-			for (uint32_t i = 0; i < kSelBatch; ++i) { lw[i] = load_field_words<uint16_t, 64>(lefts + lane, b + i, lbw); }
-		}
-		// ... the exceptions' values too (ALP: the value's bits; ALP_RD: its left part): loaded where they are used, each step with an exception in
-		// it would wait for memory once more.  (The ALP_RD loads are still waited for one by one in the generated code, see the head of this file.
-		// A form that avoids it was measured: every lane loads, without the per-lane branch, one loop per scheme.  It takes 98 registers
-		// instead of 81 and cost the mixed and float columns more, +4 % and +8 %, than the ALP_RD column gained, -3 %.)
-		uint64_t em[kSelBatch]; // wave-uniform: bit l = value 64 m + l is an exception
-		U        ev[kSelBatch];
-#pragma unroll
-		for (uint32_t i = 0; i < kSelBatch; ++i) {
-			em[i] = 0ull;
-			ev[i] = 0;
-		}
-		if (cnt > 0) {
-			uint32_t rank0 = before_exc;
-#pragma unroll
-			for (uint32_t i = 0; i < kSelBatch; ++i) {
-				const uint64_t w = s_exc[wave][b + i];
-				const uint32_t w_lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(w))); // (the builtin returns int: no sign extension into the high word)
-				const uint32_t w_hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(w >> 32)));
-				em[i]               = (static_cast<uint64_t>(w_hi) << 32) | w_lo;
-				const uint32_t rank = rank0 + mbcnt64(em[i], 0u);
-				if ((em[i] >> lane) & 1ull) { ev[i] = alp ? reinterpret_cast<const U*>(rec)[rank] : static_cast<U>(reinterpret_cast<const uint16_t*>(rec)[rank]); }
-				rank0 += static_cast<uint32_t>(__builtin_popcountll(em[i]));
-			}
-			before_exc = rank0;
-		}
-#pragma unroll
-		for (uint32_t i = 0; i < kSelBatch; ++i) {
-			const uint32_t m     = b + i;
-			const uint32_t p     = 64u * m + lane;
-			const U        right = extract_field<U>(rw[i], p >> kLog, bw); // ALP: the digit; ALP_RD: the right part
-			const bool     hit   = (em[i] >> lane) & 1ull;
-			U              bits;
-			if (alp) {
-				if constexpr (VB == 8) {
-					bits = static_cast<U>(__double_as_longlong(decode_value(static_cast<int64_t>(right + base), fact, frac)));
-				} else {
-					bits = __float_as_uint(decode_value_f32(static_cast<int32_t>(right + base), fact, frac));
-				}
-				bits = hit ? ev[i] : bits;
-			} else {
-				const uint32_t idx  = extract_field<uint16_t>(lw[i], m, lbw) & 7u;
-				const U        left = hit ? ev[i] : static_cast<U>(((idx < 4u ? dict.lo : dict.hi) >> (16u * (idx & 3u))) & 0xFFFFull);
-				bits                = static_cast<U>((left << bw) | right);
-			}
-			T x;
-			if constexpr (VB == 8) { x = __longlong_as_double(static_cast<long long>(bits)); } else { x = __uint_as_float(bits); }
+			const uint32_t m    = b + i;
+			const uint32_t p    = 64u * m + lane;
+			const U        bits = step_bits(V, R, b, i, lane);
+			const T        x    = value_of_bits<VB>(bits);
 			if constexpr (SUM) {
 				const uint64_t w = readlane64(prior, m);
 				if ((w >> lane) & 1ull) { acc += static_cast<double>(x); } // (an addition alone: nothing to contract)

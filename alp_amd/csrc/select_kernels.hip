@@ -10,21 +10,11 @@
 //   emit   k_select<VB, true>   one wavefront per vector: counts[v] == 0 -> gone after a 4-byte read; else the same decode again, and every
 //                               qualifying value's index (and value) goes to offsets[v] + its rank inside the vector, if below the capacity
 //
-// The decode of one vector by one wavefront: 16 steps, step m holds value p = 64 m + lane in lane `lane`, so a wave-wide ballot of the predicate
-// IS the 64 bits of the vector's qualify mask for indices 64 m .. 64 m + 63, in index order.  Rank inside the vector = qualifying values of the
-// steps before (a wave-uniform running popcount) + the ballot's bits below the lane (v_mbcnt).  Ranks come from index-ordered masks and the
-// offsets from a prefix sum, so the output ascends and is a function of the column and the arguments alone: no atomic decides a position.
-// With p = 64 m + lane the lanes of a wavefront read neighbouring words of every stream (layouts: gather_kernels.hip):
-//   ALP double   FastLanes lane p & 15 = lane & 15, row 4 m + (lane >> 4): four runs of 16 consecutive u64
-//   ALP float    lane p & 31, row 2 m + (lane >> 5): two runs of 32 consecutive u32
-//   ALP_RD left  lane p & 63 = lane, row m: 64 consecutive u16
-// Exceptions: the record's ascending positions become a 1024-bit mask in the wavefront's 128 bytes of LDS (ds_or, as the store decode's
-// ExcMask); step m reads its 64 bits, rank in the record = exceptions of the steps before + the mask's bits below the lane.  The packed words
-// of eight steps are requested together, and in the source the exception values with them.  In the generated code that holds for ALP vectors
-// only (three or four round trips to memory per vector instead of one per step); for ALP_RD vectors the compiler waits for each exception's
-// left part right behind its load, so a step with an exception is a round trip of its own there (profiles/r08_select.txt).
-// The arithmetic is the store decode's own (decode_value / decode_value_f32, the ALP_RD glue, the same tables, as gather_kernels.hip uses
-// them), so a selected value has the bits alpgpu_decode_* writes at its index.
+// The decode of one vector by one wavefront is register_decode.hpp's (the layout of the steps, the exception mask, the arithmetic): step m holds
+// value p = 64 m + lane in lane `lane`, so a wave-wide ballot of the predicate IS the 64 bits of the vector's qualify mask for indices 64 m ..
+// 64 m + 63, in index order.  Rank inside the vector = qualifying values of the steps before (a wave-uniform running popcount) + the ballot's
+// bits below the lane (v_mbcnt).  Ranks come from index-ordered masks and the offsets from a prefix sum, so the output ascends and is a function
+// of the column and the arguments alone: no atomic decides a position.  A selected value has the bits alpgpu_decode_* writes at its index.
 //
 // HBM traffic: count reads every vector of the range once (descriptor, packed words, exception record, for ALP_RD the dictionary) and writes
 // 4 bytes; the scan reads them and writes 8; emit reads 4 + 8 bytes per vector and, for vectors with a non-zero count only, the vector again,

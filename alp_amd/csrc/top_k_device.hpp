@@ -1,14 +1,13 @@
 // top_k_device.hpp — top-k (include/alpgpu.h, "top-k": alpgpu_top_k_*): the order, the composite keys, the state of the radix select and
-// k_top_k_candidates, one more consumer of the in-register decode of pair_device.hpp (PairVec, pair_request, pair_value: the same steps, batches,
-// exception masks and clamps) on the skeleton of k_minmax_masked.  Everything that is counted is an integer and everything that is compared is
-// a unique key, so the result is a function of the inputs alone.  k_minmax_masked, k_select and the pair decode are left as they are.
+// k_top_k_candidates, on the in-register decode of register_decode.hpp (batches of kStepBatch steps) and the skeleton of k_minmax_masked.
+// Everything that is counted is an integer and everything that is compared is a unique key, so the result is a function of the inputs alone.
 //
 // The order (include/alpgpu.h): okey(x) = bits ^ (sign ? all-ones : sign-bit), an unsigned monotone bijection on the bits of the values that are
 // not NaNs: -inf < ... < -0.0 < +0.0 < ... < +inf.  An element's composite key is {hi, lo} = {okey(x), ~index} for `largest` and
 // {~okey(x), ~index} for smallest (hi within the value's width, zero-extended): descending composite order is the result's order, no two
 // elements of a column share a key, and the value's bits come back out of hi.  A vector's key is {hi of its record's max (min), ~v}.
 #pragma once
-#include "minmax_device.hpp"
+#include "register_decode.hpp"
 
 namespace alpgpu {
 
@@ -39,7 +38,7 @@ struct TopKPass {
 };
 
 template <int VB>
-__device__ __forceinline__ uint64_t top_k_okey(typename PairVec<VB>::T x) {
+__device__ __forceinline__ uint64_t top_k_okey(typename DecodeVec<VB>::T x) {
 	if constexpr (VB == 8) {
 		const uint64_t b = static_cast<uint64_t>(__double_as_longlong(x));
 		return b ^ (static_cast<uint64_t>(static_cast<int64_t>(b) >> 63) | 0x8000000000000000ull);
@@ -49,7 +48,7 @@ __device__ __forceinline__ uint64_t top_k_okey(typename PairVec<VB>::T x) {
 	}
 }
 template <int VB>
-__device__ __forceinline__ bool top_k_is_nan(typename PairVec<VB>::T x) {
+__device__ __forceinline__ bool top_k_is_nan(typename DecodeVec<VB>::T x) {
 	if constexpr (VB == 8) {
 		return (static_cast<uint64_t>(__double_as_longlong(x)) & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull;
 	} else {
@@ -58,7 +57,7 @@ __device__ __forceinline__ bool top_k_is_nan(typename PairVec<VB>::T x) {
 }
 // hi of a value's composite key
 template <int VB>
-__device__ __forceinline__ uint64_t top_k_hi(typename PairVec<VB>::T x, bool largest) {
+__device__ __forceinline__ uint64_t top_k_hi(typename DecodeVec<VB>::T x, bool largest) {
 	const uint64_t o = top_k_okey<VB>(x);
 	return largest ? o : (VB == 8 ? ~o : (~o & 0xFFFFFFFFull));
 }
@@ -75,7 +74,7 @@ __device__ __forceinline__ bool top_k_at_or_above(uint64_t hi, uint64_t lo, uint
 // record v as {min, max}; a vector is empty when min > max (what k_minmax_masked writes for nothing selected or nothing but NaNs)
 template <int VB>
 __device__ __forceinline__ bool top_k_record(const void* zones, uint64_t v, bool largest, uint64_t& hi) {
-	typename PairVec<VB>::T mn, mx;
+	typename DecodeVec<VB>::T mn, mx;
 	if constexpr (VB == 8) {
 		const double2 z = static_cast<const double2*>(zones)[v];
 		mn = z.x, mx = z.y;
@@ -100,12 +99,12 @@ struct TopKCandArgs {
 };
 
 // One wavefront per vector, four per workgroup, sharing nothing.  A vector below Tv costs its record and the threshold; a kept one is decoded in
-// registers, and the values whose bit is set, that are no NaN and whose key reaches the value part of Tv are appended to the candidates, kPairBatch steps
+// registers, and the values whose bit is set, that are no NaN and whose key reaches the value part of Tv are appended to the candidates, kStepBatch steps
 // at a time: one atomic add per batch and wavefront of the batch's ballot popcounts, the slot of a lane from mbcnt.  Every slot is clamped
 // against the capacity, so records that lie cannot make the kernel write outside the array.
 template <int VB>
-__global__ __launch_bounds__(kSelThreads) void k_top_k_candidates(const PairColumn c, const TopKCandArgs g) {
-	typedef typename PairVec<VB>::T T;
+__global__ __launch_bounds__(kSelThreads) void k_top_k_candidates(const ColumnStreams c, const TopKCandArgs g) {
+	typedef typename DecodeVec<VB>::T T;
 	__shared__ uint64_t             s_exc[kSelWaves][16]; // per wavefront: bit p = value p is an exception
 
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -124,29 +123,24 @@ __global__ __launch_bounds__(kSelThreads) void k_top_k_candidates(const PairColu
 	const uint64_t thr_hi = kept < g.k ? 0ull : g.vec->thr_hi;
 
 	// 2. the vector's 128 bytes of bitmap, lane m < 16 holding word m (records that lie may keep a vector without a set bit)
-	const uint64_t prior = lane < 16u ? g.mask[16ull * v + lane] : 0ull;
-	if (ballot64(prior != 0ull) == 0ull) { return; }
+	uint64_t prior;
+	if (!bitmap_words(g.mask, v, lane, prior)) { return; }
 
 	// 3. the descriptor and dictionary, the exception mask
-	const PairVec<VB> A = pair_vec_load<VB>(c, v);
-	if (A.cnt > 0) {
-		if (lane < 16u) { s_exc[wave][lane] = 0ull; }
-		wave_lds_sync();
-		pair_mark_exceptions<VB>(A, s_exc[wave], lane);
-		wave_lds_sync();
-	}
+	const DecodeVec<VB> A = decode_vec_load<VB>(c, v);
+	exception_mask(A, s_exc, wave, lane);
 
 	uint32_t exc_a = 0; // exceptions of the steps done
-	for (uint32_t b = 0; b < 16u; b += kPairBatch) {
-		// 4. every load of kPairBatch steps is requested before the first is used
-		PairBatch<VB> Ra;
-		pair_request<VB>(A, s_exc[wave], b, lane, exc_a, Ra);
+	for (uint32_t b = 0; b < 16u; b += kStepBatch) {
+		// 4. every load of kStepBatch steps is requested before the first is used
+		StepBatch<VB, kStepBatch> Ra;
+		step_request(A, s_exc[wave], b, lane, exc_a, Ra);
 		// 5. the batch's keys and who keeps one
-		uint64_t hi[kPairBatch], keep[kPairBatch];
+		uint64_t hi[kStepBatch], keep[kStepBatch];
 		uint32_t total = 0;
 #pragma unroll
-		for (uint32_t i = 0; i < kPairBatch; ++i) {
-			const T        x = pair_value<VB>(A, Ra, b, i, lane);
+		for (uint32_t i = 0; i < kStepBatch; ++i) {
+			const T        x = step_value(A, Ra, b, i, lane);
 			const uint64_t w = readlane64(prior, b + i);
 			hi[i]            = top_k_hi<VB>(x, largest);
 			keep[i]          = w & ballot64(!top_k_is_nan<VB>(x)) & ballot64(hi[i] >= thr_hi);
@@ -158,7 +152,7 @@ __global__ __launch_bounds__(kSelThreads) void k_top_k_candidates(const PairColu
 		if (lane == 0u) { base = atomicAdd(&g.elem->n_items, total); }
 		base = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(base)));
 #pragma unroll
-		for (uint32_t i = 0; i < kPairBatch; ++i) {
+		for (uint32_t i = 0; i < kStepBatch; ++i) {
 			const uint32_t slot = mbcnt64(keep[i], base);
 			if (((keep[i] >> lane) & 1ull) && slot < g.capacity) {
 				const uint64_t index = (v << 10) + 64u * (b + i) + lane;

@@ -14,6 +14,7 @@
 // kTopKHistGrid workgroups) and a one-wavefront pick that walks the bins from the top and settles the digit and the remaining rank in TopKState.
 // All counts live in device memory and every grid is fixed on the host; integer counts are exact and keys unique, so nothing depends on the order
 // in which wavefronts arrive.  No workgroup waits for another.
+#include "launch.hpp"
 #include "top_k_device.hpp"
 
 namespace alpgpu {
@@ -239,7 +240,7 @@ static int top_k(hipStream_t stream, const alpgpu_column* col, const uint64_t* d
 		g.capacity  = cap;
 		g.k         = k;
 		g.largest   = largest;
-		const PairColumn c {col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc};
+		const ColumnStreams c = column_streams(col);
 		const uint64_t   n_wg = (nv + kSelWaves - 1) / kSelWaves;
 		for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
 			g.wg_off = off;

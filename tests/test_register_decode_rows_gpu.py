@@ -1,6 +1,6 @@
-"""GPU: every consumer that decodes a vector in registers, on the hand-built vectors of every packed width — the arms of k_select behind the selection
-bitmaps (select_device.hpp: alpgpu_select_mask_*, alpgpu_decode_sum_masked_*, alpgpu_decode_masked_*) and the second copy of that decode, PairVec /
-pair_request / pair_value (pair_device.hpp), under k_pair (compare, dot), k_group (three tiers), k_minmax_masked, k_group_minmax (three tiers) and k_in_list
+"""GPU: the one in-register decode of a vector (register_decode.hpp: DecodeVec / step_request / step_value) under each of its seven kernels, on the
+hand-built vectors of every packed width — the arms of k_select behind the selection bitmaps (select_device.hpp: alpgpu_select_mask_*,
+alpgpu_decode_sum_masked_*, alpgpu_decode_masked_*), k_pair (compare, dot), k_group (three tiers), k_minmax_masked, k_group_minmax (three tiers) and k_in_list
 (the LDS and the global arm).  The suites of those features read columns the encoder produces from datagen; here the columns are float_rows.py (widths 0..32,
 cuts 16..31) and double_rows.py (widths 0..64, cuts 48..63): every width under every factor, bases on the bounds of the conversion shortcut and at the ends
 of the integer range, exception records on both sides of every lane count and stage, every ALP_RD cut with a dictionary of its own.
@@ -249,7 +249,7 @@ def test_decode_masked(ctx, cols, mname):
 
 
 # =====================================================================================================================================================
-# PairVec under k_pair
+# the decode under k_pair
 # =====================================================================================================================================================
 @pytest.mark.parametrize("cmp", sorted(CMPS))
 def test_compare_mask(ctx, cols, cmp):
@@ -279,7 +279,7 @@ def test_decode_dot_masked(ctx, cols, mname):
 
 
 # =====================================================================================================================================================
-# PairVec under k_group and k_group_minmax: the value column is A, the key column is B
+# the decode under k_group and k_group_minmax: the value column is A, the key column is B
 # =====================================================================================================================================================
 GROUP_MASK = {1: "full", 4: "random", 5: "cleared", 16: "random"}
 
@@ -310,7 +310,7 @@ def test_decode_group_minmax(ctx, cols, n_groups):
 
 
 # =====================================================================================================================================================
-# PairVec under k_minmax_masked
+# the decode under k_minmax_masked
 # =====================================================================================================================================================
 @pytest.mark.parametrize("mname", ["full", "random"])
 def test_decode_minmax_masked(ctx, cols, mname):
@@ -327,7 +327,7 @@ def test_decode_minmax_masked(ctx, cols, mname):
 
 
 # =====================================================================================================================================================
-# PairVec under k_in_list: the whole list in LDS, its edge, and pivots in LDS with the list in L2
+# the decode under k_in_list: the whole list in LDS, its edge, and pivots in LDS with the list in L2
 # =====================================================================================================================================================
 IN_LISTS = ("about 50", "lds_max", "lds_max + 1")
 
