@@ -10,11 +10,11 @@ static int group_sum(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_col
                      uint32_t* d_counts, int value_bytes) {
 	if (!val || !key) { return fail(ALPGPU_ERR_INVALID, "null column"); }
 	if (val->n_vectors != key->n_vectors) { return fail(ALPGPU_ERR_INVALID, "the columns differ in n_vectors"); }
-	if (val->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
+	ALPGPU_TRY(check_n_vectors(val->n_vectors, "column.n_vectors is implausible"));
 	if (val->n_vectors == 0) { return ALPGPU_OK; }
 	if (!d_mask || !d_sums) { return fail(ALPGPU_ERR_INVALID, "null bitmap or sums"); }
-	if (reinterpret_cast<uintptr_t>(d_mask) & 7u) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
-	if (!val->d_vectors || !val->d_rowgroups || !key->d_vectors || !key->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	ALPGPU_TRY(check_bitmap_aligned(d_mask));
+	ALPGPU_TRY(check_has_descriptors(val, key));
 	const int rc = alpgpu::launch_group_sum(ctx->stream, val, key, d_mask, lo, hi, n_groups, d_sums, d_counts, value_bytes);
 	if (rc != ALPGPU_OK) { return fail(rc, "decode_group_sum launch failed"); } // (the launcher has read the HIP error)
 	return ALPGPU_OK;
@@ -59,7 +59,7 @@ int alpgpu_group_totals(alpgpu_ctx* ctx, const double* d_sums, const uint32_t* d
 	ALPGPU_CHECK_CTX(ctx);
 	if (n_groups == 0 || n_groups > ALPGPU_GROUP_MAX) { return fail(ALPGPU_ERR_INVALID, "n_groups is not in 1 .. ALPGPU_GROUP_MAX"); }
 	if (!d_total_sums) { return fail(ALPGPU_ERR_INVALID, "null totals"); }
-	if (n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "n_vectors is implausible"); }
+	ALPGPU_TRY(check_n_vectors(n_vectors, "n_vectors is implausible"));
 	if (n_vectors == 0) { // no row holds anything, so neither input is looked at: an empty array's pointer may well be NULL
 		ALPGPU_HIP(hipMemsetAsync(d_total_sums, 0, sizeof(double) * n_groups, ctx->stream));
 		if (d_total_counts) { ALPGPU_HIP(hipMemsetAsync(d_total_counts, 0, sizeof(uint64_t) * n_groups, ctx->stream)); }
@@ -67,7 +67,7 @@ int alpgpu_group_totals(alpgpu_ctx* ctx, const double* d_sums, const uint32_t* d
 	}
 	if (!d_sums) { return fail(ALPGPU_ERR_INVALID, "null sums"); }
 	if ((d_counts == nullptr) != (d_total_counts == nullptr)) { return fail(ALPGPU_ERR_INVALID, "counts without their totals, or totals without counts"); }
-	if (n_vectors > 1024 && (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15u))) { return fail(ALPGPU_ERR_INVALID, "scratch is null or not 16-byte aligned"); }
+	if (n_vectors > 1024 && (!d_scratch || misaligned(d_scratch, 16u))) { return fail(ALPGPU_ERR_INVALID, "scratch is null or not 16-byte aligned"); }
 	const int rc = alpgpu::launch_group_totals(ctx->stream, d_sums, d_counts, n_vectors, n_groups, d_total_sums, d_total_counts, d_scratch);
 	if (rc != ALPGPU_OK) { return fail(rc, "group_totals launch failed"); }
 	return ALPGPU_OK;

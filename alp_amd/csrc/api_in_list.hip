@@ -4,26 +4,22 @@
 #include "host_ctx.hpp"
 
 extern "C++" {
-// op, first, n: the checks and the n == 0 behaviour of alpgpu_select_mask_* (api_mask.hip: select_mask)
+// op, first, n: checked, and an empty range settled, as by alpgpu_select_mask_* (the shared checks of host_ctx.hpp)
 static int select_in_mask(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const void* d_list, uint64_t n_list, int negate, const void* d_zones, int op,
                           uint64_t* d_mask, int value_bytes) {
 	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }
-	if (op != ALPGPU_MASK_SET && op != ALPGPU_MASK_AND && op != ALPGPU_MASK_OR) { return fail(ALPGPU_ERR_INVALID, "op is none of ALPGPU_MASK_SET / _AND / _OR"); }
-	if (col->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
-	const uint64_t n_values = col->n_vectors << 10;
-	if (first > n_values || n > n_values - first) { return fail(ALPGPU_ERR_INVALID, "range reaches past the column's last value"); } // (first + n without the overflow)
-	if (misaligned(d_mask, 8u)) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	ALPGPU_TRY(check_mask_op(op));
+	ALPGPU_TRY(check_n_vectors(col->n_vectors, "column.n_vectors is implausible"));
+	ALPGPU_TRY(check_value_range(col->n_vectors, first, n, "range reaches past the column's last value"));
+	ALPGPU_TRY(check_bitmap_aligned(d_mask));
 	if (n_list > 0x7FFFFFFFull) { return fail(ALPGPU_ERR_INVALID, "n_list is beyond 2^31 - 1"); }
 	if (n_list > 0 && !d_list) { return fail(ALPGPU_ERR_INVALID, "null list with n_list > 0"); }
 	if (misaligned(d_list, static_cast<unsigned>(value_bytes))) { return fail(ALPGPU_ERR_INVALID, "list is not aligned to its elements"); }
 	if (misaligned(d_zones, 2u * value_bytes)) { return fail(ALPGPU_ERR_INVALID, "zones are not aligned to their records"); }
 	if (col->n_vectors == 0) { return ALPGPU_OK; }
 	if (!d_mask) { return fail(ALPGPU_ERR_INVALID, "null bitmap"); }
-	if (n == 0) { // nothing qualifies, negated or not: SET and AND clear every bit, OR changes none
-		if (op != ALPGPU_MASK_OR) { ALPGPU_HIP(hipMemsetAsync(d_mask, 0, 128ull * col->n_vectors, ctx->stream)); }
-		return ALPGPU_OK;
-	}
-	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	if (n == 0) { return clear_bitmap_for_empty_range(ctx, op, d_mask, col); }
+	ALPGPU_TRY(check_has_descriptors(col));
 	const int rc = alpgpu::launch_select_in_mask(ctx->stream, col, first, n, d_list, n_list, negate, d_zones, op, d_mask, value_bytes, ctx->n_cus);
 	if (rc != ALPGPU_OK) { return fail(rc, "select_in_mask launch failed"); } // (the launcher has read the HIP error)
 	return ALPGPU_OK;

@@ -7,18 +7,14 @@
 extern "C++" {
 static int select_mask(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int op, uint64_t* d_mask, int value_bytes) {
 	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }
-	if (op != ALPGPU_MASK_SET && op != ALPGPU_MASK_AND && op != ALPGPU_MASK_OR) { return fail(ALPGPU_ERR_INVALID, "op is none of ALPGPU_MASK_SET / _AND / _OR"); }
-	if (col->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
-	const uint64_t n_values = col->n_vectors << 10;
-	if (first > n_values || n > n_values - first) { return fail(ALPGPU_ERR_INVALID, "range reaches past the column's last value"); } // (first + n without the overflow)
-	if (reinterpret_cast<uintptr_t>(d_mask) & 7u) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	ALPGPU_TRY(check_mask_op(op));
+	ALPGPU_TRY(check_n_vectors(col->n_vectors, "column.n_vectors is implausible"));
+	ALPGPU_TRY(check_value_range(col->n_vectors, first, n, "range reaches past the column's last value"));
+	ALPGPU_TRY(check_bitmap_aligned(d_mask));
 	if (col->n_vectors == 0) { return ALPGPU_OK; }
 	if (!d_mask) { return fail(ALPGPU_ERR_INVALID, "null bitmap"); }
-	if (n == 0) { // nothing qualifies: SET and AND clear every bit, OR changes none
-		if (op != ALPGPU_MASK_OR) { ALPGPU_HIP(hipMemsetAsync(d_mask, 0, 128ull * col->n_vectors, ctx->stream)); }
-		return ALPGPU_OK;
-	}
-	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	if (n == 0) { return clear_bitmap_for_empty_range(ctx, op, d_mask, col); }
+	ALPGPU_TRY(check_has_descriptors(col));
 	const int rc = alpgpu::launch_select_mask(ctx->stream, col, first, n, lo, hi, op, d_mask, value_bytes);
 	if (rc != ALPGPU_OK) { return fail(rc, "select_mask launch failed"); } // (the launcher has read the HIP error)
 	return ALPGPU_OK;
@@ -26,11 +22,11 @@ static int select_mask(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first
 
 static int sum_masked(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts, int value_bytes) {
 	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }
-	if (reinterpret_cast<uintptr_t>(d_mask) & 7u) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	ALPGPU_TRY(check_bitmap_aligned(d_mask));
 	if (col->n_vectors == 0) { return ALPGPU_OK; }
 	if (!d_mask || !d_sums) { return fail(ALPGPU_ERR_INVALID, "null bitmap or sums"); }
-	if (col->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
-	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	ALPGPU_TRY(check_n_vectors(col->n_vectors, "column.n_vectors is implausible"));
+	ALPGPU_TRY(check_has_descriptors(col));
 	const int rc = alpgpu::launch_sum_masked(ctx->stream, col, d_mask, d_sums, d_counts, value_bytes);
 	if (rc != ALPGPU_OK) { return fail(rc, "decode_sum_masked launch failed"); }
 	return ALPGPU_OK;
@@ -41,15 +37,15 @@ static int decode_masked(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64
 	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }
 	if (!d_count) { return fail(ALPGPU_ERR_INVALID, "null count"); }
 	if (!d_mask) { return fail(ALPGPU_ERR_INVALID, "null bitmap"); }
-	if (reinterpret_cast<uintptr_t>(d_mask) & 7u) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	ALPGPU_TRY(check_bitmap_aligned(d_mask));
 	if (capacity > 0 && !d_vals) { return fail(ALPGPU_ERR_INVALID, "null value output with a capacity"); }
-	if (col->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
+	ALPGPU_TRY(check_n_vectors(col->n_vectors, "column.n_vectors is implausible"));
 	if (col->n_vectors == 0) { // no bit at all: the count alone is written
 		ALPGPU_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
 		return ALPGPU_OK;
 	}
-	if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15u)) { return fail(ALPGPU_ERR_INVALID, "scratch is null or not 16-byte aligned"); }
-	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	if (!d_scratch || misaligned(d_scratch, 16u)) { return fail(ALPGPU_ERR_INVALID, "scratch is null or not 16-byte aligned"); }
+	ALPGPU_TRY(check_has_descriptors(col));
 	const int rc = alpgpu::launch_decode_masked(ctx->stream, col, d_mask, d_vals, d_idx, capacity, d_count, d_scratch, value_bytes);
 	if (rc != ALPGPU_OK) { return fail(rc, "decode_masked launch failed"); }
 	return ALPGPU_OK;
@@ -70,15 +66,15 @@ int alpgpu_select_mask_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t f
 int alpgpu_mask_to_indices(alpgpu_ctx* ctx, const uint64_t* d_mask, uint64_t n_vectors, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch) {
 	ALPGPU_CHECK_CTX(ctx);
 	if (!d_count) { return fail(ALPGPU_ERR_INVALID, "null count"); }
-	if (n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "n_vectors is implausible"); }
-	if (reinterpret_cast<uintptr_t>(d_mask) & 7u) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	ALPGPU_TRY(check_n_vectors(n_vectors, "n_vectors is implausible"));
+	ALPGPU_TRY(check_bitmap_aligned(d_mask));
 	if (capacity > 0 && !d_idx) { return fail(ALPGPU_ERR_INVALID, "null index output with a capacity"); }
 	if (n_vectors == 0) { // no bit at all: the count alone is written
 		ALPGPU_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
 		return ALPGPU_OK;
 	}
 	if (!d_mask) { return fail(ALPGPU_ERR_INVALID, "null bitmap"); }
-	if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15u)) { return fail(ALPGPU_ERR_INVALID, "scratch is null or not 16-byte aligned"); }
+	if (!d_scratch || misaligned(d_scratch, 16u)) { return fail(ALPGPU_ERR_INVALID, "scratch is null or not 16-byte aligned"); }
 	const int rc = alpgpu::launch_mask_to_indices(ctx->stream, d_mask, n_vectors, d_idx, capacity, d_count, d_scratch);
 	if (rc != ALPGPU_OK) { return fail(rc, "mask_to_indices launch failed"); }
 	return ALPGPU_OK;

@@ -8,12 +8,12 @@
 extern "C++" {
 static int minmax_masked(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, void* d_zones, uint32_t* d_counts, int value_bytes) {
 	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }
-	if (misaligned(d_mask, 8u)) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	ALPGPU_TRY(check_bitmap_aligned(d_mask));
 	if (misaligned(d_zones, 2u * value_bytes)) { return fail(ALPGPU_ERR_INVALID, "records are not aligned to their size"); } // (16 / 8 bytes: the kernels store and load a record at once)
 	if (col->n_vectors == 0) { return ALPGPU_OK; }
 	if (!d_mask || !d_zones) { return fail(ALPGPU_ERR_INVALID, "null bitmap or records"); }
-	if (col->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
-	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	ALPGPU_TRY(check_n_vectors(col->n_vectors, "column.n_vectors is implausible"));
+	ALPGPU_TRY(check_has_descriptors(col));
 	const int rc = alpgpu::launch_minmax_masked(ctx->stream, col, d_mask, d_zones, d_counts, value_bytes);
 	if (rc != ALPGPU_OK) { return fail(rc, "decode_minmax_masked launch failed"); } // (the launcher has read the HIP error)
 	return ALPGPU_OK;
@@ -24,12 +24,12 @@ static int group_minmax(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_
                         void* d_zones, uint32_t* d_counts, int value_bytes) {
 	if (!val || !key) { return fail(ALPGPU_ERR_INVALID, "null column"); }
 	if (val->n_vectors != key->n_vectors) { return fail(ALPGPU_ERR_INVALID, "the columns differ in n_vectors"); }
-	if (val->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
-	if (misaligned(d_mask, 8u)) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	ALPGPU_TRY(check_n_vectors(val->n_vectors, "column.n_vectors is implausible"));
+	ALPGPU_TRY(check_bitmap_aligned(d_mask));
 	if (misaligned(d_zones, 2u * value_bytes)) { return fail(ALPGPU_ERR_INVALID, "records are not aligned to their size"); }
 	if (val->n_vectors == 0) { return ALPGPU_OK; }
 	if (!d_mask || !d_zones) { return fail(ALPGPU_ERR_INVALID, "null bitmap or records"); }
-	if (!val->d_vectors || !val->d_rowgroups || !key->d_vectors || !key->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	ALPGPU_TRY(check_has_descriptors(val, key));
 	const int rc = alpgpu::launch_group_minmax(ctx->stream, val, key, d_mask, lo, hi, n_groups, d_zones, d_counts, value_bytes);
 	if (rc != ALPGPU_OK) { return fail(rc, "decode_group_minmax launch failed"); }
 	return ALPGPU_OK;
@@ -45,7 +45,7 @@ static int group_minmax_totals(alpgpu_ctx* ctx, const void* d_zones, uint64_t n_
 	if (n_groups == 0 || n_groups > ALPGPU_GROUP_MAX) { return fail(ALPGPU_ERR_INVALID, "n_groups is not in 1 .. ALPGPU_GROUP_MAX"); }
 	if (!d_minmax || (n_vectors > 0 && !d_zones)) { return fail(ALPGPU_ERR_INVALID, "null records or result"); }
 	if (misaligned(d_zones, 2u * value_bytes) || misaligned(d_minmax, value_bytes)) { return fail(ALPGPU_ERR_INVALID, "records not aligned to their size or result not to its type"); }
-	if (n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "n_vectors is implausible"); }
+	ALPGPU_TRY(check_n_vectors(n_vectors, "n_vectors is implausible"));
 	const int rc = alpgpu::launch_group_minmax_totals(ctx->stream, d_zones, n_vectors, n_groups, d_minmax, value_bytes);
 	if (rc != ALPGPU_OK) { return fail(rc, "group_minmax_totals launch failed"); }
 	return ALPGPU_OK;

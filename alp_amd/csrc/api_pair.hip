@@ -9,25 +9,21 @@ extern "C++" {
 static int check_pair(const alpgpu_column* a, const alpgpu_column* b, const void* d_mask) {
 	if (!a || !b) { return fail(ALPGPU_ERR_INVALID, "null column"); }
 	if (a->n_vectors != b->n_vectors) { return fail(ALPGPU_ERR_INVALID, "the columns differ in n_vectors"); }
-	if (a->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
-	if (reinterpret_cast<uintptr_t>(d_mask) & 7u) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	ALPGPU_TRY(check_n_vectors(a->n_vectors, "column.n_vectors is implausible"));
+	ALPGPU_TRY(check_bitmap_aligned(d_mask));
 	return ALPGPU_OK;
 }
 
 static int compare_mask(alpgpu_ctx* ctx, const alpgpu_column* a, const alpgpu_column* b, uint64_t first, uint64_t n, int cmp, int op, uint64_t* d_mask, int value_bytes) {
 	if (cmp < ALPGPU_CMP_LT || cmp > ALPGPU_CMP_NE) { return fail(ALPGPU_ERR_INVALID, "cmp is none of ALPGPU_CMP_LT .. _NE"); }
-	if (op != ALPGPU_MASK_SET && op != ALPGPU_MASK_AND && op != ALPGPU_MASK_OR) { return fail(ALPGPU_ERR_INVALID, "op is none of ALPGPU_MASK_SET / _AND / _OR"); }
+	ALPGPU_TRY(check_mask_op(op));
 	const int ok = check_pair(a, b, d_mask);
 	if (ok != ALPGPU_OK) { return ok; }
-	const uint64_t n_values = a->n_vectors << 10;
-	if (first > n_values || n > n_values - first) { return fail(ALPGPU_ERR_INVALID, "range reaches past the columns' last value"); } // (first + n without the overflow)
+	ALPGPU_TRY(check_value_range(a->n_vectors, first, n, "range reaches past the columns' last value"));
 	if (a->n_vectors == 0) { return ALPGPU_OK; }
 	if (!d_mask) { return fail(ALPGPU_ERR_INVALID, "null bitmap"); }
-	if (n == 0) { // nothing qualifies: SET and AND clear every bit, OR changes none
-		if (op != ALPGPU_MASK_OR) { ALPGPU_HIP(hipMemsetAsync(d_mask, 0, 128ull * a->n_vectors, ctx->stream)); }
-		return ALPGPU_OK;
-	}
-	if (!a->d_vectors || !a->d_rowgroups || !b->d_vectors || !b->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	if (n == 0) { return clear_bitmap_for_empty_range(ctx, op, d_mask, a); }
+	ALPGPU_TRY(check_has_descriptors(a, b));
 	const int rc = alpgpu::launch_compare_mask(ctx->stream, a, b, first, n, cmp, op, d_mask, value_bytes);
 	if (rc != ALPGPU_OK) { return fail(rc, "compare_mask launch failed"); } // (the launcher has read the HIP error)
 	return ALPGPU_OK;
@@ -38,7 +34,7 @@ static int dot_masked(alpgpu_ctx* ctx, const alpgpu_column* a, const alpgpu_colu
 	if (ok != ALPGPU_OK) { return ok; }
 	if (a->n_vectors == 0) { return ALPGPU_OK; }
 	if (!d_mask || !d_sums) { return fail(ALPGPU_ERR_INVALID, "null bitmap or sums"); }
-	if (!a->d_vectors || !a->d_rowgroups || !b->d_vectors || !b->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	ALPGPU_TRY(check_has_descriptors(a, b));
 	const int rc = alpgpu::launch_dot_masked(ctx->stream, a, b, d_mask, d_sums, d_counts, value_bytes);
 	if (rc != ALPGPU_OK) { return fail(rc, "decode_dot_masked launch failed"); }
 	return ALPGPU_OK;

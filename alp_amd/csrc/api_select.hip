@@ -9,17 +9,16 @@ extern "C++" {
 static int select_range(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int64_t* d_idx, void* d_vals,
                         uint64_t capacity, uint64_t* d_count, void* d_scratch, int value_bytes, const void* d_zones = nullptr, bool zoned = false) {
 	if (!col || !d_count) { return fail(ALPGPU_ERR_INVALID, "null column or count"); }
-	if (col->n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
-	const uint64_t n_values = col->n_vectors << 10;
-	if (first > n_values || n > n_values - first) { return fail(ALPGPU_ERR_INVALID, "range reaches past the column's last value"); } // (first + n without the overflow)
+	ALPGPU_TRY(check_n_vectors(col->n_vectors, "column.n_vectors is implausible"));
+	ALPGPU_TRY(check_value_range(col->n_vectors, first, n, "range reaches past the column's last value"));
 	if (capacity > 0 && !d_idx) { return fail(ALPGPU_ERR_INVALID, "null index output with a capacity"); }
 	if (n == 0) { // nothing can qualify: the count alone is written
 		ALPGPU_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
 		return ALPGPU_OK;
 	}
-	if (zoned && (!d_zones || (reinterpret_cast<uintptr_t>(d_zones) & (2u * value_bytes - 1u)))) { return fail(ALPGPU_ERR_INVALID, "zone map is null or not aligned to its records"); }
-	if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15u)) { return fail(ALPGPU_ERR_INVALID, "scratch is null or not 16-byte aligned"); }
-	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	if (zoned && (!d_zones || misaligned(d_zones, 2u * value_bytes))) { return fail(ALPGPU_ERR_INVALID, "zone map is null or not aligned to its records"); }
+	if (!d_scratch || misaligned(d_scratch, 16u)) { return fail(ALPGPU_ERR_INVALID, "scratch is null or not 16-byte aligned"); }
+	ALPGPU_TRY(check_has_descriptors(col));
 	const int rc = alpgpu::launch_select_range(ctx->stream, col, first, n, lo, hi, d_idx, d_vals, capacity, d_count, d_scratch, value_bytes, zoned ? d_zones : nullptr);
 	if (rc != ALPGPU_OK) { return fail(rc, "select launch failed"); } // (the launcher has read the HIP error)
 	return ALPGPU_OK;

@@ -14,7 +14,7 @@ static int top_k(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_ma
 	if (misaligned(d_vals, value_bytes) || misaligned(d_idx, 8u)) { return fail(ALPGPU_ERR_INVALID, "values or indices are not aligned to their type"); }
 	if (misaligned(d_records, 16u) || misaligned(d_scratch, 16u)) { return fail(ALPGPU_ERR_INVALID, "records or scratch are not 16-byte aligned"); }
 	if (col->n_vectors > 0xFFFFFFFFull) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is implausible"); }
-	if (col->n_vectors > 0 && (!col->d_vectors || !col->d_rowgroups)) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	if (col->n_vectors > 0) { ALPGPU_TRY(check_has_descriptors(col)); }
 	if (k == 0 || col->n_vectors == 0) { // nothing to select: the count alone is written
 		ALPGPU_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
 		return ALPGPU_OK;

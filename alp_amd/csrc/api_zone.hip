@@ -11,7 +11,7 @@ static int zone_map(alpgpu_ctx* ctx, const alpgpu_column* col, void* d_zones, in
 	if (!col) { return fail(ALPGPU_ERR_INVALID, "null column"); }
 	if (col->n_vectors == 0) { return ALPGPU_OK; }
 	if (!d_zones || misaligned(d_zones, 2u * value_bytes)) { return fail(ALPGPU_ERR_INVALID, "zone output is null or not aligned to its records"); }
-	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	ALPGPU_TRY(check_has_descriptors(col));
 	const int rc = value_bytes == 8 ? alpgpu::launch_zone_map(ctx->stream, col, d_zones) : alpgpu::launch_zone_map_f32(ctx->stream, col, d_zones);
 	if (rc != ALPGPU_OK) { return fail(rc, "zone map launch failed"); }
 	return ALPGPU_OK;

@@ -10,6 +10,7 @@ namespace alpgpu {
 // the groups' closed ranges in the key's own type: kernel arguments, wave-uniform.  The host pads the tier's unused groups with lo > hi.
 template <int VB, int GT>
 struct GroupBounds {
+	static constexpr int      kTier = GT;
 	typename DecodeVec<VB>::T lo[GT], hi[GT];
 };
 struct GroupArgs {
@@ -93,6 +94,22 @@ __global__ __launch_bounds__(kSelThreads) void k_group(const ColumnStreams cv, c
 			}
 		}
 	}
+}
+
+// Host side, for k_group and k_group_minmax: the bounds of the smallest tier GT = 4, 8 or 16 that holds n_groups, in the key's own type (a float entry
+// point's bounds are floats: they pass through double unchanged), the tier's unused groups padded with lo = 1 > hi = 0.  launch(bounds) launches the
+// kernel of decltype(bounds)::kTier and returns the call's result.
+template <int VB, class Launch>
+inline int with_group_tier(const double* lo, const double* hi, uint32_t n_groups, Launch&& launch) {
+	typedef typename DecodeVec<VB>::T T;
+	const auto tier = [&](auto r) {
+		for (uint32_t j = 0; j < static_cast<uint32_t>(decltype(r)::kTier); ++j) {
+			r.lo[j] = j < n_groups ? static_cast<T>(lo[j]) : static_cast<T>(1);
+			r.hi[j] = j < n_groups ? static_cast<T>(hi[j]) : static_cast<T>(0);
+		}
+		return launch(r);
+	};
+	return n_groups <= 4u ? tier(GroupBounds<VB, 4> {}) : n_groups <= 8u ? tier(GroupBounds<VB, 8> {}) : tier(GroupBounds<VB, 16> {});
 }
 
 } // namespace alpgpu

@@ -14,30 +14,15 @@
 
 namespace alpgpu {
 
-template <int VB, int GT>
-static int launch_group_tier(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, GroupArgs args, const double* lo, const double* hi) {
-	typedef typename DecodeVec<VB>::T T;
-	GroupBounds<VB, GT>             r;
-	for (uint32_t j = 0; j < static_cast<uint32_t>(GT); ++j) { // (a float entry point's bounds are floats: they pass through double unchanged)
-		r.lo[j] = j < args.n_groups ? static_cast<T>(lo[j]) : static_cast<T>(1);
-		r.hi[j] = j < args.n_groups ? static_cast<T>(hi[j]) : static_cast<T>(0);
-	}
-	const ColumnStreams cv = column_streams(val), ck = column_streams(key);
-	const uint64_t   n_wg = (args.n_vectors + kSelWaves - 1) / kSelWaves;
-	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
-		const uint64_t n = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;
-		args.wg_off      = off;
-		hipLaunchKernelGGL((k_group<VB, GT>), dim3(static_cast<unsigned>(n)), dim3(kSelThreads), 0, stream, cv, ck, args, r);
-		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
-	}
-	return ALPGPU_OK;
-}
-
 template <int VB>
-static int launch_group_vb(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const GroupArgs& args, const double* lo, const double* hi) {
-	return args.n_groups <= 4u   ? launch_group_tier<VB, 4>(stream, val, key, args, lo, hi)
-	       : args.n_groups <= 8u ? launch_group_tier<VB, 8>(stream, val, key, args, lo, hi)
-	                             : launch_group_tier<VB, 16>(stream, val, key, args, lo, hi);
+static int group_sum(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, GroupArgs args, const double* lo, const double* hi) {
+	const ColumnStreams cv = column_streams(val), ck = column_streams(key);
+	return with_group_tier<VB>(lo, hi, args.n_groups, [&](auto r) {
+		return launch_vectors(args.n_vectors, kSelWaves, [&](dim3 grid, uint64_t off) {
+			args.wg_off = off;
+			hipLaunchKernelGGL((k_group<VB, decltype(r)::kTier>), grid, dim3(kSelThreads), 0, stream, cv, ck, args, r);
+		});
+	});
 }
 
 // val->n_vectors == key->n_vectors > 0, 1 <= n_groups <= ALPGPU_GROUP_MAX (the caller checked)
@@ -49,7 +34,7 @@ int launch_group_sum(hipStream_t stream, const alpgpu_column* val, const alpgpu_
 	args.sums      = d_sums;
 	args.counts    = d_counts;
 	args.n_groups  = n_groups;
-	return value_bytes == 8 ? launch_group_vb<8>(stream, val, key, args, lo, hi) : launch_group_vb<4>(stream, val, key, args, lo, hi);
+	return value_bytes == 8 ? group_sum<8>(stream, val, key, args, lo, hi) : group_sum<4>(stream, val, key, args, lo, hi);
 }
 
 // ---- the groups' totals -------------------------------------------------------------------------------------------------------------------------

@@ -108,6 +108,13 @@ using alpgpu_host::g_err;
 		ALPGPU_HIP(hipSetDevice((ctx)->device));                                                                        \
 	} while (0)
 
+// an argument check (below) or a helper that has already called fail(): its error is the entry point's
+#define ALPGPU_TRY(call)                                                                                                \
+	do {                                                                                                                \
+		const int rc_ = (call);                                                                                         \
+		if (rc_ != ALPGPU_OK) { return rc_; }                                                                           \
+	} while (0)
+
 #define ALPGPU_PRIM(cond_ok, call)                                                                                      \
 	do {                                                                                                                \
 		ALPGPU_CHECK_CTX(ctx);                                                                                          \
@@ -134,3 +141,38 @@ ALPGPU_INTERNAL int  validate_blob_vectors(const void* h_blob, const alpgpu_blob
 inline uint64_t align8(uint64_t x) { return (x + 7ull) & ~7ull; }
 // p does not lie on a multiple of `bytes` (a power of two); a null pointer never is misaligned
 inline bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) != 0; }
+
+// ---- argument checks that several entry points make (api_mask, api_pair, api_in_list, api_select, api_group, api_minmax, api_top_k, api_zone): each
+// returns ALPGPU_OK or fail(...); hidden, like the helpers above.  An entry point calls them in the order in which it reports its errors.
+ALPGPU_INTERNAL inline int check_mask_op(int op) {
+	if (op != ALPGPU_MASK_SET && op != ALPGPU_MASK_AND && op != ALPGPU_MASK_OR) { return fail(ALPGPU_ERR_INVALID, "op is none of ALPGPU_MASK_SET / _AND / _OR"); }
+	return ALPGPU_OK;
+}
+// n_vectors << 10, the number of values, must not overflow; text: "column.n_vectors is implausible" or "n_vectors is implausible", as the caller knows it
+ALPGPU_INTERNAL inline int check_n_vectors(uint64_t n_vectors, const char* text) {
+	if (n_vectors > (~0ull >> 10)) { return fail(ALPGPU_ERR_INVALID, text); }
+	return ALPGPU_OK;
+}
+// [first, first + n) lies within the n_vectors << 10 values (check_n_vectors came first); text: "range reaches past the column's last value" or "... columns' ..."
+ALPGPU_INTERNAL inline int check_value_range(uint64_t n_vectors, uint64_t first, uint64_t n, const char* text) {
+	const uint64_t n_values = n_vectors << 10;
+	if (first > n_values || n > n_values - first) { return fail(ALPGPU_ERR_INVALID, text); } // (first + n without the overflow)
+	return ALPGPU_OK;
+}
+ALPGPU_INTERNAL inline int check_bitmap_aligned(const void* d_mask) {
+	if (misaligned(d_mask, 8u)) { return fail(ALPGPU_ERR_INVALID, "bitmap is not 8-byte aligned"); }
+	return ALPGPU_OK;
+}
+ALPGPU_INTERNAL inline int check_has_descriptors(const alpgpu_column* col) {
+	if (!col->d_vectors || !col->d_rowgroups) { return fail(ALPGPU_ERR_INVALID, "column has no descriptors"); }
+	return ALPGPU_OK;
+}
+ALPGPU_INTERNAL inline int check_has_descriptors(const alpgpu_column* a, const alpgpu_column* b) {
+	ALPGPU_TRY(check_has_descriptors(a));
+	return check_has_descriptors(b);
+}
+// a bitmap entry point whose range is empty (n == 0): nothing qualifies, so SET and AND clear every bit and OR changes none
+ALPGPU_INTERNAL inline int clear_bitmap_for_empty_range(alpgpu_ctx* ctx, int op, uint64_t* d_mask, const alpgpu_column* col) {
+	if (op != ALPGPU_MASK_OR) { ALPGPU_HIP(hipMemsetAsync(d_mask, 0, 128ull * col->n_vectors, ctx->stream)); }
+	return ALPGPU_OK;
+}

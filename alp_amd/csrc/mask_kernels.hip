@@ -1,15 +1,15 @@
 // mask_kernels.hip — selection bitmaps (include/alpgpu.h): a predicate's qualify mask kept as 16 words per vector instead of being counted away,
 // so that a second column's predicate combines with it where the ballot is made, and what is left is listed or summed at the very end.
 //
-//   alpgpu_select_mask_*         k_select<VB, false, SelMaskArgs> (select_device.hpp): one wavefront per vector, the decode of the selection with its 16
+//   alpgpu_select_mask_*         k_select<VB, kSelMask> (select_device.hpp): one wavefront per vector, the decode of the selection with its 16
 //                                ballots stored, SET / AND / OR with what the bitmap held.  A vector outside the range, an all-zero vector under AND
 //                                and an all-ones vector under OR cost their 128 bytes of bitmap and nothing of the column.
 //   alpgpu_mask_to_indices       k_mask_count (per-vector popcount) -> launch_select_scan (select_kernels.hip) -> k_mask_emit: three launches
 //                                ordered by kernel boundaries.  A set bit's position = its vector's offset from the prefix sum + the set bits of
 //                                the words before + v_mbcnt of its own word: ascending, and no atomic anywhere.
-//   alpgpu_decode_sum_masked_*   k_select<VB, false, SelSumArgs>: the same decode, each lane adding the values whose bit is set; the order is in
+//   alpgpu_decode_sum_masked_*   k_select<VB, kSelSum>: the same decode, each lane adding the values whose bit is set; the order is in
 //                                include/alpgpu.h and belongs to this entry point (the persistent consumer of consume_kernels.hip has its own).
-//   alpgpu_decode_masked_*       k_mask_count -> launch_select_scan -> k_select<VB, false, SelTakeArgs>: the projection of a column under a bitmap.
+//   alpgpu_decode_masked_*       k_mask_count -> launch_select_scan -> k_select<VB, kSelTake>: the projection of a column under a bitmap.
 //                                The emit pass is the selection's with the predicate replaced by a bit test: a vector's values at its set bits,
 //                                compacted at offsets[v] + rank (and their indices beside them, as k_mask_emit writes them).
 //
@@ -53,93 +53,66 @@ __global__ __launch_bounds__(kSelThreads) void k_mask_emit(const uint64_t* __res
 	}
 }
 
-// one launch of k_select's mask / sum arm over vectors [v0, v0 + n_range), split only at the grid limit
-template <int VB, class ARGS>
-static int launch_arm(hipStream_t stream, const alpgpu_column* col, uint64_t v0, uint64_t n_range, uint64_t first, uint64_t end, double lo, double hi, const ARGS& args) {
-	const uint64_t n_wg = (n_range + kSelWaves - 1) / kSelWaves;
-	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
-		const uint64_t g = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;
-		hipLaunchKernelGGL((k_select<VB, false, ARGS>), dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc,
-		                   v0, n_range, off, first, end, lo, hi, static_cast<uint32_t*>(nullptr), static_cast<const uint64_t*>(nullptr), static_cast<int64_t*>(nullptr),
-		                   static_cast<void*>(nullptr), 0ull, args);
-		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
-	}
-	return ALPGPU_OK;
-}
-
 // n > 0, first + n <= n_vectors * 1024 and op one of the three (the caller checked).  SET and AND touch every vector of the column (bits outside
 // the range clear), OR only those of the range (bits outside it stay).
 int launch_select_mask(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int op, uint64_t* d_mask, int value_bytes) {
-	const uint64_t    end     = first + n;
-	const uint64_t    v0      = op == kMaskOr ? first >> 10 : 0ull;
-	const uint64_t    n_range = op == kMaskOr ? ((end - 1) >> 10) - v0 + 1 : col->n_vectors;
-	const SelMaskArgs args {d_mask, op};
-	return value_bytes == 8 ? launch_arm<8>(stream, col, v0, n_range, first, end, lo, hi, args) : launch_arm<4>(stream, col, v0, n_range, first, end, lo, hi, args);
+	SelArgs a {};
+	a.first   = first;
+	a.end     = first + n;
+	a.v0      = op == kMaskOr ? first >> 10 : 0ull;
+	a.n_range = op == kMaskOr ? ((a.end - 1) >> 10) - a.v0 + 1 : col->n_vectors;
+	a.lo      = lo;
+	a.hi      = hi;
+	a.mask    = d_mask;
+	a.op      = op;
+	return value_bytes == 8 ? launch_select<8, kSelMask>(stream, col, a) : launch_select<4, kSelMask>(stream, col, a);
 }
 
 // col->n_vectors > 0
 int launch_sum_masked(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts, int value_bytes) {
-	const SelSumArgs args {d_mask, d_sums, d_counts};
-	const uint64_t   end = col->n_vectors << 10;
-	return value_bytes == 8 ? launch_arm<8>(stream, col, 0, col->n_vectors, 0, end, 0.0, 0.0, args) : launch_arm<4>(stream, col, 0, col->n_vectors, 0, end, 0.0, 0.0, args);
+	SelArgs a {};
+	a.n_range    = col->n_vectors;
+	a.mask_in    = d_mask;
+	a.sums       = d_sums;
+	a.sum_counts = d_counts;
+	return value_bytes == 8 ? launch_select<8, kSelSum>(stream, col, a) : launch_select<4, kSelSum>(stream, col, a);
 }
 
 // the first two phases of mask_to_indices and of the masked projection: counts[v] = the vector's set bits, offsets = their exclusive prefix sum,
 // *d_count = the bitmap's set bits (n_vectors > 0; the scratch laid out as the selection's)
-static int launch_mask_count_scan(hipStream_t stream, const uint64_t* d_mask, uint64_t n_vectors, uint64_t* d_count, void* d_scratch, uint32_t** counts_out, uint64_t** offsets_out) {
-	uint64_t* offsets = static_cast<uint64_t*>(d_scratch);
-	uint32_t* counts  = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_scratch) + align16(8ull * n_vectors));
-	uint64_t* levels  = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(counts) + align16(4ull * n_vectors));
-	*counts_out       = counts;
-	*offsets_out      = offsets;
-	const uint64_t n_count_wg = (n_vectors + 15) / 16; // 256 words = 16 vectors per workgroup
-	for (uint64_t off = 0; off < n_count_wg; off += kSelMaxGrid) {
-		const uint64_t g = n_count_wg - off < kSelMaxGrid ? n_count_wg - off : kSelMaxGrid;
-		hipLaunchKernelGGL(k_mask_count, dim3(static_cast<unsigned>(g)), dim3(256), 0, stream, d_mask, n_vectors, off, counts);
-		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
-	}
-	return launch_select_scan(stream, counts, n_vectors, offsets, d_count, levels);
+static int launch_mask_count_scan(hipStream_t stream, const uint64_t* d_mask, uint64_t n_vectors, uint64_t* d_count, const SelScratch& s) {
+	const int rc = launch_vectors(n_vectors, 16, [&](dim3 grid, uint64_t off) { // 256 words = 16 vectors per workgroup
+		hipLaunchKernelGGL(k_mask_count, grid, dim3(256), 0, stream, d_mask, n_vectors, off, s.counts);
+	});
+	return rc != ALPGPU_OK ? rc : launch_select_scan(stream, s.counts, n_vectors, s.offsets, d_count, s.levels);
 }
 
 // n_vectors > 0; d_scratch: select_scratch_bytes(n_vectors) bytes, 16-byte aligned, laid out as the selection's
 int launch_mask_to_indices(hipStream_t stream, const uint64_t* d_mask, uint64_t n_vectors, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch) {
-	uint32_t* counts;
-	uint64_t* offsets;
-	const int rc = launch_mask_count_scan(stream, d_mask, n_vectors, d_count, d_scratch, &counts, &offsets);
+	const SelScratch s  = select_scratch(d_scratch, n_vectors);
+	const int        rc = launch_mask_count_scan(stream, d_mask, n_vectors, d_count, s);
 	if (rc != ALPGPU_OK || capacity == 0) { return rc; }
-	const uint64_t n_wg = (n_vectors + kSelWaves - 1) / kSelWaves;
-	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
-		const uint64_t g = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;
-		hipLaunchKernelGGL(k_mask_emit, dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, d_mask, n_vectors, off, static_cast<const uint32_t*>(counts),
-		                   static_cast<const uint64_t*>(offsets), d_idx, capacity);
-		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
-	}
-	return ALPGPU_OK;
+	return launch_vectors(n_vectors, kSelWaves, [&](dim3 grid, uint64_t off) {
+		hipLaunchKernelGGL(k_mask_emit, grid, dim3(kSelThreads), 0, stream, d_mask, n_vectors, off, static_cast<const uint32_t*>(s.counts), static_cast<const uint64_t*>(s.offsets), d_idx,
+		                   capacity);
+	});
 }
 
 // col->n_vectors > 0; d_vals non-null when capacity > 0, d_idx nullable; d_scratch as for launch_mask_to_indices
 int launch_decode_masked(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, void* d_vals, int64_t* d_idx, uint64_t capacity, uint64_t* d_count,
                          void* d_scratch, int value_bytes) {
-	uint32_t* counts;
-	uint64_t* offsets;
-	const int rc = launch_mask_count_scan(stream, d_mask, col->n_vectors, d_count, d_scratch, &counts, &offsets);
+	const SelScratch s  = select_scratch(d_scratch, col->n_vectors);
+	const int        rc = launch_mask_count_scan(stream, d_mask, col->n_vectors, d_count, s);
 	if (rc != ALPGPU_OK || capacity == 0) { return rc; }
-	const SelTakeArgs args {d_mask, counts};
-	const uint64_t    n_wg = (col->n_vectors + kSelWaves - 1) / kSelWaves;
-	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
-		const uint64_t g = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;
-		if (value_bytes == 8) {
-			hipLaunchKernelGGL((k_select<8, false, SelTakeArgs>), dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed,
-			                   col->d_exc, 0ull, col->n_vectors, off, 0ull, col->n_vectors << 10, 0.0, 0.0, static_cast<uint32_t*>(nullptr), static_cast<const uint64_t*>(offsets),
-			                   d_idx, d_vals, capacity, args);
-		} else {
-			hipLaunchKernelGGL((k_select<4, false, SelTakeArgs>), dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed,
-			                   col->d_exc, 0ull, col->n_vectors, off, 0ull, col->n_vectors << 10, 0.0, 0.0, static_cast<uint32_t*>(nullptr), static_cast<const uint64_t*>(offsets),
-			                   d_idx, d_vals, capacity, args);
-		}
-		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
-	}
-	return ALPGPU_OK;
+	SelArgs a {};
+	a.n_range   = col->n_vectors;
+	a.mask_in   = d_mask;
+	a.counts_in = s.counts;
+	a.offsets   = s.offsets;
+	a.d_idx     = d_idx;
+	a.d_vals    = d_vals;
+	a.capacity  = capacity;
+	return value_bytes == 8 ? launch_select<8, kSelTake>(stream, col, a) : launch_select<4, kSelTake>(stream, col, a);
 }
 
 } // namespace alpgpu

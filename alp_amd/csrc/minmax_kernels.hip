@@ -15,16 +15,6 @@
 
 namespace alpgpu {
 
-template <class Launch>
-static int launch_minmax_chunks(uint64_t n_vectors, Launch&& launch) {
-	const uint64_t n_wg = (n_vectors + kSelWaves - 1) / kSelWaves;
-	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
-		launch(dim3(static_cast<unsigned>(n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid)), off);
-		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
-	}
-	return ALPGPU_OK;
-}
-
 // col->n_vectors > 0 (the caller checked)
 int launch_minmax_masked(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, void* d_zones, uint32_t* d_counts, int value_bytes) {
 	MinmaxArgs args {};
@@ -33,7 +23,7 @@ int launch_minmax_masked(hipStream_t stream, const alpgpu_column* col, const uin
 	args.zones     = d_zones;
 	args.counts    = d_counts;
 	const ColumnStreams c = column_streams(col);
-	return launch_minmax_chunks(args.n_vectors, [&](dim3 grid, uint64_t off) {
+	return launch_vectors(args.n_vectors, kSelWaves, [&](dim3 grid, uint64_t off) {
 		args.wg_off = off;
 		if (value_bytes == 8) {
 			hipLaunchKernelGGL((k_minmax_masked<8>), grid, dim3(kSelThreads), 0, stream, c, args);
@@ -43,26 +33,15 @@ int launch_minmax_masked(hipStream_t stream, const alpgpu_column* col, const uin
 	});
 }
 
-template <int VB, int GT>
-static int launch_group_minmax_tier(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, MinmaxArgs args, const double* lo, const double* hi) {
-	typedef typename DecodeVec<VB>::T T;
-	GroupBounds<VB, GT>             r;
-	for (uint32_t j = 0; j < static_cast<uint32_t>(GT); ++j) { // (a float entry point's bounds are floats: they pass through double unchanged)
-		r.lo[j] = j < args.n_groups ? static_cast<T>(lo[j]) : static_cast<T>(1);
-		r.hi[j] = j < args.n_groups ? static_cast<T>(hi[j]) : static_cast<T>(0);
-	}
-	const ColumnStreams cv = column_streams(val), ck = column_streams(key);
-	return launch_minmax_chunks(args.n_vectors, [&](dim3 grid, uint64_t off) {
-		args.wg_off = off;
-		hipLaunchKernelGGL((k_group_minmax<VB, GT>), grid, dim3(kSelThreads), 0, stream, cv, ck, args, r);
-	});
-}
-
 template <int VB>
-static int launch_group_minmax_vb(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const MinmaxArgs& args, const double* lo, const double* hi) {
-	return args.n_groups <= 4u   ? launch_group_minmax_tier<VB, 4>(stream, val, key, args, lo, hi)
-	       : args.n_groups <= 8u ? launch_group_minmax_tier<VB, 8>(stream, val, key, args, lo, hi)
-	                             : launch_group_minmax_tier<VB, 16>(stream, val, key, args, lo, hi);
+static int group_minmax(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, MinmaxArgs args, const double* lo, const double* hi) {
+	const ColumnStreams cv = column_streams(val), ck = column_streams(key);
+	return with_group_tier<VB>(lo, hi, args.n_groups, [&](auto r) {
+		return launch_vectors(args.n_vectors, kSelWaves, [&](dim3 grid, uint64_t off) {
+			args.wg_off = off;
+			hipLaunchKernelGGL((k_group_minmax<VB, decltype(r)::kTier>), grid, dim3(kSelThreads), 0, stream, cv, ck, args, r);
+		});
+	});
 }
 
 // val->n_vectors == key->n_vectors > 0, 1 <= n_groups <= ALPGPU_GROUP_MAX (the caller checked)
@@ -74,7 +53,7 @@ int launch_group_minmax(hipStream_t stream, const alpgpu_column* val, const alpg
 	args.zones     = d_zones;
 	args.counts    = d_counts;
 	args.n_groups  = n_groups;
-	return value_bytes == 8 ? launch_group_minmax_vb<8>(stream, val, key, args, lo, hi) : launch_group_minmax_vb<4>(stream, val, key, args, lo, hi);
+	return value_bytes == 8 ? group_minmax<8>(stream, val, key, args, lo, hi) : group_minmax<4>(stream, val, key, args, lo, hi);
 }
 
 // ---- the groups' totals -------------------------------------------------------------------------------------------------------------------------

@@ -17,14 +17,10 @@ namespace alpgpu {
 template <int VB, int ARM>
 static int launch_pair(hipStream_t stream, const alpgpu_column* a, const alpgpu_column* b, PairArgs args) {
 	const ColumnStreams ca = column_streams(a), cb = column_streams(b);
-	const uint64_t   n_wg = (args.n_range + kSelWaves - 1) / kSelWaves;
-	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
-		const uint64_t g = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;
-		args.wg_off      = off;
-		hipLaunchKernelGGL((k_pair<VB, ARM>), dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, ca, cb, args);
-		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
-	}
-	return ALPGPU_OK;
+	return launch_vectors(args.n_range, kSelWaves, [&](dim3 grid, uint64_t off) {
+		args.wg_off = off;
+		hipLaunchKernelGGL((k_pair<VB, ARM>), grid, dim3(kSelThreads), 0, stream, ca, cb, args);
+	});
 }
 
 // n > 0, first + n <= n_vectors * 1024, cmp and op valid, a->n_vectors == b->n_vectors > 0 (the caller checked).  SET and AND touch every vector

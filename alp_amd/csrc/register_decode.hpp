@@ -16,19 +16,19 @@
 //
 // A kernel: DecodeVec (decode_vec_load), the exception mask (exception_mask, exception_masks), then per batch of NB steps step_request followed by
 // step_bits / step_value of each step.  k_select takes 8 steps of one vector to a batch (kSelBatch), the others kStepBatch = 4 (of one vector or of
-// two side by side: as many vector loads in flight).
+// two side by side: as many vector loads in flight).  Every one of them but k_in_list, which is persistent, is launched by launch_vectors below.
 #pragma once
 #include <type_traits>
 
 #include "alp_device_f32.hpp"
 #include "lane_field.hpp"
+#include "launch.hpp"
 
 namespace alpgpu {
 
 constexpr int      kSelWaves   = 4; // wavefronts per workgroup, one vector (or vector pair) each: they share nothing
 constexpr int      kSelThreads = 64 * kSelWaves;
-constexpr uint64_t kSelMaxGrid = 1ull << 30; // workgroups per launch
-constexpr uint32_t kStepBatch  = 4;          // steps of a vector whose words are requested together, for every kernel but k_select
+constexpr uint32_t kStepBatch  = 4; // steps of a vector whose words are requested together, for every kernel but k_select
 constexpr int      kMaskSet = ALPGPU_MASK_SET, kMaskAnd = ALPGPU_MASK_AND, kMaskOr = ALPGPU_MASK_OR;
 
 // lane `idx` (wave-uniform) of a 64-bit value
@@ -45,6 +45,18 @@ struct ColumnStreams { // the four streams of an alpgpu_column the decode follow
 	const uint8_t*               excs;
 };
 inline ColumnStreams column_streams(const alpgpu_column* col) { return ColumnStreams {col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc}; }
+
+// The family's one launch loop (host side): n_vectors vectors, vectors_per_wg to a workgroup (kSelWaves: one wavefront per vector), split only at the
+// grid limit (launch.hpp: grid_chunk).  launch(grid, wg_off) makes one chunk; the kernel takes wg_off, the chunk's first workgroup, as an argument.
+template <class Launch>
+inline int launch_vectors(uint64_t n_vectors, uint64_t vectors_per_wg, Launch&& launch) {
+	const uint64_t n_wg = (n_vectors + vectors_per_wg - 1) / vectors_per_wg;
+	for (uint64_t off = 0; off < n_wg; off += grid_chunk(n_wg - off)) {
+		launch(dim3(static_cast<unsigned>(grid_chunk(n_wg - off))), off);
+		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
+	}
+	return ALPGPU_OK;
+}
 
 // one vector's constants: everything wave-uniform, every field of the descriptor clamped to what its type admits
 template <int VB>

@@ -2,12 +2,12 @@
 // with lo <= x <= hi, in ascending order, and optionally those values.  The decoded column never reaches HBM.
 //
 // Three phases, ordered by kernel boundaries on one stream (no workgroup ever waits for another):
-//   count  k_select<VB, false>  one wavefront per vector decodes it in registers and writes counts[v] = its number of qualifying values (u32)
-//          k_select<VB, false, const void*>  alpgpu_select_range_zoned_*: the same after a look at the vector's zone record {min, max}; a vector the record
+//   count  k_select<VB, kSelCount>  one wavefront per vector decodes it in registers and writes counts[v] = its number of qualifying values (u32)
+//          k_select<VB, kSelCountZoned>  alpgpu_select_range_zoned_*: the same after a look at the vector's zone record {min, max}; a vector the record
 //                               excludes, or admits whole, is counted from those 16 (8) bytes and its descriptor alone
 //   scan   k_scan_*             exclusive prefix sum counts -> offsets (u64), blocks of 1024, block sums scanned the same way one level up;
 //                               the top level writes *d_count
-//   emit   k_select<VB, true>   one wavefront per vector: counts[v] == 0 -> gone after a 4-byte read; else the same decode again, and every
+//   emit   k_select<VB, kSelEmit>  one wavefront per vector: counts[v] == 0 -> gone after a 4-byte read; else the same decode again, and every
 //                               qualifying value's index (and value) goes to offsets[v] + its rank inside the vector, if below the capacity
 //
 // The decode of one vector by one wavefront is register_decode.hpp's (the layout of the steps, the exception mask, the arithmetic): step m holds
@@ -20,8 +20,8 @@
 // 4 bytes; the scan reads them and writes 8; emit reads 4 + 8 bytes per vector and, for vectors with a non-zero count only, the vector again,
 // and writes 8 (+ 8 or 4) bytes per selected value.
 //
-// k_select itself is in select_device.hpp, which mask_kernels.hip includes too (it instantiates three more arms of the kernel: the ballots kept as
-// a bitmap, a masked SUM and a masked projection); this file holds the scan, the launches and the scratch layout.
+// k_select, its one launcher (launch_select) and the scratch layout are in select_device.hpp, which mask_kernels.hip includes too (it launches three
+// more arms of the kernel: the ballots kept as a bitmap, a masked SUM and a masked projection); this file holds the scan and the three phases.
 #include "select_device.hpp"
 
 namespace alpgpu {
@@ -105,56 +105,37 @@ int launch_select_scan(hipStream_t stream, const uint32_t* d_counts, uint64_t n,
 	return scan_level<uint32_t>(stream, d_counts, n, d_offsets, d_total, d_levels);
 }
 
-template <int VB, bool EMIT>
-static int launch_select_pass(hipStream_t stream, const alpgpu_column* col, uint64_t v0, uint64_t n_range, uint64_t first, uint64_t end, double lo, double hi,
-                              uint32_t* counts, const uint64_t* offsets, int64_t* d_idx, void* d_vals, uint64_t capacity) {
-	const uint64_t n_wg = (n_range + kSelWaves - 1) / kSelWaves;
-	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
-		const uint64_t g = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;
-		hipLaunchKernelGGL((k_select<VB, EMIT>), dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc,
-		                   v0, n_range, off, first, end, lo, hi, counts, offsets, d_idx, d_vals, capacity);
-		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
-	}
-	return ALPGPU_OK;
-}
-
+// count (a.zones: the zone map, or null), scan, emit: `a` holds the count pass's arguments, the scratch's counts among them
 template <int VB>
-static int launch_select_count_zoned(hipStream_t stream, const alpgpu_column* col, const void* d_zones, uint64_t v0, uint64_t n_range, uint64_t first, uint64_t end,
-                                     double lo, double hi, uint32_t* counts) {
-	const uint64_t n_wg = (n_range + kSelWaves - 1) / kSelWaves;
-	for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
-		const uint64_t g = n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid;
-		hipLaunchKernelGGL((k_select<VB, false, const void*>), dim3(static_cast<unsigned>(g)), dim3(kSelThreads), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed,
-		                   col->d_exc, v0, n_range, off, first, end, lo, hi, counts, static_cast<const uint64_t*>(nullptr), static_cast<int64_t*>(nullptr), static_cast<void*>(nullptr),
-		                   0ull, d_zones);
-		if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
-	}
-	return ALPGPU_OK;
+static int select_range(hipStream_t stream, const alpgpu_column* col, const SelArgs& a, const SelScratch& s, int64_t* d_idx, void* d_vals, uint64_t capacity, uint64_t* d_count) {
+	int rc = a.zones != nullptr ? launch_select<VB, kSelCountZoned>(stream, col, a) : launch_select<VB, kSelCount>(stream, col, a);
+	if (rc != ALPGPU_OK) { return rc; }
+	rc = launch_select_scan(stream, s.counts, a.n_range, s.offsets, d_count, s.levels);
+	if (rc != ALPGPU_OK || capacity == 0) { return rc; }
+	SelArgs e  = a;
+	e.zones    = nullptr;
+	e.offsets  = s.offsets;
+	e.d_idx    = d_idx;
+	e.d_vals   = d_vals;
+	e.capacity = capacity;
+	return launch_select<VB, kSelEmit>(stream, col, e);
 }
 
 // n > 0 and first + n <= n_vectors * 1024 (the caller checked); d_scratch: select_scratch_bytes(col->n_vectors) bytes, 16-byte aligned
 // d_zones (nullable): the column's zone map, one record per vector — the count pass then reads a vector's record before the vector
 int launch_select_range(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int64_t* d_idx, void* d_vals,
                         uint64_t capacity, uint64_t* d_count, void* d_scratch, int value_bytes, const void* d_zones) {
-	const uint64_t end     = first + n;
-	const uint64_t v0      = first >> 10;
-	const uint64_t n_range = ((end - 1) >> 10) - v0 + 1;
-	uint64_t*      offsets = static_cast<uint64_t*>(d_scratch);
-	uint32_t*      counts  = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_scratch) + align16(8ull * col->n_vectors));
-	uint64_t*      levels  = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(counts) + align16(4ull * col->n_vectors));
-	int            rc;
-	if (d_zones != nullptr) {
-		rc = value_bytes == 8 ? launch_select_count_zoned<8>(stream, col, d_zones, v0, n_range, first, end, lo, hi, counts)
-		                      : launch_select_count_zoned<4>(stream, col, d_zones, v0, n_range, first, end, lo, hi, counts);
-	} else {
-		rc = value_bytes == 8 ? launch_select_pass<8, false>(stream, col, v0, n_range, first, end, lo, hi, counts, nullptr, nullptr, nullptr, 0)
-		                      : launch_select_pass<4, false>(stream, col, v0, n_range, first, end, lo, hi, counts, nullptr, nullptr, nullptr, 0);
-	}
-	if (rc != ALPGPU_OK) { return rc; }
-	rc = launch_select_scan(stream, counts, n_range, offsets, d_count, levels);
-	if (rc != ALPGPU_OK || capacity == 0) { return rc; }
-	return value_bytes == 8 ? launch_select_pass<8, true>(stream, col, v0, n_range, first, end, lo, hi, counts, offsets, d_idx, d_vals, capacity)
-	                        : launch_select_pass<4, true>(stream, col, v0, n_range, first, end, lo, hi, counts, offsets, d_idx, d_vals, capacity);
+	const SelScratch s = select_scratch(d_scratch, col->n_vectors);
+	SelArgs          a {};
+	a.first   = first;
+	a.end     = first + n;
+	a.v0      = first >> 10;
+	a.n_range = ((a.end - 1) >> 10) - a.v0 + 1;
+	a.lo      = lo;
+	a.hi      = hi;
+	a.counts  = s.counts;
+	a.zones   = d_zones;
+	return value_bytes == 8 ? select_range<8>(stream, col, a, s, d_idx, d_vals, capacity, d_count) : select_range<4>(stream, col, a, s, d_idx, d_vals, capacity, d_count);
 }
 
 } // namespace alpgpu

@@ -241,12 +241,11 @@ static int top_k(hipStream_t stream, const alpgpu_column* col, const uint64_t* d
 		g.k         = k;
 		g.largest   = largest;
 		const ColumnStreams c = column_streams(col);
-		const uint64_t   n_wg = (nv + kSelWaves - 1) / kSelWaves;
-		for (uint64_t off = 0; off < n_wg; off += kSelMaxGrid) {
+		const int rc = launch_vectors(nv, kSelWaves, [&](dim3 grid, uint64_t off) {
 			g.wg_off = off;
-			hipLaunchKernelGGL((k_top_k_candidates<VB>), dim3(static_cast<unsigned>(n_wg - off < kSelMaxGrid ? n_wg - off : kSelMaxGrid)), dim3(kSelThreads), 0, stream, c, g);
-			if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
-		}
+			hipLaunchKernelGGL((k_top_k_candidates<VB>), grid, dim3(kSelThreads), 0, stream, c, g);
+		});
+		if (rc != ALPGPU_OK) { return rc; }
 	}
 	// 4. the element level
 	const uint32_t idx_b    = index_bytes(nv << 10);

@@ -1,5 +1,5 @@
 """GPU: the one in-register decode of a vector (register_decode.hpp: DecodeVec / step_request / step_value) under each of its seven kernels, on the
-hand-built vectors of every packed width — the arms of k_select behind the selection bitmaps (select_device.hpp: alpgpu_select_mask_*,
+hand-built vectors of every packed width — k_select's kSelMask, kSelSum and kSelTake arms (select_device.hpp: alpgpu_select_mask_*,
 alpgpu_decode_sum_masked_*, alpgpu_decode_masked_*), k_pair (compare, dot), k_group (three tiers), k_minmax_masked, k_group_minmax (three tiers) and k_in_list
 (the LDS and the global arm).  The suites of those features read columns the encoder produces from datagen; here the columns are float_rows.py (widths 0..32,
 cuts 16..31) and double_rows.py (widths 0..64, cuts 48..63): every width under every factor, bases on the bounds of the conversion shortcut and at the ends
@@ -198,7 +198,7 @@ def test_the_second_column_pairs_every_scheme_and_narrow_with_wide(cols):
 
 
 # =====================================================================================================================================================
-# the arms of k_select
+# k_select: the kSelMask, kSelSum and kSelTake arms
 # =====================================================================================================================================================
 def test_select_mask(ctx, cols):
     for name, b in (("A", cols.A), ("B", cols.B)):
