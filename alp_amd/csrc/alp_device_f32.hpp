@@ -26,6 +26,8 @@ __device__ __constant__ const float kExpArrF[11]  = {1.0f, 10.0f, 100.0f, 1000.0
                                                      100000000.0f, 1000000000.0f, 10000000000.0f};
 __device__ __constant__ const uint32_t kFactArrF[11] = {1u, 10u, 100u, 1000u, 10000u, 100000u, 1000000u, 10000000u,
                                                         100000000u, 1000000000u, 1410065408u};
+// the decode's conversion shortcut (decode_f32_kernels.hip: finish_quad_f32; the stream kernel's plan): min(2^24, (2^31 - 1) / 10^f) for f <= 9; 0 for f = 10
+__device__ __constant__ const uint32_t kShortcutBoundF[11] = {16777216u, 16777216u, 16777216u, 2147483u, 214748u, 21474u, 2147u, 214u, 21u, 2u, 0u};
 
 constexpr float kMagicF      = 12582912.0f;             // 2^23 + 2^22, constants.hpp:34
 constexpr float kUpperLimitF = 9223372036854775808.0f;  // (float)ENCODING_UPPER_LIMIT, encoder.hpp:334

@@ -23,6 +23,7 @@
 // lanes (pairs (0,1), (2,3), ...; then pairs of pairs, ...): six levels.
 #include "alp_device.hpp"
 #include "launch.hpp"
+#include "staged_decode.hpp"
 
 namespace alpgpu {
 
@@ -141,13 +142,8 @@ __device__ __forceinline__ void wait_vmcnt_coarse(uint32_t n) {
 
 constexpr int kConsumeSum = 1, kConsumeCount = 2;
 
-// exception mask of the vector as seen by this wavefront (decode_kernels.hip: ExcMask): lane l < 32 holds mask word l and the number of
-// exceptions in the words before it
-struct ConsExcMask {
-	uint32_t word;
-	int      excl;
-};
-__device__ __forceinline__ uint32_t cons_exception_hits(const ConsExcMask& em, int m, int lane, int& rank) {
+// the pair's lookup in the vector's exception mask (staged_decode.hpp: ExcMask) by readlanes
+__device__ __forceinline__ uint32_t cons_exception_hits(const ExcMask& em, int m, int lane, int& rank) {
 	const int g    = lane >> 4; // the pair's mask word is 4m + g
 	uint32_t  word = __builtin_amdgcn_readlane(em.word, 4 * m);
 	int       pref = __builtin_amdgcn_readlane(em.excl, 4 * m);
@@ -375,7 +371,7 @@ __global__ __launch_bounds__(64 * kConsWaves, kConsWavesPerSimd) void k_consume_
 		const uint32_t rec_l    = ring_lds + (((start_piece + pk_pieces) & (kRingPieces - 1u)) << 10);
 		if (cnt > 0 && lane < 32) { lds_write_b32(mask_lds + 4u * static_cast<uint32_t>(lane), 0u); }
 		wait_vmcnt_le(issued - end_count); // everything of vector k has landed in the ring
-		ConsExcMask em {0u, 0};
+		ExcMask     em {0u, 0};
 		if (cnt > 0) { // wave-uniform
 			if (whole) {
 				const uint32_t pos_l = rec_l + val_b * static_cast<uint32_t>(cnt);

@@ -30,12 +30,12 @@
 #include "alp_device.hpp"
 #include "decode_policy.hpp"
 #include "launch.hpp"
+#include "staged_decode.hpp"
 #include "wave_minmax.hpp"
 #include <cstdlib>
 
 namespace alpgpu {
 
-constexpr int kDecWaves     = 4; // wavefronts cooperating on one vector
 constexpr int kStepsPerWave = 8 / kDecWaves;
 constexpr int kDecodeBatch  = 4; // steps whose words are requested together (decode_vector_quarters)
 constexpr int kStageBytes   = 8704; // >= 63*128 (RD right) + 3*128 (RD left) + 128 pad, and >= 64*128 + 128 (ALP bw 64)
@@ -58,94 +58,6 @@ using DecodeLds = DecodeLdsT<kStageBytes>;
 // of the HBM peak — and costs every OTHER column 2-6 % (1 KiB more LDS per vector: city_temperature 0.78 -> 0.74, nyc29 0.81 -> 0.78; call 6), so it is an instance
 // of its own, launched for columns whose hints say so (decode_policy.hpp: policy_shape_f64, DecodeShape::many_exc).
 using DecodeLdsManyExc = DecodeLdsT<kStageBytes, 2 * kExcStage>;
-
-// The exception mask (32 words) as seen by one wavefront: lane l < 32 holds word l and the number of exceptions in the
-// words before it.  The prefix is a DPP row scan (register-to-register; a __shfl_up chain would be five dependent trips
-// through the LDS crossbar on the critical path of a latency-bound workgroup), the per-step lookups below are readlanes.
-struct ExcMask {
-	uint32_t word; // mask word (lane & 31)
-	int      excl; // exceptions in words 0 .. (lane & 31) - 1
-};
-template <class LDS>
-__device__ __forceinline__ ExcMask load_exception_mask(const LDS& L, int lane) {
-	ExcMask   m;
-	m.word  = L.mask[lane & 31];
-	const int c = lane < 32 ? __builtin_popcount(m.word) : 0;
-	int       v = c;
-	v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false); // row_shr:1
-	v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false); // row_shr:2
-	v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false); // row_shr:4
-	v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false); // row_shr:8   -> inclusive scan inside each 16-lane row
-	v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> row 1 += total of row 0 (lanes 0..31 done)
-	m.excl = v - c;
-	return m;
-}
-
-// the value of the exception of that rank: staged (LDS) or, past the stage, from HBM.  all_staged (wave-uniform: the vector's count fits the
-// stage) keeps the common case to the LDS read alone — written as "LDS if rank < kStaged else HBM" the compiler selects between the two
-// ADDRESSES and issues one flat load (slower, and it waits for every counter).
-template <int VAL_BYTES, class LDS>
-__device__ __forceinline__ uint64_t fetch_exception(const LDS& L, const uint8_t* __restrict__ rec, int rank, bool all_staged) {
-	constexpr int kStaged = static_cast<int>(LDS::kExcBytes) / VAL_BYTES;
-	const int     at      = rank < kStaged ? rank : kStaged - 1;
-	uint64_t      v;
-	if constexpr (VAL_BYTES == 8) {
-		v = reinterpret_cast<const uint64_t*>(L.excv)[at];
-		if constexpr (LDS::kPrefixInLds) {
-			asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v)::"memory"); // (k_sink_direct: as in exception_hits_lds) ... and keeps the two loads two loads
-		} else {
-			asm volatile("" : "+v"(v)); // keeps the two loads two loads
-		}
-		if (!all_staged) {
-			if (rank >= kStaged) { v = reinterpret_cast<const uint64_t*>(rec)[rank]; }
-		}
-	} else {
-		v = reinterpret_cast<const uint16_t*>(L.excv)[at];
-		if constexpr (LDS::kPrefixInLds) {
-			asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v)::"memory");
-		} else {
-			asm volatile("" : "+v"(v)); // keeps the two loads two loads
-		}
-		if (!all_staged) {
-			if (rank >= kStaged) { v = reinterpret_cast<const uint16_t*>(rec)[rank]; }
-		}
-	}
-	return v;
-}
-
-// exception lookup for the pair (128*m + 2*lane, +1): 2-bit hit mask and the rank of the first hit.  m is wave-uniform.  The pair's mask
-// word is 4m + (lane >> 4): word and prefix come from the lane that holds them by ds_bpermute (the LDS crossbar, no memory) — as eight
-// readlanes and six selects per step this lookup was a quarter of the vector instructions of a vector with exceptions, and the consumers
-// (SUM / COUNT sinks) are bound by exactly those (profiles/r03_consumers.txt).
-// The same lookup out of the wavefront's LDS (mask word and its prefix as two ds_read_b32 of one address per 16 lanes) — what k_sink_direct
-// uses.  SOME BUILDS of that kernel (another register budget, another batch size, two compiler pins ...) come back with a wrong extracted
-// field in the step FOLLOWING an exception lookup — right words in the registers, wrong value — for ~5 % of the exception-carrying
-// vectors of a long column, never the same ones; a build either does it in every run or never.  Three such builds became clean with this
-// form instead of ds_bpermute; later one with this form was wrong again, clean with full LDS waits, and another wrong WITH them.  None of
-// that was the cause: the wrong builds had a 64-bit shift's amount in the LAST register of their allocation, which gfx950 reads as VGPR0
-// there (see k_sink_direct below; profiles/r03_consumers.txt has the way to it).  The LDS form stayed (same speed).  A build of this file
-// ships only if tools/check_top_vgpr.py is clean and tests/test_decode_sum_gpu.py::test_exception_records_that_change_nothing and
-// ...across_a_full_chip pass.  k_decode_column uses 44 of 48 allocated registers: the pattern cannot arise there.
-template <class LDS>
-__device__ __forceinline__ uint32_t exception_hits_lds(const LDS& L, int m, int lane, int& rank) {
-	const int      q    = 4 * m + (lane >> 4);
-	uint32_t       word = L.mask[q];
-	int            pref = static_cast<int>(L.pref[q]);
-	asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(word), "+v"(pref)::"memory"); // both words here before anything is computed from them (see above: not a cure by itself)
-	const int      b0   = (2 * lane) & 31;
-	const uint32_t hits = (word >> b0) & 3u;
-	rank                = pref + __builtin_popcount(word & ((1u << b0) - 1u));
-	return hits;
-}
-__device__ __forceinline__ uint32_t exception_hits(const ExcMask& em, int m, int lane, int& rank) {
-	const int      src  = (4 * m + (lane >> 4)) << 2; // byte address of the source lane
-	const uint32_t word = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(src, static_cast<int>(em.word)));
-	const int      pref = __builtin_amdgcn_ds_bpermute(src, em.excl);
-	const int      b0   = (2 * lane) & 31;
-	const uint32_t hits = (word >> b0) & 3u;
-	rank                = pref + __builtin_popcount(word & ((1u << b0) - 1u));
-	return hits;
-}
 
 template <bool NT_STORE>
 __device__ __forceinline__ void store_pair(double2* __restrict__ p, double x, double y) {
@@ -257,9 +169,7 @@ struct StagedWords {
 		return make_uint2(reinterpret_cast<const uint32_t*>(stage + 128 * rbw)[i], reinterpret_cast<const uint32_t*>(stage + 128 * rbw)[i + 32]);
 	}
 };
-struct BufferWords { // HBM through buffer loads: the resources are sized to the vector's packed words, so reads past its last unit / last left
-	// word return 0 (what the unpack reads there is masked off anyway) without a clamp per load, and the second unit of a pair is the
-	// first one's address with an immediate offset
+struct BufferWords { // HBM through buffer loads (staged_decode.hpp: packed_word_resources); the second unit of a pair is the first one's address with an immediate offset
 	__amdgpu_buffer_rsrc_t units, lefts;
 	__device__ __forceinline__ WordPair pair(int i) const {
 		typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -466,10 +376,10 @@ __device__ __forceinline__ void decode_vector_quarters(const LDS& L, const WORDS
 						uint32_t       hits;
 						if constexpr (LDS::kPrefixInLds) { hits = exception_hits_lds(L, m, lane, rank); } else { hits = exception_hits(em, m, lane, rank); }
 						if (hits & 1u) {
-							l0 = fetch_exception<2>(L, rec, rank, staged);
+							l0 = fetch_exception<2, uint64_t>(L, rec, rank, staged);
 							++rank;
 						}
-						if (hits & 2u) { l1 = fetch_exception<2>(L, rec, rank, staged); }
+						if (hits & 2u) { l1 = fetch_exception<2, uint64_t>(L, rec, rank, staged); }
 					}
 					const double ox = __longlong_as_double(static_cast<long long>((l0 << rbw) | u.x));
 					const double oy = __longlong_as_double(static_cast<long long>((l1 << rbw) | u.y));
@@ -505,60 +415,6 @@ __device__ __forceinline__ void decode_staged_vector(const LDS& L, const alpgpu_
 	decode_vector_quarters<NT_STORE, SINK, 1>(L, StagedWords {L.stage}, d, dict, em, rec, dst, wave, lane, acc, range_lo, range_hi);
 }
 
-// Issues every load of one vector: packed words and the values of its exceptions straight into LDS (global_load_lds, 16 resp. 4 bytes per
-// lane, no VGPR round trip), exception positions into registers.  (Until round 3 the values went through registers too, behind a branch on the
-// scheme for their width — and the compiler's wait-count pass put an s_waitcnt vmcnt(0) between the two arms, i.e. a whole HBM round trip in
-// front of the packed loads of every vector with exceptions of one of the two schemes.)
-// (a vector whose words do not fit the workgroup's stage is not staged: see vector_fits_stage)
-template <class LDS>
-__device__ __forceinline__ bool vector_fits_stage(const alpgpu_vector_desc& d) {
-	return 128 * (static_cast<int>(d.bw) + (d.scheme == ALPGPU_SCHEME_ALP ? 0 : static_cast<int>(d.lbw))) + 128 <= LDS::kStage;
-}
-template <class LDS>
-__device__ __forceinline__ uint32_t issue_vector_loads(LDS& L, const alpgpu_vector_desc& d, const uint8_t* __restrict__ packed,
-                                                       const uint8_t* __restrict__ rec, int tid, int wave) {
-	typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
-	constexpr int T       = 64 * kDecWaves;
-	const bool    is_alp  = d.scheme == ALPGPU_SCHEME_ALP;
-	const int     n_units = vector_fits_stage<LDS>(d) ? 8 * (d.bw + (is_alp ? 0 : d.lbw)) : 0;
-	const ull2*   g       = reinterpret_cast<const ull2*>(packed + d.packed_off);
-	constexpr int kMaxUnits = (LDS::kStage - 128) / 16 < 528 ? (LDS::kStage - 128) / 16 : 528;
-#pragma unroll
-	for (int j = 0; j < (kMaxUnits + T - 1) / T; ++j) {
-		const int c = tid + T * j;
-		if (c < n_units) { // LDS destination = wave-uniform base + 16 * lane
-			__builtin_amdgcn_global_load_lds(g + c, reinterpret_cast<ull2*>(L.stage) + (T * j + 64 * wave), 16, 0, 0);
-		}
-	}
-	uint32_t  pos = 0u;
-	const int cnt = d.exc_cnt;
-	if (cnt > 0) { // wave-uniform
-		const uint32_t val_bytes = (is_alp ? 8u : 2u) * static_cast<uint32_t>(cnt);
-		const int      dwords    = static_cast<int>(((val_bytes < LDS::kExcBytes ? val_bytes : LDS::kExcBytes) + 3u) >> 2); // (records are 8-byte multiples)
-		static_assert(LDS::kExcBytes / 4 <= 2 * T, "two loads per thread cover the stage");
-		if (tid < dwords) { __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t*>(rec) + tid, reinterpret_cast<uint32_t*>(L.excv) + 64 * wave, 4, 0, 0); }
-		if constexpr (LDS::kExcBytes / 4 > T) {
-			if (tid + T < dwords) { __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t*>(rec) + T + tid, reinterpret_cast<uint32_t*>(L.excv) + T + 64 * wave, 4, 0, 0); }
-		}
-		if (tid < cnt) { pos = reinterpret_cast<const uint16_t*>(rec + val_bytes)[tid]; }
-	}
-	return pos;
-}
-
-template <class LDS>
-__device__ __forceinline__ void land_exceptions(LDS& L, const alpgpu_vector_desc& d, const uint8_t* __restrict__ rec, uint32_t pos, int tid) {
-	constexpr int T   = 64 * kDecWaves;
-	const int     cnt = d.exc_cnt;
-	if (tid < cnt) { atomicOr(&L.mask[pos >> 5], 1u << (pos & 31)); }
-	if (cnt > T) { // more exceptions than threads in one vector: rare
-		const uint16_t* poss = reinterpret_cast<const uint16_t*>(rec + static_cast<size_t>(cnt) * (d.scheme == ALPGPU_SCHEME_ALP ? 8 : 2));
-		for (int j = tid + T; j < cnt; j += T) {
-			const uint32_t p = poss[j];
-			atomicOr(&L.mask[p >> 5], 1u << (p & 31));
-		}
-	}
-}
-
 // V consecutive vectors per workgroup: all of their loads are in flight together, then they are unpacked one after the
 // other by the same 4 wavefronts.  V = 2 doubles the bytes in flight per CU for the same residency (8 workgroups per CU).
 template <int V, bool NT_STORE, int SINK = kSinkStore, class LDS = DecodeLds>
@@ -586,51 +442,10 @@ __global__ __launch_bounds__(64 * kDecWaves) void k_decode_column(const alpgpu_v
 	}
 
 	alpgpu_vector_desc d[V];
-	uint32_t           pos[V];
-#pragma unroll
-	for (int i = 0; i < V; ++i) {
-		const uint64_t v = v0 + i < n_vectors ? v0 + i : v0; // the odd tail vector is simply loaded twice
-		d[i]             = descs[v];
-	}
-	VectorConsts dict[V];
-#pragma unroll
-	for (int i = 0; i < V; ++i) { dict[i] = load_vector_consts(rgs, v0 + i < n_vectors ? v0 + i : v0, d[i]); }
-	// (no_mask[i] is always false and dd below is a plain copy: with the flags and the copy gone the compiler orders the V = 2 kernels' instructions
-	// differently.  They are left from the patch-after arm, removed with it, so that the shipped instruction stream stays the one measured.)
-	bool no_mask[V];
-#pragma unroll
-	for (int i = 0; i < V; ++i) {
-		no_mask[i] = false;
-		pos[i]     = issue_vector_loads(L[i], d[i], packed, excs + d[i].exc_off, tid, wave);
-	}
-	// ALP_RD vectors: the dictionary into the vector's LDS (four lanes; visible behind the barrier below)
-#pragma unroll
-	for (int i = 0; i < V; ++i) {
-		if (d[i].scheme != ALPGPU_SCHEME_ALP && tid < 4) { reinterpret_cast<uint32_t*>(L[i].rdict)[tid] = static_cast<uint32_t>((tid < 2 ? dict[i].lo : dict[i].hi) >> (32 * (tid & 1))); }
-	}
-	// Only a workgroup that has exceptions zeroes its masks, and it does so behind the issue of all its loads: the barrier that fences the
-	// zeroes from the atomics waits for LDS only, so it falls into the shadow of the HBM round trip.  (Until round 3 every workgroup,
-	// exceptions or not, began with the zeroing write and a barrier in front of its first load.)
-	bool any_exc = false;
-#pragma unroll
-	for (int i = 0; i < V; ++i) { any_exc |= d[i].exc_cnt != 0 && !no_mask[i]; }
-	if (any_exc) { // workgroup-uniform
-		if (tid < 32 * V) { L[tid >> 5].mask[tid & 31] = 0; }
-		asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // not __syncthreads(): its fence would wait for the loads in flight
-#pragma unroll
-		for (int i = 0; i < V; ++i) {
-			if (!no_mask[i]) { land_exceptions(L[i], d[i], excs + d[i].exc_off, pos[i], tid); }
-		}
-	}
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // LDS-DMA completion is not tracked through the LDS for the compiler
-	__syncthreads();
+	VectorConsts       dict[V];
+	stage_vectors<8>(L, d, dict, descs, packed, excs, v0, n_vectors, tid, wave, [&](uint64_t v, const alpgpu_vector_desc& dv) { return load_vector_consts(rgs, v, dv); });
 
 	if constexpr (SINK != kSinkStore) {
-		// Per-vector sums: lane partial (step order) in each of the four wavefronts -> the four partials of a lane position combined as
-		// (w0 + w1) + (w2 + w3) -> ONE adjacent-lane tree over the 64 results, by one wavefront per vector.  (Counts take the same route; they
-		// are small integers, so the order does not matter.)  Until late in round 3 every wavefront ran its own tree first: 18 of the ~125
-		// vector instructions per wavefront and vector of a kernel whose VALU is 100 % busy (profiles/r03_consumers.txt).  The lane partials
-		// travel through the vectors' packed-word stages, which every wavefront is done with behind the barrier below.
 		double acc[V];
 #pragma unroll
 		for (int i = 0; i < V; ++i) {
@@ -647,31 +462,13 @@ __global__ __launch_bounds__(64 * kDecWaves) void k_decode_column(const alpgpu_v
 				}
 			}
 		}
-		__syncthreads(); // nobody reads packed words any more
-		static_assert(kStageBytes >= 8 * 64 * kDecWaves, "the lane partials of a vector fit its stage");
-#pragma unroll
-		for (int i = 0; i < V; ++i) { reinterpret_cast<double*>(L[i].stage)[64 * wave + lane] = acc[i]; }
-		__syncthreads();
-		if (wave < V && v0 + wave < n_vectors) { // wave-uniform: wavefront w finishes vector w
-			const double* part = reinterpret_cast<const double*>(L[wave].stage) + lane;
-			static_assert(kDecWaves == 4, "the documented summation order is for 4 wavefronts per vector");
-			double total = (part[0] + part[64]) + (part[128] + part[192]);
-			total = wave_tree_sum_f64(total); // balanced tree over adjacent lanes (DPP, alp_device.hpp)
-			if (lane == 0) {
-				if constexpr (SINK == kSinkCount) {
-					reinterpret_cast<uint32_t*>(out)[v0 + wave] = static_cast<uint32_t>(total);
-				} else {
-					out[v0 + wave] = total;
-				}
-			}
-		}
+		finish_vector_sinks<SINK == kSinkCount>(L, acc, out, v0, n_vectors, wave, lane, [](int, double&) {});
 		return;
 	}
 #pragma unroll
 	for (int i = 0; i < V; ++i) {
 		if (v0 + i < n_vectors) {
-			const alpgpu_vector_desc dd = d[i];
-			decode_staged_vector<NT_STORE, kSinkStore, LDS>(L[i], dd, dict[i], excs + d[i].exc_off, reinterpret_cast<double2*>(out + (v0 + i) * kVec), wave, lane);
+			decode_staged_vector<NT_STORE, kSinkStore, LDS>(L[i], d[i], dict[i], excs + d[i].exc_off, reinterpret_cast<double2*>(out + (v0 + i) * kVec), wave, lane);
 		}
 	}
 }
@@ -720,43 +517,12 @@ __global__ __launch_bounds__(64 * kDecWaves, kSinkDirectOcc) void k_sink_direct(
 	const uint8_t*           rec  = excs + d.exc_off;
 	const bool               is_alp = d.scheme == ALPGPU_SCHEME_ALP;
 	const int                cnt  = d.exc_cnt;
-	ExcMask                  em {0u, 0};
-	// a narrow ALP vector's words whole into the wavefront's LDS by LDS-DMA (1 KiB per instruction, no registers): ONE round trip for all of
-	// them instead of two batches of register loads
-	const bool staged = is_alp && 128u * d.bw <= static_cast<uint32_t>(kSinkStage) && cnt <= kSinkStageMaxExc; // wave-uniform
-	if (staged) {
-		typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
-		const ull2* g       = reinterpret_cast<const ull2*>(packed + d.packed_off);
-		const int   n_units = 8 * d.bw;
-		for (int j = 0; 64 * j < n_units; ++j) {
-			if (64 * j + lane < n_units) { __builtin_amdgcn_global_load_lds(g + 64 * j + lane, reinterpret_cast<ull2*>(L.stage) + 64 * j, 16, 0, 0); }
-		}
-	}
-	if (cnt > 0) { // wave-uniform: values of the first kExcStage exceptions by LDS-DMA, the mask from the positions
-		const uint32_t val_bytes = (is_alp ? 8u : 2u) * static_cast<uint32_t>(cnt);
-		const int      dwords    = static_cast<int>(((val_bytes < kExcStageBytes ? val_bytes : kExcStageBytes) + 3u) >> 2);
-		for (int q = 0; 64 * q < dwords; ++q) { // wave-uniform trip count; LDS destination = wave-uniform base + 4 * lane
-			if (64 * q + lane < dwords) { __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t*>(rec) + 64 * q + lane, reinterpret_cast<uint32_t*>(L.excv) + 64 * q, 4, 0, 0); }
-		}
-		if (lane < 32) { L.mask[lane] = 0u; }
-		wave_lds_sync();
-		const uint16_t* poss = reinterpret_cast<const uint16_t*>(rec + val_bytes);
-		for (int j = lane; j < cnt; j += 64) {
-			const uint32_t p = poss[j];
-			atomicOr(&L.mask[p >> 5], 1u << (p & 31u));
-		}
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the DMA'd values (LDS-DMA completion is not tracked through the LDS for the compiler)
-		wave_lds_sync();
-		em = load_exception_mask(L, lane);
-		if (lane < 32) { L.pref[lane] = static_cast<uint32_t>(em.excl); }
-		wave_lds_sync();
-	}
-	uint8_t*          first   = const_cast<uint8_t*>(packed + d.packed_off);
-	constexpr int     kRsrcFlags = 0x00020000; // gfx9 raw buffer, 32-bit data format
-	const BufferWords words {__builtin_amdgcn_make_buffer_rsrc(first, 0, 128 * d.bw, kRsrcFlags),
-	                         __builtin_amdgcn_make_buffer_rsrc(first + 128u * d.bw, 0, is_alp ? 0 : 128 * d.lbw, kRsrcFlags)};
+	// staged: a narrow ALP vector with few exceptions
+	const bool    staged = is_alp && 128u * d.bw <= static_cast<uint32_t>(kSinkStage) && cnt <= kSinkStageMaxExc; // wave-uniform
+	const ExcMask em     = stage_wave_vector<8>(L, d, packed, rec, staged, lane);
+	const BufferWords words = packed_word_resources<BufferWords>(packed + d.packed_off, d.bw, d.lbw, is_alp);
 	if (!is_alp) { // wave-uniform: the dictionary into the wavefront's LDS
-		if (lane < 4) { reinterpret_cast<uint32_t*>(L.rdict)[lane] = static_cast<uint32_t>((lane < 2 ? dict.lo : dict.hi) >> (32 * (lane & 1))); }
+		if (lane < 4) { stage_rd_dictionary(L, dict, lane); }
 		wave_lds_sync();
 	}
 	double part[kDecWaves] = {0.0, 0.0, 0.0, 0.0};
@@ -787,43 +553,24 @@ __global__ __launch_bounds__(64 * kDecWaves, kSinkDirectOcc) void k_sink_direct(
 		return;
 	}
 	static_assert(kDecWaves == 4, "the documented summation order is for 4 quarters per vector");
-	double total = (part[0] + part[1]) + (part[2] + part[3]);
-	total        = wave_tree_sum_f64(total);
-	if (lane == 0) {
-		if constexpr (SINK == kSinkCount) {
-			reinterpret_cast<uint32_t*>(out)[v] = static_cast<uint32_t>(total);
-		} else {
-			out[v] = total;
-		}
-	}
+	store_vector_result<SINK == kSinkCount>(out, v, (part[0] + part[1]) + (part[2] + part[3]), lane);
 }
 
+
 int launch_sink_direct(hipStream_t stream, const alpgpu_column* col, double lo, double hi, void* d_out, bool count) {
-	const uint64_t n = col->n_vectors;
-	launch_in_grid_chunks((n + kDecWaves - 1) / kDecWaves, [&](dim3 grid, uint64_t off) {
-		const dim3 block(64 * kDecWaves);
-		if (count) {
-			hipLaunchKernelGGL((k_sink_direct<kSinkCount>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_out), n, off, lo, hi);
-		} else {
-			hipLaunchKernelGGL((k_sink_direct<kSinkSum>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_out), n, off, 0.0, 0.0);
-		}
-	});
-	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
+	double* out = static_cast<double*>(d_out);
+	if (count) { return launch_over_column(k_sink_direct<kSinkCount>, wgs_of(col, kDecWaves), dec_block(), 0, stream, col, out, lo, hi); }
+	return launch_over_column(k_sink_direct<kSinkSum>, wgs_of(col, kDecWaves), dec_block(), 0, stream, col, out, 0.0, 0.0);
 }
 
 // d_zones[v] = {min, max} of vector v's decoded values, NaNs ignored (include/alpgpu.h: zone maps); n_vectors > 0
 int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones) {
-	const uint64_t n = col->n_vectors;
-	launch_in_grid_chunks((n + kDecWaves - 1) / kDecWaves, [&](dim3 grid, uint64_t off) {
-		hipLaunchKernelGGL((k_sink_direct<kSinkMinMax>), grid, dim3(64 * kDecWaves), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, static_cast<double*>(d_zones), n, off, 0.0, 0.0);
-	});
-	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
+	return launch_over_column(k_sink_direct<kSinkMinMax>, wgs_of(col, kDecWaves), dec_block(), 0, stream, col, static_cast<double*>(d_zones), 0.0, 0.0);
 }
 
 int launch_decode_column(hipStream_t stream, const alpgpu_column* col, double* d_out, const DecodeShape& shape, int n_cus, uint64_t* progress, uint64_t progress_tag, uint32_t gate) {
 	(void)n_cus;
 	const uint32_t gate_word = gate != 0 && progress != nullptr ? gate << 8 : 0u; // (k_decode_column: a candidate launch of an unhinted decode)
-	const uint64_t n = col->n_vectors;
 	const bool     nt       = !shape.plain_stores;
 	const int      V        = shape.vectors_per_wg == 1 ? 1 : 2;
 	// Unused dynamic LDS that caps the workgroups resident per CU (shape.pad_kib).  Wide vectors want FEWER
@@ -831,56 +578,29 @@ int launch_decode_column(hipStream_t stream, const alpgpu_column* col, double* d
 	// workgroups per CU and at 0.75 with eight, 34-38 bits like seven; up to 33 bits eight are best (tools/sweep_residency.py,
 	// profiles/r04_decode_floor.txt section 6).  policy_shape_f64 (decode_policy.hpp) sets it from the column's size hints.
 	const unsigned pad_lds  = shape.pad_kib > 0 ? static_cast<unsigned>(shape.pad_kib) * 1024u : 0u;
-	launch_in_grid_chunks((n + V - 1) / V, [&](dim3 grid, uint64_t off) {
-		const dim3 block(64 * kDecWaves);
-		if (V == 2 && nt) {
-			hipLaunchKernelGGL((k_decode_column<2, true>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
-		} else if (V == 2) {
-			hipLaunchKernelGGL((k_decode_column<2, false>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
-		} else if (shape.many_exc && nt) { // one vector per workgroup, the 256-entry exception stage (columns of exception-heavy vectors)
-			hipLaunchKernelGGL((k_decode_column<1, true, kSinkStore, DecodeLdsManyExc>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
-		} else if (nt) {
-			hipLaunchKernelGGL((k_decode_column<1, true>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
-		} else {
-			hipLaunchKernelGGL((k_decode_column<1, false>), grid, block, pad_lds, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_out, n, off, 0.0, 0.0, gate_word, progress, progress_tag);
-		}
-	});
-	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
+	const auto launch = [&](auto kernel) { return launch_over_column(kernel, wgs_of(col, V), dec_block(), pad_lds, stream, col, d_out, 0.0, 0.0, gate_word, progress, progress_tag); };
+	if (V == 2 && nt) { return launch(k_decode_column<2, true>); }
+	if (V == 2) { return launch(k_decode_column<2, false>); }
+	if (shape.many_exc && nt) { return launch(k_decode_column<1, true, kSinkStore, DecodeLdsManyExc>); } // one vector per workgroup, the 256-entry exception stage (columns of exception-heavy vectors)
+	if (nt) { return launch(k_decode_column<1, true>); }
+	return launch(k_decode_column<1, false>);
 }
 
 // vectors_per_wg in {1, 2}.  There is no output stream to compete with, so two vectors in flight per workgroup is the default
 // (measured on the benchmark column: 1.39 / 1.16 / 1.43 ms for 1 / 2 / 4 vectors per workgroup).
 int launch_decode_sum(hipStream_t stream, const alpgpu_column* col, double* d_sums, int vectors_per_wg) {
-	const uint64_t n = col->n_vectors;
-	const int      V = vectors_per_wg == 1 ? 1 : 2;
-	launch_in_grid_chunks((n + V - 1) / V, [&](dim3 grid, uint64_t off) {
-		const dim3 block(64 * kDecWaves);
-		if (V == 2) {
-			hipLaunchKernelGGL((k_decode_column<2, false, kSinkSum>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_sums, n, off, 0.0, 0.0, 0u, static_cast<uint64_t*>(nullptr), 0ull);
-		} else {
-			hipLaunchKernelGGL((k_decode_column<1, false, kSinkSum>), grid, block, 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_sums, n, off, 0.0, 0.0, 0u, static_cast<uint64_t*>(nullptr), 0ull);
-		}
-	});
-	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
+	if (vectors_per_wg == 1) { return launch_over_column(k_decode_column<1, false, kSinkSum>, wgs_of(col, 1), dec_block(), 0, stream, col, d_sums, 0.0, 0.0, 0u, kNoProgress, 0ull); }
+	return launch_over_column(k_decode_column<2, false, kSinkSum>, wgs_of(col, 2), dec_block(), 0, stream, col, d_sums, 0.0, 0.0, 0u, kNoProgress, 0ull);
 }
 
 // measurement aid: the fused consumers' loads, barrier and reduction with the unpack left out (two vectors per workgroup, like them)
 int launch_decode_probe(hipStream_t stream, const alpgpu_column* col, double* d_sums) {
-	const uint64_t n = col->n_vectors;
-	launch_in_grid_chunks((n + 1) / 2, [&](dim3 grid, uint64_t off) {
-		hipLaunchKernelGGL((k_decode_column<2, false, kSinkProbe>), grid, dim3(64 * kDecWaves), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, d_sums, n, off, 0.0, 0.0, 0u, static_cast<uint64_t*>(nullptr), 0ull);
-	});
-	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
+	return launch_over_column(k_decode_column<2, false, kSinkProbe>, wgs_of(col, 2), dec_block(), 0, stream, col, d_sums, 0.0, 0.0, 0u, kNoProgress, 0ull);
 }
 
 // per-vector number of values in [lo, hi]: the same kernel with the predicate as its consumer (two vectors per workgroup)
 int launch_decode_count_range(hipStream_t stream, const alpgpu_column* col, double lo, double hi, uint32_t* d_counts) {
-	const uint64_t n = col->n_vectors;
-	launch_in_grid_chunks((n + 1) / 2, [&](dim3 grid, uint64_t off) {
-		hipLaunchKernelGGL((k_decode_column<2, false, kSinkCount>), grid, dim3(64 * kDecWaves), 0, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc,
-		                   reinterpret_cast<double*>(d_counts), n, off, lo, hi, 0u, static_cast<uint64_t*>(nullptr), 0ull);
-	});
-	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
+	return launch_over_column(k_decode_column<2, false, kSinkCount>, wgs_of(col, 2), dec_block(), 0, stream, col, reinterpret_cast<double*>(d_counts), lo, hi, 0u, kNoProgress, 0ull);
 }
 
 } // namespace alpgpu

@@ -22,6 +22,7 @@
 #include "alp_device_f32.hpp"
 #include "decode_f32_device.hpp"
 #include "launch.hpp"
+#include "staged_decode.hpp"
 #include <cstdlib>
 
 namespace alpgpu {
@@ -46,8 +47,6 @@ struct __attribute__((aligned(16))) StreamLds {
 	uint16_t           table[2][C][256];  // chunk k: table k & 1.  Per quad of a vector: first exception index << 4 | hit bits (0: none)
 	uint32_t           fact[12], frac[12], bound[12];
 };
-
-__device__ __constant__ const uint32_t kStreamShortcutBound[11] = {16777216u, 16777216u, 16777216u, 2147483u, 214748u, 21474u, 2147u, 214u, 21u, 2u, 0u}; // decode_f32_kernels.hip: kShortcutBoundF
 
 __device__ __forceinline__ uint32_t row_exclusive_scan16(uint32_t v) { // over the 16 lanes of a DPP row
 	uint32_t s = v;
@@ -220,9 +219,7 @@ __device__ __forceinline__ void stream_decode_vector(LDS& S, int buf, int tb, in
 	const uint8_t* rec_lds = nullptr;
 	const uint8_t* rec_hbm = nullptr;
 	if constexpr (DIRECT) {
-		uint8_t*      first      = const_cast<uint8_t*>(packed + P.packed_off);
-		constexpr int kRsrcFlags = 0x00020000;
-		const BufferWordsF words {__builtin_amdgcn_make_buffer_rsrc(first, 0, 128 * bw, kRsrcFlags), __builtin_amdgcn_make_buffer_rsrc(first + 128u * bw, 0, is_alp ? 0 : 128 * lbw, kRsrcFlags)};
+		const BufferWordsF words = packed_word_resources<BufferWordsF>(packed + P.packed_off, bw, lbw, is_alp);
 #pragma unroll
 		for (int q = 0; q < 4; ++q) { w[q] = request_quad_f32(words, d, 64 * q + lane); }
 		rec_hbm = excs + P.exc_off;
@@ -350,7 +347,7 @@ __global__ __launch_bounds__(64 * (NDEC + D)) void k_decode_stream_f32(const alp
 		if (lane < 11) {
 			S.fact[lane]  = kFactArrF[lane];
 			S.frac[lane]  = __float_as_uint(kFracArrF[lane]);
-			S.bound[lane] = kStreamShortcutBound[lane];
+			S.bound[lane] = kShortcutBoundF[lane];
 		}
 		if (chunk(j) < n_chunks) {
 			stream_load_descs<C>(S, j, descs, chunk(j) * C, here(chunk(j)), lane);

@@ -15,6 +15,15 @@ template <class Launch> inline void launch_in_grid_chunks(uint64_t n_wg, Launch&
 	for (uint64_t off = 0; off < n_wg; off += grid_chunk(n_wg - off)) { launch(dim3(static_cast<unsigned>(grid_chunk(n_wg - off))), off); }
 }
 
+// A kernel over a column's vectors, n_wg workgroups in all: kernel(the column's four streams, out, n_vectors, first workgroup of the chunk, rest...)
+template <class KERNEL, class OUT, class... REST>
+inline int launch_over_column(KERNEL kernel, uint64_t n_wg, dim3 block, unsigned lds_bytes, hipStream_t stream, const alpgpu_column* col, OUT out, REST... rest) {
+	launch_in_grid_chunks(n_wg, [&](dim3 grid, uint64_t off) {
+		hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, col->d_vectors, col->d_rowgroups, col->d_packed, col->d_exc, out, col->n_vectors, off, rest...);
+	});
+	return hipGetLastError() == hipSuccess ? ALPGPU_OK : ALPGPU_ERR_HIP;
+}
+
 // what alpgpu_encode_* memsets the rowgroup states to in front of a search that PUBLISHES them beside the encode: every byte 0xFF = "not there"
 // (alp_device.hpp: rowgroup_state_is_whole — no word of a real state is all-ones, so a torn read of a state being published is recognised)
 constexpr int kStateUnpublished = 0xFF;
