@@ -169,6 +169,58 @@ def adversarial_vectors_f32():
     return cases
 
 
+def search_boundary_values_f32(tagged=False):
+    """floats on the decision boundaries of the float (e,f) search's arithmetic (alp_device_f32.hpp): v * 10^e * 10^-f around 2^31 and 2^32 (the
+    conversion's range test and its INT32_MIN, the wrap of the decoder's 32-bit product), around 2^22..2^24 and the magic number 1.5 * 2^23 (where
+    t + magic - magic keeps or loses a half), encoded integers r with r * 10^f on the int32 wrap, half-integers, signed zeros, the smallest and the
+    largest magnitudes.  Each is built in float64 and rounded once to float, except the products spelled float32 below (the encoder's own first
+    rounding).  Not deduplicated.  With `tagged` also the decimal exponent e each value was built for (-1 for the leading specials).  Used one
+    value per (constant) vector, so that the rowgroup state names the first (e,f) candidate that round-trips it (or ALP_RD if none does)."""
+    f32 = np.float32
+    vals = [0.0, -0.0, 1e-45, -1e-45, 1.1754942e-38, 1.1754944e-38, np.inf, -np.inf, np.nan, 3.4028235e38]
+    tags = [-1] * len(vals)
+    with np.errstate(over="ignore"):
+        for e in range(11):
+            here = []
+            fe = f32(10.0 ** -e)
+            for big in (2.0**31, 2147483520.0, 2.0**31 + 256.0, 2.0**32, 2.0**32 - 256.0, 2.0**30, 2.0**24, 2.0**23, 2.0**22, 2.0**63, 12582912.0):
+                for x in (f32(f32(big) * fe), f32(big / 10.0**e)):
+                    here += [x, -x]
+                    up = dn = x
+                    for _ in range(2):
+                        up, dn = np.nextafter(up, f32(np.inf)), np.nextafter(dn, f32(-np.inf))
+                        here += [up, dn, -up, -dn]
+            for f in range(e + 1):
+                for lim in (1 << 31, 1 << 32):
+                    for d in (-1, 0, 1):
+                        r = lim // 10**f + d
+                        here += [(r * 10**f) / 10.0**e, -(r * 10**f) / 10.0**e]
+            for k2 in (2**23 + 1, 2**23 + 3, 2**24 - 1, 2**24 - 3, 3 * 2**22 + 1, 2**23 - 1, 2**24 + 2, 2**22 + 1, 2**22 - 1):  # k2 / 2 = the value of t aimed at
+                here += [k2 / (2 * 10.0**e), -k2 / (2 * 10.0**e), f32(f32(k2 / 2.0) * fe), -f32(f32(k2 / 2.0) * fe)]
+            vals += here
+            tags += [e] * len(here)
+        out = np.array([f32(v) for v in vals], np.float32)
+    return (out, np.array(tags, np.int64)) if tagged else out
+
+
+def search_boundary_mixtures_f32(seed, n_vectors=25):
+    """vectors of one-to-ten-digit decimals (a decimal exponent e0 per vector) whose 32 sampled positions (every 32nd value) hold 1..8 boundary
+    values built for that e0, so that the candidates' exception counts and ranges — not just the first that fits — decide the rowgroup state.
+    A float rowgroup samples its vectors 0, 12 and 24: 25 vectors let the three disagree (k > 1)."""
+    rng = np.random.default_rng(seed)
+    pool, tag = search_boundary_values_f32(tagged=True)
+    tag = tag[np.isfinite(pool)]
+    pool = pool[np.isfinite(pool)]
+    x = np.empty(n_vectors * VEC, np.float32)
+    for v in range(n_vectors):
+        e0 = int(rng.integers(0, 11))
+        x[v * VEC:(v + 1) * VEC] = (rng.integers(-1000, 1000, VEC) / 10.0**e0).astype(np.float32)
+        k = int(rng.integers(1, 9))
+        pos = rng.choice(32, k, replace=False) * 32 + v * VEC
+        x[pos] = rng.choice(pool[tag == e0], k)
+    return x
+
+
 def every_bit_width_column(n_vectors=208, seed=77, exceptions=True):
     """ALP vectors of every packed width 0..64 inside ALP rowgroups.  The sampled vectors (index % 12 == 0 inside a rowgroup) hold
     2^62 + 1024 m, m < 2^30: only (e,f) = (0,0) encodes them (times ten they leave int64) and their range needs 40 bits, so the rowgroup is
