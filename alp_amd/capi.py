@@ -148,6 +148,24 @@ TOP_K_MAX = 1024  # ALPGPU_TOP_K_MAX
 _sig("alpgpu_top_k_scratch_bytes", _u64, _u64, _u64)
 for _t in ("f64", "f32"):
     _sig("alpgpu_top_k_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _u64, _int, _vp, _vp, _vp, _vp)
+RANK_MAX, QUANTILE_MAX = 32, 16  # ALPGPU_RANK_MAX, ALPGPU_QUANTILE_MAX
+
+
+class QuantileTuning(C.Structure):  # alpgpu_quantile_tuning
+    _fields_ = [("capacity", C.c_uint64), ("max_workgroups", C.c_uint32), ("flush_every", C.c_uint32)]
+
+
+class QuantileTrace(C.Structure):  # alpgpu_quantile_trace
+    _fields_ = [("compact_pass", C.c_uint32), ("wide_grid", C.c_uint32), ("waves_per_wg", C.c_uint32), ("reserved", C.c_uint32), ("candidates", C.c_uint64), ("n", C.c_uint64),
+                ("zero_skips", C.c_uint64), ("zone_skips", C.c_uint64 * 8)]
+
+
+_sig("alpgpu_quantile_scratch_bytes", _u64, _u64)
+for _t in ("f64", "f32"):
+    _sig("alpgpu_select_rank_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _int, _vp, _vp, _vp)
+    _sig("alpgpu_quantile_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp)
+    _sig("alpgpu_debug_quantile_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _int, _vp, _vp, _vp, C.POINTER(QuantileTuning))
+_sig("alpgpu_debug_quantile_trace", _int, _vp, _vp, C.POINTER(QuantileTrace))
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -1103,6 +1121,136 @@ class Context:
         self.top_k_into(col, mask, k, vals, count, idx, largest=largest, records=records)
         n = min(int(count.item()), k)
         return (vals[:n], idx[:n]) if indices else vals[:n]
+
+    # ---- quantiles (include/alpgpu.h: alpgpu_quantile_scratch_bytes, alpgpu_select_rank_*, alpgpu_quantile_*) ------------
+    @staticmethod
+    def _check_ranks(ranks):
+        if isinstance(ranks, (str, bytes)) or not hasattr(ranks, "__len__") or not 1 <= len(ranks) <= RANK_MAX:
+            raise ValueError("ranks must be a sequence of 1 .. %d integers" % RANK_MAX)
+        out = []
+        for r in ranks:
+            if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= int(r) < 2**64:
+                raise ValueError("a rank must be an integer in 0 .. 2^64 - 1")
+            out.append(int(r))
+        return out
+
+    @staticmethod
+    def _check_q(q):
+        if isinstance(q, (str, bytes)) or not hasattr(q, "__len__") or not 1 <= len(q) <= QUANTILE_MAX:
+            raise ValueError("q must be a sequence of 1 .. %d numbers" % QUANTILE_MAX)
+        out = []
+        for x in q:
+            if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not 0.0 <= float(x) <= 1.0:
+                raise ValueError("a quantile must be a number in [0, 1]")
+            out.append(float(x))
+        return out
+
+    def quantile_scratch(self, col: "DeviceColumn"):
+        """a scratch tensor for select_rank_into / quantile_into on this column (alpgpu_quantile_scratch_bytes; torch allocations are at least 16-byte
+        aligned)"""
+        import torch
+        return torch.empty(lib.alpgpu_quantile_scratch_bytes(col.n_vectors), dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    def _check_quantile_args(self, col, mask, vals_out, n_vals, count_out, zones, scratch):
+        import torch
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        self._check_mask(mask, col.n_vectors)
+        self._check_tensor(count_out, torch.int64, "count_out")
+        if count_out.numel() < 1:
+            raise ValueError("count_out must hold one int64")
+        self._check_tensor(vals_out, tdt, "vals_out")
+        if vals_out.numel() < n_vals:
+            raise ValueError("vals_out must hold %d values" % n_vals)
+        if zones is not None:
+            self._check_zones(zones, tdt, col.n_vectors)
+        need = lib.alpgpu_quantile_scratch_bytes(col.n_vectors)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
+        else:
+            self._check_tensor(scratch, torch.uint8, "scratch")
+            if scratch.numel() < need or scratch.data_ptr() % 16:
+                raise ValueError("scratch must hold alpgpu_quantile_scratch_bytes(n_vectors) bytes, 16-byte aligned")
+        return scratch
+
+    def select_rank_into(self, col: "DeviceColumn", mask, ranks, vals_out, count_out, from_top: bool = False, zones=None, scratch=None, tuning=None):
+        """the raw form of alpgpu_select_rank_f64 / _f32: with S the values at the set bits of the mask that are no NaNs, sorted in the order
+        include/alpgpu.h defines (-0.0 below +0.0), N = |S| goes to count_out (one int64) and S[min(ranks[i], N - 1)] — from_top: counted from the
+        largest — to vals_out[i] (the column's value type, at least len(ranks) long).  N == 0 writes the count alone.  ranks: 1 .. 32 integers on the
+        host, in any order, repeats allowed.  zones: any records that contain the vectors' masked intervals (zone_map, decode_minmax_masked,
+        widened ones): the same bytes, vectors are skipped by them.  tuning: {"capacity", "max_workgroups", "flush_every"} for the debug entry
+        (alpgpu_debug_quantile_*; the same bytes).  Nothing is synchronised and nothing read back; with a scratch given (quantile_scratch)
+        nothing is allocated either, so the call can be captured into a graph.  The mask is only read."""
+        ranks = self._check_ranks(ranks)
+        scratch = self._check_quantile_args(col, mask, vals_out, len(ranks), count_out, zones, scratch)
+        args = [C.byref(col.c), _vp(mask.data_ptr()) if mask.numel() else _vp(scratch.data_ptr()), _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
+                (_u64 * len(ranks))(*ranks), len(ranks), 1 if from_top else 0, _vp(vals_out.data_ptr()), _vp(count_out.data_ptr()), _vp(scratch.data_ptr())]
+        if tuning is None:
+            self._call("select_rank", col.dtype, *args)
+        else:
+            if set(tuning) - {"capacity", "max_workgroups", "flush_every"}:
+                raise ValueError("tuning takes capacity, max_workgroups and flush_every")
+            t = QuantileTuning(int(tuning.get("capacity", 0)), int(tuning.get("max_workgroups", 0)), int(tuning.get("flush_every", 0)))
+            self._call("debug_quantile", col.dtype, *args, C.byref(t))
+
+    def quantile_into(self, col: "DeviceColumn", mask, q, vals_out, count_out, ranks_out=None, zones=None, scratch=None):
+        """the raw form of alpgpu_quantile_f64 / _f32: for each q[i] (1 .. 16 numbers in [0, 1] on the host) the rank r = min(N - 1, floor(q[i] * (N - 1)))
+        (numpy's method="lower") goes to ranks_out[i] (optional, int64), S[r] to vals_out[2 i] and S[min(r + 1, N - 1)] to vals_out[2 i + 1] (the
+        column's value type, at least 2 len(q) long), N to count_out; S, zones, scratch and the promises as for select_rank_into."""
+        import torch
+        q = self._check_q(q)
+        if ranks_out is not None:
+            self._check_tensor(ranks_out, torch.int64, "ranks_out")
+            if ranks_out.numel() < len(q):
+                raise ValueError("ranks_out must hold len(q) ranks")
+        scratch = self._check_quantile_args(col, mask, vals_out, 2 * len(q), count_out, zones, scratch)
+        self._call("quantile", col.dtype, C.byref(col.c), _vp(mask.data_ptr()) if mask.numel() else _vp(scratch.data_ptr()),
+                   _vp(zones.data_ptr()) if zones is not None and zones.numel() else None, (C.c_double * len(q))(*q), len(q), _vp(vals_out.data_ptr()),
+                   _vp(ranks_out.data_ptr()) if ranks_out is not None else None, _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
+
+    def quantile_trace(self, scratch):
+        """what the last select_rank / quantile call on this scratch did (include/alpgpu.h: alpgpu_debug_quantile_trace); synchronises the stream"""
+        import torch
+        self._check_tensor(scratch, torch.uint8, "scratch")
+        t = QuantileTrace()
+        _check(lib.alpgpu_debug_quantile_trace(self.h, _vp(scratch.data_ptr()), C.byref(t)), "alpgpu_debug_quantile_trace")
+        return {"compact_pass": int(t.compact_pass), "wide_grid": int(t.wide_grid), "waves_per_wg": int(t.waves_per_wg), "candidates": int(t.candidates), "n": int(t.n),
+                "zero_skips": int(t.zero_skips), "zone_skips": [int(x) for x in t.zone_skips]}
+
+    def select_rank(self, col: "DeviceColumn", mask, ranks, from_top: bool = False, zones=None):
+        """(values, N): values[i] the ranks[i]-th smallest (from_top: largest) of the values at the set bits of the mask that are no NaNs, ranks
+        beyond the last clamped to it; an empty tensor for N == 0.  One read of the count, which synchronises the stream."""
+        import torch
+        dev = f"cuda:{self.device}"
+        ranks = self._check_ranks(ranks)
+        vals = torch.empty(len(ranks), dtype=torch.float64 if col.dtype == "f64" else torch.float32, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        self.select_rank_into(col, mask, ranks, vals, count, from_top=from_top, zones=zones)
+        n = int(count.item())
+        return (vals if n else vals[:0]), n
+
+    def quantile(self, col: "DeviceColumn", mask, q, interpolation: str = "linear", zones=None):
+        """the quantiles q (a number or 1 .. 16 of them, in [0, 1]) of the values at the set bits of the mask that are no NaNs, as a device tensor:
+        interpolation "lower" / "higher": the neighbour below / above q * (N - 1), of the column's type and bit for bit a value of the column (numpy's
+        method="lower" / "higher"); "linear": lo + (hi - lo) * (q * (N - 1) - r) in double, by torch ops on the device tensors.  NaN where nothing
+        is selected.  Nothing is synchronised."""
+        import torch
+        if interpolation not in ("linear", "lower", "higher"):
+            raise ValueError('interpolation must be "linear", "lower" or "higher"')
+        scalar = isinstance(q, (int, float, np.integer, np.floating)) and not isinstance(q, bool)
+        q = self._check_q([q] if scalar else q)
+        dev = f"cuda:{self.device}"
+        vals = torch.full((len(q), 2), float("nan"), dtype=torch.float64 if col.dtype == "f64" else torch.float32, device=dev)
+        ranks = torch.zeros(len(q), dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        self.quantile_into(col, mask, q, vals, count, ranks, zones=zones)
+        if interpolation == "linear":
+            pos = torch.tensor(q, dtype=torch.float64, device=dev) * (count - 1).clamp(min=0).to(torch.float64)
+            lo, hi = vals[:, 0].to(torch.float64), vals[:, 1].to(torch.float64)
+            frac = pos - ranks.to(torch.float64)
+            out = torch.where((frac == 0) | (hi == lo), lo, lo + (hi - lo) * frac)  # (an infinite neighbour at weight 0, or twice, is no NaN)
+        else:
+            out = vals[:, 0 if interpolation == "lower" else 1]
+        return out[0] if scalar else out
 
     # ---- zone maps (include/alpgpu.h: alpgpu_zone_map_*, alpgpu_zones_minmax_*) ---------------------------------------
     def _check_zones(self, zones, dtype, n_vectors):

@@ -142,7 +142,7 @@ inline uint64_t align8(uint64_t x) { return (x + 7ull) & ~7ull; }
 // p does not lie on a multiple of `bytes` (a power of two); a null pointer never is misaligned
 inline bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) != 0; }
 
-// ---- argument checks that several entry points make (api_mask, api_pair, api_in_list, api_select, api_group, api_minmax, api_top_k, api_zone): each
+// ---- argument checks that several entry points make (api_mask, api_pair, api_in_list, api_select, api_group, api_minmax, api_top_k, api_quantile, api_zone): each
 // returns ALPGPU_OK or fail(...); hidden, like the helpers above.  An entry point calls them in the order in which it reports its errors.
 ALPGPU_INTERNAL inline int check_mask_op(int op) {
 	if (op != ALPGPU_MASK_SET && op != ALPGPU_MASK_AND && op != ALPGPU_MASK_OR) { return fail(ALPGPU_ERR_INVALID, "op is none of ALPGPU_MASK_SET / _AND / _OR"); }

@@ -126,6 +126,29 @@ inline bool top_k_layout(uint64_t n_vectors, uint64_t k, TopKLayout& L) {
 int launch_top_k(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, const void* d_records, uint32_t k, int largest, void* d_vals, int64_t* d_idx,
                  uint64_t* d_count, void* d_scratch, int value_bytes);
 
+// quantile_kernels.hip: the r-th smallest selected values under a bitmap.  quantile_layout: where the pieces of the caller's scratch lie (byte
+// offsets, each a multiple of 16), their total and the candidate capacity, a function of n_vectors alone; false when n_vectors is more than the call
+// accepts.  launch_quantile: col->n_vectors in 1 .. 2^32 - 1; q != nullptr: n quantiles in [0, 1] (n <= ALPGPU_QUANTILE_MAX; d_vals takes 2 n values,
+// d_ranks, nullable, n ranks), else n ranks (n <= ALPGPU_RANK_MAX; d_vals takes n values); both host arrays, copied into the kernel arguments; d_zones
+// nullable; tuning nullable (the debug entry's record).  quantile_trace: what the last call on this scratch did; synchronises the stream.
+constexpr uint64_t kQuantileStateBytes = 2048;
+struct QuantileLayout {
+	uint64_t state, bins, cand, total;
+	uint64_t capacity; // candidate keys: max(65536, 16 * n_vectors)
+};
+inline bool quantile_layout(uint64_t n_vectors, QuantileLayout& L) {
+	if (n_vectors > 0xFFFFFFFFull) { return false; }
+	L.capacity = 16ull * n_vectors > 65536ull ? 16ull * n_vectors : 65536ull;
+	L.state    = 0;
+	L.bins     = L.state + kQuantileStateBytes;
+	L.cand     = L.bins + 8ull * ALPGPU_RANK_MAX * 256ull * sizeof(uint64_t); // at most 8 passes of 32 slots of 256 bins
+	L.total    = L.cand + 8ull * L.capacity;
+	return true;
+}
+int launch_quantile(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, const void* d_zones, const double* q, const uint64_t* ranks, uint32_t n, int from_top,
+                    void* d_vals, uint64_t* d_ranks, uint64_t* d_count, void* d_scratch, int value_bytes, int n_cus, const alpgpu_quantile_tuning* tuning);
+int quantile_trace(hipStream_t stream, const void* d_scratch, alpgpu_quantile_trace* out);
+
 // in_list_kernels.hip: set membership.  launch_select_in_mask: bit(r) = / &= / |= q(r), q(r) = first <= r < first + n and ((some j < n_list has
 // d_list[j] == x_r) != negate) (n > 0; range, op, n_list <= 2^31 - 1 and the alignments checked by the caller; d_list sorted, device memory of the
 // column's type, NULL with n_list == 0; d_zones nullable: the column's zone map); one launch of persistent workgroups, at most four per CU.

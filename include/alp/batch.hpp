@@ -712,6 +712,79 @@ struct column {
 		}
 		return out;
 	}
+	// Quantiles (include/alpgpu.h, "quantiles"): order statistics over the values whose bit is set and that are no NaNs, N = count of them, in the
+	// order of top_k (-0.0 below +0.0); every value has the bits decompress gives it.  select_rank: lower[i] = the min(ranks[i], N - 1)-th smallest
+	// (from_top: largest), 1 .. ALPGPU_RANK_MAX ranks in any order; upper and ranks stay empty.  quantile: for each q[i] in [0, 1] (1 ..
+	// ALPGPU_QUANTILE_MAX) ranks[i] = min(N - 1, floor(q[i] * (N - 1))), lower[i] the value at that rank and upper[i] the one at the next (the
+	// last: itself), what PERCENTILE_DISC and, interpolated by the caller, PERCENTILE_CONT need.  With count == 0 the vectors are empty.
+	// zones (optional): any records that contain the vectors' masked intervals (zone_map, minmax_masked, widened ones); they change no value.
+	struct quantile_result {
+		std::vector<PT>       lower, upper;
+		std::vector<uint64_t> ranks;
+		uint64_t              count = 0;
+	};
+	static quantile_result select_rank(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask, const std::vector<uint64_t>& ranks, bool from_top = false,
+	                                   const std::vector<zone>* zones = nullptr) {
+		if (ranks.empty() || ranks.size() > ALPGPU_RANK_MAX) { throw std::runtime_error("alp::gpu::column::select_rank: 1 .. ALPGPU_RANK_MAX ranks"); }
+		return order_statistics(blob, size, mask, ranks.data(), nullptr, static_cast<uint32_t>(ranks.size()), from_top, zones, "alp::gpu::column::select_rank");
+	}
+	static quantile_result quantile(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask, const std::vector<double>& q, const std::vector<zone>* zones = nullptr) {
+		if (q.empty() || q.size() > ALPGPU_QUANTILE_MAX) { throw std::runtime_error("alp::gpu::column::quantile: 1 .. ALPGPU_QUANTILE_MAX quantiles"); }
+		for (const double x : q) {
+			if (!(x >= 0.0 && x <= 1.0)) { throw std::runtime_error("alp::gpu::column::quantile: a quantile lies outside [0, 1]"); }
+		}
+		return order_statistics(blob, size, mask, nullptr, q.data(), static_cast<uint32_t>(q.size()), false, zones, "alp::gpu::column::quantile");
+	}
+
+  private:
+	static quantile_result order_statistics(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask, const uint64_t* ranks, const double* q, uint32_t n, bool from_top,
+	                                        const std::vector<zone>* zones, const char* who) {
+		uploaded_column up(blob, size, who);
+		const uint64_t  nv = up.col.n_vectors;
+		if (mask.size() != 16 * nv) { throw std::runtime_error(std::string(who) + ": the mask must hold 16 words per vector"); }
+		if (zones && zones->size() != nv) { throw std::runtime_error(std::string(who) + ": one record per vector"); }
+		quantile_result out;
+		if (nv == 0) { return out; }
+		const uint32_t n_vals   = q ? 2 * n : n;
+		uint64_t*      d_mask   = static_cast<uint64_t*>(up.get(mask.size() * sizeof(uint64_t)));
+		zone*          d_zones  = zones ? static_cast<zone*>(up.get(nv * sizeof(zone))) : nullptr;
+		PT*            d_vals   = static_cast<PT*>(up.get(n_vals * sizeof(PT)));
+		uint64_t*      d_ranks  = static_cast<uint64_t*>(up.get(n * sizeof(uint64_t)));
+		uint64_t*      d_count  = static_cast<uint64_t*>(up.get(sizeof(uint64_t)));
+		void*          d_scratch = up.get(alpgpu_quantile_scratch_bytes(nv));
+		check(alpgpu_memcpy_h2d(context(), d_mask, mask.data(), mask.size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d");
+		if (zones) { check(alpgpu_memcpy_h2d(context(), d_zones, zones->data(), nv * sizeof(zone)), "alpgpu_memcpy_h2d"); }
+		if constexpr (sizeof(PT) == 8) {
+			if (q) {
+				check(alpgpu_quantile_f64(context(), &up.col, d_mask, d_zones, q, n, reinterpret_cast<double*>(d_vals), d_ranks, d_count, d_scratch), "alpgpu_quantile_f64");
+			} else {
+				check(alpgpu_select_rank_f64(context(), &up.col, d_mask, d_zones, ranks, n, from_top ? 1 : 0, reinterpret_cast<double*>(d_vals), d_count, d_scratch), "alpgpu_select_rank_f64");
+			}
+		} else {
+			if (q) {
+				check(alpgpu_quantile_f32(context(), &up.col, d_mask, d_zones, q, n, reinterpret_cast<float*>(d_vals), d_ranks, d_count, d_scratch), "alpgpu_quantile_f32");
+			} else {
+				check(alpgpu_select_rank_f32(context(), &up.col, d_mask, d_zones, ranks, n, from_top ? 1 : 0, reinterpret_cast<float*>(d_vals), d_count, d_scratch), "alpgpu_select_rank_f32");
+			}
+		}
+		check(alpgpu_memcpy_d2h(context(), &out.count, d_count, sizeof(out.count)), "alpgpu_memcpy_d2h");
+		if (out.count == 0) { return out; }
+		std::vector<PT> vals(n_vals);
+		check(alpgpu_memcpy_d2h(context(), vals.data(), d_vals, n_vals * sizeof(PT)), "alpgpu_memcpy_d2h");
+		if (q) {
+			out.ranks.resize(n);
+			check(alpgpu_memcpy_d2h(context(), out.ranks.data(), d_ranks, n * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
+			for (uint32_t i = 0; i < n; ++i) {
+				out.lower.push_back(vals[2 * i]);
+				out.upper.push_back(vals[2 * i + 1]);
+			}
+		} else {
+			out.lower = vals;
+		}
+		return out;
+	}
+
+  public:
 	// group_minmax_masked: group_sum_masked's arguments; zones and counts (optional) come back as [n_groups][n_vectors], row g bit for bit what
 	// minmax_masked gives under the mask ANDed with select_mask(key, lo[g], hi[g]) (alpgpu_decode_group_minmax_*).  Returns n_vectors.
 	static uint64_t group_minmax_masked(const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>& mask, const PT* lo, const PT* hi,

@@ -831,6 +831,92 @@ int alpgpu_top_k_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* 
 int alpgpu_top_k_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const alpgpu_zone_f32* d_records, uint64_t k, int largest, float* d_vals, int64_t* d_idx,
                      uint64_t* d_count, void* d_scratch);
 
+/* ---- quantiles ---------------------------------------------------------------------------------------------------------------------------------
+ * Exact order statistics under a WHERE clause: the median, percentiles, the r-th smallest selected value.  No value of the column reaches HBM but
+ * candidate keys bounded by a capacity.
+ *   PERCENTILE_DISC(q) WITHIN GROUP (ORDER BY x)   quantile(x, bitmap, q): the lower neighbour (q * (N - 1) floored; numpy's method="lower");
+ *   PERCENTILE_CONT(q) ...                         the two neighbours, interpolated by the caller: lo + (hi - lo) * (q * (N - 1) - r);
+ *   ORDER BY x LIMIT 1 OFFSET r                    select_rank(x, bitmap, {r}); ORDER BY x DESC: from_top = 1.
+ * Let S be the values of the column at the set bits of the bitmap that are not NaNs (NaN by the bits, quiet or signalling, in an exception record
+ * as in packed words), N = |S|, and s_0 <= s_1 <= ... <= s_{N-1} S sorted by okey ascending: top-k's order, -inf < ... < -0.0 < +0.0 < ... < +inf.
+ * okey is a bijection on bits, so equal keys are equal bit patterns and every s_j is a bit pattern that alpgpu_decode_* writes somewhere.
+ *   alpgpu_select_rank_*        *d_count = N.  For i < n_ranks, d_vals[i] = s_{min(ranks[i], N-1)}; with from_top != 0, s_{N-1-min(ranks[i], N-1)}.
+ *                               Ranks may repeat and come in any order.  N == 0 writes the count and nothing else.
+ *   alpgpu_quantile_*           r_i = min(N-1, (uint64_t)floor(q[i] * (double)(N-1))): one IEEE double multiplication, not fused with anything, then
+ *                               floor, computed on the device (N exists only there).  d_vals[2i] = s_{r_i}, d_vals[2i+1] = s_{min(r_i + 1, N-1)},
+ *                               d_ranks[i] = r_i (d_ranks may be NULL).  q stays double for float columns.  Interpolating between the two
+ *                               neighbours is the caller's arithmetic.  A q[i] outside [0, 1] or NaN is ALPGPU_ERR_INVALID.  N == 0 writes the
+ *                               count and nothing else.
+ *                               `ranks` and `q` are HOST arrays: read before the call returns, they travel as kernel arguments (as lo / hi of
+ *                               alpgpu_decode_group_sum_*), and a captured graph keeps them.
+ *                               d_mask: a selection bitmap of col->n_vectors * 16 words, 8-byte aligned, required, read and never written.
+ *                               d_zones (may be NULL; aligned to its records): any zone map whose records CONTAIN the true masked intervals of
+ *                               the vectors: alpgpu_decode_minmax_masked_*, the unmasked alpgpu_zone_map_*, widened records.  This is the rule of
+ *                               alpgpu_select_range_zoned_*, not top-k's stricter one: the records only prune (from the second pass on, a vector
+ *                               whose record meets no interval still looked at costs 16 bytes), and such records change no output byte.  A record
+ *                               with a NaN bound prunes nothing.  Records that do not contain the truth give unspecified values; even then
+ *                               nothing is read or written out of bounds, at most the documented number of values is written, and the call
+ *                               returns.
+ *                               Cost: a radix select over okey with 8-bit digits, 8 passes for double and 4 for float.  A pass decodes the
+ *                               column in registers and counts in LDS until the values that can still be an answer fit the candidate capacity,
+ *                               max(65536, 16 * n_vectors) keys of 8 bytes (1/64 of the values); the next pass also writes those keys out and the
+ *                               remaining passes read only them.  If the bitmap's set bits fit the capacity, the first pass does: ONE decode.
+ *                               A full column of decimal data takes 2 decodes for one quantile and 4 for 16 of them, one of values that share
+ *                               their leading bytes (ALP_RD) 4 (profiles/r20_quantile.txt).  Worst case: a constant column (or any answer shared
+ *                               by more values than the capacity) never fits and takes all 8 (4) decodes.
+ *                               col->n_vectors == 0: ALPGPU_OK and *d_count = 0 (that one write is still enqueued).
+ *                               ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx, col, d_count, d_vals, d_mask, d_scratch, ranks or q;
+ *                               n_ranks == 0 or > ALPGPU_RANK_MAX, n_q == 0 or > ALPGPU_QUANTILE_MAX; d_scratch not 16-byte aligned, d_mask, d_count
+ *                               or d_ranks not 8-byte aligned, d_vals not aligned to its type, d_zones not aligned to its records; n_vectors >=
+ *                               2^32 or, with n_vectors > 0, a column without descriptors.
+ *   alpgpu_quantile_scratch_bytes  the scratch of a call: caller-owned device memory, 16-byte aligned; what it holds before does not matter and what it
+ *                               holds after is unspecified (alpgpu_debug_quantile_trace reads it).  A function of n_vectors alone: the state, the bins
+ *                               of 8 passes and the candidate keys.  Never 0, monotone; UINT64_MAX for n_vectors >= 2^32.
+ * Contract as for the top-k section: everything is enqueued on the context's stream and on that stream only: asynchronous, no host synchronisation,
+ *   no allocation; none of what the context remembers about columns is read or written; safe inside a stream capture (a replay sees the bitmap's,
+ *   the records' and the column's contents of that time).  All counts live in device memory, every grid is fixed on the host and no workgroup waits
+ *   for another.  Only integer atomics are used and keys are exact: the result is a function of the column, the bitmap and the ranks alone, not of
+ *   launch shapes or of the order in which wavefronts arrive.  (tests/quantile_replica.py holds the host replica.)
+ * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector). */
+#define ALPGPU_RANK_MAX     32
+#define ALPGPU_QUANTILE_MAX 16
+uint64_t alpgpu_quantile_scratch_bytes(uint64_t n_vectors);
+int alpgpu_select_rank_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const alpgpu_zone_f64* d_zones, const uint64_t* ranks, uint32_t n_ranks, int from_top,
+                           double* d_vals, uint64_t* d_count, void* d_scratch);
+int alpgpu_select_rank_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const alpgpu_zone_f32* d_zones, const uint64_t* ranks, uint32_t n_ranks, int from_top,
+                           float* d_vals, uint64_t* d_count, void* d_scratch);
+int alpgpu_quantile_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const alpgpu_zone_f64* d_zones, const double* q, uint32_t n_q, double* d_vals,
+                        uint64_t* d_ranks, uint64_t* d_count, void* d_scratch);
+int alpgpu_quantile_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const alpgpu_zone_f32* d_zones, const double* q, uint32_t n_q, float* d_vals,
+                        uint64_t* d_ranks, uint64_t* d_count, void* d_scratch);
+/* debug / test: alpgpu_select_rank_* with a tuning record, so that small columns reach every path.  A 0 field means the default.  capacity: the candidate
+ * keys, which may only be lowered (the scratch keeps its documented size; a larger value is the default); max_workgroups: of the decode passes' grid;
+ * flush_every: trips of a workgroup's loop (8 vectors each) between two flushes of its LDS bins (default 2^18).  No tuning changes an output byte.
+ * alpgpu_debug_quantile_trace: what the last call on this scratch did (any of the entry points above); synchronises the context's stream.  compact_pass:
+ * the pass that wrote the candidates out, 0 .. passes - 1, or the number of passes (8 / 4) for never; candidates: keys appended; n: N; zone_skips[d]:
+ * vectors skipped by their record in pass d; zero_skips: vectors skipped in the first pass for an all-zero bitmap; the decode passes' grid and
+ * wavefronts per workgroup. */
+typedef struct alpgpu_quantile_tuning {
+    uint64_t capacity;
+    uint32_t max_workgroups;
+    uint32_t flush_every;
+} alpgpu_quantile_tuning;
+typedef struct alpgpu_quantile_trace {
+    uint32_t compact_pass;
+    uint32_t wide_grid;
+    uint32_t waves_per_wg;
+    uint32_t reserved;
+    uint64_t candidates;
+    uint64_t n;
+    uint64_t zero_skips;
+    uint64_t zone_skips[8];
+} alpgpu_quantile_trace;
+int alpgpu_debug_quantile_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const alpgpu_zone_f64* d_zones, const uint64_t* ranks, uint32_t n_ranks,
+                              int from_top, double* d_vals, uint64_t* d_count, void* d_scratch, const alpgpu_quantile_tuning* tuning);
+int alpgpu_debug_quantile_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const alpgpu_zone_f32* d_zones, const uint64_t* ranks, uint32_t n_ranks,
+                              int from_top, float* d_vals, uint64_t* d_count, void* d_scratch, const alpgpu_quantile_tuning* tuning);
+int alpgpu_debug_quantile_trace(alpgpu_ctx* ctx, const void* d_scratch, alpgpu_quantile_trace* out);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
