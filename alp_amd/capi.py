@@ -166,6 +166,16 @@ for _t in ("f64", "f32"):
     _sig("alpgpu_quantile_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp)
     _sig("alpgpu_debug_quantile_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _int, _vp, _vp, _vp, C.POINTER(QuantileTuning))
 _sig("alpgpu_debug_quantile_trace", _int, _vp, _vp, C.POINTER(QuantileTrace))
+HISTOGRAM_EDGES_MAX = 4095  # ALPGPU_HISTOGRAM_EDGES_MAX
+
+
+class HistogramTuning(C.Structure):  # alpgpu_histogram_tuning
+    _fields_ = [("grid", C.c_uint32), ("flush_every", C.c_uint32)]
+
+
+for _t in ("f64", "f32"):
+    _sig("alpgpu_histogram_" + _t, _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp, _vp, _vp, C.c_uint32, _int, _int, _vp)
+    _sig("alpgpu_debug_histogram_" + _t, _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp, _vp, _vp, C.c_uint32, _int, _int, _vp, C.POINTER(HistogramTuning), _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -1251,6 +1261,100 @@ class Context:
         else:
             out = vals[:, 0 if interpolation == "lower" else 1]
         return out[0] if scalar else out
+
+    # ---- histograms (include/alpgpu.h: alpgpu_histogram_*) ---------------------------------------------------------------
+    def histogram_into(self, col: "DeviceColumn", edges, counts_out, mask=None, first: int = 0, n: int = None, right: bool = False, zones=None, accumulate: bool = False,
+                       tuning=None, trace=None):
+        """the raw form of alpgpu_histogram_f64 / _f32: counts_out (int64, exactly len(edges) + 2 words) takes — accumulate: is added — the bucket counts
+        of the values at the indices [first, first + n) whose bit is set in the mask (None: every index of the range).  Bucket b = the number of
+        edges <= x (right: < x), so 0 lies below the first edge and len(edges) at or above the last; the last word counts the NaNs.  edges: a SORTED
+        contiguous device tensor of the column's type, at most HISTOGRAM_EDGES_MAX long (NaNs last are inert, duplicates give empty buckets).  zones:
+        any records that contain the vectors' intervals (zone_map, decode_minmax_masked, widened ones): the same counts, vectors are settled or their
+        search narrowed by them.  tuning: {"grid", "flush_every"}, trace: an int64 device tensor of 4 words that is ADDED to (vectors settled without
+        the column, from their record, by the few-bucket route (always 0), decoded); either sends the call through the debug entry
+        (alpgpu_debug_histogram_*; the same counts).  Nothing is synchronised, allocated or read back, so the call can be captured into a graph."""
+        import torch
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        if not isinstance(edges, torch.Tensor) or edges.dtype != tdt:
+            raise ValueError("edges must be a tensor of the column's type (%s)" % col.dtype)
+        if edges.dim() != 1:
+            raise ValueError("edges must be one-dimensional")
+        if not edges.is_cuda or edges.device.index != self.device or not edges.is_contiguous():
+            raise ValueError("edges must be contiguous on cuda:%d" % self.device)
+        if edges.numel() > HISTOGRAM_EDGES_MAX:
+            raise ValueError("at most %d edges" % HISTOGRAM_EDGES_MAX)
+        self._check_tensor(counts_out, torch.int64, "counts_out")
+        if counts_out.dim() != 1 or counts_out.numel() != edges.numel() + 2:
+            raise ValueError("counts_out must be a one-dimensional int64 tensor of len(edges) + 2 words")
+        if mask is not None:
+            self._check_mask(mask, col.n_vectors)
+        if zones is not None:
+            self._check_zones(zones, tdt, col.n_vectors)
+        first = int(first)
+        n = col.n_vectors * VECTOR_SIZE - first if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        if trace is not None:
+            self._check_tensor(trace, torch.int64, "trace")
+            if trace.numel() != 4:
+                raise ValueError("trace must hold 4 int64 words")
+        args = [C.byref(col.c), first, n, _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
+                _vp(edges.data_ptr()) if edges.numel() else None, edges.numel(), 1 if right else 0, 1 if accumulate else 0, _vp(counts_out.data_ptr())]
+        if tuning is None and trace is None:
+            self._call("histogram", col.dtype, *args)
+        else:
+            tuning = {} if tuning is None else tuning
+            if set(tuning) - {"grid", "flush_every"}:
+                raise ValueError("tuning takes grid and flush_every")
+            t = HistogramTuning(int(tuning.get("grid", 0)), int(tuning.get("flush_every", 0)))
+            self._call("debug_histogram", col.dtype, *args, C.byref(t), _vp(trace.data_ptr()) if trace is not None else None)
+
+    def histogram(self, col: "DeviceColumn", edges, mask=None, first: int = 0, n: int = None, right: bool = False, zones=None, out=None, accumulate: bool = False,
+                  sorted: bool = False):
+        """the histogram of the column's values at the indices [first, first + n) whose bit is set in the mask (None: all of them) as an int64 device
+        tensor of len(edges) + 2 words: word b counts the values with b edges <= x (right: < x) — numpy.searchsorted(edges, x, side="right") /
+        torch.bucketize(x, edges, right=True); right=True: side="left" — and the last word the NaNs.  -0.0 == +0.0; +-inf are ordinary values and
+        edges.  edges: a device tensor, host tensor, sequence or numpy array of the column's type, at most HISTOGRAM_EDGES_MAX long; it is brought
+        into order by torch.sort on the device (NaNs sort last and are inert); sorted=True skips that for a caller who guarantees the order.
+        out: the tensor to write or, with accumulate, to add to (shards, successive ranges, several columns).  zones (zone_map(col) or any records
+        that contain the vectors' intervals): the same counts.  Nothing is synchronised; with out and a sorted device tensor given nothing is
+        allocated either (alpgpu_histogram_f64 / _f32)."""
+        import torch
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        dev = f"cuda:{self.device}"
+        if isinstance(edges, np.ndarray):
+            if edges.dtype != (np.float64 if col.dtype == "f64" else np.float32):
+                raise ValueError("edges must be of the column's type (%s)" % col.dtype)
+            edges = torch.from_numpy(np.ascontiguousarray(edges))
+        elif not isinstance(edges, torch.Tensor):
+            edges = torch.tensor(list(edges), dtype=tdt)
+        if edges.dtype != tdt:
+            raise ValueError("edges must be of the column's type (%s)" % col.dtype)
+        if edges.dim() != 1:
+            raise ValueError("edges must be one-dimensional")
+        if edges.is_cuda and edges.device.index != self.device:
+            raise ValueError("edges must be on the host or on cuda:%d" % self.device)
+        if edges.numel() > HISTOGRAM_EDGES_MAX:
+            raise ValueError("at most %d edges" % HISTOGRAM_EDGES_MAX)
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate adds to a tensor: pass out")
+        else:
+            self._check_tensor(out, torch.int64, "out")
+            if out.dim() != 1 or out.numel() != edges.numel() + 2:
+                raise ValueError("out must be a one-dimensional int64 tensor of len(edges) + 2 words")
+        if mask is not None:
+            self._check_mask(mask, col.n_vectors)
+        if zones is not None:
+            self._check_zones(zones, tdt, col.n_vectors)
+        if int(first) < 0 or (n is not None and int(n) < 0):
+            raise ValueError("first and n must not be negative")
+        if out is None:
+            out = torch.zeros(edges.numel() + 2, dtype=torch.int64, device=dev)  # (zeroed: a column of no vectors writes nothing)
+        lst = edges if edges.is_cuda else edges.to(dev)
+        lst = lst.contiguous() if sorted else torch.sort(lst).values
+        self.histogram_into(col, lst, out, mask=mask, first=first, n=n, right=right, zones=zones, accumulate=accumulate)
+        return out
 
     # ---- zone maps (include/alpgpu.h: alpgpu_zone_map_*, alpgpu_zones_minmax_*) ---------------------------------------
     def _check_zones(self, zones, dtype, n_vectors):

@@ -157,6 +157,16 @@ size_t in_list_lds_max(int value_bytes);
 int launch_select_in_mask(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const void* d_list, uint64_t n_list, int negate, const void* d_zones, int op,
                           uint64_t* d_mask, int value_bytes, int n_cus);
 
+// histogram_kernels.hip: bucket counts by sorted edges.  launch_histogram: d_counts[b] += the values x_r, r in [first, first + n) with its bit set in
+// d_mask (nullable: every r), that are no NaNs and have b = #{i : d_edges[i] <= x_r} (right: <), d_counts[n_edges + 1] += those that are NaNs
+// (col->n_vectors > 0, n > 0, n_edges <= ALPGPU_HISTOGRAM_EDGES_MAX; range and alignments checked by the caller, who has zeroed the counts unless they
+// accumulate; d_edges sorted device memory of the column's type; d_zones, tuning and d_trace nullable); one launch of persistent workgroups, at most
+// three per CU.  launch_histogram_zero: n_words (> 0) counts zeroed by a kernel (what a call that overwrites enqueues first; not hipMemsetAsync, whose
+// node in a captured graph did not survive later replays: histogram_kernels.hip)
+int launch_histogram_zero(hipStream_t stream, uint64_t* d_counts, uint32_t n_words);
+int launch_histogram(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const void* d_zones, const void* d_edges, uint32_t n_edges,
+                     int right, uint64_t* d_counts, int value_bytes, int n_cus, const alpgpu_histogram_tuning* tuning, uint64_t* d_trace);
+
 // zone maps (include/alpgpu.h).  decode_kernels.hip / decode_f32_kernels.hip: d_zones[v] = {min, max} of vector v, decoded in registers by the
 // one-wavefront sink kernels (col->n_vectors > 0)
 int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones);

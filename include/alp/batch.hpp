@@ -839,6 +839,38 @@ struct column {
 	static void select_in_mask(const uint8_t* blob, size_t size, const std::vector<PT>& values, bool negate, mask_op op, std::vector<uint64_t>& mask) {
 		select_in_mask_with(blob, size, values, negate, op, mask, false);
 	}
+	// Histograms (include/alpgpu.h, "histograms"): the bucket counts of the values [0, n_values) whose bit is set in the mask (nullptr: all of them) by
+	// the edges, edges.size() + 2 words: word b counts the values with b edges <= x (right: < x), so word 0 lies below the first edge and word
+	// edges.size() at or above the last; the last word counts the NaNs.  -0.0 == 0.0, +-inf are ordinary.  The edges (at most
+	// ALPGPU_HISTOGRAM_EDGES_MAX) are sorted here, on the host (NaNs last, where they are inert; duplicates give empty buckets).  zones (optional): any
+	// records that contain the vectors' intervals; they change no count.
+	static std::vector<uint64_t> histogram(const uint8_t* blob, size_t size, const std::vector<PT>& edges, bool right = false, const std::vector<uint64_t>* mask = nullptr,
+	                                       const std::vector<zone>* zones = nullptr) {
+		if (edges.size() > ALPGPU_HISTOGRAM_EDGES_MAX) { throw std::runtime_error("alp::gpu::column::histogram: at most ALPGPU_HISTOGRAM_EDGES_MAX edges"); }
+		uploaded_column up(blob, size, "alp::gpu::column::histogram");
+		const uint64_t  nv = up.col.n_vectors;
+		if (mask && mask->size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::histogram: the mask must hold 16 words per vector"); }
+		if (zones && zones->size() != nv) { throw std::runtime_error("alp::gpu::column::histogram: one record per vector"); }
+		std::vector<uint64_t> counts(edges.size() + 2, 0);
+		if (nv == 0) { return counts; }
+		std::vector<PT> list(edges);
+		std::sort(list.begin(), list.end(), [](PT a, PT b) { return b != b ? a == a : a < b; }); // ascending by <, NaNs last
+		uint64_t* d_mask   = mask ? static_cast<uint64_t*>(up.get(mask->size() * sizeof(uint64_t))) : nullptr;
+		zone*     d_zones  = zones ? static_cast<zone*>(up.get(nv * sizeof(zone))) : nullptr;
+		PT*       d_edges  = list.empty() ? nullptr : static_cast<PT*>(up.get(list.size() * sizeof(PT)));
+		uint64_t* d_counts = static_cast<uint64_t*>(up.get(counts.size() * sizeof(uint64_t)));
+		if (mask) { check(alpgpu_memcpy_h2d(context(), d_mask, mask->data(), mask->size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d"); }
+		if (zones) { check(alpgpu_memcpy_h2d(context(), d_zones, zones->data(), nv * sizeof(zone)), "alpgpu_memcpy_h2d"); }
+		if (d_edges) { check(alpgpu_memcpy_h2d(context(), d_edges, list.data(), list.size() * sizeof(PT)), "alpgpu_memcpy_h2d"); }
+		const uint32_t n_edges = static_cast<uint32_t>(list.size());
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_histogram_f64(context(), &up.col, 0, up.n_values, d_mask, d_zones, reinterpret_cast<const double*>(d_edges), n_edges, right ? 1 : 0, 0, d_counts), "alpgpu_histogram_f64");
+		} else {
+			check(alpgpu_histogram_f32(context(), &up.col, 0, up.n_values, d_mask, d_zones, reinterpret_cast<const float*>(d_edges), n_edges, right ? 1 : 0, 0, d_counts), "alpgpu_histogram_f32");
+		}
+		check(alpgpu_memcpy_d2h(context(), counts.data(), d_counts, counts.size() * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
+		return counts;
+	}
 	// The column's values at the set bits of the mask, ascending by index (alpgpu_decode_masked_*): each with the bits decompress gives it.  The
 	// second form also fills `indices` with their value indices (what mask_indices returns).
 	static std::vector<PT> take_masked(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask) { return take_masked_with(blob, size, mask, nullptr); }

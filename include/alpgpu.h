@@ -917,6 +917,81 @@ int alpgpu_debug_quantile_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const u
                               int from_top, float* d_vals, uint64_t* d_count, void* d_scratch, const alpgpu_quantile_tuning* tuning);
 int alpgpu_debug_quantile_trace(alpgpu_ctx* ctx, const void* d_scratch, alpgpu_quantile_trace* out);
 
+/* ---- histograms --------------------------------------------------------------------------------------------------------------------------------
+ * The bucket counts of a column's selected values by sorted edges, no decoded value reaching HBM: width_bucket(x, ...) / GROUP BY bucket with
+ * COUNT(*); COUNT(*) GROUP BY key for a dictionary-coded key with up to thousands of distinct values (point buckets: edges = the keys, bucket i + 1
+ * counts key i); equi-width and equi-depth statistics; density plots.  One decode for up to 4096 buckets, where alpgpu_decode_group_sum_* with
+ * counts serves 16 key ranges per call.
+ *   alpgpu_histogram_*          Take every value index r of [first, first + n) whose bit is set in the bitmap (d_mask == NULL: every r of the range).
+ *                               x_r is, bit for bit, what alpgpu_decode_* writes at r, exceptions patched in.
+ *                                 x_r is a NaN (by the bits: quiet or signalling)   counts in d_counts[n_edges + 1];
+ *                                 right == 0                                        counts in d_counts[b], b = #{i : d_edges[i] <= x_r}: the half-open
+ *                                                                                   buckets [e[b-1], e[b]); numpy.searchsorted(side="right"),
+ *                                                                                   torch.bucketize(right=True);
+ *                                 right != 0                                        b = #{i : d_edges[i] < x_r}: the buckets (e[b-1], e[b]].
+ *                               Bucket 0 lies below the first edge, bucket n_edges at or above the last.  The comparisons are C's: -0.0 == +0.0, and
+ *                               +-inf are ordinary values and ordinary edges.  A NaN edge is never <= anything: NaNs sorted last are inert (the rule
+ *                               alpgpu_select_in_mask_* states for its list).  n_edges == 0 is valid (d_edges may be NULL): one bucket and the NaN
+ *                               counter, COUNT of the values that are no NaNs.
+ *                               d_edges: n_edges elements of the column's type in DEVICE memory, aligned to the element, sorted as numpy.sort
+ *                               sorts, read when the kernel runs (a captured graph sees the edges' contents at replay; n_edges and the pointers are
+ *                               fixed at capture).  Duplicates are allowed and give empty buckets.  An array that is not sorted gives unspecified
+ *                               bucket counts; nothing is read outside d_edges[0 .. n_edges) nor written outside d_counts[0 .. n_edges + 2), and the
+ *                               sum over all n_edges + 2 words is still the number of selected values.  n_edges > ALPGPU_HISTOGRAM_EDGES_MAX
+ *                               returns ALPGPU_ERR_INVALID: the edges sit whole in LDS, and a pivot tier for longer arrays (what
+ *                               alpgpu_select_in_mask_* has for its list) is not built.
+ *                               d_counts: n_edges + 2 words of 8 bytes.  accumulate == 0: the call overwrites them (they are zeroed on the context's
+ *                               stream in front of the kernel; what they held does not matter).  accumulate != 0: the call adds to what they hold: shards
+ *                               of one column on several GPUs after a copy, successive ranges, several columns into one histogram; exact in
+ *                               every case.
+ *                               d_mask (may be NULL): a selection bitmap of col->n_vectors * 16 words, 8-byte aligned, read and never written.  A
+ *                               vector whose words are all zero within the range costs its 128 bytes and nothing of the column; one outside the
+ *                               range costs nothing.
+ *                               d_zones (may be NULL; aligned to its records): any zone map whose records CONTAIN the true intervals of the
+ *                               vectors' selected values: alpgpu_zone_map_*, alpgpu_decode_minmax_masked_*, widened records.  Such records change no
+ *                               count.  A vector whose record lies in ONE bucket, and whose descriptor says ALP without exceptions (a NaN in an ALP
+ *                               vector is always an exception), is the popcount of its selected bits; its packed words are not read.  Any other
+ *                               vector is decoded, its per-value search narrowed to the buckets its record admits.  A record with a NaN bound
+ *                               prunes nothing.  Records that do not contain the truth give unspecified bucket counts; the total stays right and
+ *                               nothing is read or written out of bounds.
+ *                               Cost: the zeroing (a small kernel of the library's own, which a captured graph replays faithfully) and one
+ *                               launch of persistent workgroups, sized to the device; a workgroup stages the edges into
+ *                               LDS once and counts in 32-bit LDS bins, added into d_counts by 64-bit integer atomics at its end (and every 2^18
+ *                               trips, so that no LDS bin overflows).  A value costs ceil(log2(n_edges + 1)) LDS probes and one LDS add; a step of
+ *                               64 values that agree on their bucket costs one add.
+ *                               col->n_vectors == 0: ALPGPU_OK, nothing is written.  n == 0: the counts are zeroed unless accumulate is set, and
+ *                               nothing of the column is read.
+ *                               ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx, col or d_counts; a NULL d_edges with n_edges > 0;
+ *                               n_edges > ALPGPU_HISTOGRAM_EDGES_MAX; d_mask, d_counts or d_trace not 8-byte aligned, d_edges not aligned to its
+ *                               elements, d_zones not aligned to its records; a range past the end; with n_vectors > 0 and n > 0, a column without
+ *                               descriptors.
+ * The call runs on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no scratch, no state kept; none
+ *   of what the context remembers about columns (the decode plans) is read or written; safe inside a stream capture.  Only integer atomics are used
+ *   and no workgroup waits for another: the counts are a function of the column, the bitmap, the edges and the arguments alone, not of launch shapes
+ *   or of the order in which wavefronts arrive.  (tests/histogram_replica.py holds the host replica.)
+ * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector). */
+#define ALPGPU_HISTOGRAM_EDGES_MAX 4095
+int alpgpu_histogram_f64(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const alpgpu_zone_f64* d_zones, const double* d_edges,
+                         uint32_t n_edges, int right, int accumulate, uint64_t* d_counts);
+int alpgpu_histogram_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const alpgpu_zone_f32* d_zones, const float* d_edges,
+                         uint32_t n_edges, int right, int accumulate, uint64_t* d_counts);
+/* debug / test: alpgpu_histogram_* with a tuning record, so that small columns reach every path, and a trace.  A 0 field means the default.  grid: the
+ * workgroups launched (default min(ceil(n_vectors / 8), 3 per CU); more than the column has work for is allowed, at most 65536); flush_every: trips of
+ * a workgroup's loop (8 vectors each) between two flushes of its LDS bins (default 2^18; may only be lowered).  No tuning changes a count.
+ * d_trace (may be NULL): 4 words of device memory that the call ADDS to, each wavefront once per word at its end: vectors
+ *   [0] settled without the column (their bitmap words are all zero within the range, or they lie outside the range),
+ *   [1] settled from their zone record,
+ *   [2] settled by a few-bucket route: always 0; that route is not in the library ("Histograms"),
+ *   [3] decoded. */
+typedef struct alpgpu_histogram_tuning {
+    uint32_t grid;
+    uint32_t flush_every;
+} alpgpu_histogram_tuning;
+int alpgpu_debug_histogram_f64(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const alpgpu_zone_f64* d_zones, const double* d_edges,
+                               uint32_t n_edges, int right, int accumulate, uint64_t* d_counts, const alpgpu_histogram_tuning* tuning, uint64_t* d_trace);
+int alpgpu_debug_histogram_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const alpgpu_zone_f32* d_zones, const float* d_edges,
+                               uint32_t n_edges, int right, int accumulate, uint64_t* d_counts, const alpgpu_histogram_tuning* tuning, uint64_t* d_trace);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
