@@ -166,6 +166,9 @@ for _t in ("f64", "f32"):
     _sig("alpgpu_quantile_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp)
     _sig("alpgpu_debug_quantile_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _int, _vp, _vp, _vp, C.POINTER(QuantileTuning))
 _sig("alpgpu_debug_quantile_trace", _int, _vp, _vp, C.POINTER(QuantileTrace))
+JOIN_NO_MATCH = -1  # ALPGPU_JOIN_NO_MATCH
+for _t in ("f64", "f32"):
+    _sig("alpgpu_join_probe_" + _t, _int, _vp, C.POINTER(CColumn), _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp)
 HISTOGRAM_EDGES_MAX = 4095  # ALPGPU_HISTOGRAM_EDGES_MAX
 
 
@@ -1355,6 +1358,108 @@ class Context:
         lst = lst.contiguous() if sorted else torch.sort(lst).values
         self.histogram_into(col, lst, out, mask=mask, first=first, n=n, right=right, zones=zones, accumulate=accumulate)
         return out
+
+    # ---- join probe (include/alpgpu.h: alpgpu_join_probe_*) -----------------------------------------------------------
+    def join_probe_into(self, col: "DeviceColumn", keys, pos_out, count_out, mask=None, rows=None, span_out=None, idx_out=None, zones=None, scratch=None):
+        """the raw form of alpgpu_join_probe_f64 / _f32: one row per set bit of the mask (None: every index), ascending.  keys: a SORTED contiguous
+        device tensor of the column's type (numpy.sort's order, NaNs last).  pos_out (int64; its numel() is the capacity, None or empty: a count)
+        takes the position of the first key == the value, rows[that position] with rows (int64, one per key) given, or JOIN_NO_MATCH; span_out
+        (optional, int32, at least as long) the number of equal keys; idx_out (optional, int64, at least as long) the value index; count_out (one
+        int64) the number of set bits, also beyond the capacity.  zones (zone_map(col)): the same bytes, vectors whose record admits no key are
+        not decoded.  Nothing is synchronised and nothing read back; without a mask, or with a scratch given (select_scratch), nothing is
+        allocated either, so the call can be captured into a graph."""
+        import torch
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        self._check_tensor(keys, tdt, "keys")
+        if keys.dim() != 1:
+            raise ValueError("keys must be one-dimensional")
+        self._check_tensor(count_out, torch.int64, "count_out")
+        if count_out.numel() < 1:
+            raise ValueError("count_out must hold one int64")
+        capacity = 0
+        if pos_out is not None:
+            self._check_tensor(pos_out, torch.int64, "pos_out")
+            capacity = pos_out.numel()
+        if span_out is not None:
+            self._check_tensor(span_out, torch.int32, "span_out")
+            if span_out.numel() < capacity:
+                raise ValueError("span_out is shorter than pos_out")
+        if idx_out is not None:
+            self._check_tensor(idx_out, torch.int64, "idx_out")
+            if idx_out.numel() < capacity:
+                raise ValueError("idx_out is shorter than pos_out")
+        if rows is not None:
+            self._check_tensor(rows, torch.int64, "rows")
+            if rows.numel() < keys.numel():
+                raise ValueError("rows must hold one int64 per key")
+        if zones is not None:
+            self._check_zones(zones, tdt, col.n_vectors)
+        if mask is not None:
+            self._check_mask(mask, col.n_vectors)
+            need = lib.alpgpu_select_scratch_bytes(col.n_vectors)
+            if scratch is None:
+                scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
+            else:
+                self._check_tensor(scratch, torch.uint8, "scratch")
+                if scratch.numel() < need or scratch.data_ptr() % 16:
+                    raise ValueError("scratch must hold alpgpu_select_scratch_bytes(n_vectors) bytes, 16-byte aligned")
+        self._call("join_probe", col.dtype, C.byref(col.c), _vp(mask.data_ptr()) if mask is not None else None, _vp(zones.data_ptr()) if zones is not None else None,
+                   _vp(keys.data_ptr()) if keys.numel() else None, keys.numel(), _vp(rows.data_ptr()) if rows is not None and keys.numel() else None,
+                   _vp(pos_out.data_ptr()) if capacity else None, _vp(span_out.data_ptr()) if span_out is not None and capacity else None,
+                   _vp(idx_out.data_ptr()) if idx_out is not None and capacity else None, capacity, _vp(count_out.data_ptr()),
+                   _vp(scratch.data_ptr()) if mask is not None and scratch is not None else None)
+
+    def join_probe(self, col: "DeviceColumn", keys, mask=None, rows=None, span: bool = False, indices: bool = False, zones=None, capacity: int = None, sorted: bool = False):
+        """for every set bit of the mask (None: every value of the column), ascending by index, which key the value equals: an int64 tensor pos
+        of positions in the SORTED keys (or rows[position] with rows given), JOIN_NO_MATCH (-1) where no key == the value: -0.0 matches +0.0, a
+        NaN never matches.  Returns pos, or a tuple (pos[, span][, idx]) with span=True (int32: the number of equal keys, the run
+        [pos, pos + span) of the sorted keys) and indices=True (the value indices).  keys: a device tensor, host tensor, sequence or numpy array
+        of the column's type; sorted=True promises numpy.sort's order, else the keys are sorted by torch.sort on the device and, unless rows is
+        given, rows is that sort's permutation: pos then indexes the keys AS PASSED (among equal keys, one of them), which is what
+        gather(dim_col, pos) wants.  rows given with unsorted keys is permuted alongside them.  capacity None: the mask's bits are counted
+        first (one read of the count, which synchronises the stream); without a mask the count is the column's length and nothing is read
+        back."""
+        import torch
+        dev = f"cuda:{self.device}"
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        if isinstance(keys, np.ndarray):
+            if keys.dtype != (np.float64 if col.dtype == "f64" else np.float32):
+                raise ValueError("keys must be of the column's type (%s)" % col.dtype)
+            keys = torch.from_numpy(np.ascontiguousarray(keys))
+        elif not isinstance(keys, torch.Tensor):
+            keys = torch.tensor(list(keys), dtype=tdt)
+        if keys.dtype != tdt:
+            raise ValueError("keys must be of the column's type (%s)" % col.dtype)
+        if keys.dim() != 1:
+            raise ValueError("keys must be one-dimensional")
+        if keys.is_cuda and keys.device.index != self.device:
+            raise ValueError("keys must be on the host or on cuda:%d" % self.device)
+        lst = (keys if keys.is_cuda else keys.to(dev)).contiguous()
+        if rows is not None:
+            if not isinstance(rows, torch.Tensor):
+                rows = torch.as_tensor(np.asarray(rows, dtype=np.int64))
+            rows = rows.to(dev).contiguous()
+            if rows.dtype != torch.int64 or rows.dim() != 1 or rows.numel() != lst.numel():
+                raise ValueError("rows must hold one int64 per key")
+        if not sorted:
+            lst, perm = torch.sort(lst)
+            rows = perm if rows is None else rows[perm]
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        scratch = self.select_scratch(col) if mask is not None else None
+        if capacity is None:
+            if mask is None:
+                capacity = col.n_vectors * VECTOR_SIZE
+            else:
+                self.join_probe_into(col, lst, None, count, mask=mask, scratch=scratch)
+                capacity = int(count.item())
+        capacity = int(capacity)
+        pos = torch.empty(capacity, dtype=torch.int64, device=dev)
+        spn = torch.empty(capacity, dtype=torch.int32, device=dev) if span else None
+        idx = torch.empty(capacity, dtype=torch.int64, device=dev) if indices else None
+        self.join_probe_into(col, lst, pos, count, mask=mask, rows=rows, span_out=spn, idx_out=idx, zones=zones, scratch=scratch)
+        k = capacity if mask is None and capacity <= col.n_vectors * VECTOR_SIZE else min(int(count.item()), capacity)
+        out = [pos[:k]] + ([spn[:k]] if span else []) + ([idx[:k]] if indices else [])
+        return out[0] if len(out) == 1 else tuple(out)
 
     # ---- zone maps (include/alpgpu.h: alpgpu_zone_map_*, alpgpu_zones_minmax_*) ---------------------------------------
     def _check_zones(self, zones, dtype, n_vectors):

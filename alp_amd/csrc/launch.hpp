@@ -157,6 +157,15 @@ size_t in_list_lds_max(int value_bytes);
 int launch_select_in_mask(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const void* d_list, uint64_t n_list, int negate, const void* d_zones, int op,
                           uint64_t* d_mask, int value_bytes, int n_cus);
 
+// join_kernels.hip: join probe.  launch_join_probe: one row per set bit of d_mask (nullable: every index), ascending, up to capacity: d_pos = the
+// position of the first key == x in d_keys (d_rows nullable: the payload there) or ALPGPU_JOIN_NO_MATCH, d_span (nullable) = the keys == x, d_idx
+// (nullable) = the value index; *d_count = the set bits (col->n_vectors > 0; n_keys <= 2^31 - 1, d_pos non-null with capacity > 0, d_scratch non-null with
+// a bitmap and the alignments checked by the caller; d_keys sorted device memory of the column's type; d_zones nullable).  With a bitmap the popcount
+// pass and the scan of mask_kernels.hip, then one launch of persistent workgroups, at most four per CU.  launch_join_count: *d_count = n, by a kernel
+int launch_join_count(hipStream_t stream, uint64_t* d_count, uint64_t n);
+int launch_join_probe(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, const void* d_zones, const void* d_keys, uint64_t n_keys, const int64_t* d_rows,
+                      int64_t* d_pos, uint32_t* d_span, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch, int value_bytes, int n_cus);
+
 // histogram_kernels.hip: bucket counts by sorted edges.  launch_histogram: d_counts[b] += the values x_r, r in [first, first + n) with its bit set in
 // d_mask (nullable: every r), that are no NaNs and have b = #{i : d_edges[i] <= x_r} (right: <), d_counts[n_edges + 1] += those that are NaNs
 // (col->n_vectors > 0, n > 0, n_edges <= ALPGPU_HISTOGRAM_EDGES_MAX; range and alignments checked by the caller, who has zeroed the counts unless they

@@ -79,8 +79,8 @@ int launch_sum_masked(hipStream_t stream, const alpgpu_column* col, const uint64
 }
 
 // the first two phases of mask_to_indices and of the masked projection: counts[v] = the vector's set bits, offsets = their exclusive prefix sum,
-// *d_count = the bitmap's set bits (n_vectors > 0; the scratch laid out as the selection's)
-static int launch_mask_count_scan(hipStream_t stream, const uint64_t* d_mask, uint64_t n_vectors, uint64_t* d_count, const SelScratch& s) {
+// *d_count = the bitmap's set bits (n_vectors > 0; the scratch laid out as the selection's); declared in select_device.hpp: the join probe's too
+int launch_mask_count_scan(hipStream_t stream, const uint64_t* d_mask, uint64_t n_vectors, uint64_t* d_count, const SelScratch& s) {
 	const int rc = launch_vectors(n_vectors, 16, [&](dim3 grid, uint64_t off) { // 256 words = 16 vectors per workgroup
 		hipLaunchKernelGGL(k_mask_count, grid, dim3(256), 0, stream, d_mask, n_vectors, off, s.counts);
 	});

@@ -1,8 +1,8 @@
 // register_decode.hpp — the in-register decode of one 1024-value vector by one wavefront, 64 lanes wide and step by step, and the glue its kernels
 // share.  Every kernel of the selection family decodes through it: k_select (select_device.hpp: range selection, bitmaps, masked SUM and
 // projection), k_pair (pair_device.hpp), k_group (group_device.hpp), k_minmax_masked and k_group_minmax (minmax_device.hpp), k_in_list
-// (in_list_kernels.hip), k_top_k_candidates (top_k_device.hpp) and k_quantile_wide (quantile_device.hpp).  A clamp or a layout rule is stated here
-// and nowhere else.
+// (in_list_kernels.hip), k_join_probe (join_kernels.hip), k_top_k_candidates (top_k_device.hpp) and k_quantile_wide (quantile_device.hpp).  A clamp
+// or a layout rule is stated here and nowhere else.
 //
 // The decode: 16 steps, step m holds value p = 64 m + lane in lane `lane`, so a wave-wide ballot of a predicate IS the 64 bits of the vector's
 // qualify mask for indices 64 m .. 64 m + 63, in index order.  With p = 64 m + lane the lanes of a wavefront read neighbouring words of every
@@ -17,8 +17,8 @@
 //
 // A kernel: DecodeVec (decode_vec_load), the exception mask (exception_mask, exception_masks), then per batch of NB steps step_request followed by
 // step_bits / step_value of each step.  k_select takes 8 steps of one vector to a batch (kSelBatch), the others kStepBatch = 4 (of one vector or of
-// two side by side: as many vector loads in flight).  Every one of them but k_in_list and k_quantile_wide, which are persistent, is launched by
-// launch_vectors below.
+// two side by side: as many vector loads in flight).  Every one of them but k_in_list, k_join_probe and k_quantile_wide, which are persistent, is
+// launched by launch_vectors below.
 #pragma once
 #include <type_traits>
 

@@ -2,7 +2,8 @@
 // integer constant and taking the column's streams and one record, SelArgs: shared by select_kernels.hip (kSelCount, kSelCountZoned, kSelEmit) and
 // mask_kernels.hip (kSelMask: ballots kept as a bitmap, kSelSum: masked SUM, kSelTake: masked projection).  The decode of the vector is
 // register_decode.hpp's, in batches of kSelBatch = 8 steps; what is here are the arms (their prologues and early exits, the predicate and the
-// epilogues), the one launcher of them all (launch_select) and the layout of the caller's scratch.  Only those two files include this header.
+// epilogues), the one launcher of them all (launch_select) and the layout of the caller's scratch.  Only those two files include this header for the
+// kernel; join_kernels.hip includes it for the scratch's layout and the count-and-scan prologue (launch_mask_count_scan) that its bitmap route shares.
 #pragma once
 #include "register_decode.hpp"
 
@@ -18,6 +19,8 @@ struct SelScratch {
 	uint32_t* counts;
 	uint64_t* levels;
 };
+// mask_kernels.hip: counts[v] = the set bits of vector v's 16 bitmap words, offsets = their exclusive prefix sum, *d_count = their total (n_vectors > 0)
+int launch_mask_count_scan(hipStream_t stream, const uint64_t* d_mask, uint64_t n_vectors, uint64_t* d_count, const SelScratch& s);
 inline SelScratch select_scratch(void* d_scratch, uint64_t n_vectors) {
 	uint8_t* const base = static_cast<uint8_t*>(d_scratch);
 	return SelScratch {reinterpret_cast<uint64_t*>(base), reinterpret_cast<uint32_t*>(base + align16(8ull * n_vectors)),

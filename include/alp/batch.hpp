@@ -871,6 +871,63 @@ struct column {
 		check(alpgpu_memcpy_d2h(context(), counts.data(), d_counts, counts.size() * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
 		return counts;
 	}
+	// Join probe (include/alpgpu.h, "join probe"): one row per set bit of the mask (nullptr: every value of [0, n_vectors * 1024)), ascending by index.
+	// pos[j] = the position IN `keys` AS PASSED of a key == the row's value (-0.0 == 0.0, a NaN never matches), ALPGPU_JOIN_NO_MATCH where there is
+	// none; span[j] = the number of keys == it; indices[j] = the row's value index.  The keys are sorted here, on the host (stably, NaNs last), and the
+	// sort's permutation goes along as the call's d_rows: among equal keys pos is the first of them in `keys`.  zones (optional): any records that
+	// contain the vectors' intervals; they change no row.
+	struct join_result {
+		std::vector<int64_t>  pos, indices;
+		std::vector<uint32_t> span;
+	};
+	static join_result join_probe(const uint8_t* blob, size_t size, const std::vector<PT>& keys, const std::vector<uint64_t>* mask = nullptr, const std::vector<zone>* zones = nullptr) {
+		if (keys.size() > 0x7FFFFFFFull) { throw std::runtime_error("alp::gpu::column::join_probe: at most 2^31 - 1 keys"); }
+		uploaded_column up(blob, size, "alp::gpu::column::join_probe");
+		const uint64_t  nv = up.col.n_vectors;
+		if (mask && mask->size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::join_probe: the mask must hold 16 words per vector"); }
+		if (zones && zones->size() != nv) { throw std::runtime_error("alp::gpu::column::join_probe: one record per vector"); }
+		join_result out;
+		if (nv == 0) { return out; }
+		std::vector<int64_t> rows(keys.size());
+		for (size_t i = 0; i < rows.size(); ++i) { rows[i] = static_cast<int64_t>(i); }
+		std::stable_sort(rows.begin(), rows.end(), [&](int64_t a, int64_t b) { return keys[b] != keys[b] ? keys[a] == keys[a] : keys[a] < keys[b]; }); // ascending by <, NaNs last
+		std::vector<PT> list(keys.size());
+		for (size_t i = 0; i < rows.size(); ++i) { list[i] = keys[static_cast<size_t>(rows[i])]; }
+		uint64_t* d_mask    = mask ? static_cast<uint64_t*>(up.get(mask->size() * sizeof(uint64_t))) : nullptr;
+		zone*     d_zones   = zones ? static_cast<zone*>(up.get(nv * sizeof(zone))) : nullptr;
+		PT*       d_keys    = list.empty() ? nullptr : static_cast<PT*>(up.get(list.size() * sizeof(PT)));
+		int64_t*  d_rows    = list.empty() ? nullptr : static_cast<int64_t*>(up.get(rows.size() * sizeof(int64_t)));
+		uint64_t* d_count   = static_cast<uint64_t*>(up.get(sizeof(uint64_t)));
+		void*     d_scratch = mask ? up.get(alpgpu_select_scratch_bytes(nv)) : nullptr;
+		if (mask) { check(alpgpu_memcpy_h2d(context(), d_mask, mask->data(), mask->size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d"); }
+		if (zones) { check(alpgpu_memcpy_h2d(context(), d_zones, zones->data(), nv * sizeof(zone)), "alpgpu_memcpy_h2d"); }
+		if (d_keys) {
+			check(alpgpu_memcpy_h2d(context(), d_keys, list.data(), list.size() * sizeof(PT)), "alpgpu_memcpy_h2d");
+			check(alpgpu_memcpy_h2d(context(), d_rows, rows.data(), rows.size() * sizeof(int64_t)), "alpgpu_memcpy_h2d");
+		}
+		const auto probe = [&](int64_t* d_pos, uint32_t* d_span, int64_t* d_idx, uint64_t capacity) {
+			if constexpr (sizeof(PT) == 8) {
+				return alpgpu_join_probe_f64(context(), &up.col, d_mask, d_zones, reinterpret_cast<const double*>(d_keys), list.size(), d_rows, d_pos, d_span, d_idx, capacity, d_count, d_scratch);
+			} else {
+				return alpgpu_join_probe_f32(context(), &up.col, d_mask, d_zones, reinterpret_cast<const float*>(d_keys), list.size(), d_rows, d_pos, d_span, d_idx, capacity, d_count, d_scratch);
+			}
+		};
+		uint64_t count = 0;
+		check(probe(nullptr, nullptr, nullptr, 0), "alpgpu_join_probe"); // count first, then allocate exactly
+		check(alpgpu_memcpy_d2h(context(), &count, d_count, sizeof(count)), "alpgpu_memcpy_d2h");
+		if (count == 0) { return out; }
+		int64_t*  d_pos  = static_cast<int64_t*>(up.get(count * sizeof(int64_t)));
+		int64_t*  d_idx  = static_cast<int64_t*>(up.get(count * sizeof(int64_t)));
+		uint32_t* d_span = static_cast<uint32_t*>(up.get(count * sizeof(uint32_t)));
+		check(probe(d_pos, d_span, d_idx, count), "alpgpu_join_probe");
+		out.pos.resize(count);
+		out.indices.resize(count);
+		out.span.resize(count);
+		check(alpgpu_memcpy_d2h(context(), out.pos.data(), d_pos, count * sizeof(int64_t)), "alpgpu_memcpy_d2h");
+		check(alpgpu_memcpy_d2h(context(), out.indices.data(), d_idx, count * sizeof(int64_t)), "alpgpu_memcpy_d2h");
+		check(alpgpu_memcpy_d2h(context(), out.span.data(), d_span, count * sizeof(uint32_t)), "alpgpu_memcpy_d2h");
+		return out;
+	}
 	// The column's values at the set bits of the mask, ascending by index (alpgpu_decode_masked_*): each with the bits decompress gives it.  The
 	// second form also fills `indices` with their value indices (what mask_indices returns).
 	static std::vector<PT> take_masked(const uint8_t* blob, size_t size, const std::vector<uint64_t>& mask) { return take_masked_with(blob, size, mask, nullptr); }

@@ -992,6 +992,68 @@ int alpgpu_debug_histogram_f64(alpgpu_ctx* ctx, const alpgpu_column* col, uint64
 int alpgpu_debug_histogram_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const alpgpu_zone_f32* d_zones, const float* d_edges,
                                uint32_t n_edges, int right, int accumulate, uint64_t* d_counts, const alpgpu_histogram_tuning* tuning, uint64_t* d_trace);
 
+/* ---- join probe ---------------------------------------------------------------------------------------------------------------------------------
+ * Which build-side row does each probe row match: the selected values of a compressed column (a foreign key) looked up in a sorted key list (the
+ * build side: a filtered dimension's keys, what alpgpu_decode_masked_* hands back, sorted), no decoded value reaching HBM.  alpgpu_select_in_mask_*
+ * answers WHETHER x is a key (a semi-join); this call keeps the position its lower bound found.  The two routes it completes (TPC-H Q3, Q5, Q10:
+ * lineitem x orders x customer, a foreign key looked up in a filtered dimension):
+ *   inner join        select_in_mask(fk, keys, AND) on the bitmap; join_probe(fk, bitmap, keys, rows) -> d_pos; gather(dim_col, d_pos): no row is NO_MATCH.
+ *   left outer join   join_probe alone; alpgpu_gather_* turns the index -1 into the canonical NaN, the NULL of the outer side.
+ *   alpgpu_join_probe_*         One output row per set bit of d_mask, in ascending value index: rows, order and capacity are exactly those of
+ *                               alpgpu_decode_masked_*.  *d_count = the number of set bits, also when it exceeds `capacity`; rows j <
+ *                               min(*d_count, capacity) are written, nothing at or behind `capacity` and nothing at j >= *d_count.  capacity == 0
+ *                               makes the call a count: d_pos, d_span and d_idx may then be NULL.  d_idx (may be NULL): the value index of row j,
+ *                               bit for bit what alpgpu_mask_to_indices writes.
+ *                               d_mask == NULL means every one of the n_vectors * 1024 indices: row j is index j, d_scratch may be NULL, no count
+ *                               or scan launch is made, and *d_count = n_vectors * 1024 is still written, by a kernel (not by a memset node, which
+ *                               a captured graph was seen to replay wrongly: DESIGN.md, "Histograms").  With a bitmap (n_vectors * 16 words, 8-byte
+ *                               aligned, read and never written) d_scratch is alpgpu_select_scratch_bytes(n_vectors) bytes, 16-byte aligned, in
+ *                               the selection's layout: the popcount pass and the scan are those of alpgpu_decode_masked_*.
+ *                               The match.  x = the value at row j's index, bit for bit what alpgpu_decode_* writes there, exceptions patched in.
+ *                               lb = the number of keys < x, ub = the number of keys <= x.
+ *                                 d_span[j] (d_span may be NULL) = ub - lb: the number of keys == x under C's ==.  -0.0 and +0.0 match each other,
+ *                                                                a NaN value never matches and neither does a NaN key, +-inf are ordinary.
+ *                                 d_pos[j]   no match (ub == lb)          ALPGPU_JOIN_NO_MATCH;
+ *                                            match, d_rows == NULL        lb: the position of the first equal key;
+ *                                            match, d_rows given          d_rows[lb]: the payload stored beside the keys, e.g. torch.sort's `indices`,
+ *                                                                         so that the caller has build-side row ids without a second indexing pass.
+ *                               d_rows (n_keys words of 8 bytes, 8-byte aligned) is read only at matched positions.  The equal run is [lb, lb + span)
+ *                               in d_keys, and in d_rows: all an N:M expansion needs.  The upper bound is searched only when d_span is given.
+ *                               d_keys: n_keys elements of the column's type in DEVICE memory, aligned to the element, read when the kernel runs (a
+ *                               captured graph sees the keys' contents at replay; n_keys and the pointers are fixed at capture), sorted by the
+ *                               rules of alpgpu_select_in_mask_*'s list: as numpy.sort sorts, -0.0 and +0.0 in either order, duplicates allowed,
+ *                               NaNs, if any, last.  n_keys == 0 is valid (d_keys may be NULL): nothing matches.  n_keys > 2^31 - 1 returns
+ *                               ALPGPU_ERR_INVALID.
+ *                               d_zones (may be NULL): the column's zone map, by the contract of alpgpu_select_in_mask_*.  A vector whose
+ *                               [min, max] admits no key gets ALPGPU_JOIN_NO_MATCH and span 0 at all of its set bits; its descriptor, packed words
+ *                               and exception record are not read.  For every other vector the search is narrowed to the part [j0, j1) of the keys
+ *                               that the record admits.  Any zone map that contains the vectors' true intervals gives the bytes of the call without
+ *                               zones; a NaN bound means "decode the vector".
+ *                               Robustness.  Keys that are not sorted, or a zone map that lies, change only d_pos and d_span: every d_pos is then
+ *                               ALPGPU_JOIN_NO_MATCH, or lies in [0, n_keys), or is an element of d_rows[0 .. n_keys); every span is <= n_keys;
+ *                               *d_count and d_idx are unaffected; nothing is read outside d_keys, d_rows or the column and nothing is written
+ *                               outside the first min(count, capacity) rows: every probe index is clamped.
+ *                               Cost: with a bitmap the popcount pass and the scan; then one launch of persistent workgroups, sized to the device
+ *                               and not to the column.  A workgroup stages the keys into LDS once, as alpgpu_select_in_mask_* does its list (whole
+ *                               up to alpgpu_in_list_lds_max(value bytes) elements, every stride-th beyond); a value costs the probes of one
+ *                               search (two with d_span) and one ==.  A vector without a set bit costs 4 bytes, one behind the capacity 12; the
+ *                               packed words and exception values are read only for the quarters of a vector that hold a bit.
+ *                               col->n_vectors == 0: *d_count = 0 is written and nothing else.
+ *                               ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx, col or d_count; a NULL d_pos with capacity > 0; a NULL
+ *                               d_scratch (or one not 16-byte aligned) with a bitmap and n_vectors > 0; a NULL d_keys with n_keys > 0;
+ *                               n_keys > 2^31 - 1; d_mask, d_rows, d_pos, d_idx or d_count not 8-byte aligned, d_span not 4-byte aligned, d_keys
+ *                               not aligned to its elements, d_zones not aligned to its records; with n_vectors > 0 and capacity > 0, a column
+ *                               without descriptors.
+ * The call runs on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no state kept, no atomics on
+ *   results (none at all); none of what the context remembers about columns (the decode plans) is read or written; safe inside a stream capture.
+ *   The result is a function of the column, the bitmap, the keys, the rows and the arguments alone.  (tests/join_replica.py holds the host replica.)
+ * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector). */
+#define ALPGPU_JOIN_NO_MATCH (-1)
+int alpgpu_join_probe_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const alpgpu_zone_f64* d_zones, const double* d_keys, uint64_t n_keys,
+                          const int64_t* d_rows, int64_t* d_pos, uint32_t* d_span, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch);
+int alpgpu_join_probe_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const alpgpu_zone_f32* d_zones, const float* d_keys, uint64_t n_keys,
+                          const int64_t* d_rows, int64_t* d_pos, uint32_t* d_span, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
