@@ -13,7 +13,14 @@
 // check sits on the insertion path), so the replay takes the D distinct left parts in order of first occurrence with their
 // final counts: D insertions + at most 2D node moves in rehashes + a sort of D elements, D <= 288 (typically 10-40).
 #pragma once
+#if defined(__HIPCC__)
 #include "alp_device.hpp"
+#else // the replay alone, compiled for the host as plain C++ (tests/cpp/rd_order_test.cpp holds it against the real containers)
+#include <stdint.h>
+#ifndef __device__
+#define __device__
+#endif
+#endif
 
 namespace alpgpu {
 
@@ -222,6 +229,9 @@ __device__ inline void sort(uint32_t* s, int n, int16_t* stack) {
 		int first = stack[--sp];
 		while (last - first > 16) {
 			if (depth == 0) {
+#ifdef ALPGPU_RD_ORDER_ON_HEAP_SORT // (the host test program counts its visits here; never defined in a build of the library)
+				ALPGPU_RD_ORDER_ON_HEAP_SORT;
+#endif
 				heap_sort(s + first, last - first);
 				break;
 			}

@@ -600,6 +600,34 @@ void alpo_rd_init(const double* col, size_t off, size_t n, double* sample_arr, a
 	rd_build_dictionary(sample_arr, right_bit_width, st, 1);
 }
 
+/* rd_encoder::find_best_dictionary (forced_cut = 0) or build_left_parts_dictionary<true> for ONE cut (1..16) on a sample
+ * array handed in directly: the persisted state, the estimate of that cut and the whole sorted list.  out_widths =
+ * { right width, left width, dictionary size }; sorted has room for n entries. */
+void alpo_rd_state_from_samples(const double* samples, size_t n, int forced_cut, uint8_t* out_widths, uint16_t* dict8,
+                                double* estimate, uint16_t* sorted, uint16_t* sorted_count) {
+	alpo_state* st       = (alpo_state*)calloc(1, sizeof(alpo_state));
+	st->scheme           = ALPO_SCHEME_ALP_RD;
+	st->sampled_values_n = n;
+	int    right_bit_width = 64 - forced_cut;
+	double best            = 1.7976931348623157e308;
+	if (forced_cut == 0) {
+		right_bit_width = 0;
+		for (int i = 1; i <= CUTTING_LIMIT; i++) {
+			const double est = rd_build_dictionary(samples, 64 - i, st, 0);
+			if (est < best) {
+				right_bit_width = 64 - i;
+				best            = est;
+			}
+		}
+	}
+	*estimate     = rd_build_dictionary(samples, right_bit_width, st, 1);
+	out_widths[0] = st->right_bit_width, out_widths[1] = st->left_bit_width, out_widths[2] = st->actual_dictionary_size;
+	memcpy(dict8, st->left_parts_dict, 16);
+	*sorted_count = st->rd_sorted_count;
+	memcpy(sorted, st->rd_sorted_left, (size_t)st->rd_sorted_count * 2);
+	free(st);
+}
+
 /* include/alp/rd.hpp:109-147.  Index of a left part: its dictionary position; else, if the reference's
  * left_parts_dict_map holds it (sorted positions > dict_size, rd.hpp:75), that position; else dict_size. */
 void alpo_rd_encode(const double* in, uint16_t* exc, uint16_t* pos, uint16_t* cnt, uint64_t* right, uint16_t* left,

@@ -56,6 +56,10 @@ void alpo_falp(const uint64_t* in, double* out, int bw, uint64_t base, int fac, 
 void alpo_patch(double* out, const double* exc, const uint16_t* pos, uint16_t cnt);
 
 void alpo_rd_init(const double* col, size_t off, size_t n, double* sample_arr, alpo_state* st);
+/* find_best_dictionary (forced_cut = 0) or build_left_parts_dictionary<true> of one cut (1..16) on n samples given directly:
+ * out_widths = { right width, left width, dictionary size }, the dictionary, that cut's estimate, the whole sorted list */
+void alpo_rd_state_from_samples(const double* samples, size_t n, int forced_cut, uint8_t* out_widths, uint16_t* dict8,
+                                double* estimate, uint16_t* sorted, uint16_t* sorted_count);
 void alpo_rd_encode(const double* in, uint16_t* exc, uint16_t* pos, uint16_t* cnt, uint64_t* right, uint16_t* left,
                     const alpo_state* st);
 void alpo_rd_decode(double* out, const uint64_t* right, const uint16_t* left, const uint16_t* exc, const uint16_t* pos,
@@ -95,6 +99,8 @@ void    alpof_decode(const int32_t* enc, int fac, int exp, float* out);
 void    alpof_falp(const uint32_t* in, float* out, int bw, uint32_t base, int fac, int exp);
 void    alpof_patch(float* out, const float* exc, const uint16_t* pos, uint16_t cnt);
 void    alpof_rd_init(const float* col, size_t off, size_t n, float* sample_arr, alpo_state* st);
+void    alpof_rd_state_from_samples(const float* samples, size_t n, int forced_cut, uint8_t* out_widths, uint16_t* dict8,
+                                    double* estimate, uint16_t* sorted, uint16_t* sorted_count);
 void    alpof_rd_encode(const float* in, uint16_t* exc, uint16_t* pos, uint16_t* cnt, uint32_t* right, uint16_t* left,
                         const alpo_state* st);
 void    alpof_rd_decode(float* out, const uint32_t* right, const uint16_t* left, const uint16_t* exc, const uint16_t* pos,

@@ -407,6 +407,32 @@ void alpof_rd_init(const float* col, size_t off, size_t n, float* sample_arr, al
 	rd32_build_dictionary(sample_arr, right_bit_width, st, 1);
 }
 
+/* as alpo_rd_state_from_samples (alp_oracle.c), cuts 32-1 .. 32-16 */
+void alpof_rd_state_from_samples(const float* samples, size_t n, int forced_cut, uint8_t* out_widths, uint16_t* dict8,
+                                 double* estimate, uint16_t* sorted, uint16_t* sorted_count) {
+	alpo_state* st       = (alpo_state*)calloc(1, sizeof(alpo_state));
+	st->scheme           = ALPO_SCHEME_ALP_RD;
+	st->sampled_values_n = n;
+	int    right_bit_width = 32 - forced_cut;
+	double best            = 1.7976931348623157e308;
+	if (forced_cut == 0) {
+		right_bit_width = 0;
+		for (int i = 1; i <= CUTTING_LIMIT; i++) {
+			const double est = rd32_build_dictionary(samples, 32 - i, st, 0);
+			if (est < best) {
+				right_bit_width = 32 - i;
+				best            = est;
+			}
+		}
+	}
+	*estimate     = rd32_build_dictionary(samples, right_bit_width, st, 1);
+	out_widths[0] = st->right_bit_width, out_widths[1] = st->left_bit_width, out_widths[2] = st->actual_dictionary_size;
+	memcpy(dict8, st->left_parts_dict, 16);
+	*sorted_count = st->rd_sorted_count;
+	memcpy(sorted, st->rd_sorted_left, (size_t)st->rd_sorted_count * 2);
+	free(st);
+}
+
 /* rd.hpp:109-147 */
 void alpof_rd_encode(const float* in, uint16_t* exc, uint16_t* pos, uint16_t* cnt, uint32_t* right, uint16_t* left,
                      const alpo_state* st) {

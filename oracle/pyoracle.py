@@ -48,6 +48,21 @@ class _Base:
         f.restype = restype
         return f
 
+    # ---- ALP_RD cut + dictionary of a sample array given directly ---------------------------------
+    sample_dtype = np.float64
+
+    def rd_state_from_samples(self, samples: np.ndarray, forced_cut: int = 0) -> dict:
+        """rd_encoder::find_best_dictionary (forced_cut = 0) or build_left_parts_dictionary<true> for one cut 1..16 on these
+        first-level samples -> rbw, lbw, dict_size, dict (8 entries, zeros behind the size), estimate (of that cut) and
+        sorted (all distinct left parts in the reference's sorted order)."""
+        assert samples.dtype == self.sample_dtype, "bit patterns must not go through a conversion"
+        samples = np.ascontiguousarray(samples)
+        assert 1 <= samples.size <= VECTOR_SIZE and 0 <= forced_cut <= 16
+        widths, dict8, est = np.zeros(3, np.uint8), np.zeros(8, np.uint16), np.zeros(1, np.float64)
+        srt, cnt = np.zeros(max(samples.size, 8) + 1, np.uint16), np.zeros(1, np.uint16)
+        self.fn("rd_state_from_samples")(_p(samples), C.c_size_t(samples.size), C.c_int(forced_cut), _p(widths), _p(dict8), _p(est), _p(srt), _p(cnt))
+        return dict(rbw=int(widths[0]), lbw=int(widths[1]), dict_size=int(widths[2]), dict=dict8, estimate=float(est[0]), sorted=srt[: int(cnt[0])].copy())
+
     # ---- whole column ---------------------------------------------------------------------------
     def encode_column(self, col: np.ndarray) -> dict:
         col = np.ascontiguousarray(col, dtype=np.float64)
@@ -275,6 +290,7 @@ def _encode_column_f32(fn, col: np.ndarray) -> dict:
 class OracleF32(_Base):
     """Plain-C restatement of the float path (oracle/alp_oracle_f32.c)."""
     prefix = "alpof_"
+    sample_dtype = np.float32
 
     def __init__(self, path: str = ORACLE_SO):
         if not os.path.exists(path):
@@ -332,6 +348,7 @@ class OracleF32(_Base):
 class ReferenceF32(_Base):
     """The real reference's float instantiation (ref_harness.cpp, reff_*)."""
     prefix = "reff_"
+    sample_dtype = np.float32
 
     def __init__(self, path: str = REF_SO):
         super().__init__(path)

@@ -29,7 +29,50 @@
 
 using dstate = alp::state<double>;
 
+// rd_encoder::find_best_dictionary (forced_cut = 0) or build_left_parts_dictionary<true> for ONE cut (rd.hpp:89-104 / :33-87) on a sample array
+// handed in directly.  The reference keeps its sorted list local; what it leaves behind determines it: positions < size are the dictionary,
+// positions > size are the values of left_parts_dict_map (rd.hpp:75-77), and position == size (which rd.hpp:75 skips) is the one sampled left
+// part the map does not hold.
+template <class PT, class UT>
+static void rd_state_from_samples(const PT* samples, size_t n, int forced_cut, uint8_t* out_widths, uint16_t* dict8, double* estimate,
+                                  uint16_t* sorted, uint16_t* sorted_count) {
+	alp::state<PT> stt;
+	stt.scheme           = alp::Scheme::ALP_RD;
+	stt.sampled_values_n = n;
+	constexpr int kBits  = sizeof(UT) * 8;
+	if (forced_cut == 0) { alp::rd_encoder<PT>::find_best_dictionary(samples, stt); }
+	const alp::bw_t rbw = forced_cut == 0 ? stt.right_bit_width : static_cast<alp::bw_t>(kBits - forced_cut);
+	*estimate           = alp::rd_encoder<PT>::template build_left_parts_dictionary<true>(samples, rbw, stt);
+	const int ds        = stt.actual_dictionary_size;
+	out_widths[0] = stt.right_bit_width, out_widths[1] = stt.left_bit_width, out_widths[2] = static_cast<uint8_t>(ds);
+	for (int i = 0; i < 8; ++i) { dict8[i] = i < ds ? stt.left_parts_dict[i] : 0; }
+	size_t count = 0;
+	for (auto& kv : stt.left_parts_dict_map) {
+		sorted[kv.second] = kv.first;
+		count             = kv.second + 1u > count ? kv.second + 1u : count;
+	}
+	for (size_t i = 0; i < n; ++i) {
+		UT bits;
+		std::memcpy(&bits, &samples[i], sizeof(UT));
+		const uint16_t left = static_cast<uint16_t>(bits >> rbw);
+		if (stt.left_parts_dict_map.find(left) == stt.left_parts_dict_map.end()) {
+			sorted[ds] = left;
+			count      = count > static_cast<size_t>(ds) + 1 ? count : static_cast<size_t>(ds) + 1;
+		}
+	}
+	*sorted_count = static_cast<uint16_t>(count);
+}
+
 extern "C" {
+
+void ref_rd_state_from_samples(const double* samples, size_t n, int forced_cut, uint8_t* out_widths, uint16_t* dict8, double* estimate,
+                               uint16_t* sorted, uint16_t* sorted_count) {
+	rd_state_from_samples<double, uint64_t>(samples, n, forced_cut, out_widths, dict8, estimate, sorted, sorted_count);
+}
+void reff_rd_state_from_samples(const float* samples, size_t n, int forced_cut, uint8_t* out_widths, uint16_t* dict8, double* estimate,
+                                uint16_t* sorted, uint16_t* sorted_count) {
+	rd_state_from_samples<float, uint32_t>(samples, n, forced_cut, out_widths, dict8, estimate, sorted, sorted_count);
+}
 
 // ---- state handle ---------------------------------------------------------------------------
 void* ref_state_new() { return new dstate(); }

@@ -426,6 +426,8 @@ def test_rd_dictionary_of_one_cut_matches_the_reference_formula(ctx, dtype):
     arithmetic restated in numpy (histogram of the left parts, the 8 most frequent stay, 32 bits per other sample; ties do not move the
     estimate), for every cut of 1..16 bits; and the first strictly smallest estimate is the cut alpgpu_rd_state_from_samples_* chooses."""
     from alp_amd import capi
+    from oracle.pyoracle import Oracle, OracleF32
+    orc = Oracle() if dtype == "f64" else OracleF32()
     bits = 64 if dtype == "f64" else 32
     rng = np.random.default_rng(12)
     tdt, ndt, udt = (torch.float64, np.float64, np.uint64) if dtype == "f64" else (torch.float32, np.float32, np.uint32)
@@ -448,7 +450,7 @@ def test_rd_dictionary_of_one_cut_matches_the_reference_formula(ctx, dtype):
             got_state = st.cpu().numpy().view(capi.ROWGROUP_DTYPE)[0]
             assert float(est[0]) == want, (dtype, n_smp, cut, float(est[0]), want)
             assert (got_state["rd_rbw"], got_state["rd_lbw"], got_state["rd_dict_size"], got_state["scheme"]) == (rbw, lbw, ds, capi.SCHEME_ALP_RD)
-            assert set(int(x) for x in got_state["rd_dict"][:ds]) <= set(int(x) for x in left)
+            assert np.array_equal(got_state["rd_dict"], orc.rd_state_from_samples(smp, cut)["dict"]), (dtype, n_smp, cut, "the dictionary, entry by entry in the reference's order")
             ests.append(float(est[0]))
         ctx.state_from_samples(d_smp, st, rd_only=True)
         ctx.synchronize()
