@@ -179,6 +179,17 @@ class HistogramTuning(C.Structure):  # alpgpu_histogram_tuning
 for _t in ("f64", "f32"):
     _sig("alpgpu_histogram_" + _t, _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp, _vp, _vp, C.c_uint32, _int, _int, _vp)
     _sig("alpgpu_debug_histogram_" + _t, _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp, _vp, _vp, C.c_uint32, _int, _int, _vp, C.POINTER(HistogramTuning), _vp)
+DISTINCT_MAX = 1 << 20  # ALPGPU_DISTINCT_MAX
+
+
+class DistinctTuning(C.Structure):  # alpgpu_distinct_tuning
+    _fields_ = [("grid", C.c_uint32), ("flush_every", C.c_uint32), ("lds_slots", C.c_uint32), ("table_slots", C.c_uint32), ("sort_tile", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+_sig("alpgpu_distinct_scratch_bytes", _u64, _u64)
+for _t in ("f64", "f32"):
+    _sig("alpgpu_distinct_" + _t, _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp)
+    _sig("alpgpu_debug_distinct_" + _t, _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, C.POINTER(DistinctTuning), _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -1358,6 +1369,89 @@ class Context:
         lst = lst.contiguous() if sorted else torch.sort(lst).values
         self.histogram_into(col, lst, out, mask=mask, first=first, n=n, right=right, zones=zones, accumulate=accumulate)
         return out
+
+    # ---- distinct values (include/alpgpu.h: alpgpu_distinct_*) ----------------------------------------------------------
+    _DISTINCT_TUNING = ("grid", "flush_every", "lds_slots", "table_slots", "sort_tile")
+
+    def distinct_scratch(self, capacity: int):
+        """a scratch tensor for distinct_into with this capacity (alpgpu_distinct_scratch_bytes; torch allocations are at least 16-byte aligned)"""
+        import torch
+        capacity = int(capacity)
+        if not 1 <= capacity <= DISTINCT_MAX:
+            raise ValueError("capacity must be in 1 .. %d" % DISTINCT_MAX)
+        return torch.empty(lib.alpgpu_distinct_scratch_bytes(capacity), dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    def distinct_into(self, col: "DeviceColumn", vals_out, state_out, counts_out=None, mask=None, first: int = 0, n: int = None, zones=None, scratch=None, tuning=None, trace=None):
+        """the raw form of alpgpu_distinct_f64 / _f32: the distinct values, ascending, of the values at the indices [first, first + n) whose bit is set
+        in the mask (None: every index of the range) go to vals_out (the column's type; its numel() is the capacity, 1 .. DISTINCT_MAX), how often
+        each occurs to counts_out (optional, int64, at least as long).  -0.0 and +0.0 are one value, reported as +0.0; NaNs are no values, only
+        counted.  state_out (int64, 4 words): the entries written, the selected NaNs, the selected values that are no NaNs, 1 if there are more
+        distinct values than the capacity (then the entries are unspecified; nothing is written beyond the capacity).  zones: any records that
+        contain the vectors' intervals: the same bytes, constant ALP vectors are settled from their record.  tuning: {"grid", "flush_every",
+        "lds_slots", "table_slots", "sort_tile"}, trace: an int64 device tensor of 6 words that is ADDED to; either sends the call through the
+        debug entry (alpgpu_debug_distinct_*; the same bytes).  Nothing is synchronised and nothing read back; with a scratch given
+        (distinct_scratch) nothing is allocated either, so the call can be captured into a graph."""
+        import torch
+        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        self._check_tensor(vals_out, tdt, "vals_out")
+        capacity = vals_out.numel()
+        if vals_out.dim() != 1 or not 1 <= capacity <= DISTINCT_MAX:
+            raise ValueError("vals_out must be one-dimensional and hold 1 .. %d values" % DISTINCT_MAX)
+        self._check_tensor(state_out, torch.int64, "state_out")
+        if state_out.numel() != 4:
+            raise ValueError("state_out must hold 4 int64 words")
+        if counts_out is not None:
+            self._check_tensor(counts_out, torch.int64, "counts_out")
+            if counts_out.numel() < capacity:
+                raise ValueError("counts_out is shorter than vals_out")
+        if mask is not None:
+            self._check_mask(mask, col.n_vectors)
+        if zones is not None:
+            self._check_zones(zones, tdt, col.n_vectors)
+        first = int(first)
+        n = col.n_vectors * VECTOR_SIZE - first if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        if trace is not None:
+            self._check_tensor(trace, torch.int64, "trace")
+            if trace.numel() != 6:
+                raise ValueError("trace must hold 6 int64 words")
+        need = lib.alpgpu_distinct_scratch_bytes(capacity)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
+        else:
+            self._check_tensor(scratch, torch.uint8, "scratch")
+            if scratch.numel() < need or scratch.data_ptr() % 16:
+                raise ValueError("scratch must hold alpgpu_distinct_scratch_bytes(capacity) bytes, 16-byte aligned")
+        args = [C.byref(col.c), first, n, _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
+                capacity, _vp(vals_out.data_ptr()), _vp(counts_out.data_ptr()) if counts_out is not None else None, _vp(state_out.data_ptr()), _vp(scratch.data_ptr())]
+        if tuning is None and trace is None:
+            self._call("distinct", col.dtype, *args)
+        else:
+            tuning = {} if tuning is None else tuning
+            if set(tuning) - set(self._DISTINCT_TUNING):
+                raise ValueError("tuning takes " + ", ".join(self._DISTINCT_TUNING))
+            t = DistinctTuning(*[int(tuning.get(k, 0)) for k in self._DISTINCT_TUNING], 0)
+            self._call("debug_distinct", col.dtype, *args, C.byref(t), _vp(trace.data_ptr()) if trace is not None else None)
+
+    def distinct(self, col: "DeviceColumn", mask=None, first: int = 0, n: int = None, zones=None, capacity: int = 65536, counts: bool = True):
+        """(values, counts, n_nan, overflow): the distinct values, ascending, of the column's values at the indices [first, first + n) whose bit is set in
+        the mask (None: all of them) as a device tensor of the column's type, how often each occurs as an int64 device tensor (None with
+        counts=False), the number of selected NaNs (which are no values) and whether there are more than `capacity` distinct values: then
+        values and counts are unspecified and the call wants a larger capacity (at most DISTINCT_MAX).  -0.0 == +0.0, one value, reported as +0.0.
+        The values are a valid sorted list for select_in_mask, edge array for histogram and key array for join_probe.  One read of the state,
+        which synchronises the stream (alpgpu_distinct_f64 / _f32)."""
+        import torch
+        dev = f"cuda:{self.device}"
+        capacity = int(capacity)
+        if not 1 <= capacity <= DISTINCT_MAX:
+            raise ValueError("capacity must be in 1 .. %d" % DISTINCT_MAX)
+        vals = torch.empty(capacity, dtype=torch.float64 if col.dtype == "f64" else torch.float32, device=dev)
+        cnt = torch.empty(capacity, dtype=torch.int64, device=dev) if counts else None
+        state = torch.empty(4, dtype=torch.int64, device=dev)
+        self.distinct_into(col, vals, state, counts_out=cnt, mask=mask, first=first, n=n, zones=zones)
+        d, n_nan, _, overflow = state.tolist()
+        return vals[:d], (cnt[:d] if counts else None), n_nan, bool(overflow)
 
     # ---- join probe (include/alpgpu.h: alpgpu_join_probe_*) -----------------------------------------------------------
     def join_probe_into(self, col: "DeviceColumn", keys, pos_out, count_out, mask=None, rows=None, span_out=None, idx_out=None, zones=None, scratch=None):

@@ -176,6 +176,36 @@ int launch_histogram_zero(hipStream_t stream, uint64_t* d_counts, uint32_t n_wor
 int launch_histogram(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const void* d_zones, const void* d_edges, uint32_t n_edges,
                      int right, uint64_t* d_counts, int value_bytes, int n_cus, const alpgpu_histogram_tuning* tuning, uint64_t* d_trace);
 
+// distinct_kernels.hip: sorted distinct values and their counts.  distinct_layout: where the pieces of the caller's scratch lie (byte offsets, each a
+// multiple of 16), their total and the table's sizes, a function of capacity alone (T = the power of two >= 2 * capacity slots of the global table, P =
+// the power of two >= capacity pairs of the sort); false when capacity is 0 or beyond ALPGPU_DISTINCT_MAX.  launch_distinct: col->n_vectors > 0, n > 0,
+// capacity in 1 .. ALPGPU_DISTINCT_MAX; range and alignments checked by the caller; d_counts, d_zones, tuning and d_trace nullable.  The reset, one
+// launch of persistent workgroups (at most three per CU for float, two for double), the compaction, the sort's launches (their number a function of capacity and the tuning's
+// sort_tile) and the emit, which writes d_state.  launch_distinct_zero_state: the four words zeroed by a kernel (what a call without work enqueues)
+struct DistinctLayout {
+	uint64_t state, keys, counts, pairs, total;
+	uint64_t table_slots, sort_slots; // T, P
+};
+inline uint64_t distinct_pow2_at_or_above(uint64_t x) {
+	uint64_t p = 1;
+	while (p < x) { p <<= 1; }
+	return p;
+}
+inline bool distinct_layout(uint64_t capacity, DistinctLayout& L) {
+	if (capacity == 0 || capacity > ALPGPU_DISTINCT_MAX) { return false; }
+	L.sort_slots  = distinct_pow2_at_or_above(capacity);
+	L.table_slots = 2ull * L.sort_slots; // (the power of two >= 2 * capacity)
+	L.state       = 0;
+	L.keys        = L.state + 64ull;
+	L.counts      = L.keys + 8ull * L.table_slots;
+	L.pairs       = L.counts + 8ull * L.table_slots;
+	L.total       = L.pairs + 16ull * L.sort_slots;
+	return true;
+}
+int launch_distinct_zero_state(hipStream_t stream, uint64_t* d_state);
+int launch_distinct(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const void* d_zones, uint64_t capacity, void* d_vals,
+                    uint64_t* d_counts, uint64_t* d_state, void* d_scratch, int value_bytes, int n_cus, const alpgpu_distinct_tuning* tuning, uint64_t* d_trace);
+
 // zone maps (include/alpgpu.h).  decode_kernels.hip / decode_f32_kernels.hip: d_zones[v] = {min, max} of vector v, decoded in registers by the
 // one-wavefront sink kernels (col->n_vectors > 0)
 int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones);

@@ -871,6 +871,51 @@ struct column {
 		check(alpgpu_memcpy_d2h(context(), counts.data(), d_counts, counts.size() * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
 		return counts;
 	}
+	// Distinct values (include/alpgpu.h, "distinct values"): the distinct values, ascending, of the values [0, n_values) whose bit is set in the mask
+	// (nullptr: all of them) and how often each occurs.  -0.0 == 0.0, one value, reported as +0.0; +-inf are ordinary; NaNs are no values and are only
+	// counted (nans).  numbers = the selected values that are no NaNs: the sum of counts unless overflow.  overflow: there are more than `capacity`
+	// (1 .. ALPGPU_DISTINCT_MAX) distinct values; values and counts are then empty: call again with a larger capacity.  The values are a valid sorted
+	// list for select_in_mask, edge array for histogram and key array for join_probe.  zones (optional): any records that contain the vectors'
+	// intervals; they change nothing.
+	struct distinct_result {
+		std::vector<PT>       values;
+		std::vector<uint64_t> counts;
+		uint64_t              nans = 0, numbers = 0;
+		bool                  overflow = false;
+	};
+	static distinct_result distinct(const uint8_t* blob, size_t size, const std::vector<uint64_t>* mask = nullptr, const std::vector<zone>* zones = nullptr, uint64_t capacity = 65536) {
+		if (capacity == 0 || capacity > ALPGPU_DISTINCT_MAX) { throw std::runtime_error("alp::gpu::column::distinct: the capacity must be in 1 .. ALPGPU_DISTINCT_MAX"); }
+		uploaded_column up(blob, size, "alp::gpu::column::distinct");
+		const uint64_t  nv = up.col.n_vectors;
+		if (mask && mask->size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::distinct: the mask must hold 16 words per vector"); }
+		if (zones && zones->size() != nv) { throw std::runtime_error("alp::gpu::column::distinct: one record per vector"); }
+		distinct_result out;
+		if (nv == 0) { return out; }
+		uint64_t* d_mask    = mask ? static_cast<uint64_t*>(up.get(mask->size() * sizeof(uint64_t))) : nullptr;
+		zone*     d_zones   = zones ? static_cast<zone*>(up.get(nv * sizeof(zone))) : nullptr;
+		PT*       d_vals    = static_cast<PT*>(up.get(capacity * sizeof(PT)));
+		uint64_t* d_counts  = static_cast<uint64_t*>(up.get(capacity * sizeof(uint64_t)));
+		uint64_t* d_state   = static_cast<uint64_t*>(up.get(4 * sizeof(uint64_t)));
+		void*     d_scratch = up.get(alpgpu_distinct_scratch_bytes(capacity));
+		if (mask) { check(alpgpu_memcpy_h2d(context(), d_mask, mask->data(), mask->size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d"); }
+		if (zones) { check(alpgpu_memcpy_h2d(context(), d_zones, zones->data(), nv * sizeof(zone)), "alpgpu_memcpy_h2d"); }
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_distinct_f64(context(), &up.col, 0, up.n_values, d_mask, d_zones, capacity, reinterpret_cast<double*>(d_vals), d_counts, d_state, d_scratch), "alpgpu_distinct_f64");
+		} else {
+			check(alpgpu_distinct_f32(context(), &up.col, 0, up.n_values, d_mask, d_zones, capacity, reinterpret_cast<float*>(d_vals), d_counts, d_state, d_scratch), "alpgpu_distinct_f32");
+		}
+		uint64_t state[4] = {0, 0, 0, 0};
+		check(alpgpu_memcpy_d2h(context(), state, d_state, sizeof(state)), "alpgpu_memcpy_d2h");
+		out.nans     = state[1];
+		out.numbers  = state[2];
+		out.overflow = state[3] != 0;
+		if (out.overflow || state[0] == 0) { return out; }
+		out.values.resize(state[0]);
+		out.counts.resize(state[0]);
+		check(alpgpu_memcpy_d2h(context(), out.values.data(), d_vals, state[0] * sizeof(PT)), "alpgpu_memcpy_d2h");
+		check(alpgpu_memcpy_d2h(context(), out.counts.data(), d_counts, state[0] * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
+		return out;
+	}
 	// Join probe (include/alpgpu.h, "join probe"): one row per set bit of the mask (nullptr: every value of [0, n_vectors * 1024)), ascending by index.
 	// pos[j] = the position IN `keys` AS PASSED of a key == the row's value (-0.0 == 0.0, a NaN never matches), ALPGPU_JOIN_NO_MATCH where there is
 	// none; span[j] = the number of keys == it; indices[j] = the row's value index.  The keys are sorted here, on the host (stably, NaNs last), and the

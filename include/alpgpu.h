@@ -1054,6 +1054,100 @@ int alpgpu_join_probe_f64(alpgpu_ctx* ctx, const alpgpu_column* col, const uint6
 int alpgpu_join_probe_f32(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t* d_mask, const alpgpu_zone_f32* d_zones, const float* d_keys, uint64_t n_keys,
                           const int64_t* d_rows, int64_t* d_pos, uint32_t* d_span, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch);
 
+/* ---- distinct values ------------------------------------------------------------------------------------------------------------------------------
+ * The sorted distinct values of a column's selected values and how often each occurs, no decoded value reaching HBM: SELECT DISTINCT x,
+ * COUNT(DISTINCT x), value_counts, GROUP BY key with COUNT(*) when the keys are NOT known in advance.  The output is directly a valid edge array for
+ * alpgpu_histogram_* (point buckets), a valid list for alpgpu_select_in_mask_* and a valid key array for alpgpu_join_probe_*: the call that feeds
+ * the three without a decode, a sort and a unique outside the library.
+ *   alpgpu_distinct_*           Take every value index r of [first, first + n) whose bit is set in the bitmap (d_mask == NULL: every r of the range).
+ *                               x_r is, bit for bit, what alpgpu_decode_* writes at r, exceptions patched in.
+ *                               NaNs.  A NaN (by the bits: quiet or signalling, packed or an exception) is never a distinct value: NaNs are only
+ *                               counted, in d_state[1].
+ *                               Equality is C's ==, as for alpgpu_select_in_mask_*, alpgpu_histogram_* and alpgpu_join_probe_*: -0.0 and +0.0 are ONE
+ *                               value, reported as +0.0; +-inf are ordinary values.  (A zero is made +0.0 before the order key okey of "top-k" is
+ *                               taken; from there on equal values are equal bit patterns and everything is integer.)
+ *                               Output.  Let u_0 < u_1 < ... < u_{D-1} be the distinct values, ascending.  With D <= capacity:
+ *                                 d_vals[i]   = u_i, i < D;
+ *                                 d_counts[i] (d_counts may be NULL) = the number of selected r with x_r == u_i.
+ *                               Nothing is written at d_vals[D ...] or d_counts[D ...].
+ *                               d_state: 4 words of 8 bytes, always written (also for n == 0 and for a column of no vectors):
+ *                                 [0] the number of entries written, min(D, capacity);
+ *                                 [1] the selected NaNs;
+ *                                 [2] the selected values that are no NaNs, counted by popcounts beside the table: right also on overflow;
+ *                                 [3] 1 if D > capacity (overflow), else 0.
+ *                               Without overflow the sum of d_counts[0 .. D) is d_state[2].  On overflow the contents of d_vals and
+ *                               d_counts[0 .. capacity) are unspecified; nothing is ever written at or beyond `capacity`, and the call returns as
+ *                               always: call again with a larger capacity.
+ *                               capacity: 1 .. ALPGPU_DISTINCT_MAX.  d_scratch: alpgpu_distinct_scratch_bytes(capacity) bytes, 16-byte aligned,
+ *                               contents irrelevant before and unspecified after; one formula (T = the power of two >= 2 * capacity, P = the power
+ *                               of two >= capacity): 64 bytes of state, T keys and T counts of 8 bytes (the table), P pairs of 16 bytes (the sort).
+ *                               d_mask (may be NULL): a selection bitmap of col->n_vectors * 16 words, 8-byte aligned, read and never written.  A
+ *                               vector whose words are all zero within the range costs its 128 bytes and nothing of the column; one outside the
+ *                               range costs nothing.
+ *                               d_zones (may be NULL; aligned to its records): any zone map whose records CONTAIN the true intervals of the
+ *                               vectors' selected values (alpgpu_histogram_*'s rule): alpgpu_zone_map_*, alpgpu_decode_minmax_masked_*, widened
+ *                               records.  ONE shortcut is taken: a record with min == max (neither a NaN) on a vector whose descriptor says ALP
+ *                               without exceptions (a NaN in an ALP vector is always an exception) is one insert of that value with the popcount of
+ *                               the vector's selected bits; its packed words are not requested.  Every other vector is decoded.  Truthful records
+ *                               change no output byte.  Records that do not contain the truth give unspecified values and counts; d_state[1] +
+ *                               d_state[2] is still the number of selected values and nothing is read or written out of bounds.
+ *                               Cost: a reset kernel (the table to EMPTY = all-ones, the order key of a NaN pattern, which is never inserted; not a
+ *                               memset node: DESIGN.md, "Histograms"); one launch of persistent workgroups, sized to the device, that decode in
+ *                               registers and insert into an open-addressing table in LDS (a step of 64 values that agree on their value costs one
+ *                               insert) which is flushed into the global table (multiplicative hash, linear probing, integer atomics) at the
+ *                               workgroup's end and every 2^18 trips; a compaction of the occupied slots; a bitonic sort of the at most `capacity`
+ *                               (key, count) pairs, whose launch count depends on `capacity` alone; the emit.  Every probe loop is bounded by the
+ *                               slots of the table it walks and no workgroup waits for another.  A low-cardinality column costs about one
+ *                               histogram; near 2^20 distinct values the random global atomics dominate.
+ *                               n == 0: a zero state is written and nothing of the column is read.  col->n_vectors == 0: ALPGPU_OK, the zero state
+ *                               is written.
+ *                               ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx, col, d_vals, d_state or d_scratch; capacity == 0 or
+ *                               beyond ALPGPU_DISTINCT_MAX; d_scratch not 16-byte aligned; d_mask, d_counts, d_state or d_trace not 8-byte aligned,
+ *                               d_vals not aligned to its elements, d_zones not aligned to its records; a range past the end; with n_vectors > 0 and
+ *                               n > 0, a column without descriptors.
+ *   alpgpu_distinct_scratch_bytes   the formula above: never 0, monotone in capacity, a multiple of 16; UINT64_MAX for capacity == 0 or beyond
+ *                               ALPGPU_DISTINCT_MAX.
+ * The call runs on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no state kept; none of what
+ *   the context remembers about columns (the decode plans) is read or written; safe inside a stream capture (a replay sees the bitmap's and the
+ *   column's contents of that time).  Every grid is fixed on the host, all counts live in device memory and only integer atomics are used: the result
+ *   is a function of the column, the bitmap and the arguments alone, not of launch shapes or of the order in which wavefronts arrive.
+ *   (tests/distinct_replica.py holds the host replica.)
+ * Not built: distinct by bit pattern (the zeros apart), more than 2^20 distinct values, a multi-column DISTINCT, zone pruning beyond the
+ *   constant-vector rule.
+ * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector). */
+#define ALPGPU_DISTINCT_MAX (1u << 20)
+uint64_t alpgpu_distinct_scratch_bytes(uint64_t capacity);
+int alpgpu_distinct_f64(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const alpgpu_zone_f64* d_zones, uint64_t capacity,
+                        double* d_vals, uint64_t* d_counts, uint64_t* d_state, void* d_scratch);
+int alpgpu_distinct_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const alpgpu_zone_f32* d_zones, uint64_t capacity,
+                        float* d_vals, uint64_t* d_counts, uint64_t* d_state, void* d_scratch);
+/* debug / test: alpgpu_distinct_* with a tuning record, so that small columns reach every path, and a trace.  A 0 field means the default; no field
+ * changes an output byte.  grid: the workgroups of the insert launch (default min(ceil(vectors of the range / 8), 3 per CU for float and 2 for double);
+ * more than there is work for is allowed, at most 65536).  flush_every: trips of a workgroup's loop (8 vectors each) between two flushes of its LDS table (default 2^18; may
+ * only be lowered).  lds_slots: slots of the workgroup's LDS table (default 4096; a power of two, may only be lowered, at least 64; other values are
+ * rounded down to a power of two).  table_slots: slots of the global table (default T; may be lowered down to P, the power of two at or above
+ * `capacity`, so that a full table and wrapped probes are reached with small inputs).  sort_tile: pairs sorted in LDS by one workgroup (default 4096;
+ * a power of two, may only be lowered, at least 64), so that a few hundred distinct values reach the multi-launch part of the sort.
+ * d_trace (may be NULL): 6 words of device memory that the call ADDS to:
+ *   [0] vectors of the range settled without the column (their selected bits are all zero),
+ *   [1] vectors settled from their zone record,
+ *   [2] vectors decoded,
+ *   [3] steps (64 values) settled by wave agreement: one insert,
+ *   [4] inserts offered to the LDS table (one per agreeing step or settled vector, one per selected value otherwise),
+ *   [5] inserts made into the global table (direct ones plus flushed LDS entries). */
+typedef struct alpgpu_distinct_tuning {
+    uint32_t grid;
+    uint32_t flush_every;
+    uint32_t lds_slots;
+    uint32_t table_slots;
+    uint32_t sort_tile;
+    uint32_t reserved;
+} alpgpu_distinct_tuning;
+int alpgpu_debug_distinct_f64(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const alpgpu_zone_f64* d_zones, uint64_t capacity,
+                              double* d_vals, uint64_t* d_counts, uint64_t* d_state, void* d_scratch, const alpgpu_distinct_tuning* tuning, uint64_t* d_trace);
+int alpgpu_debug_distinct_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const alpgpu_zone_f32* d_zones, uint64_t capacity,
+                              float* d_vals, uint64_t* d_counts, uint64_t* d_state, void* d_scratch, const alpgpu_distinct_tuning* tuning, uint64_t* d_trace);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
