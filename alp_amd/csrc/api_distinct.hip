@@ -19,7 +19,7 @@ static int distinct(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, u
 	if (misaligned(d_counts, 8u) || misaligned(d_state, 8u) || misaligned(d_trace, 8u)) { return fail(ALPGPU_ERR_INVALID, "counts, state or trace are not 8-byte aligned"); }
 	if (col->n_vectors > 0 && n > 0) { ALPGPU_TRY(check_has_descriptors(col)); }
 	if (col->n_vectors == 0 || n == 0) { // nothing is selected: the zero state, and nothing of the column is read
-		if (alpgpu::launch_distinct_zero_state(ctx->stream, d_state) != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "zeroing the state failed", hipGetLastError()); }
+		if (alpgpu::launch_fill_u64(ctx->stream, d_state, 4u, 0ull) != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "zeroing the state failed", hipGetLastError()); }
 		return ALPGPU_OK;
 	}
 	const int rc = alpgpu::launch_distinct(ctx->stream, col, first, n, d_mask, d_zones, capacity, d_vals, d_counts, d_state, d_scratch, value_bytes, ctx->n_cus, tuning, d_trace);

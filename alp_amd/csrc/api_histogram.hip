@@ -19,7 +19,7 @@ static int histogram(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, 
 	if (misaligned(d_counts, 8u) || misaligned(d_trace, 8u)) { return fail(ALPGPU_ERR_INVALID, "counts or trace are not 8-byte aligned"); }
 	if (col->n_vectors == 0) { return ALPGPU_OK; }
 	if (n > 0) { ALPGPU_TRY(check_has_descriptors(col)); }
-	if (!accumulate && alpgpu::launch_histogram_zero(ctx->stream, d_counts, n_edges + 2u) != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "zeroing the counts failed", hipGetLastError()); }
+	if (!accumulate && alpgpu::launch_fill_u64(ctx->stream, d_counts, n_edges + 2u, 0ull) != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "zeroing the counts failed", hipGetLastError()); }
 	if (n == 0) { return ALPGPU_OK; }
 	const int rc = alpgpu::launch_histogram(ctx->stream, col, first, n, d_mask, d_zones, d_edges, n_edges, right, d_counts, value_bytes, ctx->n_cus, tuning, d_trace);
 	if (rc != ALPGPU_OK) { return fail(rc, "histogram launch failed"); } // (the launcher has read the HIP error)

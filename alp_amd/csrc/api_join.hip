@@ -20,7 +20,7 @@ static int join_probe(alpgpu_ctx* ctx, const alpgpu_column* col, const uint64_t*
 	if (misaligned(d_count, 8u) || misaligned(d_pos, 8u) || misaligned(d_idx, 8u) || misaligned(d_span, 4u)) { return fail(ALPGPU_ERR_INVALID, "an output is not aligned to its elements"); }
 	if (d_mask && col->n_vectors > 0 && (!d_scratch || misaligned(d_scratch, 16u))) { return fail(ALPGPU_ERR_INVALID, "scratch is null or not 16-byte aligned"); }
 	if (col->n_vectors == 0) { // no index at all: the count alone is written
-		if (alpgpu::launch_join_count(ctx->stream, d_count, 0) != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "writing the count failed", hipGetLastError()); }
+		if (alpgpu::launch_fill_u64(ctx->stream, d_count, 1u, 0ull) != ALPGPU_OK) { return fail(ALPGPU_ERR_HIP, "writing the count failed", hipGetLastError()); }
 		return ALPGPU_OK;
 	}
 	if (capacity > 0) { ALPGPU_TRY(check_has_descriptors(col)); }

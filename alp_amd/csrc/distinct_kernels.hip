@@ -1,11 +1,11 @@
 // distinct_kernels.hip — distinct values (include/alpgpu.h, "distinct values": alpgpu_distinct_*): the sorted distinct values of a compressed column's
-// selected values and their counts.  It walks and decodes as k_histogram does and orders by top-k's key (top_k_device.hpp: top_k_okey), taken after a
+// selected values and their counts.  It walks and decodes as k_histogram does (persistent_scan.hpp) and orders by top-k's key (top_k_device.hpp: top_k_okey), taken after a
 // zero has been made +0.0: from there on equal values are equal 64-bit integers (a float's key zero-extended) and everything is integer.
 //
 //   k_distinct_reset       the global table's keys to EMPTY (all-ones: the order key of a NaN pattern, and NaNs are never inserted), its counts, the
 //                          state words and the sort's pairs ({EMPTY, 0}: the padding) by a kernel of the library's own, not a memset node
-//                          (histogram_kernels.hip, k_histogram_zero, says why).
-//   k_distinct_insert<VB>  k_histogram's skeleton: persistent workgroups of kDistWaves wavefronts, ONE barrier in front of the loop, the vectors of the
+//                          (mask_kernels.hip, k_fill_u64, says why).
+//   k_distinct_insert<VB>  k_histogram's shape: persistent workgroups of kDistWaves wavefronts, ONE barrier in front of the loop, the vectors of the
 //                          range v = wave id, wave id + waves, ...; every wavefront of a workgroup makes the same number of trips, so that the flush's
 //                          barriers are met by all.  A vector is decoded in registers (register_decode.hpp) in batches of kStepBatch steps.  Per step:
 //                          the selected NaNs are one popcount; if the kept lanes agree on their key that is ONE insert with the popcount, otherwise one
@@ -40,7 +40,7 @@
 //   k_distinct_insert<4>   74 VGPRs, 33796 B LDS, 6 waves per SIMD, no scratch; amdgpu_waves_per_eu(6): the three workgroups per CU the grid is sized for
 //   k_distinct_sort_tile   14 VGPRs, 65536 B LDS (two workgroups per CU); the other kernels: at most 14 VGPRs, no LDS, no scratch
 // Both insert kernels keep about 75 wave-uniform values that do not fit the scalar file in lanes of two VGPRs (counted above).
-#include "launch.hpp"
+#include "persistent_scan.hpp"
 #include "top_k_device.hpp"
 
 namespace alpgpu {
@@ -53,7 +53,6 @@ constexpr uint32_t kDistLdsSlots    = 4096;     // of the workgroup's table
 constexpr uint32_t kDistLdsSlotsMin = 64;
 constexpr uint32_t kDistLdsProbes   = 8;        // slots an LDS insert looks at before it goes to the global table
 constexpr uint32_t kDistFlushEvery  = 1u << 18; // trips of a workgroup's loop (8 vectors each, at most 8192 increments of one 32-bit LDS count) between two flushes
-constexpr uint32_t kDistGridMax     = 1u << 16; // of a tuning record's grid
 constexpr uint32_t kDistSortTile    = 4096;     // pairs sorted in LDS by one workgroup: 64 KiB
 constexpr uint32_t kDistSortTileMin = 64;
 constexpr int      kDistSortThreads = 512;
@@ -165,15 +164,6 @@ __device__ __forceinline__ void dist_offer(KT* s_keys, uint32_t* s_counts, uint3
 	}
 }
 
-// word m (= lane, < 16) of a vector's bitmap with the bits of the positions [p_begin, p_end) set
-__device__ __forceinline__ uint64_t dist_range_word(uint32_t lane, uint32_t p_begin, uint32_t p_end) {
-	const uint32_t w0 = 64u * lane;
-	const uint32_t lo = p_begin > w0 ? p_begin : w0, hi = p_end < w0 + 64u ? p_end : w0 + 64u;
-	if (hi <= lo) { return 0ull; }
-	const uint64_t run = hi - lo == 64u ? ~0ull : (1ull << (hi - lo)) - 1ull;
-	return run << (lo - w0);
-}
-
 // every occupied slot of the LDS table into the global table, and emptied; a barrier on both sides
 template <class KT>
 __device__ __forceinline__ void dist_flush(KT* s_keys, uint32_t* s_counts, uint32_t* s_made, const DistArgs& g) {
@@ -199,23 +189,16 @@ __device__ __forceinline__ uint32_t dist_vector(const ColumnStreams& c, const Di
                                                 uint64_t (&s_exc)[kDistWaves][16], uint64_t& n_nan, uint64_t& n_num, DistDid& did) {
 	typedef typename DecodeVec<VB>::T T;
 	// 1. the selected bits: the vector's 128 bytes of bitmap (all ones without one), lane m < 16 holding word m, ANDed with the range's share
-	const uint64_t r0 = v << 10; // (r0 < g.end and r0 + 1024 > g.first: the loop walks the range's vectors only)
-	uint32_t       p_begin, p_end;
-	range_share(g.first, g.end, r0, p_begin, p_end);
-	uint64_t sel = lane < 16u ? dist_range_word(lane, p_begin, p_end) : 0ull;
-	if (g.mask != nullptr) { sel &= lane < 16u ? g.mask[16ull * v + lane] : 0ull; }
-	if (ballot64(sel != 0ull) == 0ull) { return kDistSkipZero; }
+	uint64_t sel; // (the vector holds a value of the range: the loop walks the range's vectors only)
+	if (!selected_words(g.mask, g.first, g.end, v, lane, sel)) { return kDistSkipZero; }
 
 	// 2. the one shortcut: a constant vector by its record
 	if (g.zones != nullptr) {
 		const T* zone = static_cast<const T*>(g.zones) + 2 * v; // (wave-uniform)
 		const T  mn = zone[0], mx = zone[1];
 		if (mn == mx) { // (false with a NaN bound)
-			const alpgpu_vector_desc d = c.descs[v];
-			if (d.scheme == ALPGPU_SCHEME_ALP && d.exc_cnt == 0u) { // no NaN can hide here: the selected bits are the count of the one value
-				uint32_t n = static_cast<uint32_t>(__builtin_popcountll(sel));
-				n          = wave_scan_add_u32(n);
-				n          = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(n), 63));
+			if (alp_without_exceptions(c.descs[v])) { // no NaN can hide here: the selected bits are the count of the one value
+				const uint32_t n = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(selected_count(sel)), 63));
 				n_num += n;
 				++did.offered;
 				if (lane == 0u && !dist_lds_insert(s_keys, s_counts, g.log2_lds, dist_key<VB>(mn), n)) {
@@ -314,7 +297,7 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(VB
 	}
 }
 
-// The call's "memset" (k_histogram_zero says why it is a kernel): table_slots keys to EMPTY and counts to 0, sort_slots pairs to the padding, the state
+// The call's "memset" (k_fill_u64, mask_kernels.hip, says why it is a kernel): table_slots keys to EMPTY and counts to 0, sort_slots pairs to the padding, the state
 __global__ __launch_bounds__(256) void k_distinct_reset(uint64_t* __restrict__ keys, uint64_t* __restrict__ counts, ulonglong2* __restrict__ pairs, uint64_t* __restrict__ state,
                                                         uint32_t table_slots, uint32_t sort_slots) {
 	uint32_t most = table_slots > sort_slots ? table_slots : sort_slots;
@@ -327,14 +310,6 @@ __global__ __launch_bounds__(256) void k_distinct_reset(uint64_t* __restrict__ k
 		if (i < sort_slots) { pairs[i] = make_ulonglong2(kDistEmpty, 0ull); }
 		if (i < kDistStateWords) { state[i] = 0ull; }
 	}
-}
-
-__global__ __launch_bounds__(64) void k_distinct_zero_state(uint64_t* __restrict__ d_state) {
-	if (threadIdx.x < 4u) { d_state[threadIdx.x] = 0ull; }
-}
-int launch_distinct_zero_state(hipStream_t stream, uint64_t* d_state) {
-	hipLaunchKernelGGL(k_distinct_zero_state, dim3(1), dim3(64), 0, stream, d_state);
-	return hipGetLastError() != hipSuccess ? ALPGPU_ERR_HIP : ALPGPU_OK;
 }
 
 // The occupied slots into pairs[0 .. capacity): a wavefront looks at 64 neighbouring slots, one atomic add for those it found occupied.
@@ -484,11 +459,8 @@ int launch_distinct(hipStream_t stream, const alpgpu_column* col, uint64_t first
 	if (hipGetLastError() != hipSuccess) { return ALPGPU_ERR_HIP; }
 
 	// 2. the inserts: the grid is sized to the device
-	const uint64_t n_vec    = args.v_end - args.v_begin;
-	const uint64_t n_wg     = (n_vec + kDistWaves - 1) / kDistWaves;
-	const uint64_t resident = static_cast<uint64_t>(n_cus > 0 ? n_cus : 1) * (value_bytes == 8 ? kDistWgPerCuF64 : kDistWgPerCu);
-	unsigned       grid     = static_cast<unsigned>(n_wg < resident ? n_wg : resident);
-	if (tuning != nullptr && tuning->grid != 0u) { grid = tuning->grid < kDistGridMax ? tuning->grid : kDistGridMax; } // (a grid beyond the range: workgroups that find no vector)
+	const unsigned grid = persistent_grid(args.v_end - args.v_begin, kDistWaves, n_cus, value_bytes == 8 ? kDistWgPerCuF64 : kDistWgPerCu, 0,
+	                                      tuning != nullptr ? tuning->grid : 0u, kTuningGridMax);
 	const ColumnStreams c = column_streams(col);
 	if (value_bytes == 8) {
 		hipLaunchKernelGGL((k_distinct_insert<8>), dim3(grid), dim3(kDistThreads), 0, stream, c, args);

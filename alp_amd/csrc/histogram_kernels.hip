@@ -1,11 +1,11 @@
 // histogram_kernels.hip — histograms (include/alpgpu.h, "histograms": alpgpu_histogram_*): the bucket counts of a compressed column's selected values by
-// sorted edges.  It searches as k_in_list does and counts as k_quantile_wide does.
+// sorted edges.  It searches with lds_bound (sorted_list.hpp: the LDS tier of k_in_list's search) and counts as k_quantile_wide does (persistent_scan.hpp).
 //
 //   k_histogram<VB>   persistent workgroups of kHistWaves wavefronts.  The workgroup stages the edges into LDS and zeroes n_edges + 2 32-bit LDS bins,
 //                     passes ONE workgroup barrier and then walks vectors v = wave id, wave id + waves, ...; every wavefront of a workgroup makes the
 //                     same number of trips (the last may find no vector), so that the flush's barriers are met by all.  A vector is decoded in
 //                     registers by register_decode.hpp in batches of kStepBatch steps, whose values search together, so that their LDS probes overlap.
-//   the search        a branch-free bound over the edges [j0, j1), every step wave-uniform in its length: ceil(log2(j1 - j0 + 1)) probes; the result
+//   the search        lds_bound: a branch-free bound over the edges [j0, j1), every step wave-uniform in its length: ceil(log2(j1 - j0 + 1)) probes; the result
 //                     lies in [j0, j1] whatever the edges hold, and every probe index is clamped to the edges staged: an unsorted array gives
 //                     unspecified buckets, reads nothing else and keeps the total.
 //   the count         q_hist_add (quantile_device.hpp): one LDS add by the leading lane when a step's kept lanes agree on their bucket, otherwise one
@@ -30,8 +30,9 @@
 //   k_histogram<8>   78 VGPRs, 50192 B LDS, 6 waves per SIMD, no scratch (2 SGPRs kept in VGPR lanes)
 //   k_histogram<4>   68 VGPRs, 33808 B LDS, 7 waves per SIMD, no scratch
 // (The float kernel's LDS would admit a fourth workgroup per CU, its registers not the eighth wavefront per SIMD that takes: three for both.)
-#include "launch.hpp"
+#include "persistent_scan.hpp"
 #include "quantile_device.hpp"
+#include "sorted_list.hpp"
 
 namespace alpgpu {
 
@@ -41,7 +42,6 @@ constexpr int      kHistWgPerCu    = 3;        // 49 KiB of LDS each (double; 33
 constexpr uint32_t kHistEdgeWords  = ALPGPU_HISTOGRAM_EDGES_MAX + 1u; // LDS words of edges
 constexpr uint32_t kHistBinWords   = ALPGPU_HISTOGRAM_EDGES_MAX + 2u; // LDS bins: n_edges + 1 buckets and the NaN counter
 constexpr uint32_t kHistFlushEvery = 1u << 18; // trips of a workgroup's loop (8 vectors each, at most 8192 increments of one 32-bit LDS bin) between two flushes
-constexpr uint32_t kHistGridMax    = 1u << 16; // of a tuning record's grid
 
 struct HistArgs {
 	uint64_t        n_vectors;
@@ -56,54 +56,11 @@ struct HistArgs {
 	uint32_t        flush_every;
 };
 
-// NB searches side by side over the edges [j0, j1) in LDS (wave-uniform, j0 <= j1 <= n_edges): out[i] = j0 + the number of elements e of them with
-// e <= x[i] (right: e < x[i]) if the edges are sorted, in [j0, j1] whatever they hold.  A NaN edge is never <= anything, so that NaNs sorted last are
-// inert; a NaN x gives j0.  in_list_search's steps without its pivot tier.
+// out[i] = j0 + the edges e of [j0, j1) with e <= x[i] (right: e < x[i]); a NaN edge is never <= anything: inert.  No edges: j0 == j1, nothing is read.
 template <int VB, uint32_t NB>
-__device__ __forceinline__ void hist_search(const typename DecodeVec<VB>::T* s_edges, uint32_t n_edges, uint32_t j0, uint32_t j1, const typename DecodeVec<VB>::T (&x)[NB],
-                                            bool right, uint32_t (&out)[NB]) {
-	typedef typename DecodeVec<VB>::T T;
-	const uint32_t last = n_edges > 0u ? n_edges - 1u : 0u;
-#pragma unroll
-	for (uint32_t i = 0; i < NB; ++i) { out[i] = j0; }
-	uint32_t n = j1 - j0; // wave-uniform: every lane and every one of the NB searches takes the same steps
-	while (n > 1u) {
-		const uint32_t half = n >> 1;
-		T              e[NB];
-#pragma unroll
-		for (uint32_t i = 0; i < NB; ++i) {
-			const uint32_t at = out[i] + half - 1u;
-			e[i]              = s_edges[at < last ? at : last];
-		}
-#pragma unroll
-		for (uint32_t i = 0; i < NB; ++i) { out[i] += (right ? e[i] < x[i] : e[i] <= x[i]) ? half : 0u; }
-		n -= half;
-	}
-	if (n == 1u) {
-		T e[NB];
-#pragma unroll
-		for (uint32_t i = 0; i < NB; ++i) { e[i] = s_edges[out[i] < last ? out[i] : last]; }
-#pragma unroll
-		for (uint32_t i = 0; i < NB; ++i) { out[i] += (right ? e[i] < x[i] : e[i] <= x[i]) ? 1u : 0u; }
-	}
-}
-
-// word m (= lane, < 16) of a vector's bitmap with the bits of the positions [p_begin, p_end) set
-__device__ __forceinline__ uint64_t hist_range_word(uint32_t lane, uint32_t p_begin, uint32_t p_end) {
-	const uint32_t w0 = 64u * lane;
-	const uint32_t lo = p_begin > w0 ? p_begin : w0, hi = p_end < w0 + 64u ? p_end : w0 + 64u;
-	if (hi <= lo) { return 0ull; }
-	const uint64_t run = hi - lo == 64u ? ~0ull : (1ull << (hi - lo)) - 1ull;
-	return run << (lo - w0);
-}
-
-// the workgroup's non-zero bins into the global counts; a barrier first, none behind
-__device__ __forceinline__ void hist_flush(const uint32_t* s_bins, uint32_t n_bins, uint64_t* counts) {
-	__syncthreads();
-	for (uint32_t i = threadIdx.x; i < n_bins; i += kHistThreads) {
-		const uint32_t n = s_bins[i];
-		if (n != 0u) { atomicAdd(reinterpret_cast<unsigned long long*>(counts) + i, static_cast<unsigned long long>(n)); }
-	}
+__device__ __forceinline__ void hist_buckets(const typename DecodeVec<VB>::T* s_edges, const HistArgs& g, uint32_t j0, uint32_t j1, const typename DecodeVec<VB>::T (&x)[NB],
+                                             uint32_t (&out)[NB]) {
+	lds_bound<typename DecodeVec<VB>::T, NB>(s_edges, g.n_edges > 0u ? g.n_edges - 1u : 0u, j0, j1, x, g.right != 0u ? 0u : ~0u, out);
 }
 
 constexpr uint32_t kHistSkipZero = 0u, kHistZone = 1u, kHistFew = 2u, kHistDecoded = 3u; // what hist_vector did with a vector: the trace's words
@@ -116,11 +73,8 @@ __device__ __forceinline__ uint32_t hist_vector(const ColumnStreams& c, const Hi
 	// 1. the selected bits: the vector's 128 bytes of bitmap (all ones without one), lane m < 16 holding word m, ANDed with the range's share
 	const uint64_t r0 = v << 10;
 	if (r0 >= g.end || r0 + 1024u <= g.first) { return kHistSkipZero; } // no value of the vector is in the range: nothing is read
-	uint32_t p_begin, p_end;
-	range_share(g.first, g.end, r0, p_begin, p_end);
-	uint64_t sel = lane < 16u ? hist_range_word(lane, p_begin, p_end) : 0ull;
-	if (g.mask != nullptr) { sel &= lane < 16u ? g.mask[16ull * v + lane] : 0ull; }
-	if (ballot64(sel != 0ull) == 0ull) { return kHistSkipZero; }
+	uint64_t sel;
+	if (!selected_words(g.mask, g.first, g.end, v, lane, sel)) { return kHistSkipZero; }
 
 	// 2. the part [j0, j1) of the edges that the vector's zone record admits: all of them without a record, with a NaN bound or with min above max
 	uint32_t j0 = 0u, j1 = g.n_edges;
@@ -129,16 +83,14 @@ __device__ __forceinline__ uint32_t hist_vector(const ColumnStreams& c, const Hi
 		const T  z[2] = {zone[0], zone[1]};
 		if (z[0] == z[0] && z[1] == z[1]) {
 			uint32_t j[2];
-			hist_search<VB, 2>(s_edges, g.n_edges, 0u, g.n_edges, z, g.right != 0u, j); // the buckets of min and of max
+			hist_buckets<VB, 2>(s_edges, g, 0u, g.n_edges, z, j); // the buckets of min and of max
 			const uint32_t a = __builtin_amdgcn_readfirstlane(j[0]), b = __builtin_amdgcn_readfirstlane(j[1]);
 			if (a <= b) {
 				j0 = a;
 				j1 = b;
 				if (j0 == j1) {
-					const alpgpu_vector_desc d = c.descs[v];
-					if (d.scheme == ALPGPU_SCHEME_ALP && d.exc_cnt == 0u) { // no NaN can hide here: the selected bits are the count of bucket j0
-						uint32_t n = static_cast<uint32_t>(__builtin_popcountll(sel));
-						n          = wave_scan_add_u32(n);
+					if (alp_without_exceptions(c.descs[v])) { // no NaN can hide here: the selected bits are the count of bucket j0
+						const uint32_t n = selected_count(sel);
 						if (lane == 63u) { atomicAdd(&s_bins[j0], n); }
 						return kHistZone;
 					}
@@ -161,7 +113,7 @@ __device__ __forceinline__ uint32_t hist_vector(const ColumnStreams& c, const Hi
 		for (uint32_t i = 0; i < kStepBatch; ++i) { x[i] = step_value(V, R, b, i, lane); }
 		// 5. the batch's buckets, searched together
 		uint32_t at[kStepBatch];
-		hist_search<VB, kStepBatch>(s_edges, g.n_edges, j0, j1, x, g.right != 0u, at);
+		hist_buckets<VB, kStepBatch>(s_edges, g, j0, j1, x, at);
 		// 6. per step: the selected values that are no NaNs into their buckets, the selected NaNs into the last bin
 #pragma unroll
 		for (uint32_t i = 0; i < kStepBatch; ++i) {
@@ -189,7 +141,7 @@ __global__ __launch_bounds__(kHistThreads) __attribute__((amdgpu_waves_per_eu(6)
 	// 0. the edges into LDS and the bins zeroed, once per workgroup; the one barrier in front of the loop
 	const T* edges = static_cast<const T*>(g.edges);
 	for (uint32_t i = threadIdx.x; i < g.n_edges; i += kHistThreads) { s_edges[i] = edges[i]; }
-	for (uint32_t i = threadIdx.x; i < n_bins; i += kHistThreads) { s_bins[i] = 0u; }
+	bins_zero<kHistThreads>(s_bins, n_bins);
 	__syncthreads();
 
 	// every wavefront of the workgroup makes the same number of trips (the last may find no vector), so that the flush's barriers are met by all
@@ -205,32 +157,21 @@ __global__ __launch_bounds__(kHistThreads) __attribute__((amdgpu_waves_per_eu(6)
 		}
 		if (++trips == g.flush_every) {
 			trips = 0;
-			hist_flush(s_bins, n_bins, g.counts);
+			bins_flush<kHistThreads>(s_bins, n_bins, g.counts);
 			__syncthreads();
-			for (uint32_t i = threadIdx.x; i < n_bins; i += kHistThreads) { s_bins[i] = 0u; }
+			bins_zero<kHistThreads>(s_bins, n_bins);
 			__syncthreads();
 		}
 	}
-	hist_flush(s_bins, n_bins, g.counts);
+	bins_flush<kHistThreads>(s_bins, n_bins, g.counts);
 	if (g.trace != nullptr && lane < 4u) { // the trace: one add per wavefront and counter
 		const uint32_t mine = lane == 0u ? did[0] : lane == 1u ? did[1] : lane == 2u ? did[2] : did[3];
 		if (mine != 0u) { atomicAdd(reinterpret_cast<unsigned long long*>(g.trace) + lane, static_cast<unsigned long long>(mine)); }
 	}
 }
 
-// The call's "memset": the n_words counts zeroed by a kernel of the library's own.  Not hipMemsetAsync: captured into a graph with torch, its node was
-// observed to leave non-zero words at replays that came after other work on the device (tools/probe_graph_memset.py shows it with alpgpu_memset alone,
-// 24 bytes to 514 KiB; the cause is not established: DESIGN.md, "Histograms"), and a call that overwrites has to stay capturable.
-__global__ __launch_bounds__(256) void k_histogram_zero(uint64_t* __restrict__ counts, uint32_t n_words) {
-	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-	if (i < n_words) { counts[i] = 0ull; }
-}
-int launch_histogram_zero(hipStream_t stream, uint64_t* d_counts, uint32_t n_words) {
-	hipLaunchKernelGGL(k_histogram_zero, dim3((n_words + 255u) / 256u), dim3(256), 0, stream, d_counts, n_words);
-	return hipGetLastError() != hipSuccess ? ALPGPU_ERR_HIP : ALPGPU_OK;
-}
-
 // col->n_vectors > 0, n > 0, n_edges <= ALPGPU_HISTOGRAM_EDGES_MAX; range and alignments checked by the caller; the counts are added to
+// (a call that overwrites has zeroed them by launch_fill_u64: mask_kernels.hip says why that is a kernel and no memset node)
 int launch_histogram(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const void* d_zones, const void* d_edges, uint32_t n_edges,
                      int right, uint64_t* d_counts, int value_bytes, int n_cus, const alpgpu_histogram_tuning* tuning, uint64_t* d_trace) {
 	HistArgs args {};
@@ -245,10 +186,8 @@ int launch_histogram(hipStream_t stream, const alpgpu_column* col, uint64_t firs
 	args.n_edges     = n_edges;
 	args.right       = right != 0;
 	args.flush_every = tuning != nullptr && tuning->flush_every != 0u && tuning->flush_every < kHistFlushEvery ? tuning->flush_every : kHistFlushEvery;
-	const uint64_t n_wg     = (col->n_vectors + kHistWaves - 1) / kHistWaves;
-	const uint64_t resident = static_cast<uint64_t>(n_cus > 0 ? n_cus : 1) * kHistWgPerCu; // the grid is sized to the device: a workgroup stages the edges once
-	unsigned       grid     = static_cast<unsigned>(n_wg < resident ? n_wg : resident);
-	if (tuning != nullptr && tuning->grid != 0u) { grid = tuning->grid < kHistGridMax ? tuning->grid : kHistGridMax; } // (a grid beyond the column: workgroups that find no vector)
+	// sized to the device: a workgroup stages the edges once
+	const unsigned grid = persistent_grid(col->n_vectors, kHistWaves, n_cus, kHistWgPerCu, 0, tuning != nullptr ? tuning->grid : 0u, kTuningGridMax);
 	const ColumnStreams c = column_streams(col);
 	if (value_bytes == 8) {
 		hipLaunchKernelGGL((k_histogram<8>), dim3(grid), dim3(kHistThreads), 0, stream, c, args);

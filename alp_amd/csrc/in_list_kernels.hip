@@ -7,7 +7,7 @@
 //                           registers by register_decode.hpp in batches of kStepBatch steps, whose values search together, so that their LDS
 //                           (and global) probes overlap.  The ballot of step m is kept in lane m, combined with the prior words and stored as
 //                           one run of 128 bytes, as the MASK arm of k_select does.
-//   the search              (in_list_search.hpp, shared with k_join_probe) a branch-free lower bound, every step wave-uniform in its length: ceil(log2(n + 1)) probes of the LDS words
+//   the search              (in_list_search, sorted_list.hpp: shared with k_join_probe, its LDS tier with k_histogram too) a branch-free lower bound, every step wave-uniform in its length: ceil(log2(n + 1)) probes of the LDS words
 //                           [i0, i1), then, GLOBAL, ceil(log2(stride)) probes of the list itself on the slice between two pivots (stride - 1
 //                           elements at most; elements behind the slice's end count as "not less"), then one ==.  Every probe index is clamped to
 //                           the words staged and to the list: an unsorted list gives unspecified bits and reads nothing else.
@@ -23,18 +23,10 @@
 //   k_in_list<8, true>    79 VGPRs, 33792 B LDS, 6 waves per SIMD, no scratch
 //   k_in_list<4, false>   75 VGPRs, 33792 B LDS, 6 waves per SIMD, no scratch
 //   k_in_list<4, true>    71 VGPRs, 33792 B LDS, 7 waves per SIMD, no scratch
-#include "in_list_search.hpp"
+#include "persistent_scan.hpp"
+#include "sorted_list.hpp"
 
 namespace alpgpu {
-
-// word m (= lane, < 16) of a vector's bitmap with the bits of the positions [p_begin, p_end) set
-__device__ __forceinline__ uint64_t in_list_range_word(uint32_t lane, uint32_t p_begin, uint32_t p_end) {
-	const uint32_t w0 = 64u * lane;
-	const uint32_t lo = p_begin > w0 ? p_begin : w0, hi = p_end < w0 + 64u ? p_end : w0 + 64u;
-	if (hi <= lo) { return 0ull; }
-	const uint64_t run = hi - lo == 64u ? ~0ull : (1ull << (hi - lo)) - 1ull;
-	return run << (lo - w0);
-}
 
 template <int VB, bool GLOBAL>
 __global__ __launch_bounds__(kInThreads) void k_in_list(const ColumnStreams c, const InArgs g) {
@@ -47,10 +39,7 @@ __global__ __launch_bounds__(kInThreads) void k_in_list(const ColumnStreams c, c
 	const T*       list = static_cast<const T*>(g.list);
 
 	// 0. the list (GLOBAL: its pivots) into LDS, once per workgroup; the one workgroup barrier of the kernel
-	for (uint32_t i = threadIdx.x; i < g.n_piv; i += kInThreads) {
-		const uint64_t at = static_cast<uint64_t>(i) * (GLOBAL ? g.stride : 1u);
-		s_list[i]         = list[at < g.n_list ? at : g.n_list - 1u]; // (n_piv > 0 only with n_list > 0)
-	}
+	sorted_list_stage<VB, GLOBAL>(s_list, list, g);
 	__syncthreads();
 
 	const uint64_t n_waves = static_cast<uint64_t>(gridDim.x) * kInWaves;
@@ -82,18 +71,9 @@ __global__ __launch_bounds__(kInThreads) void k_in_list(const ColumnStreams c, c
 
 		// 2. the part [j0, j1) of the list that the vector's zone record admits: all of it without a record or with a NaN bound
 		uint32_t j0 = 0u, j1 = g.n_list;
-		if (g.zones != nullptr && g.n_list > 0u) {
-			const T* zone = static_cast<const T*>(g.zones) + 2 * v; // (wave-uniform)
-			const T  z[2] = {zone[0], zone[1]};
-			if (z[0] == z[0] && z[1] == z[1]) {
-				uint32_t j[2];
-				in_list_search<VB, GLOBAL, 2>(s_list, list, g, 0u, g.n_list, z, 2u, j); // the first element >= min, the first element > max
-				j0 = __builtin_amdgcn_readfirstlane(j[0]);
-				j1 = __builtin_amdgcn_readfirstlane(j[1]);
-			}
-		}
+		if (g.zones != nullptr && g.n_list > 0u) { sorted_list_zone<VB, GLOBAL>(s_list, list, g, v, j0, j1); }
 		if (j1 <= j0) { // no element can be a member here (an empty list included): the descriptor is not read
-			const uint64_t q = g.negate ? in_list_range_word(lane, p_begin, p_end) : 0ull;
+			const uint64_t q = g.negate ? range_word(lane, p_begin, p_end) : 0ull;
 			if (lane < 16u && !(g.op == kMaskOr && !g.negate)) { mw[lane] = g.op == kMaskAnd ? (prior & q) : g.op == kMaskOr ? (prior | q) : q; }
 			continue;
 		}
@@ -116,13 +96,7 @@ __global__ __launch_bounds__(kInThreads) void k_in_list(const ColumnStreams c, c
 			in_list_search<VB, GLOBAL, kStepBatch>(s_list, list, g, j0, j1, x, 0u, at);
 			T e[kStepBatch];
 #pragma unroll
-			for (uint32_t i = 0; i < kStepBatch; ++i) {
-				if constexpr (GLOBAL) {
-					e[i] = list[at[i] < g.n_list - 1u ? at[i] : g.n_list - 1u];
-				} else {
-					e[i] = s_list[at[i] < g.n_piv - 1u ? at[i] : g.n_piv - 1u];
-				}
-			}
+			for (uint32_t i = 0; i < kStepBatch; ++i) { e[i] = sorted_list_at<VB, GLOBAL>(s_list, list, g, at[i]); }
 #pragma unroll
 			for (uint32_t i = 0; i < kStepBatch; ++i) {
 				const uint32_t m      = b + i;
@@ -135,8 +109,6 @@ __global__ __launch_bounds__(kInThreads) void k_in_list(const ColumnStreams c, c
 		if (lane < 16u) { mw[lane] = g.op == kMaskAnd ? (prior & keep) : g.op == kMaskOr ? (prior | keep) : keep; } // one run of 128 bytes
 	}
 }
-
-size_t in_list_lds_max(int value_bytes) { return value_bytes == 8 || value_bytes == 4 ? kInLdsBytes / static_cast<uint32_t>(value_bytes) : 0u; }
 
 template <int VB>
 static int launch_in_list_vb(hipStream_t stream, const ColumnStreams& c, const InArgs& args, unsigned grid) {
@@ -151,9 +123,9 @@ static int launch_in_list_vb(hipStream_t stream, const ColumnStreams& c, const I
 // col->n_vectors > 0, n > 0, n_list <= 2^31 - 1; range, op and alignments checked by the caller
 int launch_select_in_mask(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const void* d_list, uint64_t n_list, int negate, const void* d_zones, int op,
                           uint64_t* d_mask, int value_bytes, int n_cus) {
-	const uint64_t end     = first + n;
-	const uint64_t lds_max = in_list_lds_max(value_bytes);
-	InArgs         args {};
+	const uint64_t    end     = first + n;
+	const ListStaging staging = list_staging(n_list, value_bytes);
+	InArgs            args {};
 	args.v0      = op == kMaskOr ? first >> 10 : 0ull; // SET and AND cover every vector, OR those of the range
 	args.n_range = op == kMaskOr ? ((end - 1) >> 10) - args.v0 + 1 : col->n_vectors;
 	args.first   = first;
@@ -162,14 +134,12 @@ int launch_select_in_mask(hipStream_t stream, const alpgpu_column* col, uint64_t
 	args.list    = d_list;
 	args.zones   = d_zones;
 	args.n_list  = static_cast<uint32_t>(n_list);
-	args.stride  = n_list > lds_max ? static_cast<uint32_t>((n_list + lds_max - 1) / lds_max) : 1u;
-	args.n_piv   = static_cast<uint32_t>((n_list + args.stride - 1) / args.stride);
+	args.stride  = staging.stride;
+	args.n_piv   = staging.n_piv;
 	args.op      = op;
 	args.negate  = negate != 0;
-	const uint64_t   n_wg     = (args.n_range + kInWaves - 1) / kInWaves;
-	const uint64_t   resident = static_cast<uint64_t>(n_cus > 0 ? n_cus : 1) * kInWgPerCu; // the grid is sized to the device: a workgroup stages the list once
-	const ColumnStreams c = column_streams(col);
-	const unsigned   grid = static_cast<unsigned>(n_wg < resident ? n_wg : resident);
+	const ColumnStreams c    = column_streams(col);
+	const unsigned      grid = persistent_grid(args.n_range, kInWaves, n_cus, kInWgPerCu); // sized to the device: a workgroup stages the list once
 	return value_bytes == 8 ? launch_in_list_vb<8>(stream, c, args, grid) : launch_in_list_vb<4>(stream, c, args, grid);
 }
 

@@ -1,6 +1,6 @@
 // join_kernels.hip — join probe (include/alpgpu.h, "join probe": alpgpu_join_probe_*): for every selected value of a compressed column, the position of
-// its match in a sorted key list (or the build-side row id stored there) and the length of the equal run, compacted in index order.  k_in_list's
-// skeleton with the epilogue of k_select's TAKE arm.
+// its match in a sorted key list (or the build-side row id stored there) and the length of the equal run, compacted in index order.  The sorted
+// list in LDS of k_in_list (sorted_list.hpp: staging, zone bounds, search and equality fetch are its functions) with the epilogue of k_select's TAKE arm.
 //
 //   k_join_probe<VB, GLOBAL, SPAN>   persistent workgroups of kInWaves wavefronts.  The workgroup stages the sorted keys (or, GLOBAL, every stride-th of
 //                           them: the pivots) into 32 KiB of static LDS, passes ONE workgroup barrier and only then walks vectors v = wave_id,
@@ -9,11 +9,11 @@
 //                           register_decode.hpp in batches of kStepBatch steps.  A batch whose words are all zero requests nothing of the column and
 //                           only moves the exception rank on, as TAKE does.  Without a bitmap counts[v] = 1024, offsets[v] = 1024 v and every word
 //                           is all ones: nothing but the column is read.
-//   the search              in_list_search (in_list_search.hpp): lb = the keys < x over [j0, j1), then one ==; SPAN: a second call with `upper` set,
+//   the search              in_list_search (sorted_list.hpp): lb = the keys < x over [j0, j1), then one ==; SPAN: a second call with `upper` set,
 //                           ub = the keys <= x, span = ub - lb.  A template flag and not a branch: the instances without a span keep lb's registers only.
 //   the output slot         offsets[v] + the set bits of the words before + v_mbcnt of the value's own word: ascending, and no atomic anywhere.  The
 //                           vector is left behind its last set bit or behind the capacity.
-//   zones                   k_in_list's two wave-uniform searches: j1 <= j0 (an empty list included) and every set bit of the vector gets NO_MATCH and
+//   zones                   sorted_list_zone's two wave-uniform searches: j1 <= j0 (an empty list included) and every set bit of the vector gets NO_MATCH and
 //                           span 0 from its bitmap words alone; else the per-value search runs over [j0, j1) only.
 //
 // HBM traffic per vector: with a bitmap the scan's 12 bytes and, where a bit is set below the capacity, the 128 bytes of bitmap; unless the zone record
@@ -30,8 +30,8 @@
 //   k_join_probe<4, true, false>    67 VGPRs, 33792 B LDS, 7 waves per SIMD, no scratch (2 SGPRs kept in VGPR lanes)
 //   k_join_probe<4, true, true>     75 VGPRs, 33792 B LDS, 6 waves per SIMD, no scratch (7 SGPRs kept in VGPR lanes)
 // (33792 B of LDS: four workgroups per CU, as k_in_list.)
-#include "in_list_search.hpp"
 #include "select_device.hpp"
+#include "sorted_list.hpp"
 
 namespace alpgpu {
 
@@ -59,10 +59,7 @@ __global__ __launch_bounds__(kInThreads) void k_join_probe(const ColumnStreams c
 	const T*       list = static_cast<const T*>(g.list);
 
 	// 0. the keys (GLOBAL: their pivots) into LDS, once per workgroup; the one workgroup barrier of the kernel
-	for (uint32_t i = threadIdx.x; i < g.n_piv; i += kInThreads) {
-		const uint64_t at = static_cast<uint64_t>(i) * (GLOBAL ? g.stride : 1u);
-		s_list[i]         = list[at < g.n_list ? at : g.n_list - 1u]; // (n_piv > 0 only with n_list > 0)
-	}
+	sorted_list_stage<VB, GLOBAL>(s_list, list, g);
 	__syncthreads();
 	if (a.d_count != nullptr && blockIdx.x == 0u && threadIdx.x == 0u) { *a.d_count = a.n_vectors << 10; } // no bitmap: the count is the column's length
 
@@ -84,16 +81,7 @@ __global__ __launch_bounds__(kInThreads) void k_join_probe(const ColumnStreams c
 
 		// 2. the part [j0, j1) of the keys that the vector's zone record admits: all of them without a record or with a NaN bound
 		uint32_t j0 = 0u, j1 = g.n_list;
-		if (g.zones != nullptr && g.n_list > 0u) {
-			const T* zone = static_cast<const T*>(g.zones) + 2 * v; // (wave-uniform)
-			const T  z[2] = {zone[0], zone[1]};
-			if (z[0] == z[0] && z[1] == z[1]) {
-				uint32_t j[2];
-				in_list_search<VB, GLOBAL, 2>(s_list, list, g, 0u, g.n_list, z, 2u, j); // the first key >= min, the first key > max
-				j0 = __builtin_amdgcn_readfirstlane(j[0]);
-				j1 = __builtin_amdgcn_readfirstlane(j[1]);
-			}
-		}
+		if (g.zones != nullptr && g.n_list > 0u) { sorted_list_zone<VB, GLOBAL>(s_list, list, g, v, j0, j1); }
 		uint32_t before_sel = 0; // set bits of the steps done (wave-uniform)
 		if (j1 <= j0) { // no key can match here (an empty list included): the rows come from the bitmap words, the descriptor is not read
 			for (uint32_t m = 0; m < 16u; ++m) {
@@ -136,13 +124,7 @@ __global__ __launch_bounds__(kInThreads) void k_join_probe(const ColumnStreams c
 			in_list_search<VB, GLOBAL, kStepBatch>(s_list, list, g, j0, j1, x, 0u, lb);
 			T e[kStepBatch];
 #pragma unroll
-			for (uint32_t i = 0; i < kStepBatch; ++i) {
-				if constexpr (GLOBAL) {
-					e[i] = list[lb[i] < g.n_list - 1u ? lb[i] : g.n_list - 1u];
-				} else {
-					e[i] = s_list[lb[i] < g.n_piv - 1u ? lb[i] : g.n_piv - 1u];
-				}
-			}
+			for (uint32_t i = 0; i < kStepBatch; ++i) { e[i] = sorted_list_at<VB, GLOBAL>(s_list, list, g, lb[i]); }
 			uint32_t ub[kStepBatch];
 			if constexpr (SPAN) { in_list_search<VB, GLOBAL, kStepBatch>(s_list, list, g, j0, j1, x, (1u << kStepBatch) - 1u, ub); }
 			// 6. the rows of the batch's set bits
@@ -166,16 +148,6 @@ __global__ __launch_bounds__(kInThreads) void k_join_probe(const ColumnStreams c
 	}
 }
 
-// the count of a call that launches no probe (a count without a bitmap, or a column without vectors); a kernel and not hipMemsetAsync, whose node in
-// a captured graph did not survive later replays (histogram_kernels.hip)
-__global__ __launch_bounds__(64) void k_join_count(uint64_t* __restrict__ d_count, uint64_t n) {
-	if (threadIdx.x == 0u) { *d_count = n; }
-}
-int launch_join_count(hipStream_t stream, uint64_t* d_count, uint64_t n) {
-	hipLaunchKernelGGL(k_join_count, dim3(1), dim3(64), 0, stream, d_count, n);
-	return hipGetLastError() != hipSuccess ? ALPGPU_ERR_HIP : ALPGPU_OK;
-}
-
 template <int VB, bool GLOBAL>
 static void launch_join_span(hipStream_t stream, const ColumnStreams& c, const InArgs& g, const JoinArgs& a, unsigned grid) {
 	if (a.d_span != nullptr) {
@@ -195,7 +167,7 @@ static int launch_join_vb(hipStream_t stream, const ColumnStreams& c, const InAr
 }
 
 // col->n_vectors > 0, n_keys <= 2^31 - 1, d_pos non-null when capacity > 0; the alignments checked by the caller.  With a bitmap: the popcount pass and the
-// scan of mask_kernels.hip, then (capacity > 0) the probe.  Without: the probe alone, which writes the count, or (capacity == 0) the count alone.
+// scan of mask_kernels.hip, then (capacity > 0) the probe.  Without: the probe alone, which writes the count, or (capacity == 0) launch_fill_u64.
 int launch_join_probe(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, const void* d_zones, const void* d_keys, uint64_t n_keys, const int64_t* d_rows,
                       int64_t* d_pos, uint32_t* d_span, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch, int value_bytes, int n_cus) {
 	JoinArgs a {};
@@ -206,7 +178,7 @@ int launch_join_probe(hipStream_t stream, const alpgpu_column* col, const uint64
 		a.counts  = s.counts;
 		a.offsets = s.offsets;
 	} else {
-		if (capacity == 0) { return launch_join_count(stream, d_count, col->n_vectors << 10); }
+		if (capacity == 0) { return launch_fill_u64(stream, d_count, 1u, col->n_vectors << 10); }
 		a.d_count = d_count;
 	}
 	a.n_vectors = col->n_vectors;
@@ -216,17 +188,15 @@ int launch_join_probe(hipStream_t stream, const alpgpu_column* col, const uint64
 	a.d_span    = d_span;
 	a.d_idx     = d_idx;
 	a.capacity  = capacity;
-	const uint64_t lds_max = in_list_lds_max(value_bytes);
-	InArgs         g {};
+	const ListStaging staging = list_staging(n_keys, value_bytes);
+	InArgs            g {};
 	g.list   = d_keys;
 	g.zones  = d_zones;
 	g.n_list = static_cast<uint32_t>(n_keys);
-	g.stride = n_keys > lds_max ? static_cast<uint32_t>((n_keys + lds_max - 1) / lds_max) : 1u;
-	g.n_piv  = static_cast<uint32_t>((n_keys + g.stride - 1) / g.stride);
-	const uint64_t      n_wg     = (col->n_vectors + kInWaves - 1) / kInWaves;
-	const uint64_t      resident = static_cast<uint64_t>(n_cus > 0 ? n_cus : 1) * kInWgPerCu; // the grid is sized to the device: a workgroup stages the keys once
-	const ColumnStreams c        = column_streams(col);
-	const unsigned      grid     = static_cast<unsigned>(n_wg < resident ? n_wg : resident);
+	g.stride = staging.stride;
+	g.n_piv  = staging.n_piv;
+	const ColumnStreams c    = column_streams(col);
+	const unsigned      grid = persistent_grid(col->n_vectors, kInWaves, n_cus, kInWgPerCu); // sized to the device: a workgroup stages the keys once
 	return value_bytes == 8 ? launch_join_vb<8>(stream, c, g, a, grid) : launch_join_vb<4>(stream, c, g, a, grid);
 }
 

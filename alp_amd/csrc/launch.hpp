@@ -5,6 +5,7 @@
 
 #include "../../include/alpgpu.h"
 #include "decode_policy.hpp"
+#include "persistent_launch.hpp"
 
 namespace alpgpu {
 
@@ -69,7 +70,9 @@ int launch_select_scan(hipStream_t stream, const uint32_t* d_counts, uint64_t n,
 // q(r) = first <= r < first + n and lo <= x_r <= hi (n > 0, range and op checked by the caller); launch_mask_to_indices: the set bits as ascending
 // indices up to capacity, *d_count = how many (n_vectors > 0; d_scratch: select_scratch_bytes(n_vectors) bytes); launch_sum_masked: d_sums[v] = the sum of
 // the vector's values whose bit is set, d_counts[v] (nullable) = its set bits (col->n_vectors > 0); launch_decode_masked: the values at the set bits,
-// ascending, into d_vals (and their indices into d_idx, nullable) up to capacity, *d_count = how many (col->n_vectors > 0, d_vals non-null when capacity > 0)
+// ascending, into d_vals (and their indices into d_idx, nullable) up to capacity, *d_count = how many (col->n_vectors > 0, d_vals non-null when capacity > 0).
+// launch_fill_u64: d_words[i] = value, i < n_words (> 0), by a kernel and not hipMemsetAsync (mask_kernels.hip, k_fill_u64, says why)
+int launch_fill_u64(hipStream_t stream, uint64_t* d_words, uint32_t n_words, uint64_t value);
 int launch_select_mask(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int op, uint64_t* d_mask, int value_bytes);
 int launch_mask_to_indices(hipStream_t stream, const uint64_t* d_mask, uint64_t n_vectors, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch);
 int launch_sum_masked(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, double* d_sums, uint32_t* d_counts, int value_bytes);
@@ -152,8 +155,7 @@ int quantile_trace(hipStream_t stream, const void* d_scratch, alpgpu_quantile_tr
 // in_list_kernels.hip: set membership.  launch_select_in_mask: bit(r) = / &= / |= q(r), q(r) = first <= r < first + n and ((some j < n_list has
 // d_list[j] == x_r) != negate) (n > 0; range, op, n_list <= 2^31 - 1 and the alignments checked by the caller; d_list sorted, device memory of the
 // column's type, NULL with n_list == 0; d_zones nullable: the column's zone map); one launch of persistent workgroups, at most four per CU.
-// in_list_lds_max: the longest list the kernel holds whole in LDS (value_bytes 8 or 4; else 0)
-size_t in_list_lds_max(int value_bytes);
+// (in_list_lds_max, the longest list the kernel holds whole in LDS, and what of a longer one is staged: persistent_launch.hpp)
 int launch_select_in_mask(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const void* d_list, uint64_t n_list, int negate, const void* d_zones, int op,
                           uint64_t* d_mask, int value_bytes, int n_cus);
 
@@ -161,8 +163,8 @@ int launch_select_in_mask(hipStream_t stream, const alpgpu_column* col, uint64_t
 // position of the first key == x in d_keys (d_rows nullable: the payload there) or ALPGPU_JOIN_NO_MATCH, d_span (nullable) = the keys == x, d_idx
 // (nullable) = the value index; *d_count = the set bits (col->n_vectors > 0; n_keys <= 2^31 - 1, d_pos non-null with capacity > 0, d_scratch non-null with
 // a bitmap and the alignments checked by the caller; d_keys sorted device memory of the column's type; d_zones nullable).  With a bitmap the popcount
-// pass and the scan of mask_kernels.hip, then one launch of persistent workgroups, at most four per CU.  launch_join_count: *d_count = n, by a kernel
-int launch_join_count(hipStream_t stream, uint64_t* d_count, uint64_t n);
+// pass and the scan of mask_kernels.hip, then one launch of persistent workgroups, at most four per CU.  A call that launches no probe (capacity == 0
+// without a bitmap) writes its count by launch_fill_u64.
 int launch_join_probe(hipStream_t stream, const alpgpu_column* col, const uint64_t* d_mask, const void* d_zones, const void* d_keys, uint64_t n_keys, const int64_t* d_rows,
                       int64_t* d_pos, uint32_t* d_span, int64_t* d_idx, uint64_t capacity, uint64_t* d_count, void* d_scratch, int value_bytes, int n_cus);
 
@@ -170,9 +172,7 @@ int launch_join_probe(hipStream_t stream, const alpgpu_column* col, const uint64
 // d_mask (nullable: every r), that are no NaNs and have b = #{i : d_edges[i] <= x_r} (right: <), d_counts[n_edges + 1] += those that are NaNs
 // (col->n_vectors > 0, n > 0, n_edges <= ALPGPU_HISTOGRAM_EDGES_MAX; range and alignments checked by the caller, who has zeroed the counts unless they
 // accumulate; d_edges sorted device memory of the column's type; d_zones, tuning and d_trace nullable); one launch of persistent workgroups, at most
-// three per CU.  launch_histogram_zero: n_words (> 0) counts zeroed by a kernel (what a call that overwrites enqueues first; not hipMemsetAsync, whose
-// node in a captured graph did not survive later replays: histogram_kernels.hip)
-int launch_histogram_zero(hipStream_t stream, uint64_t* d_counts, uint32_t n_words);
+// three per CU.  (A call that overwrites zeroes the counts first, by launch_fill_u64.)
 int launch_histogram(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const void* d_zones, const void* d_edges, uint32_t n_edges,
                      int right, uint64_t* d_counts, int value_bytes, int n_cus, const alpgpu_histogram_tuning* tuning, uint64_t* d_trace);
 
@@ -181,7 +181,7 @@ int launch_histogram(hipStream_t stream, const alpgpu_column* col, uint64_t firs
 // the power of two >= capacity pairs of the sort); false when capacity is 0 or beyond ALPGPU_DISTINCT_MAX.  launch_distinct: col->n_vectors > 0, n > 0,
 // capacity in 1 .. ALPGPU_DISTINCT_MAX; range and alignments checked by the caller; d_counts, d_zones, tuning and d_trace nullable.  The reset, one
 // launch of persistent workgroups (at most three per CU for float, two for double), the compaction, the sort's launches (their number a function of capacity and the tuning's
-// sort_tile) and the emit, which writes d_state.  launch_distinct_zero_state: the four words zeroed by a kernel (what a call without work enqueues)
+// sort_tile) and the emit, which writes d_state.  (A call without work zeroes the four words by launch_fill_u64.)
 struct DistinctLayout {
 	uint64_t state, keys, counts, pairs, total;
 	uint64_t table_slots, sort_slots; // T, P
@@ -202,7 +202,6 @@ inline bool distinct_layout(uint64_t capacity, DistinctLayout& L) {
 	L.total       = L.pairs + 16ull * L.sort_slots;
 	return true;
 }
-int launch_distinct_zero_state(hipStream_t stream, uint64_t* d_state);
 int launch_distinct(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const void* d_zones, uint64_t capacity, void* d_vals,
                     uint64_t* d_counts, uint64_t* d_state, void* d_scratch, int value_bytes, int n_cus, const alpgpu_distinct_tuning* tuning, uint64_t* d_trace);
 

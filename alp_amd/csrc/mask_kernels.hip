@@ -53,6 +53,20 @@ __global__ __launch_bounds__(kSelThreads) void k_mask_emit(const uint64_t* __res
 	}
 }
 
+// The library's "memset" of a few 64-bit words: words[i] = value, i < n_words.  What a call enqueues that zeroes its counts before it adds to them
+// (alpgpu_histogram_*), or that writes a small result with no other launch (the join probe's count, the distinct call's state without work).  A
+// kernel, not hipMemsetAsync: captured into a graph with torch, the memset's node was observed to leave non-zero words at replays that came after
+// other work on the device (tools/probe_graph_memset.py shows it with alpgpu_memset alone, 24 bytes to 514 KiB; the cause is not established:
+// DESIGN.md, "Histograms"), and these calls have to stay capturable.
+__global__ __launch_bounds__(256) void k_fill_u64(uint64_t* __restrict__ words, uint32_t n_words, uint64_t value) { // n_words > 0
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i < n_words) { words[i] = value; }
+}
+int launch_fill_u64(hipStream_t stream, uint64_t* d_words, uint32_t n_words, uint64_t value) {
+	hipLaunchKernelGGL(k_fill_u64, dim3((n_words + 255u) / 256u), dim3(256), 0, stream, d_words, n_words, value);
+	return hipGetLastError() != hipSuccess ? ALPGPU_ERR_HIP : ALPGPU_OK;
+}
+
 // n > 0, first + n <= n_vectors * 1024 and op one of the three (the caller checked).  SET and AND touch every vector of the column (bits outside
 // the range clear), OR only those of the range (bits outside it stay).
 int launch_select_mask(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, double lo, double hi, int op, uint64_t* d_mask, int value_bytes) {

@@ -9,6 +9,7 @@
 // histogram of 256 bins per slot and pass.  The ranks themselves need no order: the pick rebuilds the slots from whatever prefixes it finds
 // ("Quantiles", says why the host does not sort them).
 #pragma once
+#include "persistent_scan.hpp"
 #include "top_k_device.hpp"
 
 namespace alpgpu {
@@ -85,15 +86,6 @@ __device__ __forceinline__ void q_hist_add(uint32_t* s_bins, uint64_t keep, uint
 		if (lane == lead) { atomicAdd(&s_bins[first], static_cast<uint32_t>(__builtin_popcountll(keep))); }
 	} else if (mine) {
 		atomicAdd(&s_bins[idx], 1u);
-	}
-}
-
-// the workgroup's non-zero bins of the live slots into the pass's 64-bit global bins; a barrier first, none behind
-__device__ __forceinline__ void q_flush(const uint32_t* s_bins, uint32_t n_slots, uint64_t* bins) {
-	__syncthreads();
-	for (uint32_t i = threadIdx.x; i < 256u * n_slots; i += kQThreads) {
-		const uint32_t n = s_bins[i];
-		if (n != 0u) { atomicAdd(reinterpret_cast<unsigned long long*>(bins) + i, static_cast<unsigned long long>(n)); }
 	}
 }
 

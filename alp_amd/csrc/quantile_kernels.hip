@@ -4,7 +4,7 @@
 //   memset            the state and the bins of every pass
 //   k_quantile_popcount   the bitmap's set bits: if they fit the candidate capacity, pass 0 itself compacts and the call is ONE decode
 //   per digit d:
-//     k_quantile_wide<VB>   persistent workgroups of kQWaves wavefronts over the column's vectors (the skeleton of k_in_list: one barrier for the LDS
+//     k_quantile_wide<VB>   persistent workgroups of kQWaves wavefronts over the column's vectors (the shape of persistent_scan.hpp: one barrier for the LDS
 //                           set-up, then v = wave id, wave id + waves, ...); per vector quantile_device.hpp's q_vector.  32 slots x 256 bins of LDS
 //                           and 2 KiB of staged candidate keys per wavefront; the bins are
 //                           flushed into the pass's 64-bit global bins at the end (and every flush_every trips, so that no 32-bit bin overflows).
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void k_quantile_popcount(const uint64_t* __res
 __device__ __forceinline__ uint32_t q_stage(const QState* st, uint32_t pass, uint32_t* s_bins, uint64_t* s_pfx) {
 	uint32_t n_slots = pass == 0u ? 1u : st->n_slots;
 	n_slots          = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(n_slots < 1u ? 1u : n_slots < kQSlots ? n_slots : kQSlots)));
-	for (uint32_t i = threadIdx.x; i < 256u * n_slots; i += kQThreads) { s_bins[i] = 0u; }
+	bins_zero<kQThreads>(s_bins, 256u * n_slots);
 	if (threadIdx.x < kQSlots) { s_pfx[threadIdx.x] = pass > 0u && threadIdx.x < n_slots ? st->slot_prefix[threadIdx.x] : (threadIdx.x == 0u ? 0ull : ~0ull); }
 	__syncthreads();
 	return n_slots;
@@ -60,9 +60,9 @@ __device__ __forceinline__ void q_wide_loop(const ColumnStreams& c, const QWideA
 		}
 		if (++trips == g.flush_every) {
 			trips = 0;
-			q_flush(s_bins, n_slots, g.bins);
+			bins_flush<kQThreads>(s_bins, 256u * n_slots, g.bins);
 			__syncthreads();
-			for (uint32_t i = threadIdx.x; i < 256u * n_slots; i += kQThreads) { s_bins[i] = 0u; }
+			bins_zero<kQThreads>(s_bins, 256u * n_slots);
 			__syncthreads();
 		}
 	}
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(kQThreads) __attribute__((amdgpu_waves_per_eu(6))) 
 	} else {
 		q_wide_loop<VB, false>(c, g, wave, lane, n_slots, s_bins, s_pfx, s_exc, s_keys[wave], zero_skips, zone_skips);
 	}
-	q_flush(s_bins, n_slots, g.bins);
+	bins_flush<kQThreads>(s_bins, 256u * n_slots, g.bins);
 	if (lane == 0u) { // the trace: one add per wavefront and counter
 		if (g.pass == 0u && zero_skips != 0u) { atomicAdd(reinterpret_cast<unsigned long long*>(&g.st->zero_skips), static_cast<unsigned long long>(zero_skips)); }
 		if (zone_skips != 0u) { atomicAdd(reinterpret_cast<unsigned long long*>(&g.st->zone_skips[g.pass & 7u]), static_cast<unsigned long long>(zone_skips)); }
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(kQThreads) void k_quantile_narrow(const QNarrowArgs
 		uint32_t       slot;
 		if (q_find_slot(s_pfx, n_slots, key & g.mask_hi, slot)) { atomicAdd(&s_bins[256u * slot + static_cast<uint32_t>((key >> g.shift) & 255ull)], 1u); }
 	}
-	q_flush(s_bins, n_slots, g.bins);
+	bins_flush<kQThreads>(s_bins, 256u * n_slots, g.bins);
 }
 
 __device__ __forceinline__ uint64_t wave_scan_add_u64(uint64_t x, uint32_t lane) {
@@ -283,10 +283,7 @@ static int quantile(hipStream_t stream, const alpgpu_column* col, const uint64_t
 		// at most 2^36 words: with 1024 workgroups a wavefront sums at most 2^36 / 4096 * 64 = 2^30 bits
 		hipLaunchKernelGGL(k_quantile_popcount, dim3(static_cast<unsigned>(wgs < 1024ull ? wgs : 1024ull)), dim3(256), 0, stream, d_mask, n_words, state);
 	}
-	const uint64_t n_wg     = (nv + kQWaves - 1) / kQWaves;
-	uint64_t       resident = static_cast<uint64_t>(n_cus > 0 ? n_cus : 1) * kQWgPerCu;
-	if (tune.max_workgroups != 0 && tune.max_workgroups < resident) { resident = tune.max_workgroups; }
-	const unsigned grid_wide   = static_cast<unsigned>(n_wg < resident ? n_wg : resident);
+	const unsigned grid_wide   = persistent_grid(nv, kQWaves, n_cus, kQWgPerCu, tune.max_workgroups); // (the tuning's max_workgroups lowers what counts as resident)
 	const uint64_t wg_narrow   = (cap + kQThreads - 1) / kQThreads;
 	const unsigned grid_narrow = static_cast<unsigned>(wg_narrow < 256ull ? wg_narrow : 256ull);
 	const ColumnStreams c = column_streams(col);

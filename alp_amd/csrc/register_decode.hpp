@@ -1,8 +1,11 @@
 // register_decode.hpp — the in-register decode of one 1024-value vector by one wavefront, 64 lanes wide and step by step, and the glue its kernels
 // share.  Every kernel of the selection family decodes through it: k_select (select_device.hpp: range selection, bitmaps, masked SUM and
 // projection), k_pair (pair_device.hpp), k_group (group_device.hpp), k_minmax_masked and k_group_minmax (minmax_device.hpp), k_in_list
-// (in_list_kernels.hip), k_join_probe (join_kernels.hip), k_top_k_candidates (top_k_device.hpp) and k_quantile_wide (quantile_device.hpp).  A clamp
-// or a layout rule is stated here and nowhere else.
+// (in_list_kernels.hip), k_join_probe (join_kernels.hip), k_top_k_candidates (top_k_device.hpp), k_quantile_wide (quantile_device.hpp),
+// k_histogram (histogram_kernels.hip) and k_distinct_insert (distinct_kernels.hip).  A clamp or a layout rule of the decode is stated here and
+// nowhere else; what the five persistent kernels among them share around it is stated once in persistent_scan.hpp (the selected bits, the
+// constant-vector shortcut, the bin flush), sorted_list.hpp (a sorted list in LDS and its search) and persistent_launch.hpp (the host's grid and
+// staging rules).
 //
 // The decode: 16 steps, step m holds value p = 64 m + lane in lane `lane`, so a wave-wide ballot of a predicate IS the 64 bits of the vector's
 // qualify mask for indices 64 m .. 64 m + 63, in index order.  With p = 64 m + lane the lanes of a wavefront read neighbouring words of every
@@ -17,8 +20,8 @@
 //
 // A kernel: DecodeVec (decode_vec_load), the exception mask (exception_mask, exception_masks), then per batch of NB steps step_request followed by
 // step_bits / step_value of each step.  k_select takes 8 steps of one vector to a batch (kSelBatch), the others kStepBatch = 4 (of one vector or of
-// two side by side: as many vector loads in flight).  Every one of them but k_in_list, k_join_probe and k_quantile_wide, which are persistent, is
-// launched by launch_vectors below.
+// two side by side: as many vector loads in flight).  Every one of them but k_in_list, k_join_probe, k_quantile_wide, k_histogram and
+// k_distinct_insert, which are persistent (their grid: persistent_launch.hpp), is launched by launch_vectors below.
 #pragma once
 #include <type_traits>
 
@@ -252,6 +255,8 @@ __device__ __forceinline__ void range_share(uint64_t first, uint64_t end, uint64
 // (The SET / AND / OR rules of the kernels that write a bitmap, k_select's MASK arm, k_pair's compare arm and k_in_list, are NOT here: they stay
 // written out in the three kernels, each with its own `return` or `continue` and its own closing store.  A helper pair was built and timed: behind a
 // flag returned in place of the `return`, the launches that settle (nearly) every vector from its 128 bytes of bitmap were 5-6 % slower in k_select
-// and k_pair, and even the one-line closing store as a function changes k_pair's and k_in_list's instructions: profiles/r17_register_decode.txt.)
+// and k_pair, and even the one-line closing store as a function changes k_pair's and k_in_list's instructions: profiles/r17_register_decode.txt.
+// The glue of the persistent kernels that did become functions, and the forms of their calls that kept the kernels' instructions, are in
+// persistent_scan.hpp and sorted_list.hpp: profiles/r24_persistent_scan.txt.)
 
 } // namespace alpgpu
