@@ -384,6 +384,9 @@ __global__ __launch_bounds__(64 * kWavesPerWg) void k_rd_decode(double* __restri
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------
+// The grid is capped at n_cus * 16 workgroups of kWavesPerWg = 4 wavefronts: 64 * n_cus vectors fill one trip of ALPGPU_VECTOR_LOOP.  The smallest
+// batch in which some wavefronts take a second trip and a workgroup has one that does not is 64 * n_cus + 7 (one whole workgroup, then three
+// wavefronts of the next): what tests/test_primitive_batches_gpu.py runs every kernel of this file on.
 static unsigned prim_grid(uint64_t n, int n_cus) {
 	const uint64_t need = (n + kWavesPerWg - 1) / kWavesPerWg;
 	const uint64_t cap  = static_cast<uint64_t>(n_cus) * 16;

@@ -1185,7 +1185,17 @@ int      alpgpu_column_from_blob(alpgpu_ctx* ctx, const void* h_blob, uint64_t s
 
 /* ---- vector primitives on batches (fixed strides; the reference's per-vector API, n at a time) ------
  * Each processes n_vectors independent vectors.  "stride" arguments are in ELEMENTS of the pointed type
- * between consecutive vectors (the reference's callers use 1024-element buffers for everything). */
+ * between consecutive vectors (the reference's callers use 1024-element buffers for everything).
+ * What tests/test_primitive_batches_gpu.py pins beyond that:
+ *   - every packed row (d_packed + v * packed_stride) must be 16-byte aligned: the 64- and 32-bit lanes move packed words 16 bytes at a
+ *     time.  A 16-byte aligned d_packed and any stride that is a multiple of the tight one (16 / 32 / 64 / 128 elements per bit of the
+ *     batch's largest width for 64 / 32 / 16 / 8-bit lanes) satisfy it.  A vector touches only the first 128 * bw bytes of its row.
+ *   - a width above the lane width (bw > 64 / 32 / 16 / 8) is a no-op, as in the reference's switch: ffor, unffor and falp leave that
+ *     vector's output untouched.  bw = 0: ffor writes nothing, unffor gives the base.
+ *   - exception rows: only the first cnt entries of a vector's d_exc / d_pos row are written (encoders) or read (patch, rd_decode);
+ *     exc_stride must be at least the batch's largest count.
+ *   - rd_encode_vectors_* writes dict_size as the left index of an exception; rd_decode_vectors_* accepts any index there (an index
+ *     of 8 or more reads no dictionary entry), the exception list overwrites the slot. */
 
 /* ffor::ffor / unffor::unffor, 64-bit lanes: in/out [n][1024] int64, packed [n][packed_stride] (>= 16*bw words
  * used per vector), bw/base per vector */
