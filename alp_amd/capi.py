@@ -190,6 +190,18 @@ _sig("alpgpu_distinct_scratch_bytes", _u64, _u64)
 for _t in ("f64", "f32"):
     _sig("alpgpu_distinct_" + _t, _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp)
     _sig("alpgpu_debug_distinct_" + _t, _int, _vp, C.POINTER(CColumn), _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, C.POINTER(DistinctTuning), _vp)
+KEYED_KEYS_MAX, KEYED_STRIPES_MAX = 1024, 4096  # ALPGPU_KEYED_KEYS_MAX, ALPGPU_KEYED_STRIPES_MAX
+
+
+class KeyedTuning(C.Structure):  # alpgpu_keyed_tuning
+    _fields_ = [("grid", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+_sig("alpgpu_keyed_stripe_vectors", _u64, _u64)
+_sig("alpgpu_keyed_sum_scratch_bytes", _u64, _u64, C.c_uint32)
+for _t in ("f64",):  # (double columns only: the float entry points are not built yet, include/alpgpu.h says why)
+    _sig("alpgpu_decode_keyed_sum_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp)
+    _sig("alpgpu_debug_decode_keyed_sum_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.POINTER(KeyedTuning), _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -1452,6 +1464,106 @@ class Context:
         self.distinct_into(col, vals, state, counts_out=cnt, mask=mask, first=first, n=n, zones=zones)
         d, n_nan, _, overflow = state.tolist()
         return vals[:d], (cnt[:d] if counts else None), n_nan, bool(overflow)
+
+    # ---- keyed aggregation (include/alpgpu.h: alpgpu_decode_keyed_sum_*) ------------------------------------------------
+    def keyed_sum_scratch(self, n_vectors: int, n_keys: int):
+        """a scratch tensor for keyed_sum_into (alpgpu_keyed_sum_scratch_bytes; torch allocations are at least 16-byte aligned)"""
+        import torch
+        n_vectors, n_keys = int(n_vectors), int(n_keys)
+        if n_vectors < 0 or not 1 <= n_keys <= KEYED_KEYS_MAX:
+            raise ValueError("n_vectors must not be negative and n_keys must be in 1 .. %d" % KEYED_KEYS_MAX)
+        return torch.empty(lib.alpgpu_keyed_sum_scratch_bytes(n_vectors, n_keys), dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    def keyed_sum_into(self, val: "DeviceColumn", key: "DeviceColumn", keys, sums_out, counts_out=None, mask=None, zones=None, scratch=None, tuning=None, trace=None):
+        """the raw form of alpgpu_decode_keyed_sum_f64 (double columns only): sums_out (float64, exactly len(keys)) takes, per key, the sum of val over the rows whose
+        bit is set in the mask (None: every row) and whose value of the key column == that key (the first of equal keys; -0.0 == +0.0; a NaN
+        matches nothing), in the order include/alpgpu.h documents; counts_out (optional, int64, exactly len(keys) + 1) their exact numbers and, in
+        its last word, the selected rows that match no key.  keys: a SORTED contiguous device tensor of the columns' type, 1 .. KEYED_KEYS_MAX long.
+        zones: any records that contain the KEY vectors' intervals (zone_map(key), widened ones): the same bits.  tuning: {"grid"}, trace: an int64
+        device tensor of 4 words that is ADDED to (vectors settled without either column, by the constant-key shortcut, with a record that admits
+        no key, decoded); either sends the call through the debug entry (the same bits).  Nothing is synchronised or read back; with a scratch
+        given (keyed_sum_scratch) nothing is allocated either, so the call can be captured into a graph."""
+        import torch
+        self._check_pair(val, key)
+        if val.dtype != "f64":
+            raise ValueError("keyed_sum is built for double columns only")
+        tdt = torch.float64
+        if not isinstance(keys, torch.Tensor) or keys.dtype != tdt:
+            raise ValueError("keys must be a tensor of the columns' type (%s)" % val.dtype)
+        if keys.dim() != 1 or not 1 <= keys.numel() <= KEYED_KEYS_MAX:
+            raise ValueError("keys must be one-dimensional and hold 1 .. %d keys" % KEYED_KEYS_MAX)
+        if not keys.is_cuda or keys.device.index != self.device or not keys.is_contiguous():
+            raise ValueError("keys must be contiguous on cuda:%d" % self.device)
+        n_keys = keys.numel()
+        self._check_tensor(sums_out, torch.float64, "sums_out")
+        if sums_out.dim() != 1 or sums_out.numel() != n_keys:
+            raise ValueError("sums_out must be a one-dimensional float64 tensor of len(keys)")
+        if counts_out is not None:
+            self._check_tensor(counts_out, torch.int64, "counts_out")
+            if counts_out.dim() != 1 or counts_out.numel() != n_keys + 1:
+                raise ValueError("counts_out must be a one-dimensional int64 tensor of len(keys) + 1 words")
+        if mask is not None:
+            self._check_mask(mask, val.n_vectors)
+        if zones is not None:
+            self._check_zones(zones, tdt, key.n_vectors)
+        if trace is not None:
+            self._check_tensor(trace, torch.int64, "trace")
+            if trace.numel() != 4:
+                raise ValueError("trace must hold 4 int64 words")
+        need = lib.alpgpu_keyed_sum_scratch_bytes(val.n_vectors, n_keys)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
+        else:
+            self._check_tensor(scratch, torch.uint8, "scratch")
+            if scratch.numel() < need or scratch.data_ptr() % 16:
+                raise ValueError("scratch must hold keyed_sum_scratch(n_vectors, n_keys) bytes, 16-byte aligned")
+        args = [C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
+                _vp(keys.data_ptr()), n_keys, _vp(sums_out.data_ptr()), _vp(counts_out.data_ptr()) if counts_out is not None else None, _vp(scratch.data_ptr())]
+        if tuning is None and trace is None:
+            self._call("decode_keyed_sum", val.dtype, *args)
+        else:
+            tuning = {} if tuning is None else tuning
+            if set(tuning) - {"grid"}:
+                raise ValueError("tuning takes grid")
+            t = KeyedTuning(int(tuning.get("grid", 0)), 0)
+            self._call("debug_decode_keyed_sum", val.dtype, *args, C.byref(t), _vp(trace.data_ptr()) if trace is not None else None)
+
+    def keyed_sum(self, val: "DeviceColumn", key: "DeviceColumn", keys, mask=None, zones=None, counts: bool = True, sorted: bool = False):
+        """SUM(val), COUNT(*) GROUP BY key for the given keys in one pass over the two columns: (float64[K] sums, int64[K] counts or None with
+        counts=False, unmatched), K = len(keys) in 1 .. KEYED_KEYS_MAX, in the order of the SORTED keys.  keys: a device tensor, host tensor,
+        sequence or numpy array of the columns' type; it is brought into order by torch.sort on the device (NaNs sort last and never match);
+        sorted=True skips that for a caller who guarantees the order (what distinct returns is in order).  A row belongs to the first key equal to
+        its value of the key column; later duplicates get +0.0 and 0.  unmatched: the selected rows that match no key, an int64 device scalar
+        (None with counts=False).  zones (zone_map(key) or any records that contain the key vectors' intervals): the same bits.  Nothing is
+        synchronised (alpgpu_decode_keyed_sum_f64; double columns only)."""
+        import torch
+        self._check_pair(val, key)
+        if val.dtype != "f64":
+            raise ValueError("keyed_sum is built for double columns only")
+        tdt = torch.float64
+        dev = f"cuda:{self.device}"
+        if isinstance(keys, np.ndarray):
+            if keys.dtype != np.float64:
+                raise ValueError("keys must be of the columns' type (%s)" % val.dtype)
+            keys = torch.from_numpy(np.ascontiguousarray(keys))
+        elif not isinstance(keys, torch.Tensor):
+            keys = torch.tensor(list(keys), dtype=tdt)
+        if keys.dtype != tdt:
+            raise ValueError("keys must be of the columns' type (%s)" % val.dtype)
+        if keys.dim() != 1 or not 1 <= keys.numel() <= KEYED_KEYS_MAX:
+            raise ValueError("keys must be one-dimensional and hold 1 .. %d keys" % KEYED_KEYS_MAX)
+        if keys.is_cuda and keys.device.index != self.device:
+            raise ValueError("keys must be on the host or on cuda:%d" % self.device)
+        if mask is not None:
+            self._check_mask(mask, val.n_vectors)
+        if zones is not None:
+            self._check_zones(zones, tdt, key.n_vectors)
+        lst = keys if keys.is_cuda else keys.to(dev)
+        lst = lst.contiguous() if sorted else torch.sort(lst).values
+        sums = torch.empty(lst.numel(), dtype=torch.float64, device=dev)
+        cnt = torch.empty(lst.numel() + 1, dtype=torch.int64, device=dev) if counts else None
+        self.keyed_sum_into(val, key, lst, sums, counts_out=cnt, mask=mask, zones=zones)
+        return sums, (cnt[:-1] if counts else None), (cnt[-1] if counts else None)
 
     # ---- join probe (include/alpgpu.h: alpgpu_join_probe_*) -----------------------------------------------------------
     def join_probe_into(self, col: "DeviceColumn", keys, pos_out, count_out, mask=None, rows=None, span_out=None, idx_out=None, zones=None, scratch=None):

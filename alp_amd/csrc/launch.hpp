@@ -205,6 +205,22 @@ inline bool distinct_layout(uint64_t capacity, DistinctLayout& L) {
 int launch_distinct(hipStream_t stream, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const void* d_zones, uint64_t capacity, void* d_vals,
                     uint64_t* d_counts, uint64_t* d_state, void* d_scratch, int value_bytes, int n_cus, const alpgpu_distinct_tuning* tuning, uint64_t* d_trace);
 
+// keyed_kernels.hip: SUM and COUNT per key of a sorted key list.  keyed_stripe_vectors: L, the vectors of a stripe; keyed_stripes: S = ceil(n_vectors / L)
+// <= ALPGPU_KEYED_STRIPES_MAX, the rows of partials.  launch_keyed_sum: val->n_vectors == key->n_vectors in 1 .. 2^32 - 1 (val == key allowed), n_keys in
+// 1 .. ALPGPU_KEYED_KEYS_MAX; the alignments checked by the caller; d_keys sorted device memory of the columns' type; d_mask, d_zones (the KEY column's
+// records), d_counts (n_keys + 1 words), tuning and d_trace nullable; d_scratch: 64 bytes of header and S rows of n_keys doubles.  The init kernel, one
+// launch of persistent workgroups (two per CU up to 256 keys, one beyond) and the reduce, one workgroup per key.
+inline uint64_t keyed_stripe_vectors(uint64_t n_vectors) {
+	const uint64_t l = n_vectors / ALPGPU_KEYED_STRIPES_MAX + (n_vectors % ALPGPU_KEYED_STRIPES_MAX != 0 ? 1u : 0u);
+	return l > 0 ? l : 1;
+}
+inline uint64_t keyed_stripes(uint64_t n_vectors) {
+	const uint64_t l = keyed_stripe_vectors(n_vectors);
+	return n_vectors / l + (n_vectors % l != 0 ? 1u : 0u);
+}
+int launch_keyed_sum(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const void* d_zones, const void* d_keys, uint32_t n_keys,
+                     double* d_sums, uint64_t* d_counts, void* d_scratch, int value_bytes, int n_cus, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
+
 // zone maps (include/alpgpu.h).  decode_kernels.hip / decode_f32_kernels.hip: d_zones[v] = {min, max} of vector v, decoded in registers by the
 // one-wavefront sink kernels (col->n_vectors > 0)
 int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones);

@@ -1,5 +1,5 @@
 // persistent_launch.hpp — the host's two launch rules of the persistent scan kernels (k_in_list, k_join_probe, k_histogram, k_distinct_insert,
-// k_quantile_wide), stated once: how many workgroups a launch has, and what of a sorted list a workgroup stages into LDS.  Pure functions of
+// k_quantile_wide and k_keyed_sum, which takes the grid rule only), stated once: how many workgroups a launch has, and what of a sorted list a workgroup stages into LDS.  Pure functions of
 // numbers and plain C++ without a HIP type, as decode_policy.hpp is: tests/cpp/persistent_launch_test.cpp holds them without a GPU.
 #pragma once
 #include <stddef.h>
@@ -12,7 +12,8 @@ constexpr uint32_t kTuningGridMax = 1u << 16; // of a tuning record's grid
 // The grid of a launch whose workgroups of `waves` wavefronts walk `vectors` vectors, one per wavefront and trip: a workgroup per `waves` vectors,
 // but no more than the device holds at once (n_cus * wg_per_cu; n_cus <= 0 counts as 1), since a workgroup sets its LDS up once and then stays.
 // resident_cap (0: none) may only lower what the device holds.  grid_override (0: none) is a tuning record's grid: it replaces the rule's,
-// clamped to override_max (a grid beyond the vectors: workgroups that find none).
+// clamped to override_max (a grid beyond the vectors: workgroups that find none).  (k_keyed_sum passes its STRIPES as `vectors`: a wavefront
+// takes a stripe of consecutive vectors per trip, so the units of work the rule counts are stripes there.)
 inline unsigned persistent_grid(uint64_t vectors, uint32_t waves, int n_cus, uint32_t wg_per_cu, uint64_t resident_cap = 0, uint32_t grid_override = 0,
                                 uint32_t override_max = kTuningGridMax) {
 	if (grid_override != 0u) { return grid_override < override_max ? grid_override : override_max; }

@@ -2,8 +2,8 @@
 // share.  Every kernel of the selection family decodes through it: k_select (select_device.hpp: range selection, bitmaps, masked SUM and
 // projection), k_pair (pair_device.hpp), k_group (group_device.hpp), k_minmax_masked and k_group_minmax (minmax_device.hpp), k_in_list
 // (in_list_kernels.hip), k_join_probe (join_kernels.hip), k_top_k_candidates (top_k_device.hpp), k_quantile_wide (quantile_device.hpp),
-// k_histogram (histogram_kernels.hip) and k_distinct_insert (distinct_kernels.hip).  A clamp or a layout rule of the decode is stated here and
-// nowhere else; what the five persistent kernels among them share around it is stated once in persistent_scan.hpp (the selected bits, the
+// k_histogram (histogram_kernels.hip), k_distinct_insert (distinct_kernels.hip) and k_keyed_sum (keyed_kernels.hip).  A clamp or a layout rule of the
+// decode is stated here and nowhere else; what the six persistent kernels among them share around it is stated once in persistent_scan.hpp (the selected bits, the
 // constant-vector shortcut, the bin flush), sorted_list.hpp (a sorted list in LDS and its search) and persistent_launch.hpp (the host's grid and
 // staging rules).
 //
@@ -20,8 +20,8 @@
 //
 // A kernel: DecodeVec (decode_vec_load), the exception mask (exception_mask, exception_masks), then per batch of NB steps step_request followed by
 // step_bits / step_value of each step.  k_select takes 8 steps of one vector to a batch (kSelBatch), the others kStepBatch = 4 (of one vector or of
-// two side by side: as many vector loads in flight).  Every one of them but k_in_list, k_join_probe, k_quantile_wide, k_histogram and
-// k_distinct_insert, which are persistent (their grid: persistent_launch.hpp), is launched by launch_vectors below.
+// two side by side: as many vector loads in flight).  Every one of them but k_in_list, k_join_probe, k_quantile_wide, k_histogram,
+// k_distinct_insert and k_keyed_sum, which are persistent (their grid: persistent_launch.hpp), is launched by launch_vectors below.
 #pragma once
 #include <type_traits>
 

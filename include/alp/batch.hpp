@@ -871,6 +871,52 @@ struct column {
 		check(alpgpu_memcpy_d2h(context(), counts.data(), d_counts, counts.size() * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
 		return counts;
 	}
+	// Keyed aggregation (include/alpgpu.h, "keyed aggregation"): SUM and COUNT of this column (blob val) per key of a key column of the same type and
+	// length (blob key; the same blob is allowed), over the rows whose bit is set in the mask (nullptr: all of them), in one pass over the two columns
+	// (alpgpu_decode_keyed_sum_*).  keys: 1 .. ALPGPU_KEYED_KEYS_MAX keys, sorted here, on the host (NaNs last, where they match nothing); keys, sums
+	// and counts come back in that order.  A row belongs to the first key equal to its value of the key column (-0.0 == 0.0); later duplicates get
+	// +0.0 and 0; unmatched counts the selected rows without a key.  The sums are in the order include/alpgpu.h documents: the same blobs, mask and
+	// keys give the same bits every time.  zones (optional): any records that contain the KEY vectors' intervals; they change no bit.
+	struct keyed_result {
+		std::vector<PT>       keys;
+		std::vector<double>   sums;
+		std::vector<uint64_t> counts;
+		uint64_t              unmatched = 0;
+	};
+	static keyed_result sum_by_key(const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>* mask, const std::vector<zone>* zones,
+	                               const PT* keys, size_t n_keys) {
+		static_assert(sizeof(PT) == 8, "alp::gpu::column::sum_by_key is built for double columns only (include/alpgpu.h, \"keyed aggregation\")");
+		if (!keys || n_keys == 0 || n_keys > ALPGPU_KEYED_KEYS_MAX) { throw std::runtime_error("alp::gpu::column::sum_by_key: 1 .. ALPGPU_KEYED_KEYS_MAX keys"); }
+		uploaded_column val(blob_val, size_val, "alp::gpu::column::sum_by_key"), key(blob_key, size_key, "alp::gpu::column::sum_by_key");
+		const uint64_t  nv = val.col.n_vectors;
+		if (key.col.n_vectors != nv) { throw std::runtime_error("alp::gpu::column::sum_by_key: the columns differ in length"); }
+		if (mask && mask->size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::sum_by_key: the mask must hold 16 words per vector"); }
+		if (zones && zones->size() != nv) { throw std::runtime_error("alp::gpu::column::sum_by_key: one record per vector"); }
+		keyed_result out;
+		out.keys.assign(keys, keys + n_keys);
+		std::sort(out.keys.begin(), out.keys.end(), [](PT a, PT b) { return b != b ? a == a : a < b; }); // ascending by <, NaNs last
+		out.sums.assign(n_keys, 0.0);
+		out.counts.assign(n_keys, 0);
+		if (nv == 0) { return out; }
+		uint64_t* d_mask    = mask ? static_cast<uint64_t*>(val.get(mask->size() * sizeof(uint64_t))) : nullptr;
+		zone*     d_zones   = zones ? static_cast<zone*>(val.get(nv * sizeof(zone))) : nullptr;
+		PT*       d_keys    = static_cast<PT*>(val.get(n_keys * sizeof(PT)));
+		double*   d_sums    = static_cast<double*>(val.get(n_keys * sizeof(double)));
+		uint64_t* d_counts  = static_cast<uint64_t*>(val.get((n_keys + 1) * sizeof(uint64_t)));
+		void*     d_scratch = val.get(alpgpu_keyed_sum_scratch_bytes(nv, static_cast<uint32_t>(n_keys)));
+		if (mask) { check(alpgpu_memcpy_h2d(context(), d_mask, mask->data(), mask->size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d"); }
+		if (zones) { check(alpgpu_memcpy_h2d(context(), d_zones, zones->data(), nv * sizeof(zone)), "alpgpu_memcpy_h2d"); }
+		check(alpgpu_memcpy_h2d(context(), d_keys, out.keys.data(), n_keys * sizeof(PT)), "alpgpu_memcpy_h2d");
+		check(alpgpu_decode_keyed_sum_f64(context(), &val.col, &key.col, d_mask, reinterpret_cast<const alpgpu_zone_f64*>(d_zones), reinterpret_cast<const double*>(d_keys),
+		                                  static_cast<uint32_t>(n_keys), d_sums, d_counts, d_scratch),
+		      "alpgpu_decode_keyed_sum_f64");
+		std::vector<uint64_t> counts(n_keys + 1);
+		check(alpgpu_memcpy_d2h(context(), out.sums.data(), d_sums, n_keys * sizeof(double)), "alpgpu_memcpy_d2h");
+		check(alpgpu_memcpy_d2h(context(), counts.data(), d_counts, counts.size() * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
+		out.counts.assign(counts.begin(), counts.end() - 1);
+		out.unmatched = counts.back();
+		return out;
+	}
 	// Distinct values (include/alpgpu.h, "distinct values"): the distinct values, ascending, of the values [0, n_values) whose bit is set in the mask
 	// (nullptr: all of them) and how often each occurs.  -0.0 == 0.0, one value, reported as +0.0; +-inf are ordinary; NaNs are no values and are only
 	// counted (nans).  numbers = the selected values that are no NaNs: the sum of counts unless overflow.  overflow: there are more than `capacity`

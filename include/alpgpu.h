@@ -1148,6 +1148,88 @@ int alpgpu_debug_distinct_f64(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_
 int alpgpu_debug_distinct_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t first, uint64_t n, const uint64_t* d_mask, const alpgpu_zone_f32* d_zones, uint64_t capacity,
                               float* d_vals, uint64_t* d_counts, uint64_t* d_state, void* d_scratch, const alpgpu_distinct_tuning* tuning, uint64_t* d_trace);
 
+/* ---- keyed aggregation ----------------------------------------------------------------------------------------------------------------------------
+ * SELECT key, SUM(x), COUNT(*) ... WHERE ... GROUP BY key for up to 1024 discrete keys known in advance (alpgpu_distinct_* hands them over sorted),
+ * in ONE pass that decodes both columns in registers, no decoded value reaching HBM.  alpgpu_decode_group_sum_* stays the call for up to 16 RANGE
+ * groups with per-vector rows; alpgpu_histogram_* with point buckets is the COUNT(*) alone.
+ *   alpgpu_decode_keyed_sum_*   (built for double columns: _f64.)  val and key: two columns of the entry point's type with equal n_vectors; val == key is allowed.  Take every row r
+ *                               whose bit is set in the bitmap (d_mask == NULL: every row).  x_r and k_r are, bit for bit, what alpgpu_decode_* writes
+ *                               at r for val and for key, exceptions patched in; a float x_r is widened to double first (exactly).
+ *                               d_keys: n_keys elements of the key column's type in DEVICE memory, aligned to the element, sorted as numpy.sort
+ *                               sorts, read when the kernel runs (a captured graph sees the keys' contents at replay; n_keys and the pointers are
+ *                               fixed at capture), as alpgpu_select_in_mask_* reads its list.  n_keys is 1 .. ALPGPU_KEYED_KEYS_MAX: the keys and
+ *                               every wavefront's private table of them sit in LDS; more keys means calling again with the next 1024.
+ *                               The match.  Row r belongs to key i if i is the FIRST position with d_keys[i] == k_r: the lower bound of
+ *                               alpgpu_select_in_mask_* and one C ==.  -0.0 matches +0.0; a NaN k_r matches nothing and a NaN in d_keys (sorted
+ *                               last) is never matched; later duplicates in d_keys receive +0.0 and 0.  A selected row that matches no key is
+ *                               counted in d_counts[n_keys].
+ *                               d_counts (may be NULL): n_keys + 1 words of 8 bytes, exact integers.  With sorted keys and records that do not lie,
+ *                               the sum of all n_keys + 1 words is the number of selected rows.
+ *                               d_sums: n_keys doubles, in THIS order and no other.  Let L = alpgpu_keyed_stripe_vectors(n_vectors); stripe s is
+ *                               the vectors [s L, min((s + 1) L, n_vectors)), S = ceil(n_vectors / L) of them.  For key i, vector v and step
+ *                               m = 0..15, P(i, v, m) is the adjacent-lane tree of alpgpu_decode_sum_* over 64 lanes — (0,1), (2,3), ...; six
+ *                               levels — where lane l holds x at row 1024 v + 64 m + l if that row is selected and belongs to key i, else +0.0.
+ *                               The stripe's partial A(i, s) starts at +0.0 and takes += P(i, v, m) for v ascending within the stripe and, within
+ *                               a vector, m ascending.  (A step in which no lane belongs to i may be left out: adding +0.0 changes no accumulator
+ *                               that began at +0.0, whose sums are never -0.0.)  d_sums[i] is, bit for bit, alpgpu_tree_sum_f64 over
+ *                               A(i, 0 .. S).  A selected NaN in val makes its key's sum a NaN of unspecified payload.  Neither the grid, nor the
+ *                               device's CU count, nor the order in which wavefronts arrive enters the result: a stripe's partial is the work
+ *                               of one wavefront, whichever takes it.  (tests/keyed_replica.py holds the host replica.)
+ *                               d_mask (may be NULL): a selection bitmap of n_vectors * 16 words, 8-byte aligned, read and never written.  A vector
+ *                               whose 16 words are zero costs its 128 bytes and nothing of either column.
+ *                               d_key_zones (may be NULL; aligned to its records): any zone map whose records CONTAIN the true intervals of the
+ *                               KEY vectors' selected values (alpgpu_histogram_*'s rule).  A record narrows its vector's search to the keys it
+ *                               admits; a vector whose record admits no key is rows without a key, and neither column is read.  A record with
+ *                               min == max (neither a NaN) on a key vector whose descriptor says ALP without exceptions settles the key of every
+ *                               selected row: the key vector's packed words are not requested, only the value vector is decoded.  A record with a
+ *                               NaN bound prunes nothing.  Truthful records change no bit.  Records that do not contain the truth, or keys that
+ *                               are not sorted, give unspecified sums and counts; the sum of the n_keys + 1 counts is still the number of selected
+ *                               rows, and nothing is read outside d_keys[0 .. n_keys) or the columns nor written outside the outputs: every probe
+ *                               index is clamped.
+ *                               d_scratch: alpgpu_keyed_sum_scratch_bytes(n_vectors, n_keys) bytes, 16-byte aligned, contents irrelevant before
+ *                               and unspecified after: 64 bytes of header (the stripe ticket) and the stripe partials, S rows of n_keys doubles.
+ *                               Cost: an init kernel (the counts and the ticket zeroed; not a memset node: DESIGN.md, "Histograms"), one launch of
+ *                               persistent workgroups sized to the device, whose wavefronts take stripes by an integer ticket and keep a private
+ *                               table of n_keys doubles and 32-bit counts in LDS (two capacity tiers: up to 256 keys and up to 1024), and a
+ *                               reduce of one small workgroup per key.  A value costs ceil(log2(n_keys + 1)) LDS probes; a step of 64 rows that
+ *                               agree on their key costs one tree and one LDS add, a row alone with its key in its step one LDS add.
+ *                               n_vectors == 0: every sum is +0.0 and every count 0, written by a kernel; neither column is read.
+ *                               ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx, val, key, d_keys, d_sums or d_scratch; n_keys outside
+ *                               1 .. ALPGPU_KEYED_KEYS_MAX; columns that differ in n_vectors; n_vectors > 2^32 - 1; d_scratch not 16-byte aligned;
+ *                               d_sums, d_counts, d_mask or d_trace not 8-byte aligned; d_keys not aligned to its elements, d_key_zones not aligned
+ *                               to its records; with n_vectors > 0, a column without descriptors.
+ *   alpgpu_keyed_stripe_vectors L = max(1, ceil(n_vectors / ALPGPU_KEYED_STRIPES_MAX)); host only.
+ *   alpgpu_keyed_sum_scratch_bytes   64 + 8 * n_keys * min(n_vectors, ALPGPU_KEYED_STRIPES_MAX), rounded up to a multiple of 16: never less than the S
+ *                               rows need, monotone in both arguments, at most 64 + 8 * n_keys * 4096; UINT64_MAX for n_keys outside 1 .. ALPGPU_KEYED_KEYS_MAX.
+ * The call runs on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no state kept; none of what
+ *   the context remembers about columns (the decode plans) is read or written; safe inside a stream capture.  No floating-point atomics; integer
+ *   atomics for the counts and the ticket only; no workgroup waits for another.
+ * Not built: MIN / MAX per key, more than 1024 keys per call, range groups (alpgpu_decode_group_sum_*), multi-column keys, keys not known in advance
+ *   (alpgpu_distinct_* first).
+ * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector). */
+#define ALPGPU_KEYED_KEYS_MAX    1024u
+#define ALPGPU_KEYED_STRIPES_MAX 4096u
+uint64_t alpgpu_keyed_stripe_vectors(uint64_t n_vectors);
+uint64_t alpgpu_keyed_sum_scratch_bytes(uint64_t n_vectors, uint32_t n_keys);
+int alpgpu_decode_keyed_sum_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones, const double* d_keys,
+                                uint32_t n_keys, double* d_sums, uint64_t* d_counts, void* d_scratch);
+/* (alpgpu_decode_keyed_sum_f32 is NOT built yet: double columns only.  The kernels are templates over the value width, but the float
+ * instantiations have not been run on a 1 Mi-vector column and are left out until they have; DESIGN.md, "Keyed aggregation".) */
+/* debug / test: alpgpu_decode_keyed_sum_* with a tuning record and a trace.  A 0 field means the default.  grid: the workgroups launched (default
+ * min(ceil(S / wavefronts per workgroup), what the device holds); more than there is work for is allowed, at most 65536).  No tuning changes a bit.
+ * d_trace (may be NULL): 4 words of device memory that the call ADDS to, each wavefront once per word at its end: vectors
+ *   [0] settled without either column (their bitmap words are all zero),
+ *   [1] settled by the constant-key shortcut (the key vector's packed words not requested),
+ *   [2] whose zone record admits no key (rows without a key; neither column read),
+ *   [3] decoded, both columns. */
+typedef struct alpgpu_keyed_tuning {
+    uint32_t grid;
+    uint32_t reserved;
+} alpgpu_keyed_tuning;
+int alpgpu_debug_decode_keyed_sum_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
+                                      const double* d_keys, uint32_t n_keys, double* d_sums, uint64_t* d_counts, void* d_scratch, const alpgpu_keyed_tuning* tuning,
+                                      uint64_t* d_trace);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
