@@ -221,6 +221,13 @@ inline uint64_t keyed_stripes(uint64_t n_vectors) {
 int launch_keyed_sum(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const void* d_zones, const void* d_keys, uint32_t n_keys,
                      double* d_sums, uint64_t* d_counts, void* d_scratch, int value_bytes, int n_cus, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
 
+// keyed_minmax_kernels.hip: the record {min, max} and the COUNT per key of a sorted key list.  launch_keyed_minmax_init: {+inf, -inf} into the n_keys
+// records of d_out and 0 into the n_keys + 1 words of d_counts (nullable), by a kernel.  launch_keyed_minmax: launch_keyed_sum's arguments without a
+// scratch, d_out n_keys records of the columns' type (value_bytes 8 or 4); the init kernel and one launch of persistent workgroups, two per CU.
+int launch_keyed_minmax_init(hipStream_t stream, void* d_out, uint64_t* d_counts, uint32_t n_keys, int value_bytes);
+int launch_keyed_minmax(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const void* d_zones, const void* d_keys, uint32_t n_keys,
+                        void* d_out, uint64_t* d_counts, int value_bytes, int n_cus, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
+
 // zone maps (include/alpgpu.h).  decode_kernels.hip / decode_f32_kernels.hip: d_zones[v] = {min, max} of vector v, decoded in registers by the
 // one-wavefront sink kernels (col->n_vectors > 0)
 int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones);

@@ -1,5 +1,5 @@
 // persistent_launch.hpp — the host's two launch rules of the persistent scan kernels (k_in_list, k_join_probe, k_histogram, k_distinct_insert,
-// k_quantile_wide and k_keyed_sum, which takes the grid rule only), stated once: how many workgroups a launch has, and what of a sorted list a workgroup stages into LDS.  Pure functions of
+// k_quantile_wide, and k_keyed_sum and k_keyed_minmax, which take the grid rule only), stated once: how many workgroups a launch has, and what of a sorted list a workgroup stages into LDS.  Pure functions of
 // numbers and plain C++ without a HIP type, as decode_policy.hpp is: tests/cpp/persistent_launch_test.cpp holds them without a GPU.
 #pragma once
 #include <stddef.h>

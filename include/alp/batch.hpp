@@ -17,6 +17,7 @@
 #define ALP_BATCH_HPP
 #include <algorithm>
 #include <cstring>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -912,6 +913,55 @@ struct column {
 		      "alpgpu_decode_keyed_sum_f64");
 		std::vector<uint64_t> counts(n_keys + 1);
 		check(alpgpu_memcpy_d2h(context(), out.sums.data(), d_sums, n_keys * sizeof(double)), "alpgpu_memcpy_d2h");
+		check(alpgpu_memcpy_d2h(context(), counts.data(), d_counts, counts.size() * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
+		out.counts.assign(counts.begin(), counts.end() - 1);
+		out.unmatched = counts.back();
+		return out;
+	}
+	// Keyed MIN / MAX (include/alpgpu.h, "keyed MIN / MAX"): the record {min, max} and the COUNT of this column (blob val) per key, with sum_by_key's
+	// arguments and key handling, for double and float columns (alpgpu_decode_keyed_minmax_*).  keys, records and counts come back in the order of
+	// the sorted keys.  A record ignores NaN values (they are counted), orders -0.0 below +0.0 and is {+inf, -inf} for a key without a number and
+	// for every later duplicate.  zones (optional): any records that contain the KEY vectors' intervals; they change no byte.
+	struct keyed_minmax_result {
+		std::vector<PT>       keys;
+		std::vector<zone>     records;
+		std::vector<uint64_t> counts;
+		uint64_t              unmatched = 0;
+	};
+	static keyed_minmax_result minmax_by_key(const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>* mask,
+	                                         const std::vector<zone>* zones, const PT* keys, size_t n_keys) {
+		if (!keys || n_keys == 0 || n_keys > ALPGPU_KEYED_KEYS_MAX) { throw std::runtime_error("alp::gpu::column::minmax_by_key: 1 .. ALPGPU_KEYED_KEYS_MAX keys"); }
+		uploaded_column val(blob_val, size_val, "alp::gpu::column::minmax_by_key"), key(blob_key, size_key, "alp::gpu::column::minmax_by_key");
+		const uint64_t  nv = val.col.n_vectors;
+		if (key.col.n_vectors != nv) { throw std::runtime_error("alp::gpu::column::minmax_by_key: the columns differ in length"); }
+		if (mask && mask->size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::minmax_by_key: the mask must hold 16 words per vector"); }
+		if (zones && zones->size() != nv) { throw std::runtime_error("alp::gpu::column::minmax_by_key: one record per vector"); }
+		keyed_minmax_result out;
+		out.keys.assign(keys, keys + n_keys);
+		std::sort(out.keys.begin(), out.keys.end(), [](PT a, PT b) { return b != b ? a == a : a < b; }); // ascending by <, NaNs last
+		zone none;
+		none.min = std::numeric_limits<PT>::infinity();
+		none.max = -std::numeric_limits<PT>::infinity();
+		out.records.assign(n_keys, none);
+		out.counts.assign(n_keys, 0);
+		if (nv == 0) { return out; }
+		uint64_t* d_mask   = mask ? static_cast<uint64_t*>(val.get(mask->size() * sizeof(uint64_t))) : nullptr;
+		zone*     d_zones  = zones ? static_cast<zone*>(val.get(nv * sizeof(zone))) : nullptr;
+		PT*       d_keys   = static_cast<PT*>(val.get(n_keys * sizeof(PT)));
+		zone*     d_out    = static_cast<zone*>(val.get(n_keys * sizeof(zone)));
+		uint64_t* d_counts = static_cast<uint64_t*>(val.get((n_keys + 1) * sizeof(uint64_t)));
+		if (mask) { check(alpgpu_memcpy_h2d(context(), d_mask, mask->data(), mask->size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d"); }
+		if (zones) { check(alpgpu_memcpy_h2d(context(), d_zones, zones->data(), nv * sizeof(zone)), "alpgpu_memcpy_h2d"); }
+		check(alpgpu_memcpy_h2d(context(), d_keys, out.keys.data(), n_keys * sizeof(PT)), "alpgpu_memcpy_h2d");
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_decode_keyed_minmax_f64(context(), &val.col, &key.col, d_mask, d_zones, reinterpret_cast<const double*>(d_keys), static_cast<uint32_t>(n_keys), d_out, d_counts),
+			      "alpgpu_decode_keyed_minmax_f64");
+		} else {
+			check(alpgpu_decode_keyed_minmax_f32(context(), &val.col, &key.col, d_mask, d_zones, reinterpret_cast<const float*>(d_keys), static_cast<uint32_t>(n_keys), d_out, d_counts),
+			      "alpgpu_decode_keyed_minmax_f32");
+		}
+		std::vector<uint64_t> counts(n_keys + 1);
+		check(alpgpu_memcpy_d2h(context(), out.records.data(), d_out, n_keys * sizeof(zone)), "alpgpu_memcpy_d2h");
 		check(alpgpu_memcpy_d2h(context(), counts.data(), d_counts, counts.size() * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
 		out.counts.assign(counts.begin(), counts.end() - 1);
 		out.unmatched = counts.back();

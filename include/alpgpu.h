@@ -1204,7 +1204,7 @@ int alpgpu_debug_distinct_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_
  * The call runs on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no state kept; none of what
  *   the context remembers about columns (the decode plans) is read or written; safe inside a stream capture.  No floating-point atomics; integer
  *   atomics for the counts and the ticket only; no workgroup waits for another.
- * Not built: MIN / MAX per key, more than 1024 keys per call, range groups (alpgpu_decode_group_sum_*), multi-column keys, keys not known in advance
+ * Not built: more than 1024 keys per call, range groups (alpgpu_decode_group_sum_*), multi-column keys, keys not known in advance
  *   (alpgpu_distinct_* first).
  * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector). */
 #define ALPGPU_KEYED_KEYS_MAX    1024u
@@ -1229,6 +1229,53 @@ typedef struct alpgpu_keyed_tuning {
 int alpgpu_debug_decode_keyed_sum_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
                                       const double* d_keys, uint32_t n_keys, double* d_sums, uint64_t* d_counts, void* d_scratch, const alpgpu_keyed_tuning* tuning,
                                       uint64_t* d_trace);
+
+/* ---- keyed MIN / MAX ------------------------------------------------------------------------------------------------------------------------------
+ * SELECT key, MIN(x), MAX(x), COUNT(*) ... WHERE ... GROUP BY key for up to 1024 discrete keys known in advance, in ONE pass that decodes both
+ * columns in registers.  Built for double and float columns.
+ *   alpgpu_decode_keyed_minmax_*   val, key (val == key allowed), d_mask, d_key_zones, d_keys and n_keys (1 .. ALPGPU_KEYED_KEYS_MAX) are
+ *                               alpgpu_decode_keyed_sum_*'s, word for word, and so is the match: row r belongs to key i if i is the FIRST position
+ *                               with d_keys[i] == k_r; -0.0 matches +0.0; a NaN k_r matches nothing and a NaN in d_keys is never matched; later
+ *                               duplicates in d_keys receive nothing.  The zone-record rules are the same too: a record narrows its vector's
+ *                               search; a record that admits no key means rows without a key, neither column read; min == max on a key vector
+ *                               that is ALP without exceptions settles the key of every selected row without the key vector's packed words.
+ *                               d_out: n_keys records {min, max} of the columns' type, aligned to the record (16 / 8 bytes).  Record i covers the
+ *                               selected rows of val that belong to key i, in alpgpu_decode_minmax_masked_*'s order: NaNs ignored, -0.0 < +0.0,
+ *                               +-inf ordinary values.  A key with no row, or whose rows hold only NaNs, and every later duplicate get
+ *                               {+inf, -inf}.
+ *                               d_counts (may be NULL): n_keys + 1 words of 8 bytes.  d_counts[i] counts every selected row of key i, NaN values
+ *                               included (as alpgpu_decode_group_minmax_* counts them); the last word the selected rows without a key.  They are
+ *                               alpgpu_decode_keyed_sum_*'s counts.
+ *                               The equivalence: record i of a key that is the first of its equals is, bit for bit, alpgpu_group_minmax_totals_*
+ *                               of row g of alpgpu_decode_group_minmax_* with lo[g] = hi[g] = d_keys[i] under the same bitmap.
+ *                               Minimum and maximum are exact and order-free: records and counts are a function of the inputs alone; neither
+ *                               the grid, nor the device's CU count, nor the order in which wavefronts arrive enters them.
+ *                               Truthful zone records change no byte.  Records that do not contain the truth, or keys that are not sorted, give
+ *                               unspecified records and counts; the sum of the n_keys + 1 counts is still the number of selected rows, and
+ *                               nothing is read outside d_keys[0 .. n_keys) or the columns nor written outside the outputs: every probe index
+ *                               is clamped.
+ *                               Cost: an init kernel ({+inf, -inf} and 0; not a memset node: DESIGN.md, "Histograms") and one launch of persistent
+ *                               workgroups sized to the device.  A workgroup keeps ONE table (mn, mx, 32-bit counts) and the keys in LDS, shared
+ *                               by its wavefronts and updated by LDS integer atomics on the value bits, and joins it into d_out / d_counts at its
+ *                               end by global integer atomics.  No scratch, no reduce kernel, no floating-point atomics.
+ *                               n_vectors == 0: every record is {+inf, -inf} and every count 0, written by a kernel; neither column is read.
+ *                               ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx, val, key, d_keys or d_out; n_keys outside
+ *                               1 .. ALPGPU_KEYED_KEYS_MAX; columns that differ in n_vectors; n_vectors > 2^32 - 1; d_counts, d_mask or d_trace
+ *                               not 8-byte aligned; d_out or d_key_zones not aligned to their records, d_keys not aligned to its elements; with
+ *                               n_vectors > 0, a column without descriptors.
+ * The call runs on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no state kept; safe inside a
+ *   stream capture (the keys and the bitmap are read at replay).  No workgroup waits for another.
+ * The debug entry takes alpgpu_keyed_tuning (grid) and adds to the four trace words of alpgpu_debug_decode_keyed_sum_*; no tuning changes a byte.
+ * Not built: more than 1024 keys per call, range groups (alpgpu_decode_group_minmax_*), multi-column keys, keys not known in advance.
+ * TRUST: as for alpgpu_select_range_*. */
+int alpgpu_decode_keyed_minmax_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
+                                   const double* d_keys, uint32_t n_keys, alpgpu_zone_f64* d_out, uint64_t* d_counts);
+int alpgpu_decode_keyed_minmax_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f32* d_key_zones,
+                                   const float* d_keys, uint32_t n_keys, alpgpu_zone_f32* d_out, uint64_t* d_counts);
+int alpgpu_debug_decode_keyed_minmax_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
+                                         const double* d_keys, uint32_t n_keys, alpgpu_zone_f64* d_out, uint64_t* d_counts, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
+int alpgpu_debug_decode_keyed_minmax_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f32* d_key_zones,
+                                         const float* d_keys, uint32_t n_keys, alpgpu_zone_f32* d_out, uint64_t* d_counts, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
 
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
