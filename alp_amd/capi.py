@@ -205,6 +205,10 @@ for _t in ("f64",):  # (double columns only: the float entry points are not buil
 for _t in ("f64", "f32"):  # keyed MIN / MAX: both precisions, no scratch
     _sig("alpgpu_decode_keyed_minmax_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp)
     _sig("alpgpu_debug_decode_keyed_minmax_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.POINTER(KeyedTuning), _vp)
+KEYED_MANY_KEYS_MAX = 1 << 20  # ALPGPU_KEYED_MANY_KEYS_MAX == ALPGPU_DISTINCT_MAX
+for _t in ("f64", "f32"):  # keyed MIN / MAX beyond KEYED_KEYS_MAX keys: the table in device memory
+    _sig("alpgpu_decode_keyed_minmax_many_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp)
+    _sig("alpgpu_debug_decode_keyed_minmax_many_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.POINTER(KeyedTuning), _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -1645,6 +1649,81 @@ class Context:
         out = torch.empty((lst.numel(), 2), dtype=tdt, device=dev)
         cnt = torch.empty(lst.numel() + 1, dtype=torch.int64, device=dev) if counts else None
         self.keyed_minmax_into(val, key, lst, out, counts_out=cnt, mask=mask, zones=zones)
+        return out, (cnt[:-1] if counts else None), (cnt[-1] if counts else None)
+
+    # ---- keyed MIN / MAX, many keys (include/alpgpu.h: alpgpu_decode_keyed_minmax_many_*) -----------------------------
+    def keyed_minmax_many_into(self, val: "DeviceColumn", key: "DeviceColumn", keys, out, counts_out=None, mask=None, zones=None, tuning=None, trace=None):
+        """the raw form of alpgpu_decode_keyed_minmax_many_f64 / _f32: keyed_minmax_into's arguments, records and counts (the same bytes up to
+        KEYED_KEYS_MAX keys) with keys 1 .. KEYED_MANY_KEYS_MAX long: the keys beyond what LDS holds are searched through pivots, and the table is
+        out and counts_out themselves, updated by integer atomics in device memory.  counts_out=None issues no count atomic at all: the usual call
+        behind distinct(), whose counts on the same selection are these.  Nothing is synchronised, read back or allocated, so the call can be
+        captured."""
+        import torch
+        self._check_pair(val, key)
+        tdt = torch.float64 if val.dtype == "f64" else torch.float32
+        if not isinstance(keys, torch.Tensor) or keys.dtype != tdt:
+            raise ValueError("keys must be a tensor of the columns' type (%s)" % val.dtype)
+        if keys.dim() != 1 or not 1 <= keys.numel() <= KEYED_MANY_KEYS_MAX:
+            raise ValueError("keys must be one-dimensional and hold 1 .. %d keys" % KEYED_MANY_KEYS_MAX)
+        if not keys.is_cuda or keys.device.index != self.device or not keys.is_contiguous():
+            raise ValueError("keys must be contiguous on cuda:%d" % self.device)
+        n_keys = keys.numel()
+        self._check_tensor(out, tdt, "out")
+        if out.dim() != 2 or tuple(out.shape) != (n_keys, 2) or out.data_ptr() % (2 * out.element_size()):
+            raise ValueError("out must be a [len(keys), 2] tensor of the columns' type, aligned to its records")
+        if counts_out is not None:
+            self._check_tensor(counts_out, torch.int64, "counts_out")
+            if counts_out.dim() != 1 or counts_out.numel() != n_keys + 1:
+                raise ValueError("counts_out must be a one-dimensional int64 tensor of len(keys) + 1 words")
+        if mask is not None:
+            self._check_mask(mask, val.n_vectors)
+        if zones is not None:
+            self._check_zones(zones, tdt, key.n_vectors)
+        if trace is not None:
+            self._check_tensor(trace, torch.int64, "trace")
+            if trace.numel() != 4:
+                raise ValueError("trace must hold 4 int64 words")
+        args = [C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
+                _vp(keys.data_ptr()), n_keys, _vp(out.data_ptr()), _vp(counts_out.data_ptr()) if counts_out is not None else None]
+        if tuning is None and trace is None:
+            self._call("decode_keyed_minmax_many", val.dtype, *args)
+        else:
+            tuning = {} if tuning is None else tuning
+            if set(tuning) - {"grid"}:
+                raise ValueError("tuning takes grid")
+            t = KeyedTuning(int(tuning.get("grid", 0)), 0)
+            self._call("debug_decode_keyed_minmax_many", val.dtype, *args, C.byref(t), _vp(trace.data_ptr()) if trace is not None else None)
+
+    def keyed_minmax_many(self, val: "DeviceColumn", key: "DeviceColumn", keys, mask=None, zones=None, counts: bool = True):
+        """MIN(val), MAX(val), COUNT(*) GROUP BY key for up to KEYED_MANY_KEYS_MAX keys in one pass over the two columns: keyed_minmax's argument
+        forms and result, ([K, 2] records {min, max} of the columns' type, int64[K] counts or None with counts=False, unmatched), in the order
+        of the SORTED keys (torch.sort on the device: NaNs last, where they match nothing).  counts=False keeps no counts at all, which is the
+        cheaper call where distinct() has already counted.  Nothing is synchronised (alpgpu_decode_keyed_minmax_many_f64 / _f32)."""
+        import torch
+        self._check_pair(val, key)
+        tdt, ndt = (torch.float64, np.float64) if val.dtype == "f64" else (torch.float32, np.float32)
+        dev = f"cuda:{self.device}"
+        if isinstance(keys, np.ndarray):
+            if keys.dtype != ndt:
+                raise ValueError("keys must be of the columns' type (%s)" % val.dtype)
+            keys = torch.from_numpy(np.ascontiguousarray(keys))
+        elif not isinstance(keys, torch.Tensor):
+            keys = torch.tensor(list(keys), dtype=tdt)
+        if keys.dtype != tdt:
+            raise ValueError("keys must be of the columns' type (%s)" % val.dtype)
+        if keys.dim() != 1 or not 1 <= keys.numel() <= KEYED_MANY_KEYS_MAX:
+            raise ValueError("keys must be one-dimensional and hold 1 .. %d keys" % KEYED_MANY_KEYS_MAX)
+        if keys.is_cuda and keys.device.index != self.device:
+            raise ValueError("keys must be on the host or on cuda:%d" % self.device)
+        if mask is not None:
+            self._check_mask(mask, val.n_vectors)
+        if zones is not None:
+            self._check_zones(zones, tdt, key.n_vectors)
+        lst = keys if keys.is_cuda else keys.to(dev)
+        lst = torch.sort(lst).values
+        out = torch.empty((lst.numel(), 2), dtype=tdt, device=dev)
+        cnt = torch.empty(lst.numel() + 1, dtype=torch.int64, device=dev) if counts else None
+        self.keyed_minmax_many_into(val, key, lst, out, counts_out=cnt, mask=mask, zones=zones)
         return out, (cnt[:-1] if counts else None), (cnt[-1] if counts else None)
 
     # ---- join probe (include/alpgpu.h: alpgpu_join_probe_*) -----------------------------------------------------------

@@ -228,6 +228,12 @@ int launch_keyed_minmax_init(hipStream_t stream, void* d_out, uint64_t* d_counts
 int launch_keyed_minmax(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const void* d_zones, const void* d_keys, uint32_t n_keys,
                         void* d_out, uint64_t* d_counts, int value_bytes, int n_cus, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
 
+// keyed_minmax_many_kernels.hip: the same records and counts for n_keys in 1 .. ALPGPU_KEYED_MANY_KEYS_MAX: launch_keyed_minmax's arguments; the keys
+// staged by list_staging's rule (persistent_launch.hpp), d_out and d_counts themselves the table.  launch_keyed_minmax_init and one launch of
+// persistent workgroups, two per CU.
+int launch_keyed_minmax_many(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const void* d_zones, const void* d_keys,
+                             uint32_t n_keys, void* d_out, uint64_t* d_counts, int value_bytes, int n_cus, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
+
 // zone maps (include/alpgpu.h).  decode_kernels.hip / decode_f32_kernels.hip: d_zones[v] = {min, max} of vector v, decoded in registers by the
 // one-wavefront sink kernels (col->n_vectors > 0)
 int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones);

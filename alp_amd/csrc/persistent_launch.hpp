@@ -1,5 +1,5 @@
 // persistent_launch.hpp — the host's two launch rules of the persistent scan kernels (k_in_list, k_join_probe, k_histogram, k_distinct_insert,
-// k_quantile_wide, and k_keyed_sum and k_keyed_minmax, which take the grid rule only), stated once: how many workgroups a launch has, and what of a sorted list a workgroup stages into LDS.  Pure functions of
+// k_quantile_wide, k_keyed_minmax_many, and k_keyed_sum and k_keyed_minmax, which take the grid rule only), stated once: how many workgroups a launch has, and what of a sorted list a workgroup stages into LDS.  Pure functions of
 // numbers and plain C++ without a HIP type, as decode_policy.hpp is: tests/cpp/persistent_launch_test.cpp holds them without a GPU.
 #pragma once
 #include <stddef.h>
@@ -23,7 +23,7 @@ inline unsigned persistent_grid(uint64_t vectors, uint32_t waves, int n_cus, uin
 	return static_cast<unsigned>(n_wg < resident ? n_wg : resident);
 }
 
-// The sorted list of k_in_list and k_join_probe (sorted_list.hpp) has 32 KiB of LDS per workgroup.  in_list_lds_max: the longest list that sits
+// The sorted list of k_in_list, k_join_probe and k_keyed_minmax_many (sorted_list.hpp) has 32 KiB of LDS per workgroup.  in_list_lds_max: the longest list that sits
 // there whole (value_bytes 8 or 4; else 0).  A longer one is staged as its pivots, every stride-th element: LDS word i = list[i * stride].
 constexpr uint32_t kInLdsBytes = 32768; // 4096 doubles or 8192 floats; with the exception masks 33 KiB, four workgroups per CU
 inline size_t in_list_lds_max(int value_bytes) { return value_bytes == 8 || value_bytes == 4 ? kInLdsBytes / static_cast<uint32_t>(value_bytes) : 0u; }

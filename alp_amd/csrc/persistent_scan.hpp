@@ -1,5 +1,5 @@
 // persistent_scan.hpp — the glue the persistent scan kernels share around the in-register decode of register_decode.hpp: k_in_list, k_join_probe,
-// k_histogram, k_distinct_insert, k_quantile_wide, k_keyed_sum and k_keyed_minmax.  Each is workgroups that set their LDS up once, pass one barrier and then walk vectors
+// k_histogram, k_distinct_insert, k_quantile_wide, k_keyed_sum, k_keyed_minmax and k_keyed_minmax_many.  Each is workgroups that set their LDS up once, pass one barrier and then walk vectors
 // v = wave id, wave id + waves, ... (k_keyed_sum: its wavefronts take stripes of consecutive vectors by a ticket and flush nothing: keyed_kernels.hip);
 // what two or more of them do in the same way is stated here once: a vector's selected bits under a range and a nullable
 // bitmap, the constant-vector shortcut's predicate and count, and the flush of 32-bit LDS bins into 64-bit global counts.  The sorted list in LDS

@@ -930,12 +930,26 @@ struct column {
 	};
 	static keyed_minmax_result minmax_by_key(const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>* mask,
 	                                         const std::vector<zone>* zones, const PT* keys, size_t n_keys) {
-		if (!keys || n_keys == 0 || n_keys > ALPGPU_KEYED_KEYS_MAX) { throw std::runtime_error("alp::gpu::column::minmax_by_key: 1 .. ALPGPU_KEYED_KEYS_MAX keys"); }
-		uploaded_column val(blob_val, size_val, "alp::gpu::column::minmax_by_key"), key(blob_key, size_key, "alp::gpu::column::minmax_by_key");
+		return keyed_minmax_call(false, blob_val, size_val, blob_key, size_key, mask, zones, keys, n_keys);
+	}
+	// Keyed MIN / MAX for up to ALPGPU_KEYED_MANY_KEYS_MAX = 2^20 keys (include/alpgpu.h, "keyed MIN / MAX, many keys": alpgpu_decode_keyed_minmax_many_*):
+	// minmax_by_key's arguments and result, the same bytes up to ALPGPU_KEYED_KEYS_MAX keys; the table sits in device memory, not in LDS.
+	static keyed_minmax_result minmax_by_key_many(const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>* mask,
+	                                              const std::vector<zone>* zones, const PT* keys, size_t n_keys) {
+		return keyed_minmax_call(true, blob_val, size_val, blob_key, size_key, mask, zones, keys, n_keys);
+	}
+	// what the two share: everything but the bound on n_keys and the entry point
+	static keyed_minmax_result keyed_minmax_call(bool many, const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>* mask,
+	                                             const std::vector<zone>* zones, const PT* keys, size_t n_keys) {
+		const std::string who = many ? "alp::gpu::column::minmax_by_key_many" : "alp::gpu::column::minmax_by_key";
+		if (!keys || n_keys == 0 || n_keys > (many ? ALPGPU_KEYED_MANY_KEYS_MAX : ALPGPU_KEYED_KEYS_MAX)) {
+			throw std::runtime_error(who + (many ? ": 1 .. ALPGPU_KEYED_MANY_KEYS_MAX keys" : ": 1 .. ALPGPU_KEYED_KEYS_MAX keys"));
+		}
+		uploaded_column val(blob_val, size_val, who.c_str()), key(blob_key, size_key, who.c_str());
 		const uint64_t  nv = val.col.n_vectors;
-		if (key.col.n_vectors != nv) { throw std::runtime_error("alp::gpu::column::minmax_by_key: the columns differ in length"); }
-		if (mask && mask->size() != 16 * nv) { throw std::runtime_error("alp::gpu::column::minmax_by_key: the mask must hold 16 words per vector"); }
-		if (zones && zones->size() != nv) { throw std::runtime_error("alp::gpu::column::minmax_by_key: one record per vector"); }
+		if (key.col.n_vectors != nv) { throw std::runtime_error(who + ": the columns differ in length"); }
+		if (mask && mask->size() != 16 * nv) { throw std::runtime_error(who + ": the mask must hold 16 words per vector"); }
+		if (zones && zones->size() != nv) { throw std::runtime_error(who + ": one record per vector"); }
 		keyed_minmax_result out;
 		out.keys.assign(keys, keys + n_keys);
 		std::sort(out.keys.begin(), out.keys.end(), [](PT a, PT b) { return b != b ? a == a : a < b; }); // ascending by <, NaNs last
@@ -953,12 +967,21 @@ struct column {
 		if (mask) { check(alpgpu_memcpy_h2d(context(), d_mask, mask->data(), mask->size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d"); }
 		if (zones) { check(alpgpu_memcpy_h2d(context(), d_zones, zones->data(), nv * sizeof(zone)), "alpgpu_memcpy_h2d"); }
 		check(alpgpu_memcpy_h2d(context(), d_keys, out.keys.data(), n_keys * sizeof(PT)), "alpgpu_memcpy_h2d");
+		const uint32_t nk = static_cast<uint32_t>(n_keys);
 		if constexpr (sizeof(PT) == 8) {
-			check(alpgpu_decode_keyed_minmax_f64(context(), &val.col, &key.col, d_mask, d_zones, reinterpret_cast<const double*>(d_keys), static_cast<uint32_t>(n_keys), d_out, d_counts),
-			      "alpgpu_decode_keyed_minmax_f64");
+			const double* dk = reinterpret_cast<const double*>(d_keys);
+			if (many) {
+				check(alpgpu_decode_keyed_minmax_many_f64(context(), &val.col, &key.col, d_mask, d_zones, dk, nk, d_out, d_counts), "alpgpu_decode_keyed_minmax_many_f64");
+			} else {
+				check(alpgpu_decode_keyed_minmax_f64(context(), &val.col, &key.col, d_mask, d_zones, dk, nk, d_out, d_counts), "alpgpu_decode_keyed_minmax_f64");
+			}
 		} else {
-			check(alpgpu_decode_keyed_minmax_f32(context(), &val.col, &key.col, d_mask, d_zones, reinterpret_cast<const float*>(d_keys), static_cast<uint32_t>(n_keys), d_out, d_counts),
-			      "alpgpu_decode_keyed_minmax_f32");
+			const float* dk = reinterpret_cast<const float*>(d_keys);
+			if (many) {
+				check(alpgpu_decode_keyed_minmax_many_f32(context(), &val.col, &key.col, d_mask, d_zones, dk, nk, d_out, d_counts), "alpgpu_decode_keyed_minmax_many_f32");
+			} else {
+				check(alpgpu_decode_keyed_minmax_f32(context(), &val.col, &key.col, d_mask, d_zones, dk, nk, d_out, d_counts), "alpgpu_decode_keyed_minmax_f32");
+			}
 		}
 		std::vector<uint64_t> counts(n_keys + 1);
 		check(alpgpu_memcpy_d2h(context(), out.records.data(), d_out, n_keys * sizeof(zone)), "alpgpu_memcpy_d2h");

@@ -1266,7 +1266,8 @@ int alpgpu_debug_decode_keyed_sum_f64(alpgpu_ctx* ctx, const alpgpu_column* val,
  * The call runs on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no state kept; safe inside a
  *   stream capture (the keys and the bitmap are read at replay).  No workgroup waits for another.
  * The debug entry takes alpgpu_keyed_tuning (grid) and adds to the four trace words of alpgpu_debug_decode_keyed_sum_*; no tuning changes a byte.
- * Not built: more than 1024 keys per call, range groups (alpgpu_decode_group_minmax_*), multi-column keys, keys not known in advance.
+ * More than 1024 keys per call: alpgpu_decode_keyed_minmax_many_* (below), up to 2^20.
+ * Not built: range groups (alpgpu_decode_group_minmax_*), multi-column keys, keys not known in advance.
  * TRUST: as for alpgpu_select_range_*. */
 int alpgpu_decode_keyed_minmax_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
                                    const double* d_keys, uint32_t n_keys, alpgpu_zone_f64* d_out, uint64_t* d_counts);
@@ -1276,6 +1277,72 @@ int alpgpu_debug_decode_keyed_minmax_f64(alpgpu_ctx* ctx, const alpgpu_column* v
                                          const double* d_keys, uint32_t n_keys, alpgpu_zone_f64* d_out, uint64_t* d_counts, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
 int alpgpu_debug_decode_keyed_minmax_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f32* d_key_zones,
                                          const float* d_keys, uint32_t n_keys, alpgpu_zone_f32* d_out, uint64_t* d_counts, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
+
+/* ---- keyed MIN / MAX, many keys -------------------------------------------------------------------------------------------------------------------
+ * SELECT key, MIN(x), MAX(x), COUNT(*) ... WHERE ... GROUP BY key for up to 2^20 discrete keys known in advance, in ONE pass that decodes both
+ * columns in registers: alpgpu_decode_keyed_minmax_* without its limit of 1024 keys, the table in device memory and not in LDS.  Built for double
+ * and float columns.  alpgpu_distinct_* hands over up to ALPGPU_DISTINCT_MAX sorted keys; on the same selection it hands over their counts as well,
+ * so d_counts == NULL is the usual call behind it.
+ *   alpgpu_decode_keyed_minmax_many_*   val and key: two columns of the entry point's type with equal n_vectors; val == key is allowed.  Take every
+ *                               row r whose bit is set in the bitmap (d_mask == NULL: every row).  x_r and k_r are, bit for bit, what
+ *                               alpgpu_decode_* writes at r for val and for key, exceptions patched in.
+ *                               d_keys: n_keys elements of the columns' type in DEVICE memory, aligned to the element, sorted as numpy.sort
+ *                               sorts, read when the kernel runs (a captured graph sees the keys' contents at replay; n_keys and the pointers
+ *                               are fixed at capture).  n_keys is 1 .. ALPGPU_KEYED_MANY_KEYS_MAX.
+ *                               The match.  Row r belongs to key i if i is the FIRST position with d_keys[i] == k_r: the lower bound of
+ *                               alpgpu_select_in_mask_* and one C ==.  -0.0 matches +0.0; a NaN k_r matches nothing and a NaN in d_keys (sorted
+ *                               last) is never matched; later duplicates in d_keys receive nothing.  A selected row that matches no key is
+ *                               counted in d_counts[n_keys].
+ *                               d_out: n_keys records {min, max} of the columns' type, aligned to the record (16 / 8 bytes).  Record i covers the
+ *                               selected rows of val that belong to key i, in alpgpu_decode_minmax_masked_*'s order: NaNs ignored, -0.0 < +0.0,
+ *                               +-inf ordinary values.  A key with no row, or whose rows hold only NaNs, and every later duplicate get
+ *                               {+inf, -inf}.
+ *                               d_counts (may be NULL): n_keys + 1 words of 8 bytes.  d_counts[i] counts every selected row of key i, NaN values
+ *                               included; the last word the selected rows without a key.  With d_counts == NULL no count is kept at all.
+ *                               For n_keys <= ALPGPU_KEYED_KEYS_MAX records and counts are, byte for byte, those of
+ *                               alpgpu_decode_keyed_minmax_* on the same arguments.
+ *                               Minimum and maximum are exact and order-free: records and counts are a function of the inputs alone; neither
+ *                               the grid, nor the device's CU count, nor the order in which wavefronts arrive enters them.
+ *                               d_mask (may be NULL): a selection bitmap of n_vectors * 16 words, 8-byte aligned, read and never written.  A vector
+ *                               whose 16 words are zero costs its 128 bytes and nothing of either column.
+ *                               d_key_zones (may be NULL; aligned to its records): any zone map whose records CONTAIN the true intervals of the
+ *                               KEY vectors' selected values.  A record narrows its vector's search to the keys it admits; a vector whose record
+ *                               admits no key is rows without a key, and neither column is read.  A record with min == max (neither a NaN) on a
+ *                               key vector whose descriptor says ALP without exceptions settles the key of every selected row: the key vector's
+ *                               packed words are not requested, only the value vector is decoded.  A record with a NaN bound prunes nothing.
+ *                               Truthful records change no byte.  Records that do not contain the truth, or keys that are not sorted, give
+ *                               unspecified records and counts; the sum of the n_keys + 1 counts is still the number of selected rows, and
+ *                               nothing is read outside d_keys[0 .. n_keys) or the columns nor written outside the outputs: every probe index
+ *                               is clamped.
+ *                               Cost: an init kernel ({+inf, -inf} and 0; not a memset node: DESIGN.md, "Histograms") and one launch of persistent
+ *                               workgroups sized to the device.  A workgroup stages the keys into 32 KiB of LDS: up to 4096 doubles / 8192 floats
+ *                               whole; of a longer list every stride-th key, and a value's search then ends in the list itself, between two of
+ *                               those, ceil(log2(stride)) reads that L2 serves.  The table is d_out and d_counts: a matched row reads its key's
+ *                               record and issues a global integer atomic on the value bits only where it improves on what it read; with
+ *                               d_counts it adds one 64-bit integer atomic per row (one per step of 64 rows that agree on their key).  No
+ *                               scratch, no reduce kernel, no floating-point atomics, no compare-and-swap loop.
+ *                               n_vectors == 0: every record is {+inf, -inf} and every count 0, written by a kernel; neither column is read.
+ *                               ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx, val, key, d_keys or d_out; n_keys outside
+ *                               1 .. ALPGPU_KEYED_MANY_KEYS_MAX; columns that differ in n_vectors; n_vectors > 2^32 - 1; d_counts, d_mask or
+ *                               d_trace not 8-byte aligned; d_out or d_key_zones not aligned to their records, d_keys not aligned to its
+ *                               elements; with n_vectors > 0, a column without descriptors.
+ * The call runs on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no state kept; safe inside a
+ *   stream capture (the keys and the bitmap are read at replay).  No workgroup waits for another.
+ * The debug entry takes alpgpu_keyed_tuning (grid) and adds to the four trace words of alpgpu_debug_decode_keyed_sum_*; no tuning changes a byte.
+ * Not built: more than 2^20 keys per call, a keyed SUM beyond 1024 keys, range groups (alpgpu_decode_group_minmax_*), multi-column keys, keys not
+ *   known in advance (alpgpu_distinct_* first).
+ * TRUST: as for alpgpu_select_range_*. */
+#define ALPGPU_KEYED_MANY_KEYS_MAX (1u << 20) /* == ALPGPU_DISTINCT_MAX */
+int alpgpu_decode_keyed_minmax_many_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
+                                        const double* d_keys, uint32_t n_keys, alpgpu_zone_f64* d_out, uint64_t* d_counts);
+int alpgpu_decode_keyed_minmax_many_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f32* d_key_zones,
+                                        const float* d_keys, uint32_t n_keys, alpgpu_zone_f32* d_out, uint64_t* d_counts);
+int alpgpu_debug_decode_keyed_minmax_many_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
+                                              const double* d_keys, uint32_t n_keys, alpgpu_zone_f64* d_out, uint64_t* d_counts, const alpgpu_keyed_tuning* tuning,
+                                              uint64_t* d_trace);
+int alpgpu_debug_decode_keyed_minmax_many_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f32* d_key_zones,
+                                              const float* d_keys, uint32_t n_keys, alpgpu_zone_f32* d_out, uint64_t* d_counts, const alpgpu_keyed_tuning* tuning,
+                                              uint64_t* d_trace);
 
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
