@@ -206,9 +206,16 @@ for _t in ("f64", "f32"):  # keyed MIN / MAX: both precisions, no scratch
     _sig("alpgpu_decode_keyed_minmax_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp)
     _sig("alpgpu_debug_decode_keyed_minmax_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.POINTER(KeyedTuning), _vp)
 KEYED_MANY_KEYS_MAX = 1 << 20  # ALPGPU_KEYED_MANY_KEYS_MAX == ALPGPU_DISTINCT_MAX
+BUCKET_EDGES_MAX = 1023  # ALPGPU_BUCKET_EDGES_MAX: n_edges + 1 buckets <= KEYED_KEYS_MAX table entries
 for _t in ("f64", "f32"):  # keyed MIN / MAX beyond KEYED_KEYS_MAX keys: the table in device memory
     _sig("alpgpu_decode_keyed_minmax_many_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp)
     _sig("alpgpu_debug_decode_keyed_minmax_many_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.POINTER(KeyedTuning), _vp)
+_sig("alpgpu_bucket_sum_scratch_bytes", _u64, _u64, C.c_uint32)
+for _t in ("f64", "f32"):  # bucketed aggregation: the key column's buckets by sorted edges; (ctx, val, key, mask, zones, edges, n_edges, right, ...)
+    _sig("alpgpu_decode_bucket_sum_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _int, _vp, _vp, _vp)
+    _sig("alpgpu_debug_decode_bucket_sum_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _int, _vp, _vp, _vp, C.POINTER(KeyedTuning), _vp)
+    _sig("alpgpu_decode_bucket_minmax_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _int, _vp, _vp)
+    _sig("alpgpu_debug_decode_bucket_minmax_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _int, _vp, _vp, C.POINTER(KeyedTuning), _vp)
 _sig("alpgpu_column_validate", _int, _vp, C.POINTER(CColumn), _int, C.POINTER(_u64))
 _sig("alpgpu_rowgroup_init_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
 _sig("alpgpu_encode_vectors_f64", _int, _vp, _vp, _u64, C.POINTER(CColumn))
@@ -1725,6 +1732,141 @@ class Context:
         cnt = torch.empty(lst.numel() + 1, dtype=torch.int64, device=dev) if counts else None
         self.keyed_minmax_many_into(val, key, lst, out, counts_out=cnt, mask=mask, zones=zones)
         return out, (cnt[:-1] if counts else None), (cnt[-1] if counts else None)
+
+    # ---- bucketed aggregation (include/alpgpu.h: alpgpu_decode_bucket_sum_* / alpgpu_decode_bucket_minmax_*) -----------
+    def bucket_sum_scratch(self, n_vectors: int, n_edges: int):
+        """a scratch tensor for bucket_sum_into (alpgpu_bucket_sum_scratch_bytes = keyed_sum_scratch's for n_edges + 1 keys)"""
+        import torch
+        n_vectors, n_edges = int(n_vectors), int(n_edges)
+        if n_vectors < 0 or not 0 <= n_edges <= BUCKET_EDGES_MAX:
+            raise ValueError("n_vectors must not be negative and n_edges must be in 0 .. %d" % BUCKET_EDGES_MAX)
+        return torch.empty(lib.alpgpu_bucket_sum_scratch_bytes(n_vectors, n_edges), dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    def _bucket_args(self, val, key, edges, counts_out, mask, zones, trace):
+        """what bucket_sum_into and bucket_minmax_into check alike; returns the columns' torch type"""
+        import torch
+        self._check_pair(val, key)
+        tdt = torch.float64 if val.dtype == "f64" else torch.float32
+        if not isinstance(edges, torch.Tensor) or edges.dtype != tdt:
+            raise ValueError("edges must be a tensor of the columns' type (%s)" % val.dtype)
+        if edges.dim() != 1 or edges.numel() > BUCKET_EDGES_MAX:
+            raise ValueError("edges must be one-dimensional and hold at most %d edges" % BUCKET_EDGES_MAX)
+        if not edges.is_cuda or edges.device.index != self.device or not edges.is_contiguous():
+            raise ValueError("edges must be contiguous on cuda:%d" % self.device)
+        if counts_out is not None:
+            self._check_tensor(counts_out, torch.int64, "counts_out")
+            if counts_out.dim() != 1 or counts_out.numel() != edges.numel() + 2:
+                raise ValueError("counts_out must be a one-dimensional int64 tensor of len(edges) + 2 words")
+        if mask is not None:
+            self._check_mask(mask, val.n_vectors)
+        if zones is not None:
+            self._check_zones(zones, tdt, key.n_vectors)
+        if trace is not None:
+            self._check_tensor(trace, torch.int64, "trace")
+            if trace.numel() != 4:
+                raise ValueError("trace must hold 4 int64 words")
+        return tdt
+
+    def _bucket_call(self, name, val, args, tuning, trace):
+        if tuning is None and trace is None:
+            self._call("decode_" + name, val.dtype, *args)
+        else:
+            tuning = {} if tuning is None else tuning
+            if set(tuning) - {"grid"}:
+                raise ValueError("tuning takes grid")
+            t = KeyedTuning(int(tuning.get("grid", 0)), 0)
+            self._call("debug_decode_" + name, val.dtype, *args, C.byref(t), _vp(trace.data_ptr()) if trace is not None else None)
+
+    def bucket_sum_into(self, val: "DeviceColumn", key: "DeviceColumn", edges, sums_out, counts_out=None, right: bool = False, mask=None, zones=None, scratch=None,
+                        tuning=None, trace=None):
+        """the raw form of alpgpu_decode_bucket_sum_f64 / _f32: sums_out (float64, exactly len(edges) + 1) takes, per bucket of the KEY column, the sum
+        of val over the rows whose bit is set in the mask (None: every row), in keyed_sum_into's documented order; counts_out (optional, int64,
+        exactly len(edges) + 2) what histogram_into writes for key: the buckets' rows and, last, the rows whose key is a NaN (they enter no sum).
+        Bucket b = the number of edges <= key (right: < key).  edges: a SORTED contiguous device tensor of the columns' type, 0 .. BUCKET_EDGES_MAX
+        long (NaNs last are inert, duplicates give empty buckets).  zones: any records that contain the KEY vectors' intervals: the same bits; a
+        vector whose record lies in one bucket is settled without its key values.  tuning: {"grid"}, trace: an int64 device tensor of 4 words that
+        is ADDED to (vectors settled without either column, by the one-bucket shortcut, always 0, decoded); either sends the call through the
+        debug entry (the same bits).  Nothing is synchronised or read back; with a scratch given (bucket_sum_scratch) nothing is allocated either,
+        so the call can be captured into a graph."""
+        import torch
+        self._bucket_args(val, key, edges, counts_out, mask, zones, trace)
+        n_edges = edges.numel()
+        self._check_tensor(sums_out, torch.float64, "sums_out")
+        if sums_out.dim() != 1 or sums_out.numel() != n_edges + 1:
+            raise ValueError("sums_out must be a one-dimensional float64 tensor of len(edges) + 1")
+        need = lib.alpgpu_bucket_sum_scratch_bytes(val.n_vectors, n_edges)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
+        else:
+            self._check_tensor(scratch, torch.uint8, "scratch")
+            if scratch.numel() < need or scratch.data_ptr() % 16:
+                raise ValueError("scratch must hold bucket_sum_scratch(n_vectors, n_edges) bytes, 16-byte aligned")
+        args = [C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
+                _vp(edges.data_ptr()) if n_edges else None, n_edges, 1 if right else 0, _vp(sums_out.data_ptr()), _vp(counts_out.data_ptr()) if counts_out is not None else None,
+                _vp(scratch.data_ptr())]
+        self._bucket_call("bucket_sum", val, args, tuning, trace)
+
+    def bucket_minmax_into(self, val: "DeviceColumn", key: "DeviceColumn", edges, out, counts_out=None, right: bool = False, mask=None, zones=None, tuning=None, trace=None):
+        """the raw form of alpgpu_decode_bucket_minmax_f64 / _f32: out ([len(edges) + 1, 2] of the columns' type) takes, per bucket of the KEY column,
+        the record {min, max} of val over the selected rows: NaN values ignored but counted, -0.0 < +0.0, {+inf, -inf} for a bucket without a
+        number; counts_out, right, edges, zones, tuning and trace are bucket_sum_into's.  counts_out=None keeps no count at all.  Nothing is
+        synchronised, read back or allocated, so the call can be captured."""
+        tdt = self._bucket_args(val, key, edges, counts_out, mask, zones, trace)
+        n_edges = edges.numel()
+        self._check_tensor(out, tdt, "out")
+        if out.dim() != 2 or tuple(out.shape) != (n_edges + 1, 2) or out.data_ptr() % (2 * out.element_size()):
+            raise ValueError("out must be a [len(edges) + 1, 2] tensor of the columns' type, aligned to its records")
+        args = [C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
+                _vp(edges.data_ptr()) if n_edges else None, n_edges, 1 if right else 0, _vp(out.data_ptr()), _vp(counts_out.data_ptr()) if counts_out is not None else None]
+        self._bucket_call("bucket_minmax", val, args, tuning, trace)
+
+    def _bucket_edges(self, val, edges, sorted_):
+        """the allocating wrappers' edges: any sequence of the columns' type onto the device and, unless sorted, into order (histogram's rule)"""
+        import torch
+        tdt, ndt = (torch.float64, np.float64) if val.dtype == "f64" else (torch.float32, np.float32)
+        if isinstance(edges, np.ndarray):
+            if edges.dtype != ndt:
+                raise ValueError("edges must be of the columns' type (%s)" % val.dtype)
+            edges = torch.from_numpy(np.ascontiguousarray(edges))
+        elif not isinstance(edges, torch.Tensor):
+            edges = torch.tensor(list(edges), dtype=tdt)
+        if edges.dtype != tdt:
+            raise ValueError("edges must be of the columns' type (%s)" % val.dtype)
+        if edges.dim() != 1 or edges.numel() > BUCKET_EDGES_MAX:
+            raise ValueError("edges must be one-dimensional and hold at most %d edges" % BUCKET_EDGES_MAX)
+        if edges.is_cuda and edges.device.index != self.device:
+            raise ValueError("edges must be on the host or on cuda:%d" % self.device)
+        lst = edges if edges.is_cuda else edges.to(f"cuda:{self.device}")
+        return lst.contiguous() if sorted_ else torch.sort(lst).values
+
+    def bucket_sum(self, val: "DeviceColumn", key: "DeviceColumn", edges, right: bool = False, mask=None, zones=None, counts: bool = True, sorted: bool = False):
+        """SUM(val), COUNT(*) GROUP BY bucket(key) in one pass over the two columns: (float64[B] sums, int64[B + 1] counts or None with
+        counts=False), B = len(edges) + 1 buckets, so len(edges) + 2 count words.  Bucket b holds the rows with b edges <= key (right: < key) — numpy.searchsorted(edges, key,
+        side="right") / side="left" —; counts are histogram(key, edges)'s words: counts[:B] the buckets' rows, counts[-1] the rows whose key is a NaN.  AVG is
+        sums / counts[:B].  edges: a device tensor, host tensor, sequence or numpy array of the columns' type, at most BUCKET_EDGES_MAX long,
+        brought into order by torch.sort on the device (NaNs sort last and are inert); sorted=True skips that.  zones (zone_map(key) or any
+        records that contain the key vectors' intervals): the same bits.  Nothing is synchronised (alpgpu_decode_bucket_sum_f64 / _f32)."""
+        import torch
+        self._check_pair(val, key)
+        lst = self._bucket_edges(val, edges, sorted)
+        dev = f"cuda:{self.device}"
+        sums = torch.empty(lst.numel() + 1, dtype=torch.float64, device=dev)
+        cnt = torch.empty(lst.numel() + 2, dtype=torch.int64, device=dev) if counts else None
+        self.bucket_sum_into(val, key, lst, sums, counts_out=cnt, right=right, mask=mask, zones=zones)
+        return sums, cnt
+
+    def bucket_minmax(self, val: "DeviceColumn", key: "DeviceColumn", edges, right: bool = False, mask=None, zones=None, counts: bool = True, sorted: bool = False):
+        """MIN(val), MAX(val), COUNT(*) GROUP BY bucket(key) in one pass over the two columns: ([B, 2] records {min, max} of the columns' type,
+        int64[B + 1] counts or None with counts=False), B = len(edges) + 1; bucket_sum's buckets, edges and counts.  NaN values are counted and
+        ignored; a bucket without a number gets {+inf, -inf}.  Nothing is synchronised (alpgpu_decode_bucket_minmax_f64 / _f32)."""
+        import torch
+        self._check_pair(val, key)
+        lst = self._bucket_edges(val, edges, sorted)
+        dev = f"cuda:{self.device}"
+        out = torch.empty((lst.numel() + 1, 2), dtype=lst.dtype, device=dev)
+        cnt = torch.empty(lst.numel() + 2, dtype=torch.int64, device=dev) if counts else None
+        self.bucket_minmax_into(val, key, lst, out, counts_out=cnt, right=right, mask=mask, zones=zones)
+        return out, cnt
 
     # ---- join probe (include/alpgpu.h: alpgpu_join_probe_*) -----------------------------------------------------------
     def join_probe_into(self, col: "DeviceColumn", keys, pos_out, count_out, mask=None, rows=None, span_out=None, idx_out=None, zones=None, scratch=None):

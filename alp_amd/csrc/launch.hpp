@@ -234,6 +234,14 @@ int launch_keyed_minmax(hipStream_t stream, const alpgpu_column* val, const alpg
 int launch_keyed_minmax_many(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const void* d_zones, const void* d_keys,
                              uint32_t n_keys, void* d_out, uint64_t* d_counts, int value_bytes, int n_cus, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
 
+// bucket_kernels.hip: SUM, the record {min, max} and the COUNT per bucket of the key column by n_edges (0 .. ALPGPU_BUCKET_EDGES_MAX) sorted edges:
+// launch_keyed_sum's / launch_keyed_minmax's arguments with d_edges (nullable with n_edges == 0) and `right` in place of the keys, n_edges + 1 sums or
+// records, d_counts n_edges + 2 words, d_scratch 64 bytes of header and S rows of n_edges + 1 doubles; value_bytes 8 or 4 for both.
+int launch_bucket_sum(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const void* d_zones, const void* d_edges, uint32_t n_edges,
+                      int right, double* d_sums, uint64_t* d_counts, void* d_scratch, int value_bytes, int n_cus, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
+int launch_bucket_minmax(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const void* d_zones, const void* d_edges, uint32_t n_edges,
+                         int right, void* d_out, uint64_t* d_counts, int value_bytes, int n_cus, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
+
 // zone maps (include/alpgpu.h).  decode_kernels.hip / decode_f32_kernels.hip: d_zones[v] = {min, max} of vector v, decoded in registers by the
 // one-wavefront sink kernels (col->n_vectors > 0)
 int launch_zone_map(hipStream_t stream, const alpgpu_column* col, void* d_zones);

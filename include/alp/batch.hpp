@@ -990,6 +990,85 @@ struct column {
 		out.unmatched = counts.back();
 		return out;
 	}
+	// Bucketed aggregation (include/alpgpu.h, "bucketed aggregation"): SUM, or the record {min, max}, and the COUNT of this column (blob val) per bucket
+	// of a key column of the same type and length (blob key; the same blob is allowed), over the rows whose bit is set in the mask (nullptr: all of
+	// them), in one pass over the two columns (alpgpu_decode_bucket_sum_* / alpgpu_decode_bucket_minmax_*), for double and float columns.  edges:
+	// 0 .. ALPGPU_BUCKET_EDGES_MAX edges, sorted here, on the host (NaNs last, where they are inert).  Bucket b holds the rows with b edges <= key
+	// (right: < key): histogram's buckets.  sums / records: n_edges + 1; counts: the buckets' rows, as histogram(key) counts them; nan_keys: the
+	// selected rows whose key is a NaN, which enter nothing else.  AVG is sums[b] / counts[b].  zones (optional): any records that contain the KEY
+	// vectors' intervals; they change no byte.
+	struct bucket_result {
+		std::vector<PT>       edges;
+		std::vector<double>   sums;    // sum_by_bucket
+		std::vector<zone>     records; // minmax_by_bucket
+		std::vector<uint64_t> counts;
+		uint64_t              nan_keys = 0;
+	};
+	static bucket_result sum_by_bucket(const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>* mask,
+	                                   const std::vector<zone>* zones, const PT* edges, size_t n_edges, bool right = false) {
+		return bucket_call(true, blob_val, size_val, blob_key, size_key, mask, zones, edges, n_edges, right);
+	}
+	static bucket_result minmax_by_bucket(const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>* mask,
+	                                      const std::vector<zone>* zones, const PT* edges, size_t n_edges, bool right = false) {
+		return bucket_call(false, blob_val, size_val, blob_key, size_key, mask, zones, edges, n_edges, right);
+	}
+	// what the two share: everything but the result buffer and the entry point
+	static bucket_result bucket_call(bool sum, const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>* mask,
+	                                 const std::vector<zone>* zones, const PT* edges, size_t n_edges, bool right) {
+		const std::string who = sum ? "alp::gpu::column::sum_by_bucket" : "alp::gpu::column::minmax_by_bucket";
+		if ((!edges && n_edges > 0) || n_edges > ALPGPU_BUCKET_EDGES_MAX) { throw std::runtime_error(who + ": 0 .. ALPGPU_BUCKET_EDGES_MAX edges"); }
+		uploaded_column val(blob_val, size_val, who.c_str()), key(blob_key, size_key, who.c_str());
+		const uint64_t  nv = val.col.n_vectors;
+		if (key.col.n_vectors != nv) { throw std::runtime_error(who + ": the columns differ in length"); }
+		if (mask && mask->size() != 16 * nv) { throw std::runtime_error(who + ": the mask must hold 16 words per vector"); }
+		if (zones && zones->size() != nv) { throw std::runtime_error(who + ": one record per vector"); }
+		const size_t  n_buckets = n_edges + 1;
+		bucket_result out;
+		if (n_edges > 0) { out.edges.assign(edges, edges + n_edges); }
+		std::sort(out.edges.begin(), out.edges.end(), [](PT a, PT b) { return b != b ? a == a : a < b; }); // ascending by <, NaNs last
+		zone none;
+		none.min = std::numeric_limits<PT>::infinity();
+		none.max = -std::numeric_limits<PT>::infinity();
+		if (sum) { out.sums.assign(n_buckets, 0.0); } else { out.records.assign(n_buckets, none); }
+		out.counts.assign(n_buckets, 0);
+		if (nv == 0) { return out; }
+		uint64_t* d_mask   = mask ? static_cast<uint64_t*>(val.get(mask->size() * sizeof(uint64_t))) : nullptr;
+		zone*     d_zones  = zones ? static_cast<zone*>(val.get(nv * sizeof(zone))) : nullptr;
+		PT*       d_edges  = n_edges > 0 ? static_cast<PT*>(val.get(n_edges * sizeof(PT))) : nullptr;
+		void*     d_result = val.get(n_buckets * (sum ? sizeof(double) : sizeof(zone)));
+		uint64_t* d_counts = static_cast<uint64_t*>(val.get((n_buckets + 1) * sizeof(uint64_t)));
+		const uint32_t ne = static_cast<uint32_t>(n_edges);
+		void*     d_scratch = sum ? val.get(alpgpu_bucket_sum_scratch_bytes(nv, ne)) : nullptr;
+		if (mask) { check(alpgpu_memcpy_h2d(context(), d_mask, mask->data(), mask->size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d"); }
+		if (zones) { check(alpgpu_memcpy_h2d(context(), d_zones, zones->data(), nv * sizeof(zone)), "alpgpu_memcpy_h2d"); }
+		if (n_edges > 0) { check(alpgpu_memcpy_h2d(context(), d_edges, out.edges.data(), n_edges * sizeof(PT)), "alpgpu_memcpy_h2d"); }
+		const int r = right ? 1 : 0;
+		if constexpr (sizeof(PT) == 8) {
+			const double* de = reinterpret_cast<const double*>(d_edges);
+			if (sum) {
+				check(alpgpu_decode_bucket_sum_f64(context(), &val.col, &key.col, d_mask, d_zones, de, ne, r, static_cast<double*>(d_result), d_counts, d_scratch), "alpgpu_decode_bucket_sum_f64");
+			} else {
+				check(alpgpu_decode_bucket_minmax_f64(context(), &val.col, &key.col, d_mask, d_zones, de, ne, r, static_cast<zone*>(d_result), d_counts), "alpgpu_decode_bucket_minmax_f64");
+			}
+		} else {
+			const float* de = reinterpret_cast<const float*>(d_edges);
+			if (sum) {
+				check(alpgpu_decode_bucket_sum_f32(context(), &val.col, &key.col, d_mask, d_zones, de, ne, r, static_cast<double*>(d_result), d_counts, d_scratch), "alpgpu_decode_bucket_sum_f32");
+			} else {
+				check(alpgpu_decode_bucket_minmax_f32(context(), &val.col, &key.col, d_mask, d_zones, de, ne, r, static_cast<zone*>(d_result), d_counts), "alpgpu_decode_bucket_minmax_f32");
+			}
+		}
+		std::vector<uint64_t> counts(n_buckets + 1);
+		if (sum) {
+			check(alpgpu_memcpy_d2h(context(), out.sums.data(), d_result, n_buckets * sizeof(double)), "alpgpu_memcpy_d2h");
+		} else {
+			check(alpgpu_memcpy_d2h(context(), out.records.data(), d_result, n_buckets * sizeof(zone)), "alpgpu_memcpy_d2h");
+		}
+		check(alpgpu_memcpy_d2h(context(), counts.data(), d_counts, counts.size() * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
+		out.counts.assign(counts.begin(), counts.end() - 1);
+		out.nan_keys = counts.back();
+		return out;
+	}
 	// Distinct values (include/alpgpu.h, "distinct values"): the distinct values, ascending, of the values [0, n_values) whose bit is set in the mask
 	// (nullptr: all of them) and how often each occurs.  -0.0 == 0.0, one value, reported as +0.0; +-inf are ordinary; NaNs are no values and are only
 	// counted (nans).  numbers = the selected values that are no NaNs: the sum of counts unless overflow.  overflow: there are more than `capacity`

@@ -1344,6 +1344,101 @@ int alpgpu_debug_decode_keyed_minmax_many_f32(alpgpu_ctx* ctx, const alpgpu_colu
                                               const float* d_keys, uint32_t n_keys, alpgpu_zone_f32* d_out, uint64_t* d_counts, const alpgpu_keyed_tuning* tuning,
                                               uint64_t* d_trace);
 
+/* ---- bucketed aggregation -------------------------------------------------------------------------------------------------------------------------
+ * SELECT width_bucket(key, edges), SUM(x) / MIN(x) / MAX(x), COUNT(*) ... WHERE ... GROUP BY 1: resampling a column into bins of a second column
+ * (date_trunc(ts), OHLC bars, equi-width and equi-depth profiles), for up to 1024 buckets given by sorted edges, in ONE pass that decodes both
+ * columns in registers, no decoded value reaching HBM.  The bucket is alpgpu_histogram_*'s, the tables are the keyed calls'.  Built for double and
+ * float columns.
+ *   alpgpu_decode_bucket_sum_* / alpgpu_decode_bucket_minmax_*
+ *                               Rows.  val and key: two columns of the entry point's type with equal n_vectors; val == key is allowed.  Take every
+ *                               row r whose bit is set in the bitmap (d_mask == NULL: every row).  x_r and k_r are, bit for bit, what
+ *                               alpgpu_decode_* writes at r for val and for key, exceptions patched in; a float x_r is widened to double,
+ *                               exactly, for the sums.
+ *                               The bucket is alpgpu_histogram_*'s, word for word.  k_r a NaN (by the bits): the row is counted in
+ *                               d_counts[n_edges + 1] and enters no sum and no record.  right == 0: b = #{i : d_edges[i] <= k_r}, the half-open
+ *                               buckets [e[b-1], e[b]); right != 0: b = #{i : d_edges[i] < k_r}, the buckets (e[b-1], e[b]].  Bucket 0 lies
+ *                               below the first edge and bucket n_edges at or above the last.  The comparisons are C's: -0.0 == +0.0, +-inf are
+ *                               ordinary values and edges.  NaN edges, sorted last, are inert; duplicate edges give empty buckets.  n_edges == 0
+ *                               is valid and d_edges may then be NULL: there is one bucket.  n_edges is at most ALPGPU_BUCKET_EDGES_MAX: the
+ *                               n_edges + 1 buckets are the keyed calls' table entries.  d_edges: n_edges elements of the columns' type in
+ *                               DEVICE memory, aligned to the element, sorted as numpy.sort sorts, read when the kernel runs (a captured graph
+ *                               sees the edges' contents at replay; n_edges, right and the pointers are fixed at capture).
+ *                               d_counts (may be NULL): n_edges + 2 words of 8 bytes, exact: the n_edges + 1 buckets' selected rows (NaN values
+ *                               included) and, last, the rows whose key is a NaN.  They are, byte for byte, what alpgpu_histogram_* writes for
+ *                               key over the whole column under the same bitmap, edges and right.  With d_counts == NULL
+ *                               alpgpu_decode_bucket_minmax_* keeps no count at all.
+ *                               d_sums (SUM): n_edges + 1 doubles in alpgpu_decode_keyed_sum_*'s order and no other, "belongs to key i" read as
+ *                               "lies in bucket b": L = alpgpu_keyed_stripe_vectors(n_vectors); P(b, v, m) is the adjacent-lane tree over a
+ *                               step's 64 lanes with +0.0 where a row is not selected or is not of bucket b; a stripe's partial starts at +0.0
+ *                               and takes the steps in (v, m) order; alpgpu_tree_sum_f64 runs over the S stripes.  A selected NaN in val makes
+ *                               its bucket's sum a NaN of unspecified payload.  Neither the grid, nor the device's CU count, nor the order in
+ *                               which wavefronts arrive enters a bit.  A consequence: if d_edges are distinct keys without NaNs, right == 0 and
+ *                               every selected key value is one of them or lies below the first, d_sums[i + 1] is, bit for bit,
+ *                               alpgpu_decode_keyed_sum_f64's d_sums[i] for d_keys = d_edges, and d_sums[0] covers the rows below.
+ *                               d_out (MIN / MAX): n_edges + 1 records {min, max} of the columns' type, aligned to the record (16 / 8 bytes), in
+ *                               alpgpu_decode_minmax_masked_*'s order: NaN values ignored but counted, -0.0 < +0.0, a bucket without a number
+ *                               gets {+inf, -inf}.  Exact and order-free: a function of the inputs alone.  Under the premise above record i + 1
+ *                               is, byte for byte, alpgpu_decode_keyed_minmax_*'s record i.
+ *                               d_mask (may be NULL): a selection bitmap of n_vectors * 16 words, 8-byte aligned, read and never written.  A vector
+ *                               whose 16 words are zero costs its 128 bytes and nothing of either column.
+ *                               d_key_zones (may be NULL; aligned to its records): any records that CONTAIN the true intervals of the KEY
+ *                               vectors' selected values.  The rules are alpgpu_histogram_*'s, not the keyed calls': a record without a NaN
+ *                               bound and with bucket(min) <= bucket(max) narrows the per-value search to the edges between the two.  If both
+ *                               bounds lie in ONE bucket and the key vector's descriptor says ALP without exceptions, every selected row has
+ *                               that bucket: the key vector's packed words are not requested and only the value vector is decoded.  This takes
+ *                               min == max no longer: a sorted timestamp column with bins wider than a vector takes this route almost
+ *                               everywhere.  A record with a NaN bound prunes nothing.  Truthful records change no byte.  Records that do not
+ *                               contain the truth, or edges that are not sorted, give unspecified sums, records and per-bucket counts; the
+ *                               n_edges + 2 counts still add up to the number of selected rows, nothing is read outside d_edges[0 .. n_edges) or
+ *                               the columns and nothing is written outside the outputs: every probe index and every table index is clamped.
+ *                               d_scratch (SUM): alpgpu_bucket_sum_scratch_bytes(n_vectors, n_edges) bytes, 16-byte aligned, contents irrelevant
+ *                               before and unspecified after (alpgpu_decode_keyed_sum_*'s: the stripe ticket and S rows of n_edges + 1 doubles).
+ *                               Cost: alpgpu_decode_keyed_sum_*'s (init kernel, persistent workgroups with private per-wavefront tables in two
+ *                               capacity tiers, up to 256 and up to 1024 buckets, a reduce of one small workgroup per bucket) and
+ *                               alpgpu_decode_keyed_minmax_*'s (init kernel, persistent workgroups with one table each on LDS integer atomics,
+ *                               joined by global integer atomics); the edges take the keys' place in LDS.  A value costs
+ *                               ceil(log2(n_edges + 1)) LDS probes, fewer under a zone record.
+ *                               n_vectors == 0: +0.0, {+inf, -inf} and 0 everywhere, written by a kernel; neither column is read.
+ *                               ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx, val, key, d_sums / d_out or d_scratch; a NULL d_edges
+ *                               with n_edges > 0; n_edges > ALPGPU_BUCKET_EDGES_MAX; columns that differ in n_vectors; n_vectors > 2^32 - 1;
+ *                               d_scratch not 16-byte aligned; d_sums, d_counts, d_mask or d_trace not 8-byte aligned; d_edges not aligned to its
+ *                               elements, d_out or d_key_zones not aligned to their records; with n_vectors > 0, a column without descriptors.
+ *   alpgpu_bucket_sum_scratch_bytes   alpgpu_keyed_sum_scratch_bytes(n_vectors, n_edges + 1); UINT64_MAX for n_edges > ALPGPU_BUCKET_EDGES_MAX.
+ * The calls run on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no state kept; none of what
+ *   the context remembers about columns is read or written; safe inside a stream capture (the edges and the bitmap are read at replay).  No
+ *   floating-point atomics and no compare-and-swap loop; no workgroup waits for another.
+ * The debug entries take alpgpu_keyed_tuning (grid) and add to four trace words, each wavefront once per word at its end.  They count vectors:
+ *   [0] settled without either column (their bitmap words are all zero),
+ *   [1] settled by the one-bucket shortcut (the key vector's packed words not requested),
+ *   [2] always 0: every key that is not a NaN has a bucket,
+ *   [3] decoded, both columns.
+ *   No tuning changes a byte.
+ * Not built: more than 1024 buckets per call (the reason alpgpu_decode_keyed_sum_* stops there: the tables sit in LDS), first / n sub-ranges,
+ *   accumulate, multi-column keys, alpgpu_decode_keyed_sum_f32.
+ * TRUST: as for alpgpu_select_range_*. */
+#define ALPGPU_BUCKET_EDGES_MAX 1023u /* n_edges + 1 buckets <= ALPGPU_KEYED_KEYS_MAX table entries */
+uint64_t alpgpu_bucket_sum_scratch_bytes(uint64_t n_vectors, uint32_t n_edges);
+int alpgpu_decode_bucket_sum_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
+                                 const double* d_edges, uint32_t n_edges, int right, double* d_sums, uint64_t* d_counts, void* d_scratch);
+int alpgpu_decode_bucket_sum_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f32* d_key_zones,
+                                 const float* d_edges, uint32_t n_edges, int right, double* d_sums, uint64_t* d_counts, void* d_scratch);
+int alpgpu_decode_bucket_minmax_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
+                                    const double* d_edges, uint32_t n_edges, int right, alpgpu_zone_f64* d_out, uint64_t* d_counts);
+int alpgpu_decode_bucket_minmax_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f32* d_key_zones,
+                                    const float* d_edges, uint32_t n_edges, int right, alpgpu_zone_f32* d_out, uint64_t* d_counts);
+int alpgpu_debug_decode_bucket_sum_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
+                                       const double* d_edges, uint32_t n_edges, int right, double* d_sums, uint64_t* d_counts, void* d_scratch,
+                                       const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
+int alpgpu_debug_decode_bucket_sum_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f32* d_key_zones,
+                                       const float* d_edges, uint32_t n_edges, int right, double* d_sums, uint64_t* d_counts, void* d_scratch,
+                                       const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
+int alpgpu_debug_decode_bucket_minmax_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
+                                          const double* d_edges, uint32_t n_edges, int right, alpgpu_zone_f64* d_out, uint64_t* d_counts,
+                                          const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
+int alpgpu_debug_decode_bucket_minmax_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f32* d_key_zones,
+                                          const float* d_edges, uint32_t n_edges, int right, alpgpu_zone_f32* d_out, uint64_t* d_counts,
+                                          const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
+
 /* Opt-in guard for device-resident columns of unknown origin: one pass over the descriptors on the device checks, for every vector,
  * scheme (and that it is its rowgroup's), widths, exponent / factor, exception count, alignment, that its packed words and its
  * exception record lie inside packed_capacity / exc_capacity, and that every exception position is < 1024.  value_bytes = 8
