@@ -11,13 +11,9 @@ static int bucket_common(const alpgpu_column* val, const alpgpu_column* key, con
 	if (!d_result) { return fail(ALPGPU_ERR_INVALID, "null sums or records"); }
 	if (n_edges > ALPGPU_BUCKET_EDGES_MAX) { return fail(ALPGPU_ERR_INVALID, "n_edges is beyond ALPGPU_BUCKET_EDGES_MAX"); }
 	if (!d_edges && n_edges > 0) { return fail(ALPGPU_ERR_INVALID, "null edges with n_edges > 0"); }
-	if (val->n_vectors != key->n_vectors) { return fail(ALPGPU_ERR_INVALID, "the columns differ in n_vectors"); }
-	if (val->n_vectors > 0xFFFFFFFFull) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is beyond 2^32 - 1"); }
-	ALPGPU_TRY(check_bitmap_aligned(d_mask));
-	if (misaligned(d_counts, 8u) || misaligned(d_trace, 8u)) { return fail(ALPGPU_ERR_INVALID, "counts or trace are not 8-byte aligned"); }
-	if (misaligned(d_edges, static_cast<unsigned>(value_bytes))) { return fail(ALPGPU_ERR_INVALID, "edges are not aligned to their elements"); }
-	if (misaligned(d_zones, 2u * value_bytes)) { return fail(ALPGPU_ERR_INVALID, "zones are not aligned to their records"); }
-	return ALPGPU_OK;
+	ALPGPU_TRY(check_pair_n_vectors(val, key));
+	ALPGPU_TRY(check_bitmap_counts_trace(d_mask, d_counts, d_trace));
+	return check_list_and_zones(d_edges, "edges are not aligned to their elements", d_zones, value_bytes);
 }
 
 static int bucket_sum(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const void* d_zones, const void* d_edges, uint32_t n_edges,
@@ -43,13 +39,9 @@ static int bucket_minmax(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu
                          int right, void* d_out, uint64_t* d_counts, int value_bytes, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace) {
 	ALPGPU_TRY(bucket_common(val, key, d_mask, d_zones, d_edges, n_edges, d_out, d_counts, value_bytes, d_trace));
 	if (misaligned(d_out, 2u * value_bytes)) { return fail(ALPGPU_ERR_INVALID, "the records are not aligned to their size"); }
-	if (val->n_vectors == 0) { // {+inf, -inf} and 0 everywhere, by a kernel
-		if (alpgpu::launch_keyed_minmax_init(ctx->stream, d_out, d_counts, n_edges + 1u, value_bytes) != ALPGPU_OK) {
-			return fail(ALPGPU_ERR_HIP, "emptying the records and counts failed", hipGetLastError());
-		}
-		return ALPGPU_OK;
-	}
-	ALPGPU_TRY(check_has_descriptors(val, key));
+	bool done;
+	ALPGPU_TRY(minmax_empty_or_descriptors(ctx, val, key, d_out, d_counts, n_edges + 1u, value_bytes, &done));
+	if (done) { return ALPGPU_OK; }
 	const int rc = alpgpu::launch_bucket_minmax(ctx->stream, val, key, d_mask, d_zones, d_edges, n_edges, right, d_out, d_counts, value_bytes, ctx->n_cus, tuning, d_trace);
 	if (rc != ALPGPU_OK) { return fail(rc, "decode_bucket_minmax launch failed"); } // (the launcher has read the HIP error)
 	return ALPGPU_OK;

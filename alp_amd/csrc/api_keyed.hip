@@ -10,13 +10,11 @@ static int keyed_sum(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_col
 	if (!val || !key) { return fail(ALPGPU_ERR_INVALID, "null column"); }
 	if (!d_keys || !d_sums || !d_scratch) { return fail(ALPGPU_ERR_INVALID, "null keys, sums or scratch"); }
 	if (n_keys == 0 || n_keys > ALPGPU_KEYED_KEYS_MAX) { return fail(ALPGPU_ERR_INVALID, "n_keys is not in 1 .. ALPGPU_KEYED_KEYS_MAX"); }
-	if (val->n_vectors != key->n_vectors) { return fail(ALPGPU_ERR_INVALID, "the columns differ in n_vectors"); }
-	if (val->n_vectors > 0xFFFFFFFFull) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is beyond 2^32 - 1"); }
+	ALPGPU_TRY(check_pair_n_vectors(val, key));
 	if (misaligned(d_scratch, 16u)) { return fail(ALPGPU_ERR_INVALID, "scratch is not 16-byte aligned"); }
 	ALPGPU_TRY(check_bitmap_aligned(d_mask));
 	if (misaligned(d_sums, 8u) || misaligned(d_counts, 8u) || misaligned(d_trace, 8u)) { return fail(ALPGPU_ERR_INVALID, "sums, counts or trace are not 8-byte aligned"); }
-	if (misaligned(d_keys, static_cast<unsigned>(value_bytes))) { return fail(ALPGPU_ERR_INVALID, "keys are not aligned to their elements"); }
-	if (misaligned(d_zones, 2u * value_bytes)) { return fail(ALPGPU_ERR_INVALID, "zones are not aligned to their records"); }
+	ALPGPU_TRY(check_list_and_zones(d_keys, "keys are not aligned to their elements", d_zones, value_bytes));
 	if (val->n_vectors == 0) { // +0.0 and 0 everywhere, by a kernel
 		if (alpgpu::launch_fill_u64(ctx->stream, reinterpret_cast<uint64_t*>(d_sums), n_keys, 0ull) != ALPGPU_OK ||
 		    (d_counts && alpgpu::launch_fill_u64(ctx->stream, d_counts, n_keys + 1u, 0ull) != ALPGPU_OK)) {

@@ -9,20 +9,13 @@ static int keyed_minmax(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_
 	if (!val || !key) { return fail(ALPGPU_ERR_INVALID, "null column"); }
 	if (!d_keys || !d_out) { return fail(ALPGPU_ERR_INVALID, "null keys or records"); }
 	if (n_keys == 0 || n_keys > ALPGPU_KEYED_KEYS_MAX) { return fail(ALPGPU_ERR_INVALID, "n_keys is not in 1 .. ALPGPU_KEYED_KEYS_MAX"); }
-	if (val->n_vectors != key->n_vectors) { return fail(ALPGPU_ERR_INVALID, "the columns differ in n_vectors"); }
-	if (val->n_vectors > 0xFFFFFFFFull) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is beyond 2^32 - 1"); }
-	ALPGPU_TRY(check_bitmap_aligned(d_mask));
-	if (misaligned(d_counts, 8u) || misaligned(d_trace, 8u)) { return fail(ALPGPU_ERR_INVALID, "counts or trace are not 8-byte aligned"); }
+	ALPGPU_TRY(check_pair_n_vectors(val, key));
+	ALPGPU_TRY(check_bitmap_counts_trace(d_mask, d_counts, d_trace));
 	if (misaligned(d_out, 2u * value_bytes)) { return fail(ALPGPU_ERR_INVALID, "the records are not aligned to their size"); }
-	if (misaligned(d_keys, static_cast<unsigned>(value_bytes))) { return fail(ALPGPU_ERR_INVALID, "keys are not aligned to their elements"); }
-	if (misaligned(d_zones, 2u * value_bytes)) { return fail(ALPGPU_ERR_INVALID, "zones are not aligned to their records"); }
-	if (val->n_vectors == 0) { // {+inf, -inf} and 0 everywhere, by a kernel
-		if (alpgpu::launch_keyed_minmax_init(ctx->stream, d_out, d_counts, n_keys, value_bytes) != ALPGPU_OK) {
-			return fail(ALPGPU_ERR_HIP, "emptying the records and counts failed", hipGetLastError());
-		}
-		return ALPGPU_OK;
-	}
-	ALPGPU_TRY(check_has_descriptors(val, key));
+	ALPGPU_TRY(check_list_and_zones(d_keys, "keys are not aligned to their elements", d_zones, value_bytes));
+	bool done;
+	ALPGPU_TRY(minmax_empty_or_descriptors(ctx, val, key, d_out, d_counts, n_keys, value_bytes, &done));
+	if (done) { return ALPGPU_OK; }
 	const int rc = alpgpu::launch_keyed_minmax(ctx->stream, val, key, d_mask, d_zones, d_keys, n_keys, d_out, d_counts, value_bytes, ctx->n_cus, tuning, d_trace);
 	if (rc != ALPGPU_OK) { return fail(rc, "decode_keyed_minmax launch failed"); } // (the launcher has read the HIP error)
 	return ALPGPU_OK;

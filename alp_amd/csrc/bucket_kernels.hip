@@ -8,7 +8,7 @@
 //                         k_keyed_sum's skeleton: persistent workgroups, the edges staged into LDS behind ONE barrier, stripes taken by an integer
 //                         ticket, a PRIVATE table per wavefront of n_edges + 1 doubles and 32-bit counts, the partials stored to row s of the scratch
 //                         by plain vector stores; then k_keyed_reduce's tree over the S rows (k_keyed_init and k_keyed_reduce are keyed_kernels.hip's,
-//                         reached through a declaration).
+//                         declared in keyed_table.hpp).
 //   k_bucket_minmax<VB, WAVES>
 //                         k_keyed_minmax's skeleton: one table per workgroup (mn, mx, cnt), atomic_min_value / atomic_max_value on the value's bits
 //                         behind the read-before-atomic guard, the 32-bit counts flushed every kKmmFlushEvery trips, a join by global integer atomics
@@ -23,9 +23,9 @@
 //                         words are not requested and only the value vector is decoded.  b < a (a record that lies) and a NaN bound prune nothing.
 //                         There is no "admits no key" class: word 2 of the trace stays 0.
 //
-// The steps (bucket_sum_step, bucket_mm_step), bucket_mm_join and bucket_order_key are keyed_step, kmm_step, kmm_join and order_key WRITTEN OUT AGAIN
-// and not moved into a header: k_keyed_sum<8, 256, 8> sits 2 registers under its occupancy step and both keyed files stay byte for byte as they
-// compile (keyed_minmax_kernels.hip did the same for keyed_vector).
+// The steps (keyed_step, kmm_step), kmm_join, order_key, kmm_counts_flush, the tiers and the declarations of k_keyed_init / k_keyed_reduce are
+// keyed_table.hpp's, the ones the keyed kernels use; the move was checked against the device assembly (profiles/r29_keyed_tables.txt).  The vector
+// functions and kernel bodies stay this file's: as templates shared with the keyed kernels they compiled differently and k_bucket_sum ran behind.
 //
 // LDS: the edges take the keys' array, so the budget is k_keyed_sum's / k_keyed_minmax's.  HBM traffic per vector: theirs.
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; launch bounds 512 and 768):
@@ -40,23 +40,9 @@
 // keyed ones and the NaN ballot is a second mask per step), which is 3 waves per SIMD, one workgroup per CU fewer than the grid is sized for.
 // amdgpu_waves_per_eu(4) on the 8-wavefront kernels holds it to 128 registers; it meets that without scratch (the lines above).  The 12-wavefront
 // tier is bound by its LDS to one workgroup per CU = 3 waves per SIMD, where 130 registers cost nothing, and asks for 3.
-#include "minmax_device.hpp"
-#include "persistent_scan.hpp"
-#include "sorted_list.hpp"
+#include "keyed_table.hpp"
 
 namespace alpgpu {
-
-// keyed_kernels.hip's: the counts and the scratch's header zeroed; out[key] = k_tree_sum's tree over the key's column of the partials
-__global__ void k_keyed_init(uint64_t* counts, uint32_t n_counts, uint64_t* header);
-__global__ void k_keyed_reduce(const double* __restrict__ partials, uint32_t n_stripes, uint32_t n_keys, double* __restrict__ out);
-
-constexpr uint32_t kBucketSmall = 256u; // the small tier's capacity in table entries (n_edges + 1)
-constexpr int      kBucketSmallWaves = 8, kBucketLargeWaves = 12;
-constexpr int      kBucketSmallWgPerCu = 2, kBucketLargeWgPerCu = 1;
-constexpr int      kBucketMmWaves   = 8;
-constexpr int      kBucketMmThreads = 64 * kBucketMmWaves;
-constexpr int      kBucketMmWgPerCu = 2;
-constexpr uint32_t kBucketMmFlushEvery = 1u << 18; // (kKmmFlushEvery: a trip adds at most 8 x 1024 to one 32-bit LDS count)
 
 struct BucketArgs {
 	uint64_t        n_vectors;
@@ -73,8 +59,6 @@ struct BucketArgs {
 	uint64_t*       counts;         // nullable: n_edges + 2 words, added to
 	uint64_t*       trace;          // nullable: 4 words, added to
 };
-
-constexpr uint32_t kBucketSkipZero = 0u, kBucketOne = 1u, kBucketDecoded = 3u; // what a vector function did with a vector: the trace's words (2 is never returned)
 
 // The key vector's zone record into [j0, j1] (wave-uniform; histogram's rule).  True: both bounds lie in the one bucket j0.
 template <class T>
@@ -96,41 +80,6 @@ __device__ __forceinline__ bool bucket_zone(const T* s_edges, const BucketArgs& 
 
 // ---- SUM -------------------------------------------------------------------------------------------------------------------------------------------
 
-// keyed_step, written out again: one step's member lanes m (wave-uniform) into the wavefront's table; lane l holds the value x and the bucket idx (<= n_edges)
-__device__ __forceinline__ void bucket_sum_step(double* s_sums, uint32_t* s_cnt, uint64_t m, uint32_t idx, double x, uint32_t lane) {
-	if (m == 0ull) { return; }
-	const bool     in    = (m >> lane) & 1ull;
-	const uint32_t first = static_cast<uint32_t>(__builtin_amdgcn_readlane(idx, static_cast<uint32_t>(__builtin_ctzll(m))));
-	uint64_t       same  = m & ballot64(idx == first);
-	if (same == m) { // the step's lanes agree on one bucket
-		const double p = wave_tree_sum_f64(in ? x : 0.0);
-		if (lane == 0u) {
-			s_sums[first] += p;
-			s_cnt[first] += static_cast<uint32_t>(__builtin_popcountll(m));
-		}
-		wave_lds_sync(); // (as every exit of this function: the next step's first LDS access, of any lane, comes behind lane 0's)
-		return;
-	}
-	// the counts of all of m by one LDS atomic; a lane that saw its bucket's count grow by exactly 1 is alone with that bucket in this step
-	const uint32_t c0 = in ? s_cnt[idx] : 0u;
-	wave_lds_sync();
-	if (in) { atomicAdd(&s_cnt[idx], 1u); }
-	wave_lds_sync();
-	const uint32_t c1    = in ? s_cnt[idx] : 0u;
-	const uint64_t alone = ballot64(in && c1 - c0 == 1u);
-	if ((alone >> lane) & 1ull) { s_sums[idx] += x; } // 64 different addresses
-	wave_lds_sync();
-	uint64_t left = m & ~alone;
-	while (left != 0ull) { // bucket by bucket, in the order of the buckets' first lanes
-		const uint32_t i = static_cast<uint32_t>(__builtin_amdgcn_readlane(idx, static_cast<uint32_t>(__builtin_ctzll(left))));
-		same             = left & ballot64(idx == i);
-		const double p   = wave_tree_sum_f64(((same >> lane) & 1ull) ? x : 0.0);
-		if (lane == 0u) { s_sums[i] += p; }
-		left &= ~same;
-	}
-	wave_lds_sync();
-}
-
 // One vector pair by one wavefront.  Returns the class of the trace it fell into; nan_rows (wave-uniform) takes the selected rows whose key is a NaN.
 template <int VB, int WAVES>
 __device__ __forceinline__ uint32_t bucket_sum_vector(const ColumnStreams& cv, const ColumnStreams& ck, const BucketArgs& g, uint64_t v, uint32_t wave, uint32_t lane,
@@ -138,7 +87,7 @@ __device__ __forceinline__ uint32_t bucket_sum_vector(const ColumnStreams& cv, c
 	typedef typename DecodeVec<VB>::T T;
 	// 1. the selected bits, lane m < 16 holding word m
 	uint64_t sel;
-	if (!selected_words(g.mask, 0ull, g.n_vectors << 10, v, lane, sel)) { return kBucketSkipZero; }
+	if (!selected_words(g.mask, 0ull, g.n_vectors << 10, v, lane, sel)) { return kVectorSkipZero; }
 
 	// 2. the part [j0, j1) of the edges that the key vector's zone record admits: all of them without a record, with a NaN bound or with min above max
 	const uint32_t last_edge = g.n_edges > 0u ? g.n_edges - 1u : 0u;
@@ -173,7 +122,7 @@ __device__ __forceinline__ uint32_t bucket_sum_vector(const ColumnStreams& cv, c
 				s_cnt[j0] += n_rows;
 			}
 			wave_lds_sync();
-			return kBucketOne;
+			return kVectorOneEntry;
 		}
 	}
 
@@ -204,14 +153,14 @@ __device__ __forceinline__ uint32_t bucket_sum_vector(const ColumnStreams& cv, c
 			const uint64_t w    = readlane64(sel, b + i);
 			const uint64_t nans = ballot64(!(k[i] == k[i]));
 			nan_rows += static_cast<uint32_t>(__builtin_popcountll(w & nans));
-			bucket_sum_step(s_sums, s_cnt, w & ~nans, idx, x[i], lane);
+			keyed_step(s_sums, s_cnt, w & ~nans, idx, x[i], lane);
 		}
 	}
-	return kBucketDecoded;
+	return kVectorDecoded;
 }
 
 template <int VB, uint32_t KCAP, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES == kBucketLargeWaves ? 3 : 4))) void k_bucket_sum(const ColumnStreams cv, const ColumnStreams ck, const BucketArgs g) {
+__global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES == kKeyedLargeWaves ? 3 : 4))) void k_bucket_sum(const ColumnStreams cv, const ColumnStreams ck, const BucketArgs g) {
 	typedef typename DecodeVec<VB>::T T;
 	__shared__ double   s_sums[WAVES][KCAP]; // per wavefront: the stripe's partials
 	__shared__ uint32_t s_cnt[WAVES][KCAP];  // ... and counts
@@ -274,59 +223,16 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVE
 
 // ---- MIN / MAX -------------------------------------------------------------------------------------------------------------------------------------
 
-// order_key, written out again: the records' order as a signed integer (-0.0 -> -1, just below +0.0 -> 0); x is not a NaN
-__device__ __forceinline__ long long bucket_order_key(double x) {
-	const long long b = __double_as_longlong(x);
-	return b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFll);
-}
-__device__ __forceinline__ int bucket_order_key(float x) {
-	const int b = static_cast<int>(__float_as_uint(x));
-	return b ^ ((b >> 31) & 0x7FFFFFFF);
-}
-
-// kmm_join, written out again: a wave-uniform record {mn, mx} (lane 0 acts) into entry i of the table, unless it is the empty one
-template <class T>
-__device__ __forceinline__ void bucket_mm_join(T* s_mn, T* s_mx, uint32_t i, T mn, T mx, uint32_t lane) {
-	if (lane == 0u && mn <= mx) { // ({+inf, -inf}: no number was fed; -0.0 <= +0.0 and inf <= inf hold)
-		atomic_min_value(&s_mn[i], mn);
-		atomic_max_value(&s_mx[i], mx);
-	}
-}
-
-// kmm_step, written out again: one step's member lanes m (wave-uniform) into the workgroup's table; lane l holds the canonical value q and the bucket idx (<= n_edges)
-template <class T>
-__device__ __forceinline__ void bucket_mm_step(T* s_mn, T* s_mx, uint32_t* s_cnt, bool counted, uint64_t m, uint32_t idx, T q, uint32_t lane) {
-	if (m == 0ull) { return; }
-	const bool     in    = (m >> lane) & 1ull;
-	const uint32_t first = static_cast<uint32_t>(__builtin_amdgcn_readlane(idx, static_cast<uint32_t>(__builtin_ctzll(m))));
-	if ((m & ballot64(idx == first)) == m) { // the step's lanes agree on one bucket
-		T mn = pos_inf<T>(), mx = -pos_inf<T>();
-		minmax_feed(mn, mx, in ? q : minmax_skip<T>()); // (a NaN q is a quiet one: skipped)
-		wave_minmax<T>(mn, mx);
-		bucket_mm_join(s_mn, s_mx, first, mn, mx, lane);
-		if (counted && lane == 0u) { atomicAdd(&s_cnt[first], static_cast<uint32_t>(__builtin_popcountll(m))); }
-		return;
-	}
-	if (in) {
-		if (q == q) { // a stale read is safe: the table moves one way, so it can cause a needless atomic and never a missed one
-			const auto k = bucket_order_key(q);
-			if (k < bucket_order_key(s_mn[idx])) { atomic_min_value(&s_mn[idx], q); }
-			if (k > bucket_order_key(s_mx[idx])) { atomic_max_value(&s_mx[idx], q); }
-		}
-		if (counted) { atomicAdd(&s_cnt[idx], 1u); }
-	}
-}
-
 // One vector pair by one wavefront.  Returns the class of the trace it fell into.  s_cnt[n_edges + 1] takes the selected rows whose key is a NaN.
 template <int VB>
 __device__ __forceinline__ uint32_t bucket_mm_vector(const ColumnStreams& cv, const ColumnStreams& ck, const BucketArgs& g, uint64_t v, uint32_t wave, uint32_t lane,
                                                      const typename DecodeVec<VB>::T* s_edges, typename DecodeVec<VB>::T* s_mn, typename DecodeVec<VB>::T* s_mx, uint32_t* s_cnt,
-                                                     uint64_t (&s_exc)[kBucketMmWaves][2][16]) {
+                                                     uint64_t (&s_exc)[kKmmWaves][2][16]) {
 	typedef typename DecodeVec<VB>::T T;
 	const bool counted = g.counts != nullptr;
 	// 1. the selected bits, lane m < 16 holding word m
 	uint64_t sel;
-	if (!selected_words(g.mask, 0ull, g.n_vectors << 10, v, lane, sel)) { return kBucketSkipZero; }
+	if (!selected_words(g.mask, 0ull, g.n_vectors << 10, v, lane, sel)) { return kVectorSkipZero; }
 
 	// 2. the part [j0, j1) of the edges that the key vector's zone record admits
 	const uint32_t last_edge = g.n_edges > 0u ? g.n_edges - 1u : 0u;
@@ -354,9 +260,9 @@ __device__ __forceinline__ uint32_t bucket_mm_vector(const ColumnStreams& cv, co
 				}
 			}
 			wave_minmax<T>(mn, mx);
-			bucket_mm_join(s_mn, s_mx, j0, mn, mx, lane);
+			kmm_join(s_mn, s_mx, j0, mn, mx, lane);
 			if (counted && lane == 0u) { atomicAdd(&s_cnt[j0], n_rows); }
-			return kBucketOne;
+			return kVectorOneEntry;
 		}
 	}
 
@@ -387,30 +293,17 @@ __device__ __forceinline__ uint32_t bucket_mm_vector(const ColumnStreams& cv, co
 			const uint64_t w    = readlane64(sel, b + i);
 			const uint64_t nans = ballot64(!(k[i] == k[i]));
 			nan_rows += static_cast<uint32_t>(__builtin_popcountll(w & nans));
-			bucket_mm_step<T>(s_mn, s_mx, s_cnt, counted, w & ~nans, idx, q[i], lane);
+			kmm_step<T>(s_mn, s_mx, s_cnt, counted, w & ~nans, idx, q[i], lane);
 		}
 	}
 	if (counted && nan_rows != 0u && lane == 0u) { atomicAdd(&s_cnt[g.n_edges + 1u], nan_rows); }
-	return kBucketDecoded;
-}
-
-// the workgroup's non-zero LDS counts into the call's and zeroed again; a barrier in front and behind
-__device__ __forceinline__ void bucket_counts_flush(uint32_t* s_cnt, uint32_t n, uint64_t* counts) {
-	__syncthreads();
-	for (uint32_t i = threadIdx.x; i < n; i += kBucketMmThreads) {
-		const uint32_t c = s_cnt[i];
-		if (c != 0u) {
-			atomicAdd(reinterpret_cast<unsigned long long*>(counts) + i, static_cast<unsigned long long>(c));
-			s_cnt[i] = 0u;
-		}
-	}
-	__syncthreads();
+	return kVectorDecoded;
 }
 
 template <int VB, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4))) void k_bucket_minmax(const ColumnStreams cv, const ColumnStreams ck, const BucketArgs g) {
 	typedef typename DecodeVec<VB>::T T;
-	static_assert(WAVES == kBucketMmWaves, "the table's helpers are written for kBucketMmWaves");
+	static_assert(WAVES == kKmmWaves, "the table's helpers are written for kKmmWaves");
 	__shared__ T        s_mn[ALPGPU_KEYED_KEYS_MAX];
 	__shared__ T        s_mx[ALPGPU_KEYED_KEYS_MAX];
 	__shared__ T        s_edges[ALPGPU_KEYED_KEYS_MAX];
@@ -442,9 +335,9 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4)))
 #pragma unroll
 			for (uint32_t i = 0; i < 4u; ++i) { did[i] += what == i ? 1u : 0u; }
 		}
-		if (++trips == kBucketMmFlushEvery) {
+		if (++trips == kKmmFlushEvery) {
 			trips = 0;
-			if (g.counts != nullptr) { bucket_counts_flush(s_cnt, n_buckets + 1u, g.counts); }
+			if (g.counts != nullptr) { kmm_counts_flush(s_cnt, n_buckets + 1u, g.counts); }
 		}
 	}
 	// the flush: the table's non-empty entries into the call's records, the counts into the call's
@@ -474,12 +367,12 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4)))
 template <int VB>
 static void bucket_sum_launch(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const BucketArgs& args, int n_cus, uint32_t grid_override) {
 	const ColumnStreams cv = column_streams(val), ck = column_streams(key);
-	if (args.n_edges + 1u <= kBucketSmall) {
-		const unsigned grid = persistent_grid(args.n_stripes, kBucketSmallWaves, n_cus, kBucketSmallWgPerCu, 0, grid_override, kTuningGridMax);
-		hipLaunchKernelGGL((k_bucket_sum<VB, kBucketSmall, kBucketSmallWaves>), dim3(grid), dim3(64 * kBucketSmallWaves), 0, stream, cv, ck, args);
+	if (args.n_edges + 1u <= kKeyedSmallKeys) {
+		const unsigned grid = persistent_grid(args.n_stripes, kKeyedSmallWaves, n_cus, kKeyedSmallWgPerCu, 0, grid_override, kTuningGridMax);
+		hipLaunchKernelGGL((k_bucket_sum<VB, kKeyedSmallKeys, kKeyedSmallWaves>), dim3(grid), dim3(64 * kKeyedSmallWaves), 0, stream, cv, ck, args);
 	} else {
-		const unsigned grid = persistent_grid(args.n_stripes, kBucketLargeWaves, n_cus, kBucketLargeWgPerCu, 0, grid_override, kTuningGridMax);
-		hipLaunchKernelGGL((k_bucket_sum<VB, ALPGPU_KEYED_KEYS_MAX, kBucketLargeWaves>), dim3(grid), dim3(64 * kBucketLargeWaves), 0, stream, cv, ck, args);
+		const unsigned grid = persistent_grid(args.n_stripes, kKeyedLargeWaves, n_cus, kKeyedLargeWgPerCu, 0, grid_override, kTuningGridMax);
+		hipLaunchKernelGGL((k_bucket_sum<VB, ALPGPU_KEYED_KEYS_MAX, kKeyedLargeWaves>), dim3(grid), dim3(64 * kKeyedLargeWaves), 0, stream, cv, ck, args);
 	}
 }
 
@@ -529,12 +422,12 @@ int launch_bucket_minmax(hipStream_t stream, const alpgpu_column* val, const alp
 	args.trace     = d_trace;
 	const int rc = launch_keyed_minmax_init(stream, d_out, d_counts, n_edges + 1u, value_bytes);
 	if (rc != ALPGPU_OK) { return rc; }
-	const unsigned      grid = persistent_grid(val->n_vectors, kBucketMmWaves, n_cus, kBucketMmWgPerCu, 0, tuning != nullptr ? tuning->grid : 0u, kTuningGridMax);
+	const unsigned      grid = persistent_grid(val->n_vectors, kKmmWaves, n_cus, kKmmWgPerCu, 0, tuning != nullptr ? tuning->grid : 0u, kTuningGridMax);
 	const ColumnStreams cv = column_streams(val), ck = column_streams(key);
 	if (value_bytes == 8) {
-		hipLaunchKernelGGL((k_bucket_minmax<8, kBucketMmWaves>), dim3(grid), dim3(kBucketMmThreads), 0, stream, cv, ck, args);
+		hipLaunchKernelGGL((k_bucket_minmax<8, kKmmWaves>), dim3(grid), dim3(kKmmThreads), 0, stream, cv, ck, args);
 	} else {
-		hipLaunchKernelGGL((k_bucket_minmax<4, kBucketMmWaves>), dim3(grid), dim3(kBucketMmThreads), 0, stream, cv, ck, args);
+		hipLaunchKernelGGL((k_bucket_minmax<4, kKmmWaves>), dim3(grid), dim3(kKmmThreads), 0, stream, cv, ck, args);
 	}
 	return hipGetLastError() != hipSuccess ? ALPGPU_ERR_HIP : ALPGPU_OK;
 }

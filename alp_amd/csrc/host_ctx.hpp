@@ -171,6 +171,38 @@ ALPGPU_INTERNAL inline int check_has_descriptors(const alpgpu_column* a, const a
 	ALPGPU_TRY(check_has_descriptors(a));
 	return check_has_descriptors(b);
 }
+// ---- what the keyed and bucketed aggregations (api_keyed, api_keyed_minmax, api_keyed_minmax_many, api_bucket) check alike; each entry point calls them
+// in the order in which it has always reported its errors, between its own checks.  Null pointers are aligned.
+// the two columns (non-null)
+ALPGPU_INTERNAL inline int check_pair_n_vectors(const alpgpu_column* val, const alpgpu_column* key) {
+	if (val->n_vectors != key->n_vectors) { return fail(ALPGPU_ERR_INVALID, "the columns differ in n_vectors"); }
+	if (val->n_vectors > 0xFFFFFFFFull) { return fail(ALPGPU_ERR_INVALID, "column.n_vectors is beyond 2^32 - 1"); }
+	return ALPGPU_OK;
+}
+ALPGPU_INTERNAL inline int check_bitmap_counts_trace(const uint64_t* d_mask, const uint64_t* d_counts, const uint64_t* d_trace) {
+	ALPGPU_TRY(check_bitmap_aligned(d_mask));
+	if (misaligned(d_counts, 8u) || misaligned(d_trace, 8u)) { return fail(ALPGPU_ERR_INVALID, "counts or trace are not 8-byte aligned"); }
+	return ALPGPU_OK;
+}
+// the sorted list (list_text: "keys are not aligned to their elements" / "edges are ...") and the key column's zone records
+ALPGPU_INTERNAL inline int check_list_and_zones(const void* d_list, const char* list_text, const void* d_zones, int value_bytes) {
+	if (misaligned(d_list, static_cast<unsigned>(value_bytes))) { return fail(ALPGPU_ERR_INVALID, list_text); }
+	if (misaligned(d_zones, 2u * value_bytes)) { return fail(ALPGPU_ERR_INVALID, "zones are not aligned to their records"); }
+	return ALPGPU_OK;
+}
+// the last step of the three MIN / MAX calls: an empty column gets {+inf, -inf} in its n_records records and 0 in its n_records + 1 counts by a kernel
+// and *done is set; otherwise the columns must have descriptors
+ALPGPU_INTERNAL inline int minmax_empty_or_descriptors(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, void* d_out, uint64_t* d_counts, uint32_t n_records,
+                                                       int value_bytes, bool* done) {
+	*done = val->n_vectors == 0;
+	if (*done) {
+		if (alpgpu::launch_keyed_minmax_init(ctx->stream, d_out, d_counts, n_records, value_bytes) != ALPGPU_OK) {
+			return fail(ALPGPU_ERR_HIP, "emptying the records and counts failed", hipGetLastError());
+		}
+		return ALPGPU_OK;
+	}
+	return check_has_descriptors(val, key);
+}
 // a bitmap entry point whose range is empty (n == 0): nothing qualifies, so SET and AND clear every bit and OR changes none
 ALPGPU_INTERNAL inline int clear_bitmap_for_empty_range(alpgpu_ctx* ctx, int op, uint64_t* d_mask, const alpgpu_column* col) {
 	if (op != ALPGPU_MASK_OR) { ALPGPU_HIP(hipMemsetAsync(d_mask, 0, 128ull * col->n_vectors, ctx->stream)); }

@@ -1,6 +1,7 @@
 // keyed_kernels.hip — keyed aggregation (include/alpgpu.h, "keyed aggregation": alpgpu_decode_keyed_sum_*): SUM and COUNT of a value column per key of a
 // sorted key list, the key column decoded beside it, no decoded value reaching HBM.  The parts are k_pair's side-by-side decode (register_decode.hpp),
-// lds_bound over the staged keys (sorted_list.hpp) and selected_words with the constant-vector predicate (persistent_scan.hpp).
+// lds_bound over the staged keys (sorted_list.hpp) and selected_words with the constant-vector predicate (persistent_scan.hpp).  The step (keyed_step)
+// and the tiers are keyed_table.hpp's, shared with bucket_kernels.hip; the move was checked against the device assembly (profiles/r29_keyed_tables.txt).
 //
 //   k_keyed_init          zeroes the counts and the scratch's header (the stripe ticket): a kernel, no memset node (mask_kernels.hip says why).
 //   k_keyed_sum<VB, KCAP, WAVES>
@@ -42,14 +43,9 @@
 //   k_keyed_reduce              15 VGPRs,     64 B LDS, 8 waves per SIMD, no scratch;  k_keyed_init  6 VGPRs, no LDS, no scratch
 // The lone-lane shortcut of a step was measured against the step without it (-DALPGPU_KEYED_BASELINE_STEP, tools/time_keyed.py --ab;
 // profiles/r25_keyed_sum.txt, second part; DESIGN.md, "Keyed aggregation").
-#include "persistent_scan.hpp"
-#include "sorted_list.hpp"
+#include "keyed_table.hpp"
 
 namespace alpgpu {
-
-constexpr uint32_t kKeyedSmallKeys = 256u; // the small tier's capacity
-constexpr int      kKeyedSmallWaves = 8, kKeyedLargeWaves = 12;
-constexpr int      kKeyedSmallWgPerCu = 2, kKeyedLargeWgPerCu = 1;
 
 struct KeyedArgs {
 	uint64_t        n_vectors;
@@ -65,48 +61,6 @@ struct KeyedArgs {
 	uint64_t*       trace;          // nullable: 4 words, added to
 };
 
-constexpr uint32_t kKeyedSkipZero = 0u, kKeyedConstant = 1u, kKeyedNoKey = 2u, kKeyedDecoded = 3u; // what keyed_vector did with a vector: the trace's words
-
-// One step's selected, matched lanes m (wave-uniform) into the wavefront's table: lane l holds the value x and the key index idx (< n_keys where its bit of m is set).
-__device__ __forceinline__ void keyed_step(double* s_sums, uint32_t* s_cnt, uint64_t m, uint32_t idx, double x, uint32_t lane) {
-	if (m == 0ull) { return; }
-	const bool     in    = (m >> lane) & 1ull;
-	const uint32_t first = static_cast<uint32_t>(__builtin_amdgcn_readlane(idx, static_cast<uint32_t>(__builtin_ctzll(m))));
-	uint64_t       same  = m & ballot64(idx == first);
-	if (same == m) { // the step's lanes agree on one key
-		const double p = wave_tree_sum_f64(in ? x : 0.0);
-		if (lane == 0u) {
-			s_sums[first] += p;
-			s_cnt[first] += static_cast<uint32_t>(__builtin_popcountll(m));
-		}
-		wave_lds_sync(); // (as every exit of this function: the next step's first LDS access, of any lane, comes behind lane 0's)
-		return;
-	}
-	// the counts of all of m by one LDS atomic; a lane that saw its key's count grow by exactly 1 is alone with that key in this step
-	const uint32_t c0 = in ? s_cnt[idx] : 0u;
-	wave_lds_sync();
-	if (in) { atomicAdd(&s_cnt[idx], 1u); }
-	wave_lds_sync();
-#ifndef ALPGPU_KEYED_BASELINE_STEP
-	const uint32_t c1    = in ? s_cnt[idx] : 0u;
-	const uint64_t alone = ballot64(in && c1 - c0 == 1u);
-	if ((alone >> lane) & 1ull) { s_sums[idx] += x; } // 64 different addresses
-	wave_lds_sync();
-	uint64_t left = m & ~alone;
-#else // the measurement's baseline (tools/time_keyed.py --ab): every key of the step through ballot, tree and lane 0; the same bits
-	(void)c0;
-	uint64_t left = m;
-#endif
-	while (left != 0ull) { // key by key, in the order of the keys' first lanes
-		const uint32_t i = static_cast<uint32_t>(__builtin_amdgcn_readlane(idx, static_cast<uint32_t>(__builtin_ctzll(left))));
-		same             = left & ballot64(idx == i);
-		const double p   = wave_tree_sum_f64(((same >> lane) & 1ull) ? x : 0.0);
-		if (lane == 0u) { s_sums[i] += p; }
-		left &= ~same;
-	}
-	wave_lds_sync();
-}
-
 // One vector pair by one wavefront.  Returns the class of the trace it fell into; unmatched (wave-uniform) takes the selected rows without a key.
 template <int VB, int WAVES>
 __device__ __forceinline__ uint32_t keyed_vector(const ColumnStreams& cv, const ColumnStreams& ck, const KeyedArgs& g, uint64_t v, uint32_t wave, uint32_t lane,
@@ -114,7 +68,7 @@ __device__ __forceinline__ uint32_t keyed_vector(const ColumnStreams& cv, const 
 	typedef typename DecodeVec<VB>::T T;
 	// 1. the selected bits, lane m < 16 holding word m
 	uint64_t sel;
-	if (!selected_words(g.mask, 0ull, g.n_vectors << 10, v, lane, sel)) { return kKeyedSkipZero; }
+	if (!selected_words(g.mask, 0ull, g.n_vectors << 10, v, lane, sel)) { return kVectorSkipZero; }
 
 	// 2. the part [j0, j1) of the keys that the key vector's zone record admits: all of them without a record or with a NaN bound
 	const uint32_t last_key = g.n_keys - 1u;
@@ -129,7 +83,7 @@ __device__ __forceinline__ uint32_t keyed_vector(const ColumnStreams& cv, const 
 			j1 = __builtin_amdgcn_readfirstlane(j[1]);
 			if (j1 <= j0) { // no key lies in the record: rows without a key
 				unmatched += __builtin_amdgcn_readlane(selected_count(sel), 63);
-				return kKeyedNoKey;
+				return kVectorNoEntry;
 			}
 			if (z[0] == z[1] && alp_without_exceptions(ck.descs[v])) { // no NaN can hide here: every selected row has key j0; the value vector alone is decoded
 				const DecodeVec<VB> A = decode_vec_load<VB>(cv, v);
@@ -160,7 +114,7 @@ __device__ __forceinline__ uint32_t keyed_vector(const ColumnStreams& cv, const 
 					s_cnt[j0] += n_rows;
 				}
 				wave_lds_sync();
-				return kKeyedConstant;
+				return kVectorOneEntry;
 			}
 		}
 	}
@@ -195,7 +149,7 @@ __device__ __forceinline__ uint32_t keyed_vector(const ColumnStreams& cv, const 
 			keyed_step(s_sums, s_cnt, m, idx, x[i], lane);
 		}
 	}
-	return kKeyedDecoded;
+	return kVectorDecoded;
 }
 
 __global__ __launch_bounds__(256) void k_keyed_init(uint64_t* counts, uint32_t n_counts, uint64_t* header) {

@@ -1,8 +1,8 @@
 // keyed_minmax_kernels.hip — keyed MIN / MAX (include/alpgpu.h, "keyed MIN / MAX": alpgpu_decode_keyed_minmax_*): the record {min, max} and the COUNT of a
 // value column per key of a sorted key list, the key column decoded beside it, no decoded value reaching HBM.  The parts are keyed_kernels.hip's (the
 // side-by-side decode of register_decode.hpp, lds_bound over the staged keys, selected_words with the constant-vector predicate), k_histogram's
-// skeleton (histogram_kernels.hip) and the records' order of wave_minmax.hpp.  keyed_vector's body is written out again here and not shared through a
-// header: k_keyed_sum's small tier sits 2 registers under its occupancy step (keyed_kernels.hip) and is left as it compiles.
+// skeleton (histogram_kernels.hip) and the records' order of wave_minmax.hpp.  The step (kmm_step, kmm_join, order_key), the count flush
+// and the tiers are keyed_table.hpp's, shared with bucket_kernels.hip; the move was checked against the device assembly (profiles/r29_keyed_tables.txt).
 //
 //   k_keyed_minmax_init   {+inf, -inf} into the n_keys records and 0 into the n_keys + 1 counts: a kernel, no memset node (mask_kernels.hip says why).
 //   k_keyed_minmax<VB, WAVES>
@@ -47,16 +47,9 @@
 // one barrier; 4 wavefronts per workgroup would stage the keys and fill the table twice as often.  Both precisions take the same grid.
 // The guard (read before atomic) is measured against unconditional atomics with -DALPGPU_KEYED_MINMAX_NO_GUARD (tools/time_keyed_minmax.py --ab); the
 // bits are the same.
-#include "minmax_device.hpp"
-#include "persistent_scan.hpp"
-#include "sorted_list.hpp"
+#include "keyed_table.hpp"
 
 namespace alpgpu {
-
-constexpr int      kKmmWaves      = 8;
-constexpr int      kKmmThreads    = 64 * kKmmWaves;
-constexpr int      kKmmWgPerCu    = 2;
-constexpr uint32_t kKmmFlushEvery = 1u << 18; // trips of a workgroup's loop (8 vectors each, at most 8192 increments of one 32-bit LDS count) between two count flushes
 
 struct KeyedMinmaxArgs {
 	uint64_t        n_vectors;
@@ -69,56 +62,6 @@ struct KeyedMinmaxArgs {
 	uint32_t        n_keys; // 1 .. ALPGPU_KEYED_KEYS_MAX
 };
 
-constexpr uint32_t kKmmSkipZero = 0u, kKmmConstant = 1u, kKmmNoKey = 2u, kKmmDecoded = 3u; // what kmm_vector did with a vector: the trace's words (keyed_kernels.hip's)
-
-// the records' order as a signed integer: the value's bits, the negative half turned round (-0.0 -> -1, just below +0.0 -> 0); x is not a NaN
-__device__ __forceinline__ long long order_key(double x) {
-	const long long b = __double_as_longlong(x);
-	return b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFll);
-}
-__device__ __forceinline__ int order_key(float x) {
-	const int b = static_cast<int>(__float_as_uint(x));
-	return b ^ ((b >> 31) & 0x7FFFFFFF);
-}
-
-// a wave-uniform record {mn, mx} (lane 0 acts) into entry i of the table, unless it is the empty one
-template <class T>
-__device__ __forceinline__ void kmm_join(T* s_mn, T* s_mx, uint32_t i, T mn, T mx, uint32_t lane) {
-	if (lane == 0u && mn <= mx) { // ({+inf, -inf}: no number was fed; -0.0 <= +0.0 and inf <= inf hold)
-		atomic_min_value(&s_mn[i], mn);
-		atomic_max_value(&s_mx[i], mx);
-	}
-}
-
-// One step's selected, matched lanes m (wave-uniform) into the workgroup's table: lane l holds the canonical value q and the key index idx (< n_keys where its bit of m is set).
-template <class T>
-__device__ __forceinline__ void kmm_step(T* s_mn, T* s_mx, uint32_t* s_cnt, bool counted, uint64_t m, uint32_t idx, T q, uint32_t lane) {
-	if (m == 0ull) { return; }
-	const bool     in    = (m >> lane) & 1ull;
-	const uint32_t first = static_cast<uint32_t>(__builtin_amdgcn_readlane(idx, static_cast<uint32_t>(__builtin_ctzll(m))));
-	if ((m & ballot64(idx == first)) == m) { // the step's lanes agree on one key
-		T mn = pos_inf<T>(), mx = -pos_inf<T>();
-		minmax_feed(mn, mx, in ? q : minmax_skip<T>()); // (a NaN q is a quiet one: skipped)
-		wave_minmax<T>(mn, mx);
-		kmm_join(s_mn, s_mx, first, mn, mx, lane);
-		if (counted && lane == 0u) { atomicAdd(&s_cnt[first], static_cast<uint32_t>(__builtin_popcountll(m))); }
-		return;
-	}
-	if (in) {
-		if (q == q) {
-#ifndef ALPGPU_KEYED_MINMAX_NO_GUARD
-			const auto k = order_key(q);
-			if (k < order_key(s_mn[idx])) { atomic_min_value(&s_mn[idx], q); }
-			if (k > order_key(s_mx[idx])) { atomic_max_value(&s_mx[idx], q); }
-#else // the measurement's other arm (tools/time_keyed_minmax.py --ab): every number issues both atomics; the same bits
-			atomic_min_value(&s_mn[idx], q);
-			atomic_max_value(&s_mx[idx], q);
-#endif
-		}
-		if (counted) { atomicAdd(&s_cnt[idx], 1u); }
-	}
-}
-
 // One vector pair by one wavefront.  Returns the class of the trace it fell into.  s_cnt[n_keys] takes the selected rows without a key.
 template <int VB>
 __device__ __forceinline__ uint32_t kmm_vector(const ColumnStreams& cv, const ColumnStreams& ck, const KeyedMinmaxArgs& g, uint64_t v, uint32_t wave, uint32_t lane,
@@ -128,7 +71,7 @@ __device__ __forceinline__ uint32_t kmm_vector(const ColumnStreams& cv, const Co
 	const bool counted = g.counts != nullptr;
 	// 1. the selected bits, lane m < 16 holding word m
 	uint64_t sel;
-	if (!selected_words(g.mask, 0ull, g.n_vectors << 10, v, lane, sel)) { return kKmmSkipZero; }
+	if (!selected_words(g.mask, 0ull, g.n_vectors << 10, v, lane, sel)) { return kVectorSkipZero; }
 
 	// 2. the part [j0, j1) of the keys that the key vector's zone record admits: all of them without a record or with a NaN bound
 	const uint32_t last_key = g.n_keys - 1u;
@@ -146,7 +89,7 @@ __device__ __forceinline__ uint32_t kmm_vector(const ColumnStreams& cv, const Co
 					const uint32_t n = selected_count(sel);
 					if (lane == 63u) { atomicAdd(&s_cnt[g.n_keys], n); }
 				}
-				return kKmmNoKey;
+				return kVectorNoEntry;
 			}
 			if (z[0] == z[1] && alp_without_exceptions(ck.descs[v])) { // no NaN can hide here: every selected row has key j0; the value vector alone is decoded
 				const DecodeVec<VB> A = decode_vec_load<VB>(cv, v);
@@ -172,7 +115,7 @@ __device__ __forceinline__ uint32_t kmm_vector(const ColumnStreams& cv, const Co
 				wave_minmax<T>(mn, mx);
 				kmm_join(s_mn, s_mx, j0, mn, mx, lane);
 				if (counted && lane == 0u) { atomicAdd(&s_cnt[j0], n_rows); }
-				return kKmmConstant;
+				return kVectorOneEntry;
 			}
 		}
 	}
@@ -208,7 +151,7 @@ __device__ __forceinline__ uint32_t kmm_vector(const ColumnStreams& cv, const Co
 		}
 	}
 	if (counted && unmatched != 0u && lane == 0u) { atomicAdd(&s_cnt[g.n_keys], unmatched); }
-	return kKmmDecoded;
+	return kVectorDecoded;
 }
 
 template <class T>
@@ -219,19 +162,6 @@ __global__ __launch_bounds__(256) void k_keyed_minmax_init(T* out, uint32_t n_ke
 		out[2u * i + 1u] = -pos_inf<T>();
 	}
 	if (counts != nullptr && i <= n_keys) { counts[i] = 0ull; }
-}
-
-// the workgroup's non-zero LDS counts into the call's and zeroed again; a barrier in front and behind
-__device__ __forceinline__ void kmm_counts_flush(uint32_t* s_cnt, uint32_t n, uint64_t* counts) {
-	__syncthreads();
-	for (uint32_t i = threadIdx.x; i < n; i += kKmmThreads) {
-		const uint32_t c = s_cnt[i];
-		if (c != 0u) {
-			atomicAdd(reinterpret_cast<unsigned long long*>(counts) + i, static_cast<unsigned long long>(c));
-			s_cnt[i] = 0u;
-		}
-	}
-	__syncthreads();
 }
 
 template <int VB, int WAVES>

@@ -1,8 +1,8 @@
 // keyed_minmax_many_kernels.hip — keyed MIN / MAX for up to 2^20 keys (include/alpgpu.h, "keyed MIN / MAX, many keys": alpgpu_decode_keyed_minmax_many_*):
 // the record {min, max} and the COUNT of a value column per key of a sorted key list, the key column decoded beside it, no decoded value reaching HBM.
 // kmm_vector's per-vector flow (keyed_minmax_kernels.hip) on k_join_probe's list handling (join_kernels.hip, sorted_list.hpp): the keys no longer
-// have to fit LDS, and the table is the call's outputs themselves.  A translation unit of its own, so that the kernels of keyed_kernels.hip and
-// keyed_minmax_kernels.hip compile as they did (k_keyed_sum's small tier sits 2 registers under its occupancy step).
+// have to fit LDS, and the table is the call's outputs themselves.  The records' order key and the trace's classes are
+// keyed_table.hpp's; the move was checked against the device assembly (profiles/r29_keyed_tables.txt).
 //
 //   k_keyed_minmax_many<VB, GLOBAL>
 //                         persistent workgroups of kInWaves wavefronts.  The workgroup stages the sorted keys (GLOBAL: every stride-th of them, the
@@ -41,9 +41,7 @@
 // amdgpu_waves_per_eu(4): left to itself the compiler takes 129 VGPRs for the double kernels (103 for float), one beyond the edge of 4 wavefronts
 // per SIMD; asked for 4 it keeps 124 and still no scratch, so the search runs in batches of kStepBatch values in all four and no smaller batch
 // was needed.  kManyWgPerCu = 2: two workgroups of 8 wavefronts are those 4 wavefronts per SIMD; their LDS, 2 x 34 KiB, decides nothing.
-#include "minmax_device.hpp"
-#include "persistent_scan.hpp"
-#include "sorted_list.hpp"
+#include "keyed_table.hpp"
 
 namespace alpgpu {
 
@@ -57,18 +55,6 @@ struct KeyedManyArgs {
 	uint64_t*       trace;  // nullable: 4 words, added to
 };
 
-constexpr uint32_t kManySkipZero = 0u, kManyConstant = 1u, kManyNoKey = 2u, kManyDecoded = 3u; // what kmany_vector did with a vector: the trace's words (keyed_kernels.hip's)
-
-// the records' order as a signed integer: the value's bits, the negative half turned round (-0.0 -> -1, just below +0.0 -> 0); x is not a NaN
-__device__ __forceinline__ long long many_order_key(double x) {
-	const long long b = __double_as_longlong(x);
-	return b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFll);
-}
-__device__ __forceinline__ int many_order_key(float x) {
-	const int b = static_cast<int>(__float_as_uint(x));
-	return b ^ ((b >> 31) & 0x7FFFFFFF);
-}
-
 // The number q (not a NaN) into record i of d_out, by the calling lane: the guard and the atomics.
 // Why the guard is safe.  Between k_keyed_minmax_init and the kernel's end, out[2 i] only ever falls and out[2 i + 1] only ever rises in the records'
 // order: every writer is an atomic minimum or maximum.  The plain loads below may be served by this CU's L1 or, for a record last written from another
@@ -80,9 +66,9 @@ __device__ __forceinline__ int many_order_key(float x) {
 // init kernel wrote an infinity and an atomic only ever carries a number.
 template <class T>
 __device__ __forceinline__ void kmany_update(T* out, uint32_t i, T q) {
-	const auto k = many_order_key(q);
-	if (k < many_order_key(out[2u * i])) { atomic_min_value(&out[2u * i], q); }
-	if (k > many_order_key(out[2u * i + 1u])) { atomic_max_value(&out[2u * i + 1u], q); }
+	const auto k = order_key(q);
+	if (k < order_key(out[2u * i])) { atomic_min_value(&out[2u * i], q); }
+	if (k > order_key(out[2u * i + 1u])) { atomic_max_value(&out[2u * i + 1u], q); }
 }
 
 // a wave-uniform record {mn, mx} (lane 0 acts) into record i, unless it is the empty one.  mn and mx go through the same guard: a sorted key column
@@ -90,8 +76,8 @@ __device__ __forceinline__ void kmany_update(T* out, uint32_t i, T q) {
 template <class T>
 __device__ __forceinline__ void kmany_join(T* out, uint32_t i, T mn, T mx, uint32_t lane) {
 	if (lane == 0u && mn <= mx) { // ({+inf, -inf}: no number was fed; -0.0 <= +0.0 and inf <= inf hold)
-		if (many_order_key(mn) < many_order_key(out[2u * i])) { atomic_min_value(&out[2u * i], mn); }
-		if (many_order_key(mx) > many_order_key(out[2u * i + 1u])) { atomic_max_value(&out[2u * i + 1u], mx); }
+		if (order_key(mn) < order_key(out[2u * i])) { atomic_min_value(&out[2u * i], mn); }
+		if (order_key(mx) > order_key(out[2u * i + 1u])) { atomic_max_value(&out[2u * i + 1u], mx); }
 	}
 }
 
@@ -130,7 +116,7 @@ __device__ __forceinline__ uint32_t kmany_vector(const ColumnStreams& cv, const 
 	const uint32_t last_key = g.n_list - 1u;
 	// 1. the selected bits, lane m < 16 holding word m
 	uint64_t sel;
-	if (!selected_words(a.mask, 0ull, a.n_vectors << 10, v, lane, sel)) { return kManySkipZero; }
+	if (!selected_words(a.mask, 0ull, a.n_vectors << 10, v, lane, sel)) { return kVectorSkipZero; }
 
 	// 2. the part [j0, j1) of the keys that the key vector's zone record admits: all of them without a record or with a NaN bound
 	uint32_t j0 = 0u, j1 = g.n_list;
@@ -141,7 +127,7 @@ __device__ __forceinline__ uint32_t kmany_vector(const ColumnStreams& cv, const 
 				const uint32_t n = selected_count(sel);
 				if (lane == 63u) { kmany_count(a.counts, g.n_list, n); }
 			}
-			return kManyNoKey;
+			return kVectorNoEntry;
 		}
 		const T* zone = static_cast<const T*>(g.zones) + 2 * v; // (wave-uniform)
 		if (zone[0] == zone[1] && alp_without_exceptions(ck.descs[v])) { // (no NaN bound is equal) no NaN can hide here: every selected row has key j0; the value vector alone is decoded
@@ -169,7 +155,7 @@ __device__ __forceinline__ uint32_t kmany_vector(const ColumnStreams& cv, const 
 			const uint32_t i0 = j0 < last_key ? j0 : last_key; // (j0 < j1 <= n_list: the clamp changes nothing and costs one instruction)
 			kmany_join(out, i0, mn, mx, lane);
 			if (counted && lane == 0u) { kmany_count(a.counts, i0, n_rows); }
-			return kManyConstant;
+			return kVectorOneEntry;
 		}
 	}
 
@@ -207,7 +193,7 @@ __device__ __forceinline__ uint32_t kmany_vector(const ColumnStreams& cv, const 
 		}
 	}
 	if (counted && unmatched != 0u && lane == 0u) { kmany_count(a.counts, g.n_list, unmatched); }
-	return kManyDecoded;
+	return kVectorDecoded;
 }
 
 template <int VB, bool GLOBAL>

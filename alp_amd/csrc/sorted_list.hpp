@@ -3,7 +3,7 @@
 // (keyed_kernels.hip: its keys), k_keyed_minmax (keyed_minmax_kernels.hip: its keys) and k_bucket_sum / k_bucket_minmax (bucket_kernels.hip: their edges) share, and, for the first two and k_keyed_minmax_many
 // (keyed_minmax_many_kernels.hip), the workgroup shape, the record that says what was staged (InArgs; k_join_probe and k_keyed_minmax_many leave
 // the bitmap fields zero), the staging loop, in_list_search with its pivot tier, the zone bounds and the fetch for the equality test.  Only those
-// seven files include this header.
+// seven files include this header, the last four through keyed_table.hpp.
 #pragma once
 #include "launch.hpp"
 #include "register_decode.hpp"
