@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from functools import partialmethod
 
 import numpy as np
 # torch ships its own libamdhip64.so (same SONAME as /opt/rocm's).  It MUST be loaded first so that
@@ -280,6 +281,15 @@ def _check(rc: int, what: str):
         raise AlpGpuError(f"{what} failed ({rc}): {lib.alpgpu_last_error().decode()}")
 
 
+_TORCH_TYPE = {"f64": torch.float64, "f32": torch.float32}  # a column's dtype -> its value type
+_NUMPY_TYPE = {"f64": np.float64, "f32": np.float32}
+
+
+def _ptr(t):
+    """an optional argument's address: NULL for None and for a tensor without elements (whose data_ptr() is 0 already)"""
+    return _vp(t.data_ptr()) if t is not None and t.numel() else None
+
+
 class Context:
     """One per device / process.  With use_torch_stream (default) every call is enqueued on torch's CURRENT stream of the
     device at the time of the call (so `with torch.cuda.stream(s):` works as for torch's own ops); set_stream() pins a
@@ -297,7 +307,6 @@ class Context:
     def h(self):
         """the context handle; re-points the context at torch's current stream first when it follows torch"""
         if self._follow_torch and self._h:
-            import torch
             cur = torch.cuda.current_stream(self.device).cuda_stream
             if cur != self._last_stream:
                 _check(lib.alpgpu_set_stream(self._h, _vp(cur)), "alpgpu_set_stream")
@@ -350,7 +359,6 @@ class Context:
     @staticmethod
     def compress_host_multi(ctxs, x_host, blob_host=None):
         """alpgpu_compress_host_multi_*: the host column cut into whole-rowgroup shards over the contexts (one per GPU, normally), one blob"""
-        import torch
         t = "f64" if x_host.dtype == torch.float64 else "f32"
         n = (x_host.numel() + 1023) // 1024
         if blob_host is None:
@@ -364,7 +372,6 @@ class Context:
 
     @staticmethod
     def decompress_host_multi(ctxs, blob_host, out_host):
-        import torch
         t = "f64" if out_host.dtype == torch.float64 else "f32"
         arr = (_vp * len(ctxs))(*[c.h for c in ctxs])
         nv = _u64()
@@ -441,7 +448,6 @@ class Context:
     # points, float32 / "f32" -> *_f32.
     @staticmethod
     def _sfx(x):
-        import torch
         assert x.dtype in (torch.float64, torch.float32)
         return "f64" if x.dtype == torch.float64 else "f32"
 
@@ -515,87 +521,87 @@ class Context:
         return pb.value, eb.value, ov.value
 
     # ---- batch primitives (torch tensors on this device; shapes [n, 1024] unless noted) ---------------
-    @staticmethod
-    def _p(t):
-        return _vp(t.data_ptr()) if t is not None else _vp(0)
+    # One body per primitive takes the entry point's suffix; the public names are the double codec's (i64 / f64 words), its ALP_RD streams'
+    # (u16 / u8) and, with _i32 / _f32, the float codec's (32-bit words, the same argument shapes).
+    def _ffor(self, sfx, vals, packed, bw, base):
+        self._call("ffor", sfx, _ptr(vals), _ptr(packed), packed.shape[1], _ptr(bw), _ptr(base), vals.shape[0])
 
-    def ffor_i64(self, vals, packed, bw, base):
-        _check(lib.alpgpu_ffor_i64(self.h, self._p(vals), self._p(packed), packed.shape[1], self._p(bw), self._p(base), vals.shape[0]), "alpgpu_ffor_i64")
+    def _unffor(self, sfx, packed, out, bw, base):
+        self._call("unffor", sfx, _ptr(packed), packed.shape[1], _ptr(out), _ptr(bw), _ptr(base), out.shape[0])
 
-    def unffor_i64(self, packed, out, bw, base):
-        _check(lib.alpgpu_unffor_i64(self.h, self._p(packed), packed.shape[1], self._p(out), self._p(bw), self._p(base), out.shape[0]), "alpgpu_unffor_i64")
+    def _falp(self, sfx, packed, out, bw, base, fac, exp):
+        self._call("falp", sfx, _ptr(packed), packed.shape[1], _ptr(out), _ptr(bw), _ptr(base), _ptr(fac), _ptr(exp), out.shape[0])
 
-    def ffor_u16(self, vals, packed, bw, base=None):
-        _check(lib.alpgpu_ffor_u16(self.h, self._p(vals), self._p(packed), packed.shape[1], self._p(bw), self._p(base), vals.shape[0]), "alpgpu_ffor_u16")
+    def _decode_values(self, sfx, enc, out, fac, exp):
+        self._call("decode_values", sfx, _ptr(enc), _ptr(out), _ptr(fac), _ptr(exp), out.shape[0])
+
+    def _patch(self, sfx, out, exc, pos, cnt):
+        self._call("patch", sfx, _ptr(out), _ptr(exc), _ptr(pos), exc.shape[1], _ptr(cnt), out.shape[0])
+
+    def _encode_simdized(self, sfx, x, exc, pos, cnt, enc, fac, exp):
+        self._call("encode_simdized", sfx, _ptr(x), _ptr(exc), _ptr(pos), exc.shape[1], _ptr(cnt), _ptr(enc), _ptr(fac), _ptr(exp), x.shape[0])
+
+    def _encode_values(self, sfx, x, states, state_idx, exc, pos, cnt, enc, fac, exp):
+        self._call("encode_values", sfx, _ptr(x), _ptr(states), _ptr(state_idx), _ptr(exc), _ptr(pos), exc.shape[1], _ptr(cnt), _ptr(enc), _ptr(fac), _ptr(exp),
+                   x.shape[0])
+
+    def _analyze_ffor(self, sfx, enc, bw, base):
+        self._call("analyze_ffor", sfx, _ptr(enc), _ptr(bw), _ptr(base), enc.shape[0])
+
+    def _rd_encode_vectors(self, sfx, x, states, state_idx, exc, pos, cnt, right, left):
+        self._call("rd_encode_vectors", sfx, _ptr(x), _ptr(states), _ptr(state_idx), _ptr(exc), _ptr(pos), exc.shape[1], _ptr(cnt), _ptr(right), _ptr(left),
+                   x.shape[0])
+
+    def _rd_decode_vectors(self, sfx, out, right, left, states, state_idx, exc, pos, cnt):
+        self._call("rd_decode_vectors", sfx, _ptr(out), _ptr(right), _ptr(left), _ptr(states), _ptr(state_idx), _ptr(exc), _ptr(pos), exc.shape[1], _ptr(cnt),
+                   out.shape[0])
+
+    ffor_i64, ffor_i32 = partialmethod(_ffor, "i64"), partialmethod(_ffor, "i32")
+    unffor_i64, unffor_i32 = partialmethod(_unffor, "i64"), partialmethod(_unffor, "i32")
+    falp, falp_f32 = partialmethod(_falp, "f64"), partialmethod(_falp, "f32")
+    decode_values, decode_values_f32 = partialmethod(_decode_values, "f64"), partialmethod(_decode_values, "f32")
+    patch, patch_f32 = partialmethod(_patch, "f64"), partialmethod(_patch, "f32")
+    encode_simdized, encode_simdized_f32 = partialmethod(_encode_simdized, "f64"), partialmethod(_encode_simdized, "f32")
+    encode_values, encode_values_f32 = partialmethod(_encode_values, "f64"), partialmethod(_encode_values, "f32")
+    analyze_ffor, analyze_ffor_i32 = partialmethod(_analyze_ffor, "i64"), partialmethod(_analyze_ffor, "i32")
+    rd_encode_vectors, rd_encode_vectors_f32 = partialmethod(_rd_encode_vectors, "f64"), partialmethod(_rd_encode_vectors, "f32")
+    rd_decode_vectors, rd_decode_vectors_f32 = partialmethod(_rd_decode_vectors, "f64"), partialmethod(_rd_decode_vectors, "f32")
+
+    def ffor_u16(self, vals, packed, bw, base=None):  # (the ALP_RD streams pack without a base)
+        self._ffor("u16", vals, packed, bw, base)
 
     def unffor_u16(self, packed, out, bw, base=None):
-        _check(lib.alpgpu_unffor_u16(self.h, self._p(packed), packed.shape[1], self._p(out), self._p(bw), self._p(base), out.shape[0]), "alpgpu_unffor_u16")
+        self._unffor("u16", packed, out, bw, base)
 
     def ffor_u8(self, vals, packed, bw, base=None):
-        _check(lib.alpgpu_ffor_u8(self.h, self._p(vals), self._p(packed), packed.shape[1], self._p(bw), self._p(base), vals.shape[0]), "alpgpu_ffor_u8")
+        self._ffor("u8", vals, packed, bw, base)
 
     def unffor_u8(self, packed, out, bw, base=None):
-        _check(lib.alpgpu_unffor_u8(self.h, self._p(packed), packed.shape[1], self._p(out), self._p(bw), self._p(base), out.shape[0]), "alpgpu_unffor_u8")
-
-    def falp(self, packed, out, bw, base, fac, exp):
-        _check(lib.alpgpu_falp_f64(self.h, self._p(packed), packed.shape[1], self._p(out), self._p(bw), self._p(base), self._p(fac), self._p(exp),
-                                   out.shape[0]), "alpgpu_falp_f64")
-
-    def decode_values(self, enc, out, fac, exp):
-        _check(lib.alpgpu_decode_values_f64(self.h, self._p(enc), self._p(out), self._p(fac), self._p(exp), out.shape[0]), "alpgpu_decode_values_f64")
-
-    def patch(self, out, exc, pos, cnt):
-        _check(lib.alpgpu_patch_f64(self.h, self._p(out), self._p(exc), self._p(pos), exc.shape[1], self._p(cnt), out.shape[0]), "alpgpu_patch_f64")
-
-    def encode_simdized(self, x, exc, pos, cnt, enc, fac, exp):
-        _check(lib.alpgpu_encode_simdized_f64(self.h, self._p(x), self._p(exc), self._p(pos), exc.shape[1], self._p(cnt), self._p(enc),
-                                              self._p(fac), self._p(exp), x.shape[0]), "alpgpu_encode_simdized_f64")
-
-    def encode_values(self, x, states, state_idx, exc, pos, cnt, enc, fac, exp):
-        _check(lib.alpgpu_encode_values_f64(self.h, self._p(x), self._p(states), self._p(state_idx), self._p(exc), self._p(pos), exc.shape[1],
-                                            self._p(cnt), self._p(enc), self._p(fac), self._p(exp), x.shape[0]), "alpgpu_encode_values_f64")
+        self._unffor("u8", packed, out, bw, base)
 
     def encode_value(self, x, fac: int, exp: int, safe: bool = True):
         """alpgpu_encode_value_f64 / _f32 on a 1-d device tensor: the encoded integers (int64 / int32)"""
-        import torch
         f64 = x.dtype == torch.float64
         out = torch.empty(x.numel(), dtype=torch.int64 if f64 else torch.int32, device=x.device)
-        fn = lib.alpgpu_encode_value_f64 if f64 else lib.alpgpu_encode_value_f32
-        _check(fn(self.h, self._p(x), self._p(out), fac, exp, 1 if safe else 0, x.numel()), "alpgpu_encode_value")
+        self._call("encode_value", "f64" if f64 else "f32", _ptr(x), _ptr(out), fac, exp, 1 if safe else 0, x.numel())
         return out
-
-    def analyze_ffor(self, enc, bw, base):
-        _check(lib.alpgpu_analyze_ffor_i64(self.h, self._p(enc), self._p(bw), self._p(base), enc.shape[0]), "alpgpu_analyze_ffor_i64")
-
-    def rd_encode_vectors(self, x, states, state_idx, exc, pos, cnt, right, left):
-        _check(lib.alpgpu_rd_encode_vectors_f64(self.h, self._p(x), self._p(states), self._p(state_idx), self._p(exc), self._p(pos), exc.shape[1],
-                                                self._p(cnt), self._p(right), self._p(left), x.shape[0]), "alpgpu_rd_encode_vectors_f64")
-
-    def rd_decode_vectors(self, out, right, left, states, state_idx, exc, pos, cnt):
-        _check(lib.alpgpu_rd_decode_vectors_f64(self.h, self._p(out), self._p(right), self._p(left), self._p(states), self._p(state_idx),
-                                                self._p(exc), self._p(pos), exc.shape[1], self._p(cnt), out.shape[0]), "alpgpu_rd_decode_vectors_f64")
 
     def decode_count_range(self, col: "DeviceColumn", lo: float, hi: float, out=None):
         """per-vector count of decoded values in [lo, hi] without materialising them (alpgpu_decode_count_range_f64 / _f32)"""
-        import torch
         if out is None:
             out = torch.empty(col.n_vectors, dtype=torch.int32, device=f"cuda:{self.device}")
-        fn = lib.alpgpu_decode_count_range_f64 if col.dtype == "f64" else lib.alpgpu_decode_count_range_f32
-        _check(fn(self.h, C.byref(col.c), lo, hi, _vp(out.data_ptr())), "alpgpu_decode_count_range")
+        self._call("decode_count_range", col.dtype, C.byref(col.c), lo, hi, _vp(out.data_ptr()))
         return out
 
     def column_sum(self, col: "DeviceColumn", out=None):
         """the whole column's total in the documented tree order (alpgpu_column_sum_f64 / _f32): a 1-element float64 tensor"""
-        import torch
         if out is None:
             out = torch.empty(1, dtype=torch.float64, device=col.vectors.device)
-        fn = lib.alpgpu_column_sum_f64 if col.dtype == "f64" else lib.alpgpu_column_sum_f32
-        _check(fn(self.h, C.byref(col.c), _vp(out.data_ptr())), "alpgpu_column_sum")
+        self._call("column_sum", col.dtype, C.byref(col.c), _vp(out.data_ptr()))
         return out
 
     def tree_sum(self, x, out=None):
         """alpgpu_tree_sum_f64 over a float64 device tensor"""
-        import torch
         if out is None:
             out = torch.empty(1, dtype=torch.float64, device=x.device)
         _check(lib.alpgpu_tree_sum_f64(self.h, _vp(x.data_ptr()), x.numel(), _vp(out.data_ptr())), "alpgpu_tree_sum_f64")
@@ -613,16 +619,13 @@ class Context:
 
     def decode_sum(self, col: "DeviceColumn", out=None):
         """per-vector sums (float64) of the decoded values without materialising them (alpgpu_decode_sum_f64 / _f32)"""
-        import torch
         if out is None:
             out = torch.empty(col.n_vectors, dtype=torch.float64, device=f"cuda:{self.device}")
-        fn = lib.alpgpu_decode_sum_f64 if col.dtype == "f64" else lib.alpgpu_decode_sum_f32
-        _check(fn(self.h, C.byref(col.c), _vp(out.data_ptr())), "alpgpu_decode_sum")
+        self._call("decode_sum", col.dtype, C.byref(col.c), _vp(out.data_ptr()))
         return out
 
     def decode(self, col: "DeviceColumn", out=None):
-        import torch
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        tdt = _TORCH_TYPE[col.dtype]
         if out is None:
             out = torch.empty(col.n_vectors * VECTOR_SIZE, dtype=tdt, device=f"cuda:{self.device}")
         assert out.is_contiguous() and out.numel() >= col.n_vectors * VECTOR_SIZE and out.dtype == tdt
@@ -633,35 +636,123 @@ class Context:
     def gather(self, col: "DeviceColumn", idx, out=None):
         """the values at the value indices idx (a contiguous int64 tensor on this context's device; any order, repeats allowed) as a float64 /
         float32 tensor; an index outside [0, n_vectors * 1024) gives the canonical quiet NaN"""
-        import torch
-        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or not idx.is_cuda or idx.device.index != self.device or not idx.is_contiguous():
-            raise ValueError("idx must be a contiguous int64 tensor on cuda:%d" % self.device)
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        self._check_tensor(idx, torch.int64, "idx")
+        tdt = _TORCH_TYPE[col.dtype]
         if out is None:
-            out = torch.empty(idx.numel(), dtype=tdt, device=f"cuda:{self.device}")
+            out = torch.empty(idx.numel(), dtype=tdt, device=self._dev)
         assert out.is_contiguous() and out.numel() >= idx.numel() and out.dtype == tdt
         self._call("gather", col.dtype, C.byref(col.c), _vp(idx.data_ptr()), idx.numel(), _vp(out.data_ptr()))
         return out
 
     def decode_slice(self, col: "DeviceColumn", first: int, n: int, out=None):
         """values first .. first + n - 1 of the column (any first); AlpGpuError if the slice reaches past the column's n_vectors * 1024 values"""
-        import torch
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        tdt = _TORCH_TYPE[col.dtype]
         if out is None:
-            out = torch.empty(max(0, int(n)), dtype=tdt, device=f"cuda:{self.device}")
+            out = torch.empty(max(0, int(n)), dtype=tdt, device=self._dev)
         assert out.is_contiguous() and out.numel() >= n and out.dtype == tdt
         self._call("decode_slice", col.dtype, C.byref(col.c), first, n, _vp(out.data_ptr()))
         return out
 
-    # ---- selection (include/alpgpu.h: alpgpu_select_range_*) --------------------------------------------------------
+    # ---- the argument rules the query wrappers share: each refuses with ValueError, and nothing here touches the device but _scratch and the
+    # last lines of _list_to_device ---------------------------------------------------------------------------------------
+    @property
+    def _dev(self):
+        return f"cuda:{self.device}"
+
     def _check_tensor(self, t, dtype, name):
-        import torch
         if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or t.device.index != self.device or not t.is_contiguous():
             raise ValueError("%s must be a contiguous %s tensor on cuda:%d" % (name, str(dtype).replace("torch.", ""), self.device))
 
+    def _check_shape(self, t, dtype, name, shape, what, records=False):
+        """an output of exactly this shape (what: the shape in the caller's words); records: rows {min, max}, aligned to them"""
+        self._check_tensor(t, dtype, name)
+        if tuple(t.shape) != tuple(shape) or (records and t.data_ptr() % (2 * t.element_size())):
+            raise ValueError("%s must be a contiguous %s tensor of shape %s%s" % (name, str(dtype).replace("torch.", ""), what, ", aligned to its records" if records else ""))
+
+    def _check_at_least(self, t, dtype, name, n, what):
+        """an output of at least n elements (what: that number in the caller's words)"""
+        self._check_tensor(t, dtype, name)
+        if t.numel() < n:
+            raise ValueError("%s must hold %s" % (name, what))
+
+    @staticmethod
+    def _range(col, first, n):
+        """(first, n) of a call over the value indices [first, first + n): n None is the rest of the column"""
+        first = int(first)
+        n = col.n_vectors * VECTOR_SIZE - first if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        return first, n
+
+    def _check_mask_zones(self, mask, zones, col):
+        """the optional bitmap and the optional records of a column's vectors (of two paired columns: of either)"""
+        if mask is not None:
+            self._check_mask(mask, col.n_vectors)
+        if zones is not None:
+            self._check_zones(zones, _TORCH_TYPE[col.dtype], col.n_vectors)
+
+    def _check_trace(self, trace, words=4):
+        if trace is not None:
+            self._check_tensor(trace, torch.int64, "trace")
+            if trace.numel() != words:
+                raise ValueError("trace must hold %d int64 words" % words)
+
+    def _scratch(self, scratch, need, what):
+        """the scratch of a call that needs `need` bytes (what: that number in the caller's words): a new one for None, else the caller's, checked"""
+        if scratch is None:
+            return torch.empty(need, dtype=torch.uint8, device=self._dev)
+        self._check_tensor(scratch, torch.uint8, "scratch")
+        if scratch.numel() < need or scratch.data_ptr() % 16:
+            raise ValueError("scratch must hold %s bytes, 16-byte aligned" % what)
+        return scratch
+
+    @staticmethod
+    def _check_len(t, what, lo, hi):
+        if t.dim() != 1 or t.numel() < lo or (hi is not None and t.numel() > hi):
+            raise ValueError("%s must be one-dimensional and hold %s elements" % (what, "any number of" if hi is None else "%d .. %d" % (lo, hi)))
+
+    def _check_list(self, t, what, col, lo=0, hi=None):
+        """the raw forms' list (keys, edges): a contiguous one-dimensional tensor of the column's type on this device, lo .. hi long; returns its length"""
+        if not isinstance(t, torch.Tensor) or t.dtype != _TORCH_TYPE[col.dtype]:
+            raise ValueError("%s must be a tensor of the column's type (%s)" % (what, col.dtype))
+        self._check_len(t, what, lo, hi)
+        if not t.is_cuda or t.device.index != self.device or not t.is_contiguous():
+            raise ValueError("%s must be contiguous on cuda:%d" % (what, self.device))
+        return t.numel()
+
+    def _list_to_device(self, values, what, col, lo=0, hi=None, sorted=False, want_perm=False):
+        """the allocating wrappers' list: a device tensor, host tensor, numpy array (of the column's type: none is converted) or sequence (converted
+        to it), one-dimensional and lo .. hi long, as the contiguous device tensor the raw form wants, in order by torch.sort on the device unless
+        sorted.  want_perm: (list, the sort's permutation or None).  Every refusal comes before anything is moved to or allocated on the device."""
+        if isinstance(values, np.ndarray):
+            if values.dtype != _NUMPY_TYPE[col.dtype]:
+                raise ValueError("%s must be of the column's type (%s)" % (what, col.dtype))
+            values = torch.from_numpy(np.ascontiguousarray(values))
+        elif not isinstance(values, torch.Tensor):
+            values = torch.tensor(list(values), dtype=_TORCH_TYPE[col.dtype])
+        if values.dtype != _TORCH_TYPE[col.dtype]:
+            raise ValueError("%s must be of the column's type (%s)" % (what, col.dtype))
+        self._check_len(values, what, lo, hi)
+        if values.is_cuda and values.device.index != self.device:
+            raise ValueError("%s must be on the host or on cuda:%d" % (what, self.device))
+        lst = values if values.is_cuda else values.to(self._dev)
+        lst, perm = (lst.contiguous(), None) if sorted else torch.sort(lst)
+        return (lst, perm) if want_perm else lst
+
+    def _call_tuned(self, stem, sfx, args, tuning, trace, record, fields):
+        """the plain entry, or with a tuning dict or a trace tensor given debug_<stem>: the same arguments, then the tuning record (a field the
+        dict leaves out is 0: the library's choice) and the trace"""
+        if tuning is None and trace is None:
+            return self._call(stem, sfx, *args)
+        tuning = {} if tuning is None else tuning
+        if set(tuning) - set(fields):
+            raise ValueError("tuning takes " + ", ".join(fields))
+        t = record(*[int(tuning.get(k, 0)) for k in fields])
+        self._call("debug_" + stem, sfx, *args, C.byref(t), _ptr(trace))
+
+    # ---- selection (include/alpgpu.h: alpgpu_select_range_*) --------------------------------------------------------
     def select_scratch(self, col: "DeviceColumn"):
         """a scratch tensor for select_range_into on this column (alpgpu_select_scratch_bytes; torch allocations are at least 16-byte aligned)"""
-        import torch
         return torch.empty(lib.alpgpu_select_scratch_bytes(col.n_vectors), dtype=torch.uint8, device=f"cuda:{self.device}")
 
     def select_range_into(self, col: "DeviceColumn", lo: float, hi: float, idx_out, count_out, vals_out=None, first: int = 0, n: int = None, scratch=None, zones=None):
@@ -670,31 +761,17 @@ class Context:
         least as long), their number to count_out (one int64, the full count also beyond the capacity).  Nothing is synchronised and nothing
         read back; with a scratch given (select_scratch) nothing is allocated either, so the call can be captured into a graph.
         zones (zone_map(col)): alpgpu_select_range_zoned_* — the same result, vectors whose record excludes or contains them are not decoded."""
-        import torch
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
-        self._check_tensor(count_out, torch.int64, "count_out")
-        if count_out.numel() < 1:
-            raise ValueError("count_out must hold one int64")
+        tdt = _TORCH_TYPE[col.dtype]
+        self._check_at_least(count_out, torch.int64, "count_out", 1, "one int64")
         capacity = 0
         if idx_out is not None:
             self._check_tensor(idx_out, torch.int64, "idx_out")
             capacity = idx_out.numel()
         if vals_out is not None:
-            self._check_tensor(vals_out, tdt, "vals_out")
-            if vals_out.numel() < capacity:
-                raise ValueError("vals_out is shorter than idx_out")
-        first = int(first)
-        n = col.n_vectors * VECTOR_SIZE - first if n is None else int(n)
-        if first < 0 or n < 0:
-            raise ValueError("first and n must not be negative")
-        if scratch is None:
-            scratch = self.select_scratch(col)
-        else:
-            self._check_tensor(scratch, torch.uint8, "scratch")
-            if scratch.numel() < lib.alpgpu_select_scratch_bytes(col.n_vectors) or scratch.data_ptr() % 16:
-                raise ValueError("scratch must hold alpgpu_select_scratch_bytes(n_vectors) bytes, 16-byte aligned")
-        outs = (_vp(idx_out.data_ptr()) if capacity else None, _vp(vals_out.data_ptr()) if vals_out is not None and capacity else None, capacity,
-                _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
+            self._check_at_least(vals_out, tdt, "vals_out", capacity, "as many values as idx_out")
+        first, n = self._range(col, first, n)
+        scratch = self._scratch(scratch, lib.alpgpu_select_scratch_bytes(col.n_vectors), "alpgpu_select_scratch_bytes(n_vectors)")
+        outs = (_ptr(idx_out), _ptr(vals_out) if capacity else None, capacity, _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
         if zones is None:
             self._call("select_range", col.dtype, C.byref(col.c), first, n, lo, hi, *outs)
         else:
@@ -706,16 +783,13 @@ class Context:
         values=True.  capacity None: the call counts first (one device-to-host read of the count, which synchronises the stream), allocates
         exactly and selects; with a capacity given there is no read-back before the selection, one after it to trim the result to
         min(count, capacity)."""
-        import torch
-        dev = f"cuda:{self.device}"
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
-        count = torch.empty(1, dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=self._dev)
         scratch = self.select_scratch(col)
         if capacity is None:
             self.select_range_into(col, lo, hi, None, count, first=first, n=n, scratch=scratch, zones=zones)
             capacity = int(count.item())
-        idx = torch.empty(int(capacity), dtype=torch.int64, device=dev)
-        vals = torch.empty(int(capacity), dtype=tdt, device=dev) if values else None
+        idx = torch.empty(int(capacity), dtype=torch.int64, device=self._dev)
+        vals = torch.empty(int(capacity), dtype=_TORCH_TYPE[col.dtype], device=self._dev) if values else None
         self.select_range_into(col, lo, hi, idx, count, vals, first=first, n=n, scratch=scratch, zones=zones)
         k = min(int(count.item()), int(capacity))
         return (idx[:k], vals[:k]) if values else idx[:k]
@@ -724,88 +798,75 @@ class Context:
     _MASK_OPS = {"set": MASK_SET, "and": MASK_AND, "or": MASK_OR}
 
     def _check_mask(self, mask, n_vectors=None):
-        import torch
         self._check_tensor(mask, torch.int64, "mask")
         if mask.dim() != 1 or mask.numel() % 16 or (n_vectors is not None and mask.numel() != 16 * n_vectors):
             raise ValueError("mask must be a one-dimensional int64 tensor of 16 words per vector" + ("" if n_vectors is None else " (%d)" % (16 * n_vectors)))
+
+    def _check_op(self, op, mask, n_vectors):
+        """ALPGPU_MASK_* of op, which without a mask to combine into can only be "set" (the caller then makes one, after its other checks)"""
+        if op not in self._MASK_OPS:
+            raise ValueError('op must be "set", "and" or "or"')
+        if mask is not None:
+            self._check_mask(mask, n_vectors)
+        elif op != "set":
+            raise ValueError('op "%s" combines into a mask: pass one' % op)
+        return self._MASK_OPS[op]
 
     def select_mask(self, col: "DeviceColumn", lo: float, hi: float, first: int = 0, n: int = None, op: str = "set", mask=None):
         """the qualify mask of lo <= x <= hi over the value indices [first, first + n) (n None: to the column's end) as a selection bitmap: an int64
         tensor of 16 words per vector, bit r & 63 of word r >> 6 = value index r.  op "set" writes it (mask None: a new tensor), "and" / "or"
         combine it into the mask given: "and" clears the bits outside the range, "or" leaves them.  Returns the mask.  Nothing is
         synchronised; with a mask given nothing is allocated either (alpgpu_select_mask_f64 / _f32)."""
-        import torch
-        if op not in self._MASK_OPS:
-            raise ValueError('op must be "set", "and" or "or"')
+        op = self._check_op(op, mask, col.n_vectors)
+        first, n = self._range(col, first, n)
         if mask is None:
-            if op != "set":
-                raise ValueError('op "%s" combines into a mask: pass one' % op)
-            mask = torch.empty(16 * col.n_vectors, dtype=torch.int64, device=f"cuda:{self.device}")
-        else:
-            self._check_mask(mask, col.n_vectors)
-        first = int(first)
-        n = col.n_vectors * VECTOR_SIZE - first if n is None else int(n)
-        if first < 0 or n < 0:
-            raise ValueError("first and n must not be negative")
-        self._call("select_mask", col.dtype, C.byref(col.c), first, n, lo, hi, self._MASK_OPS[op], _vp(mask.data_ptr()))
+            mask = torch.empty(16 * col.n_vectors, dtype=torch.int64, device=self._dev)
+        self._call("select_mask", col.dtype, C.byref(col.c), first, n, lo, hi, op, _vp(mask.data_ptr()))
         return mask
 
     def mask_to_indices_into(self, mask, idx_out, count_out, scratch=None):
         """the raw form of alpgpu_mask_to_indices: the set bits of the mask as ascending value indices into idx_out (int64; its numel() is the
         capacity, None or empty: a count), their number into count_out (one int64, the full count also beyond the capacity).  Nothing is
         synchronised; with a scratch given (alpgpu_select_scratch_bytes(mask.numel() // 16) bytes of uint8) nothing is allocated."""
-        import torch
         self._check_mask(mask)
         n_vectors = mask.numel() // 16
-        self._check_tensor(count_out, torch.int64, "count_out")
-        if count_out.numel() < 1:
-            raise ValueError("count_out must hold one int64")
-        capacity = 0
+        self._check_at_least(count_out, torch.int64, "count_out", 1, "one int64")
         if idx_out is not None:
             self._check_tensor(idx_out, torch.int64, "idx_out")
-            capacity = idx_out.numel()
-        need = lib.alpgpu_select_scratch_bytes(n_vectors)
-        if scratch is None:
-            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
-        else:
-            self._check_tensor(scratch, torch.uint8, "scratch")
-            if scratch.numel() < need or scratch.data_ptr() % 16:
-                raise ValueError("scratch must hold alpgpu_select_scratch_bytes(n_vectors) bytes, 16-byte aligned")
-        _check(lib.alpgpu_mask_to_indices(self.h, _vp(mask.data_ptr()), n_vectors, _vp(idx_out.data_ptr()) if capacity else None, capacity,
-                                          _vp(count_out.data_ptr()), _vp(scratch.data_ptr())), "alpgpu_mask_to_indices")
+        scratch = self._scratch(scratch, lib.alpgpu_select_scratch_bytes(n_vectors), "alpgpu_select_scratch_bytes(n_vectors)")
+        _check(lib.alpgpu_mask_to_indices(self.h, _vp(mask.data_ptr()), n_vectors, _ptr(idx_out), 0 if idx_out is None else idx_out.numel(), _vp(count_out.data_ptr()),
+                                          _vp(scratch.data_ptr())), "alpgpu_mask_to_indices")
 
     def mask_to_indices(self, mask, capacity: int = None):
         """the set bits of a selection bitmap as an ascending int64 tensor of value indices.  capacity None: the call counts first (one read of
         the count, which synchronises the stream) and allocates exactly; with a capacity the result is trimmed to min(count, capacity)."""
-        import torch
-        dev = f"cuda:{self.device}"
         self._check_mask(mask)
-        count = torch.empty(1, dtype=torch.int64, device=dev)
-        scratch = torch.empty(lib.alpgpu_select_scratch_bytes(mask.numel() // 16), dtype=torch.uint8, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=self._dev)
+        scratch = torch.empty(lib.alpgpu_select_scratch_bytes(mask.numel() // 16), dtype=torch.uint8, device=self._dev)
         if capacity is None:
             self.mask_to_indices_into(mask, None, count, scratch)
             capacity = int(count.item())
-        idx = torch.empty(int(capacity), dtype=torch.int64, device=dev)
+        idx = torch.empty(int(capacity), dtype=torch.int64, device=self._dev)
         self.mask_to_indices_into(mask, idx, count, scratch)
         return idx[:min(int(count.item()), int(capacity))]
+
+    def _per_vector_out(self, out, counts, n_vectors):
+        """the masked sums' outputs: one float64 per vector (a new tensor for None) and, optionally, one int32 count per vector"""
+        if out is None:
+            out = torch.empty(n_vectors, dtype=torch.float64, device=self._dev)
+        else:
+            self._check_at_least(out, torch.float64, "out", n_vectors, "one float64 per vector")
+        if counts is not None:
+            self._check_at_least(counts, torch.int32, "counts", n_vectors, "one int32 per vector")
+        return out
 
     def decode_sum_masked(self, col: "DeviceColumn", mask, out=None, counts=None):
         """per-vector sums (float64) of the decoded values whose bit is set in the mask, in the order include/alpgpu.h documents for
         alpgpu_decode_sum_masked_f64 / _f32; counts (optional, int32, one per vector) receives each vector's number of set bits.  The column's
         total is tree_sum(out)."""
-        import torch
         self._check_mask(mask, col.n_vectors)
-        if out is None:
-            out = torch.empty(col.n_vectors, dtype=torch.float64, device=f"cuda:{self.device}")
-        else:
-            self._check_tensor(out, torch.float64, "out")
-            if out.numel() < col.n_vectors:
-                raise ValueError("out must hold one float64 per vector")
-        if counts is not None:
-            self._check_tensor(counts, torch.int32, "counts")
-            if counts.numel() < col.n_vectors:
-                raise ValueError("counts must hold one int32 per vector")
-        self._call("decode_sum_masked", col.dtype, C.byref(col.c), _vp(mask.data_ptr()), _vp(out.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None)
+        out = self._per_vector_out(out, counts, col.n_vectors)
+        self._call("decode_sum_masked", col.dtype, C.byref(col.c), _vp(mask.data_ptr()), _vp(out.data_ptr()), _ptr(counts))
         return out
 
     def decode_masked_into(self, col: "DeviceColumn", mask, vals_out, count_out, idx_out=None, scratch=None):
@@ -814,45 +875,30 @@ class Context:
         int64, at least as long), their number into count_out (one int64, the full count also beyond the capacity).  Nothing is
         synchronised and nothing read back; with a scratch given (select_scratch) nothing is allocated either, so the call can be captured
         into a graph.  The mask is only read."""
-        import torch
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
         self._check_mask(mask, col.n_vectors)
-        self._check_tensor(count_out, torch.int64, "count_out")
-        if count_out.numel() < 1:
-            raise ValueError("count_out must hold one int64")
+        self._check_at_least(count_out, torch.int64, "count_out", 1, "one int64")
         capacity = 0
         if vals_out is not None:
-            self._check_tensor(vals_out, tdt, "vals_out")
+            self._check_tensor(vals_out, _TORCH_TYPE[col.dtype], "vals_out")
             capacity = vals_out.numel()
         if idx_out is not None:
-            self._check_tensor(idx_out, torch.int64, "idx_out")
-            if idx_out.numel() < capacity:
-                raise ValueError("idx_out is shorter than vals_out")
-        need = lib.alpgpu_select_scratch_bytes(col.n_vectors)
-        if scratch is None:
-            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
-        else:
-            self._check_tensor(scratch, torch.uint8, "scratch")
-            if scratch.numel() < need or scratch.data_ptr() % 16:
-                raise ValueError("scratch must hold alpgpu_select_scratch_bytes(n_vectors) bytes, 16-byte aligned")
-        self._call("decode_masked", col.dtype, C.byref(col.c), _vp(mask.data_ptr()), _vp(vals_out.data_ptr()) if capacity else None,
-                   _vp(idx_out.data_ptr()) if idx_out is not None and capacity else None, capacity, _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
+            self._check_at_least(idx_out, torch.int64, "idx_out", capacity, "as many indices as vals_out")
+        scratch = self._scratch(scratch, lib.alpgpu_select_scratch_bytes(col.n_vectors), "alpgpu_select_scratch_bytes(n_vectors)")
+        self._call("decode_masked", col.dtype, C.byref(col.c), _vp(mask.data_ptr()), _ptr(vals_out), _ptr(idx_out) if capacity else None, capacity,
+                   _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
 
     def decode_masked(self, col: "DeviceColumn", mask, indices: bool = False, capacity: int = None):
         """the column's values at the set bits of a selection bitmap as a tensor of the column's value type, ascending by index, or
         (indices, values) with indices=True.  capacity None: the call counts first (one read of the count, which synchronises the stream) and
         allocates exactly; with a capacity there is no read-back before the projection, one after it to trim the result to
         min(count, capacity)."""
-        import torch
-        dev = f"cuda:{self.device}"
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
-        count = torch.empty(1, dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=self._dev)
         scratch = self.select_scratch(col)
         if capacity is None:
             self.decode_masked_into(col, mask, None, count, scratch=scratch)
             capacity = int(count.item())
-        vals = torch.empty(int(capacity), dtype=tdt, device=dev)
-        idx = torch.empty(int(capacity), dtype=torch.int64, device=dev) if indices else None
+        vals = torch.empty(int(capacity), dtype=_TORCH_TYPE[col.dtype], device=self._dev)
+        idx = torch.empty(int(capacity), dtype=torch.int64, device=self._dev) if indices else None
         self.decode_masked_into(col, mask, vals, count, idx, scratch=scratch)
         k = min(int(count.item()), int(capacity))
         return (idx[:k], vals[:k]) if indices else vals[:k]
@@ -870,119 +916,89 @@ class Context:
         columns' end) as a selection bitmap.  cmp is "lt", "le", "gt", "ge", "eq" or "ne" with C's meaning (a NaN on either side: only "ne"
         holds); op and mask as in select_mask.  Returns the mask.  Nothing is synchronised; with a mask given nothing is allocated either
         (alpgpu_compare_mask_f64 / _f32)."""
-        import torch
         self._check_pair(a, b)
         if cmp not in self._CMP_OPS:
             raise ValueError('cmp must be "lt", "le", "gt", "ge", "eq" or "ne"')
-        if op not in self._MASK_OPS:
-            raise ValueError('op must be "set", "and" or "or"')
+        op = self._check_op(op, mask, a.n_vectors)
+        first, n = self._range(a, first, n)
         if mask is None:
-            if op != "set":
-                raise ValueError('op "%s" combines into a mask: pass one' % op)
-            mask = torch.empty(16 * a.n_vectors, dtype=torch.int64, device=f"cuda:{self.device}")
-        else:
-            self._check_mask(mask, a.n_vectors)
-        first = int(first)
-        n = a.n_vectors * VECTOR_SIZE - first if n is None else int(n)
-        if first < 0 or n < 0:
-            raise ValueError("first and n must not be negative")
-        self._call("compare_mask", a.dtype, C.byref(a.c), C.byref(b.c), first, n, self._CMP_OPS[cmp], self._MASK_OPS[op], _vp(mask.data_ptr()))
+            mask = torch.empty(16 * a.n_vectors, dtype=torch.int64, device=self._dev)
+        self._call("compare_mask", a.dtype, C.byref(a.c), C.byref(b.c), first, n, self._CMP_OPS[cmp], op, _vp(mask.data_ptr()))
         return mask
 
     def decode_dot_masked(self, a: "DeviceColumn", b: "DeviceColumn", mask, out=None, counts=None):
         """per-vector sums (float64) of a_r * b_r over the set bits of the mask, product and sum rounded separately in the order
         include/alpgpu.h documents for alpgpu_decode_dot_masked_f64 / _f32; counts (optional, int32, one per vector) receives each vector's
         number of set bits.  The total is tree_sum(out)."""
-        import torch
         self._check_pair(a, b)
         self._check_mask(mask, a.n_vectors)
-        if out is None:
-            out = torch.empty(a.n_vectors, dtype=torch.float64, device=f"cuda:{self.device}")
-        else:
-            self._check_tensor(out, torch.float64, "out")
-            if out.numel() < a.n_vectors:
-                raise ValueError("out must hold one float64 per vector")
-        if counts is not None:
-            self._check_tensor(counts, torch.int32, "counts")
-            if counts.numel() < a.n_vectors:
-                raise ValueError("counts must hold one int32 per vector")
-        self._call("decode_dot_masked", a.dtype, C.byref(a.c), C.byref(b.c), _vp(mask.data_ptr()), _vp(out.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None)
+        out = self._per_vector_out(out, counts, a.n_vectors)
+        self._call("decode_dot_masked", a.dtype, C.byref(a.c), C.byref(b.c), _vp(mask.data_ptr()), _vp(out.data_ptr()), _ptr(counts))
         return out
 
     # ---- grouped aggregation (include/alpgpu.h: alpgpu_decode_group_sum_*, alpgpu_group_totals) -----------------------------------
+    @staticmethod
+    def _group_bounds(lo, hi, dtype):
+        """(n_groups, lo, hi) with the bounds as C arrays of the columns' type"""
+        try:
+            lo, hi = [float(t) for t in lo], [float(t) for t in hi]
+        except TypeError:
+            raise ValueError("lo and hi must be sequences of numbers") from None
+        if len(hi) != len(lo) or not 1 <= len(lo) <= GROUP_MAX:
+            raise ValueError("lo and hi must hold the same number of bounds, 1 .. %d" % GROUP_MAX)
+        ft = (C.c_double if dtype == "f64" else C.c_float) * len(lo)
+        return len(lo), ft(*lo), ft(*hi)
+
     def decode_group_sum(self, val: "DeviceColumn", key: "DeviceColumn", mask, lo, hi, out=None, counts=None):
         """per-group, per-vector sums of val over the set bits of the mask whose key lies in the closed range lo[g] <= k <= hi[g] (select_mask's
         predicate), every group settled in one pass over the two columns: a [n_groups, n_vectors] float64 tensor, row g bit for bit what
         decode_sum_masked(val) gives under the mask ANDed with select_mask(key, lo[g], hi[g]).  lo, hi: sequences of 1 .. GROUP_MAX floats of
         equal length; counts (optional, int32, the same shape) receives the number of values each sum adds.  Every group's total is
         group_totals(out, counts).  Nothing is synchronised (alpgpu_decode_group_sum_f64 / _f32)."""
-        import torch
         self._check_pair(val, key)
         self._check_mask(mask, val.n_vectors)
-        try:
-            lo, hi = [float(t) for t in lo], [float(t) for t in hi]
-        except TypeError:
-            raise ValueError("lo and hi must be sequences of numbers") from None
-        n_groups = len(lo)
-        if len(hi) != n_groups or not 1 <= n_groups <= GROUP_MAX:
-            raise ValueError("lo and hi must hold the same number of bounds, 1 .. %d" % GROUP_MAX)
+        n_groups, lo, hi = self._group_bounds(lo, hi, val.dtype)
         if out is None:
-            out = torch.empty((n_groups, val.n_vectors), dtype=torch.float64, device=f"cuda:{self.device}")
+            out = torch.empty((n_groups, val.n_vectors), dtype=torch.float64, device=self._dev)
         else:
-            self._check_tensor(out, torch.float64, "out")
-            if tuple(out.shape) != (n_groups, val.n_vectors):
-                raise ValueError("out must be a [n_groups, n_vectors] float64 tensor")
+            self._check_shape(out, torch.float64, "out", (n_groups, val.n_vectors), "[n_groups, n_vectors]")
         if counts is not None:
-            self._check_tensor(counts, torch.int32, "counts")
-            if tuple(counts.shape) != (n_groups, val.n_vectors):
-                raise ValueError("counts must be a [n_groups, n_vectors] int32 tensor")
-        ft = C.c_double if val.dtype == "f64" else C.c_float
-        self._call("decode_group_sum", val.dtype, C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()), (ft * n_groups)(*lo), (ft * n_groups)(*hi), n_groups, _vp(out.data_ptr()),
-                   _vp(counts.data_ptr()) if counts is not None else None)
+            self._check_shape(counts, torch.int32, "counts", (n_groups, val.n_vectors), "[n_groups, n_vectors]")
+        self._call("decode_group_sum", val.dtype, C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()), lo, hi, n_groups, _vp(out.data_ptr()), _ptr(counts))
         return out
 
     def group_totals_scratch(self, n_vectors: int, n_groups: int):
         """a scratch tensor for group_totals (alpgpu_group_totals_scratch_bytes; torch allocations are at least 16-byte aligned)"""
-        import torch
         return torch.empty(lib.alpgpu_group_totals_scratch_bytes(int(n_vectors), int(n_groups)), dtype=torch.uint8, device=f"cuda:{self.device}")
 
     def group_totals(self, sums, counts=None, scratch=None, out=None, counts_out=None):
         """every group's total of a [n_groups, n_vectors] float64 tensor of per-vector sums, row by row the tree of tree_sum, and (with counts,
         int32 of the same shape) every group's exact count: (float64[n_groups], int64[n_groups] or None).  With scratch (group_totals_scratch),
         out and counts_out given nothing is allocated (alpgpu_group_totals)."""
-        import torch
         self._check_tensor(sums, torch.float64, "sums")
         if sums.dim() != 2 or not 1 <= sums.shape[0] <= GROUP_MAX:
             raise ValueError("sums must be a [n_groups, n_vectors] float64 tensor of 1 .. %d groups" % GROUP_MAX)
         n_groups, n_vectors = int(sums.shape[0]), int(sums.shape[1])
         if counts is not None:
-            self._check_tensor(counts, torch.int32, "counts")
-            if tuple(counts.shape) != (n_groups, n_vectors):
-                raise ValueError("counts must be a [n_groups, n_vectors] int32 tensor")
+            self._check_shape(counts, torch.int32, "counts", (n_groups, n_vectors), "[n_groups, n_vectors]")
         elif counts_out is not None:
             raise ValueError("counts_out without counts")
-        need = lib.alpgpu_group_totals_scratch_bytes(n_vectors, n_groups)
-        if scratch is None:
-            scratch = self.group_totals_scratch(n_vectors, n_groups)
-        else:
-            self._check_tensor(scratch, torch.uint8, "scratch")
-            if scratch.numel() < need or scratch.data_ptr() % 16:
-                raise ValueError("scratch must hold group_totals_scratch(n_vectors, n_groups) bytes, 16-byte aligned")
+        scratch = self._scratch(scratch, lib.alpgpu_group_totals_scratch_bytes(n_vectors, n_groups), "group_totals_scratch(n_vectors, n_groups)")
         if out is None:
-            out = torch.empty(n_groups, dtype=torch.float64, device=f"cuda:{self.device}")
+            out = torch.empty(n_groups, dtype=torch.float64, device=self._dev)
         else:
             self._check_tensor(out, torch.float64, "out")
             if out.numel() != n_groups:
                 raise ValueError("out must hold one float64 per group")
         if counts is not None:
             if counts_out is None:
-                counts_out = torch.empty(n_groups, dtype=torch.int64, device=f"cuda:{self.device}")
+                counts_out = torch.empty(n_groups, dtype=torch.int64, device=self._dev)
             else:
                 self._check_tensor(counts_out, torch.int64, "counts_out")
                 if counts_out.numel() != n_groups:
                     raise ValueError("counts_out must hold one int64 per group")
-        _check(lib.alpgpu_group_totals(self.h, _vp(sums.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None, n_vectors, n_groups, _vp(out.data_ptr()),
-                                       _vp(counts_out.data_ptr()) if counts is not None else None, _vp(scratch.data_ptr())), "alpgpu_group_totals")
+        _check(lib.alpgpu_group_totals(self.h, _vp(sums.data_ptr()), _ptr(counts), n_vectors, n_groups, _vp(out.data_ptr()), _ptr(counts_out) if counts is not None else None,
+                                       _vp(scratch.data_ptr())), "alpgpu_group_totals")
         return out, counts_out
 
     # ---- masked and grouped MIN / MAX (include/alpgpu.h: alpgpu_decode_minmax_masked_*, alpgpu_decode_group_minmax_*, alpgpu_group_minmax_totals_*) ---
@@ -991,18 +1007,14 @@ class Context:
         with the rules of zone_map (NaNs ignored, -0.0 < +0.0, {+inf, -inf} when nothing selected is a number); counts (optional, int32, one per
         vector) receives each vector's number of set bits.  The column's MIN / MAX is column_minmax(out).  The records are narrower than the
         vectors' intervals: not a zone map for select_range.  Nothing is synchronised (alpgpu_decode_minmax_masked_f64 / _f32)."""
-        import torch
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
         self._check_mask(mask, col.n_vectors)
         if out is None:
-            out = torch.empty((col.n_vectors, 2), dtype=tdt, device=f"cuda:{self.device}")
+            out = torch.empty((col.n_vectors, 2), dtype=_TORCH_TYPE[col.dtype], device=self._dev)
         else:
-            self._check_zones(out, tdt, col.n_vectors)
+            self._check_zones(out, _TORCH_TYPE[col.dtype], col.n_vectors)
         if counts is not None:
-            self._check_tensor(counts, torch.int32, "counts")
-            if counts.numel() < col.n_vectors:
-                raise ValueError("counts must hold one int32 per vector")
-        self._call("decode_minmax_masked", col.dtype, C.byref(col.c), _vp(mask.data_ptr()), _vp(out.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None)
+            self._check_at_least(counts, torch.int32, "counts", col.n_vectors, "one int32 per vector")
+        self._call("decode_minmax_masked", col.dtype, C.byref(col.c), _vp(mask.data_ptr()), _vp(out.data_ptr()), _ptr(counts))
         return out
 
     def decode_group_minmax(self, val: "DeviceColumn", key: "DeviceColumn", mask, lo, hi, out=None, counts=None):
@@ -1011,36 +1023,21 @@ class Context:
         type, row g bit for bit what decode_minmax_masked(val) gives under the mask ANDed with select_mask(key, lo[g], hi[g]).  lo, hi: sequences
         of 1 .. GROUP_MAX floats of equal length; counts (optional, int32 [n_groups, n_vectors]) receives what decode_group_sum counts.  Every
         group's MIN / MAX is group_minmax_totals(out).  Nothing is synchronised (alpgpu_decode_group_minmax_f64 / _f32)."""
-        import torch
         self._check_pair(val, key)
         self._check_mask(mask, val.n_vectors)
-        try:
-            lo, hi = [float(t) for t in lo], [float(t) for t in hi]
-        except TypeError:
-            raise ValueError("lo and hi must be sequences of numbers") from None
-        n_groups = len(lo)
-        if len(hi) != n_groups or not 1 <= n_groups <= GROUP_MAX:
-            raise ValueError("lo and hi must hold the same number of bounds, 1 .. %d" % GROUP_MAX)
-        tdt = torch.float64 if val.dtype == "f64" else torch.float32
+        n_groups, lo, hi = self._group_bounds(lo, hi, val.dtype)
         if out is None:
-            out = torch.empty((n_groups, val.n_vectors, 2), dtype=tdt, device=f"cuda:{self.device}")
+            out = torch.empty((n_groups, val.n_vectors, 2), dtype=_TORCH_TYPE[val.dtype], device=self._dev)
         else:
-            self._check_tensor(out, tdt, "out")
-            if tuple(out.shape) != (n_groups, val.n_vectors, 2) or out.data_ptr() % (2 * out.element_size()):
-                raise ValueError("out must be a [n_groups, n_vectors, 2] tensor of the columns' value type, aligned to its records")
+            self._check_shape(out, _TORCH_TYPE[val.dtype], "out", (n_groups, val.n_vectors, 2), "[n_groups, n_vectors, 2]", records=True)
         if counts is not None:
-            self._check_tensor(counts, torch.int32, "counts")
-            if tuple(counts.shape) != (n_groups, val.n_vectors):
-                raise ValueError("counts must be a [n_groups, n_vectors] int32 tensor")
-        ft = C.c_double if val.dtype == "f64" else C.c_float
-        self._call("decode_group_minmax", val.dtype, C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()), (ft * n_groups)(*lo), (ft * n_groups)(*hi), n_groups,
-                   _vp(out.data_ptr()), _vp(counts.data_ptr()) if counts is not None else None)
+            self._check_shape(counts, torch.int32, "counts", (n_groups, val.n_vectors), "[n_groups, n_vectors]")
+        self._call("decode_group_minmax", val.dtype, C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()), lo, hi, n_groups, _vp(out.data_ptr()), _ptr(counts))
         return out
 
     def group_minmax_totals(self, zones, out=None):
         """every group's {min, max} of a [n_groups, n_vectors, 2] tensor of records: a [n_groups, 2] tensor, row g what column_minmax(zones[g])
         gives; {+inf, -inf} for n_vectors == 0.  No scratch (alpgpu_group_minmax_totals_f64 / _f32)."""
-        import torch
         if not isinstance(zones, torch.Tensor) or zones.dtype not in (torch.float64, torch.float32):
             raise ValueError("zones must be a float64 or float32 tensor")
         self._check_tensor(zones, zones.dtype, "zones")
@@ -1050,10 +1047,8 @@ class Context:
         if out is None:
             out = torch.empty((n_groups, 2), dtype=zones.dtype, device=zones.device)
         else:
-            self._check_tensor(out, zones.dtype, "out")
-            if tuple(out.shape) != (n_groups, 2):
-                raise ValueError("out must be a [n_groups, 2] tensor of the records' type")
-        self._call("group_minmax_totals", self._sfx(zones), _vp(zones.data_ptr()) if n_vectors else None, n_vectors, n_groups, _vp(out.data_ptr()))
+            self._check_shape(out, zones.dtype, "out", (n_groups, 2), "[n_groups, 2]")
+        self._call("group_minmax_totals", self._sfx(zones), _ptr(zones), n_vectors, n_groups, _vp(out.data_ptr()))
         return out
 
     # ---- set membership (include/alpgpu.h: alpgpu_select_in_mask_*, alpgpu_in_list_lds_max) ---------------------------------
@@ -1070,40 +1065,14 @@ class Context:
         the device (nothing dropped or deduplicated: NaNs sort last and are inert); sorted=True skips that for a caller who guarantees the
         order.  zones (zone_map(col)): the same bytes, vectors whose record holds no element are not decoded.  Returns the mask.  Nothing is
         synchronised; with a mask and a sorted device tensor given nothing is allocated either (alpgpu_select_in_mask_f64 / _f32)."""
-        import torch
-        if op not in self._MASK_OPS:
-            raise ValueError('op must be "set", "and" or "or"')
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
-        dev = f"cuda:{self.device}"
-        if isinstance(values, np.ndarray):
-            if values.dtype != (np.float64 if col.dtype == "f64" else np.float32):
-                raise ValueError("values must be of the column's type (%s)" % col.dtype)
-            values = torch.from_numpy(np.ascontiguousarray(values))
-        elif not isinstance(values, torch.Tensor):
-            values = torch.tensor(list(values), dtype=tdt)
-        if values.dtype != tdt:
-            raise ValueError("values must be of the column's type (%s)" % col.dtype)
-        if values.dim() != 1:
-            raise ValueError("values must be one-dimensional")
-        if values.is_cuda and values.device.index != self.device:
-            raise ValueError("values must be on the host or on cuda:%d" % self.device)
+        op = self._check_op(op, mask, col.n_vectors)
         if zones is not None:
-            self._check_zones(zones, tdt, col.n_vectors)
+            self._check_zones(zones, _TORCH_TYPE[col.dtype], col.n_vectors)
+        first, n = self._range(col, first, n)
+        lst = self._list_to_device(values, "values", col, sorted=sorted)
         if mask is None:
-            if op != "set":
-                raise ValueError('op "%s" combines into a mask: pass one' % op)
-        else:
-            self._check_mask(mask, col.n_vectors)
-        first = int(first)
-        n = col.n_vectors * VECTOR_SIZE - first if n is None else int(n)
-        if first < 0 or n < 0:
-            raise ValueError("first and n must not be negative")
-        if mask is None:
-            mask = torch.empty(16 * col.n_vectors, dtype=torch.int64, device=dev)
-        lst = values if values.is_cuda else values.to(dev)
-        lst = lst.contiguous() if sorted else torch.sort(lst).values
-        self._call("select_in_mask", col.dtype, C.byref(col.c), first, n, _vp(lst.data_ptr()) if lst.numel() else None, lst.numel(), 1 if negate else 0,
-                   _vp(zones.data_ptr()) if zones is not None else None, self._MASK_OPS[op], _vp(mask.data_ptr()))
+            mask = torch.empty(16 * col.n_vectors, dtype=torch.int64, device=self._dev)
+        self._call("select_in_mask", col.dtype, C.byref(col.c), first, n, _ptr(lst), lst.numel(), 1 if negate else 0, _ptr(zones), op, _vp(mask.data_ptr()))
         return mask
 
     # ---- top-k (include/alpgpu.h: alpgpu_top_k_scratch_bytes, alpgpu_top_k_*) ---------------------------------------------
@@ -1116,7 +1085,6 @@ class Context:
     def top_k_scratch(self, col: "DeviceColumn", k: int):
         """a scratch tensor for top_k_into on this column with this k or a smaller one (alpgpu_top_k_scratch_bytes; torch allocations are at least
         16-byte aligned)"""
-        import torch
         return torch.empty(lib.alpgpu_top_k_scratch_bytes(col.n_vectors, self._check_k(k)), dtype=torch.uint8, device=f"cuda:{self.device}")
 
     def top_k_into(self, col: "DeviceColumn", mask, k: int, vals_out, count_out, idx_out=None, largest: bool = True, records=None, scratch=None):
@@ -1127,47 +1095,30 @@ class Context:
         (decode_minmax_masked, or zone_map under a mask of every real value): the first decode pass is skipped; anything else there gives an
         unspecified selection.  Nothing is synchronised and nothing read back; with a scratch given (top_k_scratch) nothing is allocated
         either, so the call can be captured into a graph.  The mask is only read."""
-        import torch
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
+        tdt = _TORCH_TYPE[col.dtype]
         k = self._check_k(k)
         self._check_mask(mask, col.n_vectors)
-        self._check_tensor(count_out, torch.int64, "count_out")
-        if count_out.numel() < 1:
-            raise ValueError("count_out must hold one int64")
-        self._check_tensor(vals_out, tdt, "vals_out")
-        if vals_out.numel() < k:
-            raise ValueError("vals_out must hold k values")
+        self._check_at_least(count_out, torch.int64, "count_out", 1, "one int64")
+        self._check_at_least(vals_out, tdt, "vals_out", k, "k values")
         if idx_out is not None:
-            self._check_tensor(idx_out, torch.int64, "idx_out")
-            if idx_out.numel() < k:
-                raise ValueError("idx_out must hold k indices")
+            self._check_at_least(idx_out, torch.int64, "idx_out", k, "k indices")
         if records is not None:
             self._check_zones(records, tdt, col.n_vectors)
             if records.data_ptr() % 16:
                 raise ValueError("records must be 16-byte aligned")
-        need = lib.alpgpu_top_k_scratch_bytes(col.n_vectors, k)
-        if scratch is None:
-            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
-        else:
-            self._check_tensor(scratch, torch.uint8, "scratch")
-            if scratch.numel() < need or scratch.data_ptr() % 16:
-                raise ValueError("scratch must hold alpgpu_top_k_scratch_bytes(n_vectors, k) bytes, 16-byte aligned")
-        # (a tensor without elements has no address: the library wants one even where it writes nothing)
-        self._call("top_k", col.dtype, C.byref(col.c), _vp(mask.data_ptr()) if mask.numel() else _vp(scratch.data_ptr()), _vp(records.data_ptr()) if records is not None else None, k,
-                   1 if largest else 0, _vp(vals_out.data_ptr()) if vals_out.numel() else _vp(scratch.data_ptr()), _vp(idx_out.data_ptr()) if idx_out is not None and idx_out.numel() else None,
-                   _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
+        scratch = self._scratch(scratch, lib.alpgpu_top_k_scratch_bytes(col.n_vectors, k), "alpgpu_top_k_scratch_bytes(n_vectors, k)")
+        nowhere = _vp(scratch.data_ptr())  # (a tensor without elements has no address: the library wants one even where it writes nothing)
+        self._call("top_k", col.dtype, C.byref(col.c), _ptr(mask) or nowhere, _ptr(records), k, 1 if largest else 0, _ptr(vals_out) or nowhere, _ptr(idx_out),
+                   _vp(count_out.data_ptr()), nowhere)
 
     def top_k(self, col: "DeviceColumn", mask, k: int, largest: bool = True, records=None, indices: bool = True):
         """(values, indices) — values alone with indices=False — of the k largest (largest=False: smallest) values among the set bits of the mask,
         NaNs left out, largest (smallest) first, equal bit patterns by ascending index; trimmed to min(k, how many there are).  One read of the
         count, which synchronises the stream."""
-        import torch
-        dev = f"cuda:{self.device}"
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
         k = self._check_k(k)
-        vals = torch.empty(k, dtype=tdt, device=dev)
-        idx = torch.empty(k, dtype=torch.int64, device=dev) if indices else None
-        count = torch.empty(1, dtype=torch.int64, device=dev)
+        vals = torch.empty(k, dtype=_TORCH_TYPE[col.dtype], device=self._dev)
+        idx = torch.empty(k, dtype=torch.int64, device=self._dev) if indices else None
+        count = torch.empty(1, dtype=torch.int64, device=self._dev)
         self.top_k_into(col, mask, k, vals, count, idx, largest=largest, records=records)
         n = min(int(count.item()), k)
         return (vals[:n], idx[:n]) if indices else vals[:n]
@@ -1198,29 +1149,15 @@ class Context:
     def quantile_scratch(self, col: "DeviceColumn"):
         """a scratch tensor for select_rank_into / quantile_into on this column (alpgpu_quantile_scratch_bytes; torch allocations are at least 16-byte
         aligned)"""
-        import torch
         return torch.empty(lib.alpgpu_quantile_scratch_bytes(col.n_vectors), dtype=torch.uint8, device=f"cuda:{self.device}")
 
     def _check_quantile_args(self, col, mask, vals_out, n_vals, count_out, zones, scratch):
-        import torch
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
         self._check_mask(mask, col.n_vectors)
-        self._check_tensor(count_out, torch.int64, "count_out")
-        if count_out.numel() < 1:
-            raise ValueError("count_out must hold one int64")
-        self._check_tensor(vals_out, tdt, "vals_out")
-        if vals_out.numel() < n_vals:
-            raise ValueError("vals_out must hold %d values" % n_vals)
+        self._check_at_least(count_out, torch.int64, "count_out", 1, "one int64")
+        self._check_at_least(vals_out, _TORCH_TYPE[col.dtype], "vals_out", n_vals, "%d values" % n_vals)
         if zones is not None:
-            self._check_zones(zones, tdt, col.n_vectors)
-        need = lib.alpgpu_quantile_scratch_bytes(col.n_vectors)
-        if scratch is None:
-            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
-        else:
-            self._check_tensor(scratch, torch.uint8, "scratch")
-            if scratch.numel() < need or scratch.data_ptr() % 16:
-                raise ValueError("scratch must hold alpgpu_quantile_scratch_bytes(n_vectors) bytes, 16-byte aligned")
-        return scratch
+            self._check_zones(zones, _TORCH_TYPE[col.dtype], col.n_vectors)
+        return self._scratch(scratch, lib.alpgpu_quantile_scratch_bytes(col.n_vectors), "alpgpu_quantile_scratch_bytes(n_vectors)")
 
     def select_rank_into(self, col: "DeviceColumn", mask, ranks, vals_out, count_out, from_top: bool = False, zones=None, scratch=None, tuning=None):
         """the raw form of alpgpu_select_rank_f64 / _f32: with S the values at the set bits of the mask that are no NaNs, sorted in the order
@@ -1232,13 +1169,13 @@ class Context:
         nothing is allocated either, so the call can be captured into a graph.  The mask is only read."""
         ranks = self._check_ranks(ranks)
         scratch = self._check_quantile_args(col, mask, vals_out, len(ranks), count_out, zones, scratch)
-        args = [C.byref(col.c), _vp(mask.data_ptr()) if mask.numel() else _vp(scratch.data_ptr()), _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
-                (_u64 * len(ranks))(*ranks), len(ranks), 1 if from_top else 0, _vp(vals_out.data_ptr()), _vp(count_out.data_ptr()), _vp(scratch.data_ptr())]
-        if tuning is None:
+        args = [C.byref(col.c), _ptr(mask) or _vp(scratch.data_ptr()), _ptr(zones), (_u64 * len(ranks))(*ranks), len(ranks), 1 if from_top else 0, _vp(vals_out.data_ptr()),
+                _vp(count_out.data_ptr()), _vp(scratch.data_ptr())]
+        if tuning is None:  # (not _call_tuned: the debug entry is named for the family, not for select_rank, and takes no trace)
             self._call("select_rank", col.dtype, *args)
         else:
             if set(tuning) - {"capacity", "max_workgroups", "flush_every"}:
-                raise ValueError("tuning takes capacity, max_workgroups and flush_every")
+                raise ValueError("tuning takes capacity, max_workgroups, flush_every")
             t = QuantileTuning(int(tuning.get("capacity", 0)), int(tuning.get("max_workgroups", 0)), int(tuning.get("flush_every", 0)))
             self._call("debug_quantile", col.dtype, *args, C.byref(t))
 
@@ -1246,20 +1183,15 @@ class Context:
         """the raw form of alpgpu_quantile_f64 / _f32: for each q[i] (1 .. 16 numbers in [0, 1] on the host) the rank r = min(N - 1, floor(q[i] * (N - 1)))
         (numpy's method="lower") goes to ranks_out[i] (optional, int64), S[r] to vals_out[2 i] and S[min(r + 1, N - 1)] to vals_out[2 i + 1] (the
         column's value type, at least 2 len(q) long), N to count_out; S, zones, scratch and the promises as for select_rank_into."""
-        import torch
         q = self._check_q(q)
         if ranks_out is not None:
-            self._check_tensor(ranks_out, torch.int64, "ranks_out")
-            if ranks_out.numel() < len(q):
-                raise ValueError("ranks_out must hold len(q) ranks")
+            self._check_at_least(ranks_out, torch.int64, "ranks_out", len(q), "len(q) ranks")
         scratch = self._check_quantile_args(col, mask, vals_out, 2 * len(q), count_out, zones, scratch)
-        self._call("quantile", col.dtype, C.byref(col.c), _vp(mask.data_ptr()) if mask.numel() else _vp(scratch.data_ptr()),
-                   _vp(zones.data_ptr()) if zones is not None and zones.numel() else None, (C.c_double * len(q))(*q), len(q), _vp(vals_out.data_ptr()),
-                   _vp(ranks_out.data_ptr()) if ranks_out is not None else None, _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
+        self._call("quantile", col.dtype, C.byref(col.c), _ptr(mask) or _vp(scratch.data_ptr()), _ptr(zones), (C.c_double * len(q))(*q), len(q), _vp(vals_out.data_ptr()),
+                   _ptr(ranks_out), _vp(count_out.data_ptr()), _vp(scratch.data_ptr()))
 
     def quantile_trace(self, scratch):
         """what the last select_rank / quantile call on this scratch did (include/alpgpu.h: alpgpu_debug_quantile_trace); synchronises the stream"""
-        import torch
         self._check_tensor(scratch, torch.uint8, "scratch")
         t = QuantileTrace()
         _check(lib.alpgpu_debug_quantile_trace(self.h, _vp(scratch.data_ptr()), C.byref(t)), "alpgpu_debug_quantile_trace")
@@ -1269,11 +1201,9 @@ class Context:
     def select_rank(self, col: "DeviceColumn", mask, ranks, from_top: bool = False, zones=None):
         """(values, N): values[i] the ranks[i]-th smallest (from_top: largest) of the values at the set bits of the mask that are no NaNs, ranks
         beyond the last clamped to it; an empty tensor for N == 0.  One read of the count, which synchronises the stream."""
-        import torch
-        dev = f"cuda:{self.device}"
         ranks = self._check_ranks(ranks)
-        vals = torch.empty(len(ranks), dtype=torch.float64 if col.dtype == "f64" else torch.float32, device=dev)
-        count = torch.empty(1, dtype=torch.int64, device=dev)
+        vals = torch.empty(len(ranks), dtype=_TORCH_TYPE[col.dtype], device=self._dev)
+        count = torch.empty(1, dtype=torch.int64, device=self._dev)
         self.select_rank_into(col, mask, ranks, vals, count, from_top=from_top, zones=zones)
         n = int(count.item())
         return (vals if n else vals[:0]), n
@@ -1283,13 +1213,12 @@ class Context:
         interpolation "lower" / "higher": the neighbour below / above q * (N - 1), of the column's type and bit for bit a value of the column (numpy's
         method="lower" / "higher"); "linear": lo + (hi - lo) * (q * (N - 1) - r) in double, by torch ops on the device tensors.  NaN where nothing
         is selected.  Nothing is synchronised."""
-        import torch
         if interpolation not in ("linear", "lower", "higher"):
             raise ValueError('interpolation must be "linear", "lower" or "higher"')
         scalar = isinstance(q, (int, float, np.integer, np.floating)) and not isinstance(q, bool)
         q = self._check_q([q] if scalar else q)
         dev = f"cuda:{self.device}"
-        vals = torch.full((len(q), 2), float("nan"), dtype=torch.float64 if col.dtype == "f64" else torch.float32, device=dev)
+        vals = torch.full((len(q), 2), float("nan"), dtype=_TORCH_TYPE[col.dtype], device=dev)
         ranks = torch.zeros(len(q), dtype=torch.int64, device=dev)
         count = torch.empty(1, dtype=torch.int64, device=dev)
         self.quantile_into(col, mask, q, vals, count, ranks, zones=zones)
@@ -1313,41 +1242,13 @@ class Context:
         search narrowed by them.  tuning: {"grid", "flush_every"}, trace: an int64 device tensor of 4 words that is ADDED to (vectors settled without
         the column, from their record, by the few-bucket route (always 0), decoded); either sends the call through the debug entry
         (alpgpu_debug_histogram_*; the same counts).  Nothing is synchronised, allocated or read back, so the call can be captured into a graph."""
-        import torch
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
-        if not isinstance(edges, torch.Tensor) or edges.dtype != tdt:
-            raise ValueError("edges must be a tensor of the column's type (%s)" % col.dtype)
-        if edges.dim() != 1:
-            raise ValueError("edges must be one-dimensional")
-        if not edges.is_cuda or edges.device.index != self.device or not edges.is_contiguous():
-            raise ValueError("edges must be contiguous on cuda:%d" % self.device)
-        if edges.numel() > HISTOGRAM_EDGES_MAX:
-            raise ValueError("at most %d edges" % HISTOGRAM_EDGES_MAX)
-        self._check_tensor(counts_out, torch.int64, "counts_out")
-        if counts_out.dim() != 1 or counts_out.numel() != edges.numel() + 2:
-            raise ValueError("counts_out must be a one-dimensional int64 tensor of len(edges) + 2 words")
-        if mask is not None:
-            self._check_mask(mask, col.n_vectors)
-        if zones is not None:
-            self._check_zones(zones, tdt, col.n_vectors)
-        first = int(first)
-        n = col.n_vectors * VECTOR_SIZE - first if n is None else int(n)
-        if first < 0 or n < 0:
-            raise ValueError("first and n must not be negative")
-        if trace is not None:
-            self._check_tensor(trace, torch.int64, "trace")
-            if trace.numel() != 4:
-                raise ValueError("trace must hold 4 int64 words")
-        args = [C.byref(col.c), first, n, _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
-                _vp(edges.data_ptr()) if edges.numel() else None, edges.numel(), 1 if right else 0, 1 if accumulate else 0, _vp(counts_out.data_ptr())]
-        if tuning is None and trace is None:
-            self._call("histogram", col.dtype, *args)
-        else:
-            tuning = {} if tuning is None else tuning
-            if set(tuning) - {"grid", "flush_every"}:
-                raise ValueError("tuning takes grid and flush_every")
-            t = HistogramTuning(int(tuning.get("grid", 0)), int(tuning.get("flush_every", 0)))
-            self._call("debug_histogram", col.dtype, *args, C.byref(t), _vp(trace.data_ptr()) if trace is not None else None)
+        n_edges = self._check_list(edges, "edges", col, 0, HISTOGRAM_EDGES_MAX)
+        self._check_shape(counts_out, torch.int64, "counts_out", (n_edges + 2,), "[len(edges) + 2]")
+        self._check_mask_zones(mask, zones, col)
+        first, n = self._range(col, first, n)
+        self._check_trace(trace)
+        args = [C.byref(col.c), first, n, _ptr(mask), _ptr(zones), _ptr(edges), n_edges, 1 if right else 0, 1 if accumulate else 0, _vp(counts_out.data_ptr())]
+        self._call_tuned("histogram", col.dtype, args, tuning, trace, HistogramTuning, ("grid", "flush_every"))
 
     def histogram(self, col: "DeviceColumn", edges, mask=None, first: int = 0, n: int = None, right: bool = False, zones=None, out=None, accumulate: bool = False,
                   sorted: bool = False):
@@ -1359,40 +1260,14 @@ class Context:
         out: the tensor to write or, with accumulate, to add to (shards, successive ranges, several columns).  zones (zone_map(col) or any records
         that contain the vectors' intervals): the same counts.  Nothing is synchronised; with out and a sorted device tensor given nothing is
         allocated either (alpgpu_histogram_f64 / _f32)."""
-        import torch
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
-        dev = f"cuda:{self.device}"
-        if isinstance(edges, np.ndarray):
-            if edges.dtype != (np.float64 if col.dtype == "f64" else np.float32):
-                raise ValueError("edges must be of the column's type (%s)" % col.dtype)
-            edges = torch.from_numpy(np.ascontiguousarray(edges))
-        elif not isinstance(edges, torch.Tensor):
-            edges = torch.tensor(list(edges), dtype=tdt)
-        if edges.dtype != tdt:
-            raise ValueError("edges must be of the column's type (%s)" % col.dtype)
-        if edges.dim() != 1:
-            raise ValueError("edges must be one-dimensional")
-        if edges.is_cuda and edges.device.index != self.device:
-            raise ValueError("edges must be on the host or on cuda:%d" % self.device)
-        if edges.numel() > HISTOGRAM_EDGES_MAX:
-            raise ValueError("at most %d edges" % HISTOGRAM_EDGES_MAX)
+        if out is None and accumulate:
+            raise ValueError("accumulate adds to a tensor: pass out")
+        first, n = self._range(col, first, n)
+        lst = self._list_to_device(edges, "edges", col, 0, HISTOGRAM_EDGES_MAX, sorted=sorted)
         if out is None:
-            if accumulate:
-                raise ValueError("accumulate adds to a tensor: pass out")
+            out = torch.zeros(lst.numel() + 2, dtype=torch.int64, device=self._dev)  # (zeroed, where the others are empty: a column of no vectors writes nothing)
         else:
-            self._check_tensor(out, torch.int64, "out")
-            if out.dim() != 1 or out.numel() != edges.numel() + 2:
-                raise ValueError("out must be a one-dimensional int64 tensor of len(edges) + 2 words")
-        if mask is not None:
-            self._check_mask(mask, col.n_vectors)
-        if zones is not None:
-            self._check_zones(zones, tdt, col.n_vectors)
-        if int(first) < 0 or (n is not None and int(n) < 0):
-            raise ValueError("first and n must not be negative")
-        if out is None:
-            out = torch.zeros(edges.numel() + 2, dtype=torch.int64, device=dev)  # (zeroed: a column of no vectors writes nothing)
-        lst = edges if edges.is_cuda else edges.to(dev)
-        lst = lst.contiguous() if sorted else torch.sort(lst).values
+            self._check_shape(out, torch.int64, "out", (lst.numel() + 2,), "[len(edges) + 2]")
         self.histogram_into(col, lst, out, mask=mask, first=first, n=n, right=right, zones=zones, accumulate=accumulate)
         return out
 
@@ -1401,7 +1276,6 @@ class Context:
 
     def distinct_scratch(self, capacity: int):
         """a scratch tensor for distinct_into with this capacity (alpgpu_distinct_scratch_bytes; torch allocations are at least 16-byte aligned)"""
-        import torch
         capacity = int(capacity)
         if not 1 <= capacity <= DISTINCT_MAX:
             raise ValueError("capacity must be in 1 .. %d" % DISTINCT_MAX)
@@ -1417,9 +1291,7 @@ class Context:
         "lds_slots", "table_slots", "sort_tile"}, trace: an int64 device tensor of 6 words that is ADDED to; either sends the call through the
         debug entry (alpgpu_debug_distinct_*; the same bytes).  Nothing is synchronised and nothing read back; with a scratch given
         (distinct_scratch) nothing is allocated either, so the call can be captured into a graph."""
-        import torch
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
-        self._check_tensor(vals_out, tdt, "vals_out")
+        self._check_tensor(vals_out, _TORCH_TYPE[col.dtype], "vals_out")
         capacity = vals_out.numel()
         if vals_out.dim() != 1 or not 1 <= capacity <= DISTINCT_MAX:
             raise ValueError("vals_out must be one-dimensional and hold 1 .. %d values" % DISTINCT_MAX)
@@ -1427,38 +1299,13 @@ class Context:
         if state_out.numel() != 4:
             raise ValueError("state_out must hold 4 int64 words")
         if counts_out is not None:
-            self._check_tensor(counts_out, torch.int64, "counts_out")
-            if counts_out.numel() < capacity:
-                raise ValueError("counts_out is shorter than vals_out")
-        if mask is not None:
-            self._check_mask(mask, col.n_vectors)
-        if zones is not None:
-            self._check_zones(zones, tdt, col.n_vectors)
-        first = int(first)
-        n = col.n_vectors * VECTOR_SIZE - first if n is None else int(n)
-        if first < 0 or n < 0:
-            raise ValueError("first and n must not be negative")
-        if trace is not None:
-            self._check_tensor(trace, torch.int64, "trace")
-            if trace.numel() != 6:
-                raise ValueError("trace must hold 6 int64 words")
-        need = lib.alpgpu_distinct_scratch_bytes(capacity)
-        if scratch is None:
-            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
-        else:
-            self._check_tensor(scratch, torch.uint8, "scratch")
-            if scratch.numel() < need or scratch.data_ptr() % 16:
-                raise ValueError("scratch must hold alpgpu_distinct_scratch_bytes(capacity) bytes, 16-byte aligned")
-        args = [C.byref(col.c), first, n, _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
-                capacity, _vp(vals_out.data_ptr()), _vp(counts_out.data_ptr()) if counts_out is not None else None, _vp(state_out.data_ptr()), _vp(scratch.data_ptr())]
-        if tuning is None and trace is None:
-            self._call("distinct", col.dtype, *args)
-        else:
-            tuning = {} if tuning is None else tuning
-            if set(tuning) - set(self._DISTINCT_TUNING):
-                raise ValueError("tuning takes " + ", ".join(self._DISTINCT_TUNING))
-            t = DistinctTuning(*[int(tuning.get(k, 0)) for k in self._DISTINCT_TUNING], 0)
-            self._call("debug_distinct", col.dtype, *args, C.byref(t), _vp(trace.data_ptr()) if trace is not None else None)
+            self._check_at_least(counts_out, torch.int64, "counts_out", capacity, "as many counts as vals_out")
+        self._check_mask_zones(mask, zones, col)
+        first, n = self._range(col, first, n)
+        self._check_trace(trace, 6)  # (6 words where the other families' traces have 4)
+        scratch = self._scratch(scratch, lib.alpgpu_distinct_scratch_bytes(capacity), "alpgpu_distinct_scratch_bytes(capacity)")
+        args = [C.byref(col.c), first, n, _ptr(mask), _ptr(zones), capacity, _vp(vals_out.data_ptr()), _ptr(counts_out), _vp(state_out.data_ptr()), _vp(scratch.data_ptr())]
+        self._call_tuned("distinct", col.dtype, args, tuning, trace, DistinctTuning, self._DISTINCT_TUNING)
 
     def distinct(self, col: "DeviceColumn", mask=None, first: int = 0, n: int = None, zones=None, capacity: int = 65536, counts: bool = True):
         """(values, counts, n_nan, overflow): the distinct values, ascending, of the column's values at the indices [first, first + n) whose bit is set in
@@ -1467,12 +1314,11 @@ class Context:
         values and counts are unspecified and the call wants a larger capacity (at most DISTINCT_MAX).  -0.0 == +0.0, one value, reported as +0.0.
         The values are a valid sorted list for select_in_mask, edge array for histogram and key array for join_probe.  One read of the state,
         which synchronises the stream (alpgpu_distinct_f64 / _f32)."""
-        import torch
         dev = f"cuda:{self.device}"
         capacity = int(capacity)
         if not 1 <= capacity <= DISTINCT_MAX:
             raise ValueError("capacity must be in 1 .. %d" % DISTINCT_MAX)
-        vals = torch.empty(capacity, dtype=torch.float64 if col.dtype == "f64" else torch.float32, device=dev)
+        vals = torch.empty(capacity, dtype=_TORCH_TYPE[col.dtype], device=dev)
         cnt = torch.empty(capacity, dtype=torch.int64, device=dev) if counts else None
         state = torch.empty(4, dtype=torch.int64, device=dev)
         self.distinct_into(col, vals, state, counts_out=cnt, mask=mask, first=first, n=n, zones=zones)
@@ -1482,7 +1328,6 @@ class Context:
     # ---- keyed aggregation (include/alpgpu.h: alpgpu_decode_keyed_sum_*) ------------------------------------------------
     def keyed_sum_scratch(self, n_vectors: int, n_keys: int):
         """a scratch tensor for keyed_sum_into (alpgpu_keyed_sum_scratch_bytes; torch allocations are at least 16-byte aligned)"""
-        import torch
         n_vectors, n_keys = int(n_vectors), int(n_keys)
         if n_vectors < 0 or not 1 <= n_keys <= KEYED_KEYS_MAX:
             raise ValueError("n_vectors must not be negative and n_keys must be in 1 .. %d" % KEYED_KEYS_MAX)
@@ -1497,50 +1342,18 @@ class Context:
         device tensor of 4 words that is ADDED to (vectors settled without either column, by the constant-key shortcut, with a record that admits
         no key, decoded); either sends the call through the debug entry (the same bits).  Nothing is synchronised or read back; with a scratch
         given (keyed_sum_scratch) nothing is allocated either, so the call can be captured into a graph."""
-        import torch
         self._check_pair(val, key)
         if val.dtype != "f64":
             raise ValueError("keyed_sum is built for double columns only")
-        tdt = torch.float64
-        if not isinstance(keys, torch.Tensor) or keys.dtype != tdt:
-            raise ValueError("keys must be a tensor of the columns' type (%s)" % val.dtype)
-        if keys.dim() != 1 or not 1 <= keys.numel() <= KEYED_KEYS_MAX:
-            raise ValueError("keys must be one-dimensional and hold 1 .. %d keys" % KEYED_KEYS_MAX)
-        if not keys.is_cuda or keys.device.index != self.device or not keys.is_contiguous():
-            raise ValueError("keys must be contiguous on cuda:%d" % self.device)
-        n_keys = keys.numel()
-        self._check_tensor(sums_out, torch.float64, "sums_out")
-        if sums_out.dim() != 1 or sums_out.numel() != n_keys:
-            raise ValueError("sums_out must be a one-dimensional float64 tensor of len(keys)")
+        n_keys = self._check_list(keys, "keys", val, 1, KEYED_KEYS_MAX)
+        self._check_shape(sums_out, torch.float64, "sums_out", (n_keys,), "[len(keys)]")
         if counts_out is not None:
-            self._check_tensor(counts_out, torch.int64, "counts_out")
-            if counts_out.dim() != 1 or counts_out.numel() != n_keys + 1:
-                raise ValueError("counts_out must be a one-dimensional int64 tensor of len(keys) + 1 words")
-        if mask is not None:
-            self._check_mask(mask, val.n_vectors)
-        if zones is not None:
-            self._check_zones(zones, tdt, key.n_vectors)
-        if trace is not None:
-            self._check_tensor(trace, torch.int64, "trace")
-            if trace.numel() != 4:
-                raise ValueError("trace must hold 4 int64 words")
-        need = lib.alpgpu_keyed_sum_scratch_bytes(val.n_vectors, n_keys)
-        if scratch is None:
-            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
-        else:
-            self._check_tensor(scratch, torch.uint8, "scratch")
-            if scratch.numel() < need or scratch.data_ptr() % 16:
-                raise ValueError("scratch must hold keyed_sum_scratch(n_vectors, n_keys) bytes, 16-byte aligned")
-        args = [C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
-                _vp(keys.data_ptr()), n_keys, _vp(sums_out.data_ptr()), _vp(counts_out.data_ptr()) if counts_out is not None else None, _vp(scratch.data_ptr())]
-        if tuning is None and trace is None:
-            self._call("decode_keyed_sum", val.dtype, *args)
-        else:
-            tuning = {} if tuning is None else tuning
-            if set(tuning) - {"grid"}:
-                raise ValueError("tuning takes grid")
-            t = KeyedTuning(int(tuning.get("grid", 0)), 0)
-            self._call("debug_decode_keyed_sum", val.dtype, *args, C.byref(t), _vp(trace.data_ptr()) if trace is not None else None)
+            self._check_shape(counts_out, torch.int64, "counts_out", (n_keys + 1,), "[len(keys) + 1]")
+        self._check_mask_zones(mask, zones, key)
+        self._check_trace(trace)
+        scratch = self._scratch(scratch, lib.alpgpu_keyed_sum_scratch_bytes(val.n_vectors, n_keys), "keyed_sum_scratch(n_vectors, n_keys)")
+        args = [C.byref(val.c), C.byref(key.c), _ptr(mask), _ptr(zones), _vp(keys.data_ptr()), n_keys, _vp(sums_out.data_ptr()), _ptr(counts_out), _vp(scratch.data_ptr())]
+        self._call_tuned("decode_keyed_sum", val.dtype, args, tuning, trace, KeyedTuning, ("grid",))
 
     def keyed_sum(self, val: "DeviceColumn", key: "DeviceColumn", keys, mask=None, zones=None, counts: bool = True, sorted: bool = False):
         """SUM(val), COUNT(*) GROUP BY key for the given keys in one pass over the two columns: (float64[K] sums, int64[K] counts or None with
@@ -1550,32 +1363,12 @@ class Context:
         its value of the key column; later duplicates get +0.0 and 0.  unmatched: the selected rows that match no key, an int64 device scalar
         (None with counts=False).  zones (zone_map(key) or any records that contain the key vectors' intervals): the same bits.  Nothing is
         synchronised (alpgpu_decode_keyed_sum_f64; double columns only)."""
-        import torch
         self._check_pair(val, key)
         if val.dtype != "f64":
-            raise ValueError("keyed_sum is built for double columns only")
-        tdt = torch.float64
-        dev = f"cuda:{self.device}"
-        if isinstance(keys, np.ndarray):
-            if keys.dtype != np.float64:
-                raise ValueError("keys must be of the columns' type (%s)" % val.dtype)
-            keys = torch.from_numpy(np.ascontiguousarray(keys))
-        elif not isinstance(keys, torch.Tensor):
-            keys = torch.tensor(list(keys), dtype=tdt)
-        if keys.dtype != tdt:
-            raise ValueError("keys must be of the columns' type (%s)" % val.dtype)
-        if keys.dim() != 1 or not 1 <= keys.numel() <= KEYED_KEYS_MAX:
-            raise ValueError("keys must be one-dimensional and hold 1 .. %d keys" % KEYED_KEYS_MAX)
-        if keys.is_cuda and keys.device.index != self.device:
-            raise ValueError("keys must be on the host or on cuda:%d" % self.device)
-        if mask is not None:
-            self._check_mask(mask, val.n_vectors)
-        if zones is not None:
-            self._check_zones(zones, tdt, key.n_vectors)
-        lst = keys if keys.is_cuda else keys.to(dev)
-        lst = lst.contiguous() if sorted else torch.sort(lst).values
-        sums = torch.empty(lst.numel(), dtype=torch.float64, device=dev)
-        cnt = torch.empty(lst.numel() + 1, dtype=torch.int64, device=dev) if counts else None
+            raise ValueError("keyed_sum is built for double columns only")  # (the float entry points are not built: include/alpgpu.h says why)
+        lst = self._list_to_device(keys, "keys", val, 1, KEYED_KEYS_MAX, sorted=sorted)
+        sums = torch.empty(lst.numel(), dtype=torch.float64, device=self._dev)
+        cnt = torch.empty(lst.numel() + 1, dtype=torch.int64, device=self._dev) if counts else None
         self.keyed_sum_into(val, key, lst, sums, counts_out=cnt, mask=mask, zones=zones)
         return sums, (cnt[:-1] if counts else None), (cnt[-1] if counts else None)
 
@@ -1588,41 +1381,28 @@ class Context:
         keys: a SORTED contiguous device tensor of the columns' type, 1 .. KEYED_KEYS_MAX long.  zones: any records that contain the KEY vectors'
         intervals: the same bytes.  tuning: {"grid"}, trace: an int64 device tensor of 4 words that is ADDED to (keyed_sum_into's); either sends
         the call through the debug entry (the same bytes).  Nothing is synchronised, read back or allocated, so the call can be captured."""
-        import torch
+        self._keyed_minmax_into("decode_keyed_minmax", KEYED_KEYS_MAX, val, key, keys, out, counts_out, mask, zones, tuning, trace)
+
+    def _keyed_minmax_into(self, stem, keys_max, val, key, keys, out, counts_out, mask, zones, tuning, trace):
+        """keyed_minmax_into and keyed_minmax_many_into: the same arguments and checks, up to keys_max keys, into the entry points of this stem"""
         self._check_pair(val, key)
-        tdt = torch.float64 if val.dtype == "f64" else torch.float32
-        if not isinstance(keys, torch.Tensor) or keys.dtype != tdt:
-            raise ValueError("keys must be a tensor of the columns' type (%s)" % val.dtype)
-        if keys.dim() != 1 or not 1 <= keys.numel() <= KEYED_KEYS_MAX:
-            raise ValueError("keys must be one-dimensional and hold 1 .. %d keys" % KEYED_KEYS_MAX)
-        if not keys.is_cuda or keys.device.index != self.device or not keys.is_contiguous():
-            raise ValueError("keys must be contiguous on cuda:%d" % self.device)
-        n_keys = keys.numel()
-        self._check_tensor(out, tdt, "out")
-        if out.dim() != 2 or tuple(out.shape) != (n_keys, 2) or out.data_ptr() % (2 * out.element_size()):
-            raise ValueError("out must be a [len(keys), 2] tensor of the columns' type, aligned to its records")
+        n_keys = self._check_list(keys, "keys", val, 1, keys_max)
+        self._check_shape(out, _TORCH_TYPE[val.dtype], "out", (n_keys, 2), "[len(keys), 2]", records=True)
         if counts_out is not None:
-            self._check_tensor(counts_out, torch.int64, "counts_out")
-            if counts_out.dim() != 1 or counts_out.numel() != n_keys + 1:
-                raise ValueError("counts_out must be a one-dimensional int64 tensor of len(keys) + 1 words")
-        if mask is not None:
-            self._check_mask(mask, val.n_vectors)
-        if zones is not None:
-            self._check_zones(zones, tdt, key.n_vectors)
-        if trace is not None:
-            self._check_tensor(trace, torch.int64, "trace")
-            if trace.numel() != 4:
-                raise ValueError("trace must hold 4 int64 words")
-        args = [C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
-                _vp(keys.data_ptr()), n_keys, _vp(out.data_ptr()), _vp(counts_out.data_ptr()) if counts_out is not None else None]
-        if tuning is None and trace is None:
-            self._call("decode_keyed_minmax", val.dtype, *args)
-        else:
-            tuning = {} if tuning is None else tuning
-            if set(tuning) - {"grid"}:
-                raise ValueError("tuning takes grid")
-            t = KeyedTuning(int(tuning.get("grid", 0)), 0)
-            self._call("debug_decode_keyed_minmax", val.dtype, *args, C.byref(t), _vp(trace.data_ptr()) if trace is not None else None)
+            self._check_shape(counts_out, torch.int64, "counts_out", (n_keys + 1,), "[len(keys) + 1]")
+        self._check_mask_zones(mask, zones, key)
+        self._check_trace(trace)
+        args = [C.byref(val.c), C.byref(key.c), _ptr(mask), _ptr(zones), _vp(keys.data_ptr()), n_keys, _vp(out.data_ptr()), _ptr(counts_out)]
+        self._call_tuned(stem, val.dtype, args, tuning, trace, KeyedTuning, ("grid",))
+
+    def _keyed_minmax(self, into, keys_max, val, key, keys, mask, zones, counts, sorted):
+        """keyed_minmax and keyed_minmax_many: the keys onto the device and into order, the outputs made, the raw form called"""
+        self._check_pair(val, key)
+        lst = self._list_to_device(keys, "keys", val, 1, keys_max, sorted=sorted)
+        out = torch.empty((lst.numel(), 2), dtype=lst.dtype, device=self._dev)
+        cnt = torch.empty(lst.numel() + 1, dtype=torch.int64, device=self._dev) if counts else None
+        into(val, key, lst, out, counts_out=cnt, mask=mask, zones=zones)
+        return out, (cnt[:-1] if counts else None), (cnt[-1] if counts else None)
 
     def keyed_minmax(self, val: "DeviceColumn", key: "DeviceColumn", keys, mask=None, zones=None, counts: bool = True, sorted: bool = False):
         """MIN(val), MAX(val), COUNT(*) GROUP BY key for the given keys in one pass over the two columns: ([K, 2] records {min, max} of the
@@ -1631,32 +1411,7 @@ class Context:
         (NaNs sort last and never match); sorted=True skips that.  A row belongs to the first key equal to its value of the key column; a key
         without a number, and every later duplicate, gets {+inf, -inf}.  NaN values are counted and ignored.  unmatched: the selected rows that
         match no key, an int64 device scalar (None with counts=False).  Nothing is synchronised (alpgpu_decode_keyed_minmax_f64 / _f32)."""
-        import torch
-        self._check_pair(val, key)
-        tdt, ndt = (torch.float64, np.float64) if val.dtype == "f64" else (torch.float32, np.float32)
-        dev = f"cuda:{self.device}"
-        if isinstance(keys, np.ndarray):
-            if keys.dtype != ndt:
-                raise ValueError("keys must be of the columns' type (%s)" % val.dtype)
-            keys = torch.from_numpy(np.ascontiguousarray(keys))
-        elif not isinstance(keys, torch.Tensor):
-            keys = torch.tensor(list(keys), dtype=tdt)
-        if keys.dtype != tdt:
-            raise ValueError("keys must be of the columns' type (%s)" % val.dtype)
-        if keys.dim() != 1 or not 1 <= keys.numel() <= KEYED_KEYS_MAX:
-            raise ValueError("keys must be one-dimensional and hold 1 .. %d keys" % KEYED_KEYS_MAX)
-        if keys.is_cuda and keys.device.index != self.device:
-            raise ValueError("keys must be on the host or on cuda:%d" % self.device)
-        if mask is not None:
-            self._check_mask(mask, val.n_vectors)
-        if zones is not None:
-            self._check_zones(zones, tdt, key.n_vectors)
-        lst = keys if keys.is_cuda else keys.to(dev)
-        lst = lst.contiguous() if sorted else torch.sort(lst).values
-        out = torch.empty((lst.numel(), 2), dtype=tdt, device=dev)
-        cnt = torch.empty(lst.numel() + 1, dtype=torch.int64, device=dev) if counts else None
-        self.keyed_minmax_into(val, key, lst, out, counts_out=cnt, mask=mask, zones=zones)
-        return out, (cnt[:-1] if counts else None), (cnt[-1] if counts else None)
+        return self._keyed_minmax(self.keyed_minmax_into, KEYED_KEYS_MAX, val, key, keys, mask, zones, counts, sorted)
 
     # ---- keyed MIN / MAX, many keys (include/alpgpu.h: alpgpu_decode_keyed_minmax_many_*) -----------------------------
     def keyed_minmax_many_into(self, val: "DeviceColumn", key: "DeviceColumn", keys, out, counts_out=None, mask=None, zones=None, tuning=None, trace=None):
@@ -1665,117 +1420,22 @@ class Context:
         out and counts_out themselves, updated by integer atomics in device memory.  counts_out=None issues no count atomic at all: the usual call
         behind distinct(), whose counts on the same selection are these.  Nothing is synchronised, read back or allocated, so the call can be
         captured."""
-        import torch
-        self._check_pair(val, key)
-        tdt = torch.float64 if val.dtype == "f64" else torch.float32
-        if not isinstance(keys, torch.Tensor) or keys.dtype != tdt:
-            raise ValueError("keys must be a tensor of the columns' type (%s)" % val.dtype)
-        if keys.dim() != 1 or not 1 <= keys.numel() <= KEYED_MANY_KEYS_MAX:
-            raise ValueError("keys must be one-dimensional and hold 1 .. %d keys" % KEYED_MANY_KEYS_MAX)
-        if not keys.is_cuda or keys.device.index != self.device or not keys.is_contiguous():
-            raise ValueError("keys must be contiguous on cuda:%d" % self.device)
-        n_keys = keys.numel()
-        self._check_tensor(out, tdt, "out")
-        if out.dim() != 2 or tuple(out.shape) != (n_keys, 2) or out.data_ptr() % (2 * out.element_size()):
-            raise ValueError("out must be a [len(keys), 2] tensor of the columns' type, aligned to its records")
-        if counts_out is not None:
-            self._check_tensor(counts_out, torch.int64, "counts_out")
-            if counts_out.dim() != 1 or counts_out.numel() != n_keys + 1:
-                raise ValueError("counts_out must be a one-dimensional int64 tensor of len(keys) + 1 words")
-        if mask is not None:
-            self._check_mask(mask, val.n_vectors)
-        if zones is not None:
-            self._check_zones(zones, tdt, key.n_vectors)
-        if trace is not None:
-            self._check_tensor(trace, torch.int64, "trace")
-            if trace.numel() != 4:
-                raise ValueError("trace must hold 4 int64 words")
-        args = [C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
-                _vp(keys.data_ptr()), n_keys, _vp(out.data_ptr()), _vp(counts_out.data_ptr()) if counts_out is not None else None]
-        if tuning is None and trace is None:
-            self._call("decode_keyed_minmax_many", val.dtype, *args)
-        else:
-            tuning = {} if tuning is None else tuning
-            if set(tuning) - {"grid"}:
-                raise ValueError("tuning takes grid")
-            t = KeyedTuning(int(tuning.get("grid", 0)), 0)
-            self._call("debug_decode_keyed_minmax_many", val.dtype, *args, C.byref(t), _vp(trace.data_ptr()) if trace is not None else None)
+        self._keyed_minmax_into("decode_keyed_minmax_many", KEYED_MANY_KEYS_MAX, val, key, keys, out, counts_out, mask, zones, tuning, trace)
 
     def keyed_minmax_many(self, val: "DeviceColumn", key: "DeviceColumn", keys, mask=None, zones=None, counts: bool = True):
         """MIN(val), MAX(val), COUNT(*) GROUP BY key for up to KEYED_MANY_KEYS_MAX keys in one pass over the two columns: keyed_minmax's argument
         forms and result, ([K, 2] records {min, max} of the columns' type, int64[K] counts or None with counts=False, unmatched), in the order
         of the SORTED keys (torch.sort on the device: NaNs last, where they match nothing).  counts=False keeps no counts at all, which is the
         cheaper call where distinct() has already counted.  Nothing is synchronised (alpgpu_decode_keyed_minmax_many_f64 / _f32)."""
-        import torch
-        self._check_pair(val, key)
-        tdt, ndt = (torch.float64, np.float64) if val.dtype == "f64" else (torch.float32, np.float32)
-        dev = f"cuda:{self.device}"
-        if isinstance(keys, np.ndarray):
-            if keys.dtype != ndt:
-                raise ValueError("keys must be of the columns' type (%s)" % val.dtype)
-            keys = torch.from_numpy(np.ascontiguousarray(keys))
-        elif not isinstance(keys, torch.Tensor):
-            keys = torch.tensor(list(keys), dtype=tdt)
-        if keys.dtype != tdt:
-            raise ValueError("keys must be of the columns' type (%s)" % val.dtype)
-        if keys.dim() != 1 or not 1 <= keys.numel() <= KEYED_MANY_KEYS_MAX:
-            raise ValueError("keys must be one-dimensional and hold 1 .. %d keys" % KEYED_MANY_KEYS_MAX)
-        if keys.is_cuda and keys.device.index != self.device:
-            raise ValueError("keys must be on the host or on cuda:%d" % self.device)
-        if mask is not None:
-            self._check_mask(mask, val.n_vectors)
-        if zones is not None:
-            self._check_zones(zones, tdt, key.n_vectors)
-        lst = keys if keys.is_cuda else keys.to(dev)
-        lst = torch.sort(lst).values
-        out = torch.empty((lst.numel(), 2), dtype=tdt, device=dev)
-        cnt = torch.empty(lst.numel() + 1, dtype=torch.int64, device=dev) if counts else None
-        self.keyed_minmax_many_into(val, key, lst, out, counts_out=cnt, mask=mask, zones=zones)
-        return out, (cnt[:-1] if counts else None), (cnt[-1] if counts else None)
+        return self._keyed_minmax(self.keyed_minmax_many_into, KEYED_MANY_KEYS_MAX, val, key, keys, mask, zones, counts, sorted=False)  # (always sorts)
 
     # ---- bucketed aggregation (include/alpgpu.h: alpgpu_decode_bucket_sum_* / alpgpu_decode_bucket_minmax_*) -----------
     def bucket_sum_scratch(self, n_vectors: int, n_edges: int):
         """a scratch tensor for bucket_sum_into (alpgpu_bucket_sum_scratch_bytes = keyed_sum_scratch's for n_edges + 1 keys)"""
-        import torch
         n_vectors, n_edges = int(n_vectors), int(n_edges)
         if n_vectors < 0 or not 0 <= n_edges <= BUCKET_EDGES_MAX:
             raise ValueError("n_vectors must not be negative and n_edges must be in 0 .. %d" % BUCKET_EDGES_MAX)
         return torch.empty(lib.alpgpu_bucket_sum_scratch_bytes(n_vectors, n_edges), dtype=torch.uint8, device=f"cuda:{self.device}")
-
-    def _bucket_args(self, val, key, edges, counts_out, mask, zones, trace):
-        """what bucket_sum_into and bucket_minmax_into check alike; returns the columns' torch type"""
-        import torch
-        self._check_pair(val, key)
-        tdt = torch.float64 if val.dtype == "f64" else torch.float32
-        if not isinstance(edges, torch.Tensor) or edges.dtype != tdt:
-            raise ValueError("edges must be a tensor of the columns' type (%s)" % val.dtype)
-        if edges.dim() != 1 or edges.numel() > BUCKET_EDGES_MAX:
-            raise ValueError("edges must be one-dimensional and hold at most %d edges" % BUCKET_EDGES_MAX)
-        if not edges.is_cuda or edges.device.index != self.device or not edges.is_contiguous():
-            raise ValueError("edges must be contiguous on cuda:%d" % self.device)
-        if counts_out is not None:
-            self._check_tensor(counts_out, torch.int64, "counts_out")
-            if counts_out.dim() != 1 or counts_out.numel() != edges.numel() + 2:
-                raise ValueError("counts_out must be a one-dimensional int64 tensor of len(edges) + 2 words")
-        if mask is not None:
-            self._check_mask(mask, val.n_vectors)
-        if zones is not None:
-            self._check_zones(zones, tdt, key.n_vectors)
-        if trace is not None:
-            self._check_tensor(trace, torch.int64, "trace")
-            if trace.numel() != 4:
-                raise ValueError("trace must hold 4 int64 words")
-        return tdt
-
-    def _bucket_call(self, name, val, args, tuning, trace):
-        if tuning is None and trace is None:
-            self._call("decode_" + name, val.dtype, *args)
-        else:
-            tuning = {} if tuning is None else tuning
-            if set(tuning) - {"grid"}:
-                raise ValueError("tuning takes grid")
-            t = KeyedTuning(int(tuning.get("grid", 0)), 0)
-            self._call("debug_decode_" + name, val.dtype, *args, C.byref(t), _vp(trace.data_ptr()) if trace is not None else None)
 
     def bucket_sum_into(self, val: "DeviceColumn", key: "DeviceColumn", edges, sums_out, counts_out=None, right: bool = False, mask=None, zones=None, scratch=None,
                         tuning=None, trace=None):
@@ -1788,56 +1448,32 @@ class Context:
         is ADDED to (vectors settled without either column, by the one-bucket shortcut, always 0, decoded); either sends the call through the
         debug entry (the same bits).  Nothing is synchronised or read back; with a scratch given (bucket_sum_scratch) nothing is allocated either,
         so the call can be captured into a graph."""
-        import torch
-        self._bucket_args(val, key, edges, counts_out, mask, zones, trace)
-        n_edges = edges.numel()
-        self._check_tensor(sums_out, torch.float64, "sums_out")
-        if sums_out.dim() != 1 or sums_out.numel() != n_edges + 1:
-            raise ValueError("sums_out must be a one-dimensional float64 tensor of len(edges) + 1")
-        need = lib.alpgpu_bucket_sum_scratch_bytes(val.n_vectors, n_edges)
-        if scratch is None:
-            scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
-        else:
-            self._check_tensor(scratch, torch.uint8, "scratch")
-            if scratch.numel() < need or scratch.data_ptr() % 16:
-                raise ValueError("scratch must hold bucket_sum_scratch(n_vectors, n_edges) bytes, 16-byte aligned")
-        args = [C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
-                _vp(edges.data_ptr()) if n_edges else None, n_edges, 1 if right else 0, _vp(sums_out.data_ptr()), _vp(counts_out.data_ptr()) if counts_out is not None else None,
+        self._check_pair(val, key)
+        n_edges = self._check_list(edges, "edges", val, 0, BUCKET_EDGES_MAX)
+        self._check_shape(sums_out, torch.float64, "sums_out", (n_edges + 1,), "[len(edges) + 1]")
+        if counts_out is not None:
+            self._check_shape(counts_out, torch.int64, "counts_out", (n_edges + 2,), "[len(edges) + 2]")  # (histogram's words; the keyed forms have len + 1)
+        self._check_mask_zones(mask, zones, key)
+        self._check_trace(trace)
+        scratch = self._scratch(scratch, lib.alpgpu_bucket_sum_scratch_bytes(val.n_vectors, n_edges), "bucket_sum_scratch(n_vectors, n_edges)")
+        args = [C.byref(val.c), C.byref(key.c), _ptr(mask), _ptr(zones), _ptr(edges), n_edges, 1 if right else 0, _vp(sums_out.data_ptr()), _ptr(counts_out),
                 _vp(scratch.data_ptr())]
-        self._bucket_call("bucket_sum", val, args, tuning, trace)
+        self._call_tuned("decode_bucket_sum", val.dtype, args, tuning, trace, KeyedTuning, ("grid",))
 
     def bucket_minmax_into(self, val: "DeviceColumn", key: "DeviceColumn", edges, out, counts_out=None, right: bool = False, mask=None, zones=None, tuning=None, trace=None):
         """the raw form of alpgpu_decode_bucket_minmax_f64 / _f32: out ([len(edges) + 1, 2] of the columns' type) takes, per bucket of the KEY column,
         the record {min, max} of val over the selected rows: NaN values ignored but counted, -0.0 < +0.0, {+inf, -inf} for a bucket without a
         number; counts_out, right, edges, zones, tuning and trace are bucket_sum_into's.  counts_out=None keeps no count at all.  Nothing is
         synchronised, read back or allocated, so the call can be captured."""
-        tdt = self._bucket_args(val, key, edges, counts_out, mask, zones, trace)
-        n_edges = edges.numel()
-        self._check_tensor(out, tdt, "out")
-        if out.dim() != 2 or tuple(out.shape) != (n_edges + 1, 2) or out.data_ptr() % (2 * out.element_size()):
-            raise ValueError("out must be a [len(edges) + 1, 2] tensor of the columns' type, aligned to its records")
-        args = [C.byref(val.c), C.byref(key.c), _vp(mask.data_ptr()) if mask is not None and mask.numel() else None, _vp(zones.data_ptr()) if zones is not None and zones.numel() else None,
-                _vp(edges.data_ptr()) if n_edges else None, n_edges, 1 if right else 0, _vp(out.data_ptr()), _vp(counts_out.data_ptr()) if counts_out is not None else None]
-        self._bucket_call("bucket_minmax", val, args, tuning, trace)
-
-    def _bucket_edges(self, val, edges, sorted_):
-        """the allocating wrappers' edges: any sequence of the columns' type onto the device and, unless sorted, into order (histogram's rule)"""
-        import torch
-        tdt, ndt = (torch.float64, np.float64) if val.dtype == "f64" else (torch.float32, np.float32)
-        if isinstance(edges, np.ndarray):
-            if edges.dtype != ndt:
-                raise ValueError("edges must be of the columns' type (%s)" % val.dtype)
-            edges = torch.from_numpy(np.ascontiguousarray(edges))
-        elif not isinstance(edges, torch.Tensor):
-            edges = torch.tensor(list(edges), dtype=tdt)
-        if edges.dtype != tdt:
-            raise ValueError("edges must be of the columns' type (%s)" % val.dtype)
-        if edges.dim() != 1 or edges.numel() > BUCKET_EDGES_MAX:
-            raise ValueError("edges must be one-dimensional and hold at most %d edges" % BUCKET_EDGES_MAX)
-        if edges.is_cuda and edges.device.index != self.device:
-            raise ValueError("edges must be on the host or on cuda:%d" % self.device)
-        lst = edges if edges.is_cuda else edges.to(f"cuda:{self.device}")
-        return lst.contiguous() if sorted_ else torch.sort(lst).values
+        self._check_pair(val, key)
+        n_edges = self._check_list(edges, "edges", val, 0, BUCKET_EDGES_MAX)
+        self._check_shape(out, _TORCH_TYPE[val.dtype], "out", (n_edges + 1, 2), "[len(edges) + 1, 2]", records=True)
+        if counts_out is not None:
+            self._check_shape(counts_out, torch.int64, "counts_out", (n_edges + 2,), "[len(edges) + 2]")
+        self._check_mask_zones(mask, zones, key)
+        self._check_trace(trace)
+        args = [C.byref(val.c), C.byref(key.c), _ptr(mask), _ptr(zones), _ptr(edges), n_edges, 1 if right else 0, _vp(out.data_ptr()), _ptr(counts_out)]
+        self._call_tuned("decode_bucket_minmax", val.dtype, args, tuning, trace, KeyedTuning, ("grid",))
 
     def bucket_sum(self, val: "DeviceColumn", key: "DeviceColumn", edges, right: bool = False, mask=None, zones=None, counts: bool = True, sorted: bool = False):
         """SUM(val), COUNT(*) GROUP BY bucket(key) in one pass over the two columns: (float64[B] sums, int64[B + 1] counts or None with
@@ -1846,12 +1482,10 @@ class Context:
         sums / counts[:B].  edges: a device tensor, host tensor, sequence or numpy array of the columns' type, at most BUCKET_EDGES_MAX long,
         brought into order by torch.sort on the device (NaNs sort last and are inert); sorted=True skips that.  zones (zone_map(key) or any
         records that contain the key vectors' intervals): the same bits.  Nothing is synchronised (alpgpu_decode_bucket_sum_f64 / _f32)."""
-        import torch
         self._check_pair(val, key)
-        lst = self._bucket_edges(val, edges, sorted)
-        dev = f"cuda:{self.device}"
-        sums = torch.empty(lst.numel() + 1, dtype=torch.float64, device=dev)
-        cnt = torch.empty(lst.numel() + 2, dtype=torch.int64, device=dev) if counts else None
+        lst = self._list_to_device(edges, "edges", val, 0, BUCKET_EDGES_MAX, sorted=sorted)
+        sums = torch.empty(lst.numel() + 1, dtype=torch.float64, device=self._dev)
+        cnt = torch.empty(lst.numel() + 2, dtype=torch.int64, device=self._dev) if counts else None
         self.bucket_sum_into(val, key, lst, sums, counts_out=cnt, right=right, mask=mask, zones=zones)
         return sums, cnt
 
@@ -1859,12 +1493,10 @@ class Context:
         """MIN(val), MAX(val), COUNT(*) GROUP BY bucket(key) in one pass over the two columns: ([B, 2] records {min, max} of the columns' type,
         int64[B + 1] counts or None with counts=False), B = len(edges) + 1; bucket_sum's buckets, edges and counts.  NaN values are counted and
         ignored; a bucket without a number gets {+inf, -inf}.  Nothing is synchronised (alpgpu_decode_bucket_minmax_f64 / _f32)."""
-        import torch
         self._check_pair(val, key)
-        lst = self._bucket_edges(val, edges, sorted)
-        dev = f"cuda:{self.device}"
-        out = torch.empty((lst.numel() + 1, 2), dtype=lst.dtype, device=dev)
-        cnt = torch.empty(lst.numel() + 2, dtype=torch.int64, device=dev) if counts else None
+        lst = self._list_to_device(edges, "edges", val, 0, BUCKET_EDGES_MAX, sorted=sorted)
+        out = torch.empty((lst.numel() + 1, 2), dtype=lst.dtype, device=self._dev)
+        cnt = torch.empty(lst.numel() + 2, dtype=torch.int64, device=self._dev) if counts else None
         self.bucket_minmax_into(val, key, lst, out, counts_out=cnt, right=right, mask=mask, zones=zones)
         return out, cnt
 
@@ -1877,46 +1509,24 @@ class Context:
         int64) the number of set bits, also beyond the capacity.  zones (zone_map(col)): the same bytes, vectors whose record admits no key are
         not decoded.  Nothing is synchronised and nothing read back; without a mask, or with a scratch given (select_scratch), nothing is
         allocated either, so the call can be captured into a graph."""
-        import torch
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
-        self._check_tensor(keys, tdt, "keys")
-        if keys.dim() != 1:
-            raise ValueError("keys must be one-dimensional")
-        self._check_tensor(count_out, torch.int64, "count_out")
-        if count_out.numel() < 1:
-            raise ValueError("count_out must hold one int64")
+        n_keys = self._check_list(keys, "keys", col)
+        self._check_at_least(count_out, torch.int64, "count_out", 1, "one int64")
         capacity = 0
         if pos_out is not None:
             self._check_tensor(pos_out, torch.int64, "pos_out")
             capacity = pos_out.numel()
         if span_out is not None:
-            self._check_tensor(span_out, torch.int32, "span_out")
-            if span_out.numel() < capacity:
-                raise ValueError("span_out is shorter than pos_out")
+            self._check_at_least(span_out, torch.int32, "span_out", capacity, "as many spans as pos_out")
         if idx_out is not None:
-            self._check_tensor(idx_out, torch.int64, "idx_out")
-            if idx_out.numel() < capacity:
-                raise ValueError("idx_out is shorter than pos_out")
+            self._check_at_least(idx_out, torch.int64, "idx_out", capacity, "as many indices as pos_out")
         if rows is not None:
-            self._check_tensor(rows, torch.int64, "rows")
-            if rows.numel() < keys.numel():
-                raise ValueError("rows must hold one int64 per key")
-        if zones is not None:
-            self._check_zones(zones, tdt, col.n_vectors)
-        if mask is not None:
-            self._check_mask(mask, col.n_vectors)
-            need = lib.alpgpu_select_scratch_bytes(col.n_vectors)
-            if scratch is None:
-                scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{self.device}")
-            else:
-                self._check_tensor(scratch, torch.uint8, "scratch")
-                if scratch.numel() < need or scratch.data_ptr() % 16:
-                    raise ValueError("scratch must hold alpgpu_select_scratch_bytes(n_vectors) bytes, 16-byte aligned")
-        self._call("join_probe", col.dtype, C.byref(col.c), _vp(mask.data_ptr()) if mask is not None else None, _vp(zones.data_ptr()) if zones is not None else None,
-                   _vp(keys.data_ptr()) if keys.numel() else None, keys.numel(), _vp(rows.data_ptr()) if rows is not None and keys.numel() else None,
-                   _vp(pos_out.data_ptr()) if capacity else None, _vp(span_out.data_ptr()) if span_out is not None and capacity else None,
-                   _vp(idx_out.data_ptr()) if idx_out is not None and capacity else None, capacity, _vp(count_out.data_ptr()),
-                   _vp(scratch.data_ptr()) if mask is not None and scratch is not None else None)
+            self._check_at_least(rows, torch.int64, "rows", n_keys, "one int64 per key")
+        self._check_mask_zones(mask, zones, col)
+        if mask is not None:  # (the scratch serves the mask's scan alone)
+            scratch = self._scratch(scratch, lib.alpgpu_select_scratch_bytes(col.n_vectors), "alpgpu_select_scratch_bytes(n_vectors)")
+        self._call("join_probe", col.dtype, C.byref(col.c), _ptr(mask), _ptr(zones), _ptr(keys), n_keys, _ptr(rows) if n_keys else None, _ptr(pos_out),
+                   _ptr(span_out) if capacity else None, _ptr(idx_out) if capacity else None, capacity, _vp(count_out.data_ptr()),
+                   _vp(scratch.data_ptr()) if mask is not None else None)
 
     def join_probe(self, col: "DeviceColumn", keys, mask=None, rows=None, span: bool = False, indices: bool = False, zones=None, capacity: int = None, sorted: bool = False):
         """for every set bit of the mask (None: every value of the column), ascending by index, which key the value equals: an int64 tensor pos
@@ -1928,30 +1538,15 @@ class Context:
         gather(dim_col, pos) wants.  rows given with unsorted keys is permuted alongside them.  capacity None: the mask's bits are counted
         first (one read of the count, which synchronises the stream); without a mask the count is the column's length and nothing is read
         back."""
-        import torch
-        dev = f"cuda:{self.device}"
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
-        if isinstance(keys, np.ndarray):
-            if keys.dtype != (np.float64 if col.dtype == "f64" else np.float32):
-                raise ValueError("keys must be of the column's type (%s)" % col.dtype)
-            keys = torch.from_numpy(np.ascontiguousarray(keys))
-        elif not isinstance(keys, torch.Tensor):
-            keys = torch.tensor(list(keys), dtype=tdt)
-        if keys.dtype != tdt:
-            raise ValueError("keys must be of the column's type (%s)" % col.dtype)
-        if keys.dim() != 1:
-            raise ValueError("keys must be one-dimensional")
-        if keys.is_cuda and keys.device.index != self.device:
-            raise ValueError("keys must be on the host or on cuda:%d" % self.device)
-        lst = (keys if keys.is_cuda else keys.to(dev)).contiguous()
+        dev = self._dev
+        lst, perm = self._list_to_device(keys, "keys", col, sorted=sorted, want_perm=True)
         if rows is not None:
             if not isinstance(rows, torch.Tensor):
                 rows = torch.as_tensor(np.asarray(rows, dtype=np.int64))
             rows = rows.to(dev).contiguous()
             if rows.dtype != torch.int64 or rows.dim() != 1 or rows.numel() != lst.numel():
                 raise ValueError("rows must hold one int64 per key")
-        if not sorted:
-            lst, perm = torch.sort(lst)
+        if perm is not None:  # (the keys were sorted: rows goes alongside, and without rows the positions are those of the keys as passed)
             rows = perm if rows is None else rows[perm]
         count = torch.empty(1, dtype=torch.int64, device=dev)
         scratch = self.select_scratch(col) if mask is not None else None
@@ -1979,18 +1574,15 @@ class Context:
     def zone_map(self, col: "DeviceColumn", out=None):
         """the zone map of an encoded column, a [n_vectors, 2] tensor of the column's value type: row v = {min, max} of vector v's decoded
         values, NaNs ignored, -0.0 < +0.0, {+inf, -inf} for a vector of NaNs only (alpgpu_zone_map_f64 / _f32)"""
-        import torch
-        tdt = torch.float64 if col.dtype == "f64" else torch.float32
         if out is None:
-            out = torch.empty((col.n_vectors, 2), dtype=tdt, device=f"cuda:{self.device}")
+            out = torch.empty((col.n_vectors, 2), dtype=_TORCH_TYPE[col.dtype], device=self._dev)
         else:
-            self._check_zones(out, tdt, col.n_vectors)
+            self._check_zones(out, _TORCH_TYPE[col.dtype], col.n_vectors)
         self._call("zone_map", col.dtype, C.byref(col.c), _vp(out.data_ptr()))
         return out
 
     def zone_map_of_values(self, x, out=None):
         """the same records from the raw values: x is a contiguous float64 / float32 tensor of whole vectors on this context's device"""
-        import torch
         if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float64, torch.float32):
             raise ValueError("x must be a float64 or float32 tensor")
         self._check_tensor(x, x.dtype, "x")
@@ -2006,7 +1598,6 @@ class Context:
 
     def column_minmax(self, zones, out=None):
         """the column's {min, max} as a 2-element tensor: the reduction of a zone map (alpgpu_zones_minmax_f64 / _f32); {+inf, -inf} for no records"""
-        import torch
         if not isinstance(zones, torch.Tensor) or zones.dtype not in (torch.float64, torch.float32):
             raise ValueError("zones must be a float64 or float32 tensor")
         self._check_zones(zones, zones.dtype, 0)
@@ -2018,42 +1609,6 @@ class Context:
                 raise ValueError("out must hold two values")
         self._call("zones_minmax", self._sfx(zones), _vp(zones.data_ptr()), zones.shape[0], _vp(out.data_ptr()))
         return out
-
-    # ---- batch primitives, 32-bit words (float) --------------------------------------------------------
-    def ffor_i32(self, vals, packed, bw, base):
-        _check(lib.alpgpu_ffor_i32(self.h, self._p(vals), self._p(packed), packed.shape[1], self._p(bw), self._p(base), vals.shape[0]), "alpgpu_ffor_i32")
-
-    def unffor_i32(self, packed, out, bw, base):
-        _check(lib.alpgpu_unffor_i32(self.h, self._p(packed), packed.shape[1], self._p(out), self._p(bw), self._p(base), out.shape[0]), "alpgpu_unffor_i32")
-
-    def falp_f32(self, packed, out, bw, base, fac, exp):
-        _check(lib.alpgpu_falp_f32(self.h, self._p(packed), packed.shape[1], self._p(out), self._p(bw), self._p(base), self._p(fac), self._p(exp),
-                                   out.shape[0]), "alpgpu_falp_f32")
-
-    def decode_values_f32(self, enc, out, fac, exp):
-        _check(lib.alpgpu_decode_values_f32(self.h, self._p(enc), self._p(out), self._p(fac), self._p(exp), out.shape[0]), "alpgpu_decode_values_f32")
-
-    def patch_f32(self, out, exc, pos, cnt):
-        _check(lib.alpgpu_patch_f32(self.h, self._p(out), self._p(exc), self._p(pos), exc.shape[1], self._p(cnt), out.shape[0]), "alpgpu_patch_f32")
-
-    def encode_simdized_f32(self, x, exc, pos, cnt, enc, fac, exp):
-        _check(lib.alpgpu_encode_simdized_f32(self.h, self._p(x), self._p(exc), self._p(pos), exc.shape[1], self._p(cnt), self._p(enc),
-                                              self._p(fac), self._p(exp), x.shape[0]), "alpgpu_encode_simdized_f32")
-
-    def encode_values_f32(self, x, states, state_idx, exc, pos, cnt, enc, fac, exp):
-        _check(lib.alpgpu_encode_values_f32(self.h, self._p(x), self._p(states), self._p(state_idx), self._p(exc), self._p(pos), exc.shape[1],
-                                            self._p(cnt), self._p(enc), self._p(fac), self._p(exp), x.shape[0]), "alpgpu_encode_values_f32")
-
-    def analyze_ffor_i32(self, enc, bw, base):
-        _check(lib.alpgpu_analyze_ffor_i32(self.h, self._p(enc), self._p(bw), self._p(base), enc.shape[0]), "alpgpu_analyze_ffor_i32")
-
-    def rd_encode_vectors_f32(self, x, states, state_idx, exc, pos, cnt, right, left):
-        _check(lib.alpgpu_rd_encode_vectors_f32(self.h, self._p(x), self._p(states), self._p(state_idx), self._p(exc), self._p(pos), exc.shape[1],
-                                                self._p(cnt), self._p(right), self._p(left), x.shape[0]), "alpgpu_rd_encode_vectors_f32")
-
-    def rd_decode_vectors_f32(self, out, right, left, states, state_idx, exc, pos, cnt):
-        _check(lib.alpgpu_rd_decode_vectors_f32(self.h, self._p(out), self._p(right), self._p(left), self._p(states), self._p(state_idx),
-                                                self._p(exc), self._p(pos), exc.shape[1], self._p(cnt), out.shape[0]), "alpgpu_rd_decode_vectors_f32")
 
 
 class DeviceColumn:
