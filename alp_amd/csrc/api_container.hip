@@ -1,4 +1,5 @@
 // api_container.hip — the serialized column (blob) and the descriptor checks of include/alpgpu.h (see host_ctx.hpp for the map).
+#include "blob_check.hpp"
 #include "host_ctx.hpp"
 
 extern "C" {
@@ -53,66 +54,33 @@ int alpgpu_column_to_blob_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_
 	return column_to_blob(ctx, col, n_values, h_blob, capacity, written, 4);
 }
 
-// header of a serialized column: identity, value type, consistent counts, not truncated
+// header of a serialized column: identity, value type, consistent counts, not truncated (the rule: blob_check.hpp)
 int validate_blob_header(const void* h_blob, uint64_t size, uint64_t value_bytes, alpgpu_blob_header& h) {
-	if (size < sizeof(alpgpu_blob_header)) { return fail(ALPGPU_ERR_INVALID, "blob shorter than its header"); }
-	std::memcpy(&h, h_blob, sizeof(h));
-	if (std::memcmp(h.magic, "ALPGPU1", 8) != 0 || h.version != 1 || h.header_bytes != sizeof(h)) { return fail(ALPGPU_ERR_INVALID, "not an ALPGPU v1 blob"); }
-	if ((h.reserved == 0 ? 8ull : h.reserved) != value_bytes) { return fail(ALPGPU_ERR_INVALID, "blob holds a column of the other value type"); }
-	if (h.n_rowgroups != (h.n_vectors + 99) / 100 || h.n_values > h.n_vectors * 1024ull || (h.n_vectors && h.n_values + 1024ull <= h.n_vectors * 1024ull)) {
-		return fail(ALPGPU_ERR_INVALID, "inconsistent blob header");
+	switch (alpgpu::blob_check_header(h_blob, size, value_bytes, h)) {
+	case alpgpu::kBlobOk: return ALPGPU_OK;
+	case alpgpu::kBlobShort: return fail(ALPGPU_ERR_INVALID, "blob shorter than its header");
+	case alpgpu::kBlobIdentity: return fail(ALPGPU_ERR_INVALID, "not an ALPGPU v1 blob");
+	case alpgpu::kBlobValueType: return fail(ALPGPU_ERR_INVALID, "blob holds a column of the other value type");
+	case alpgpu::kBlobInconsistent: return fail(ALPGPU_ERR_INVALID, "inconsistent blob header");
+	default: return fail(ALPGPU_ERR_INVALID, "blob truncated");
 	}
-	if (h.packed_bytes > (1ull << 56) || h.exc_bytes > (1ull << 56) || size < alpgpu_blob_size(h.n_vectors, h.packed_bytes, h.exc_bytes)) {
-		return fail(ALPGPU_ERR_INVALID, "blob truncated");
-	}
-	return ALPGPU_OK;
 }
 
-// vectors [v_begin, v_end) of a blob whose header passed: every extent a kernel will dereference is checked here, so a corrupt
-// blob cannot make the decoder read out of bounds
+// vectors [v_begin, v_end) of a blob whose header passed: every extent a kernel will dereference is checked (blob_check.hpp: blob_check_vectors), so a
+// corrupt blob cannot make the decoder read out of bounds
 // window (optional) = {p0, p1, e0, e1}: the byte ranges of the two streams that will be resident when these vectors are decoded (the
 // chunked host route uploads [p0, p1) / [e0, e1) only) — every record must lie inside them, not merely inside the whole streams.
 int validate_blob_vectors(const void* h_blob, const alpgpu_blob_header& h, uint64_t value_bytes, uint64_t v_begin, uint64_t v_end,
                                  const uint64_t* window) {
-	const unsigned vbits = static_cast<unsigned>(8 * value_bytes); // 64 or 32
-	const unsigned max_e = value_bytes == 8 ? 18u : 10u;
-	const uint8_t* p   = static_cast<const uint8_t*>(h_blob) + sizeof(h);
-	const auto*    rgs = reinterpret_cast<const alpgpu_rowgroup_state*>(p);
-	const auto*    vds = reinterpret_cast<const alpgpu_vector_desc*>(p + 32ull * h.n_rowgroups);
-	for (uint64_t v = v_begin; v < v_end; ++v) {
-		alpgpu_vector_desc d;
-		std::memcpy(&d, vds + v, sizeof(d));
-		alpgpu_rowgroup_state rg;
-		std::memcpy(&rg, rgs + v / 100, sizeof(rg));
-		const bool alp = d.scheme == ALPGPU_SCHEME_ALP, rd = d.scheme == ALPGPU_SCHEME_ALP_RD;
-		if ((!alp && !rd) || rg.scheme != d.scheme) { return fail(ALPGPU_ERR_INVALID, "blob: bad scheme in a descriptor"); }
-		const uint64_t psz = 128ull * (d.bw + (rd ? d.lbw : 0));
-		const uint64_t esz = align8((alp ? value_bytes + 2ull : 4ull) * d.exc_cnt);
-		if (d.bw > vbits || d.exc_cnt > 1024 || (alp && (d.e > max_e || d.f > d.e)) ||
-		    (rd && (d.lbw < 1 || d.lbw > 3 || d.bw > vbits - 1 || d.bw != rg.rd_rbw || d.lbw != rg.rd_lbw))) {
-			return fail(ALPGPU_ERR_INVALID, "blob: descriptor field out of range");
-		}
-		if ((d.packed_off & 127ull) || (d.exc_off & 7ull) || d.packed_off > h.packed_bytes || psz > h.packed_bytes - d.packed_off || d.exc_off > h.exc_bytes ||
-		    esz > h.exc_bytes - d.exc_off) {
-			return fail(ALPGPU_ERR_INVALID, "blob: descriptor extent outside its stream");
-		}
-		if (window != nullptr && ((psz != 0 && (d.packed_off < window[0] || d.packed_off + psz > window[1])) ||
-		                          (esz != 0 && (d.exc_off < window[2] || d.exc_off + esz > window[3])))) {
-			return fail(ALPGPU_ERR_INVALID, "blob: a vector's record lies outside its chunk's stream range (offsets must ascend with the vector index)");
-		}
-		if (d.exc_cnt) { // positions must be < 1024
-			const uint8_t*  rec = p + 32ull * h.n_rowgroups + 32ull * h.n_vectors + align8(h.packed_bytes) + d.exc_off;
-			const uint16_t* pos = reinterpret_cast<const uint16_t*>(rec + (alp ? value_bytes : 2ull) * d.exc_cnt);
-			uint32_t        any = 0; // positions are 16-bit: OR them and look at the bits above 1023 once
-			for (uint32_t j = 0; j < d.exc_cnt; ++j) {
-				uint16_t q;
-				std::memcpy(&q, pos + j, 2);
-				any |= q;
-			}
-			if (any >= 1024) { return fail(ALPGPU_ERR_INVALID, "blob: exception position out of range"); }
-		}
+	switch (alpgpu::blob_check_vectors(h_blob, h, static_cast<uint32_t>(value_bytes), v_begin, v_end, window, nullptr)) {
+	case alpgpu::kBlobOk: return ALPGPU_OK;
+	case alpgpu::kBlobScheme: return fail(ALPGPU_ERR_INVALID, "blob: bad scheme in a descriptor");
+	case alpgpu::kBlobField: return fail(ALPGPU_ERR_INVALID, "blob: descriptor field out of range");
+	case alpgpu::kBlobExtent: return fail(ALPGPU_ERR_INVALID, "blob: descriptor extent outside its stream");
+	case alpgpu::kBlobWindowRecord:
+		return fail(ALPGPU_ERR_INVALID, "blob: a vector's record lies outside its chunk's stream range (offsets must ascend with the vector index)");
+	default: return fail(ALPGPU_ERR_INVALID, "blob: exception position out of range");
 	}
-	return ALPGPU_OK;
 }
 
 static int validate_blob(const void* h_blob, uint64_t size, uint64_t value_bytes, alpgpu_blob_header& h) {

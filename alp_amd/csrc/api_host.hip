@@ -1,4 +1,5 @@
 // api_host.hip — columns that live in HOST memory: the chunked two-stream pipelines over one or several contexts (include/alpgpu.h; see host_ctx.hpp for the map).
+#include "blob_check.hpp"
 #include "host_ctx.hpp"
 
 extern "C" {
@@ -379,18 +380,12 @@ int decompress_host_range(alpgpu_ctx* ctx, const void* h_blob, const alpgpu_blob
 	const uint8_t* blob_vec = blob_rg + 32ull * h.n_rowgroups;
 	const uint8_t* blob_p   = blob_vec + 32ull * n;
 	const uint8_t* blob_e   = blob_p + align8(h.packed_bytes);
-	auto desc_at = [&](uint64_t v) {
-		alpgpu_vector_desc d;
-		std::memcpy(&d, blob_vec + 32ull * v, sizeof(d));
-		return d;
-	};
-	const uint64_t nr       = v_end - v_begin;
+	const uint64_t nr      = v_end - v_begin;
 	const uint64_t rg_begin = v_begin / 100, rg_end = (v_end + 99) / 100;
-	// the range's stream extents (offsets ascend with the vector index: checked chunk by chunk below)
-	const uint64_t P0 = desc_at(v_begin).packed_off, E0 = desc_at(v_begin).exc_off;
-	const uint64_t P1 = v_end < n ? desc_at(v_end).packed_off : h.packed_bytes;
-	const uint64_t E1 = v_end < n ? desc_at(v_end).exc_off : h.exc_bytes;
-	if (P0 > P1 || E0 > E1 || P1 > h.packed_bytes || E1 > h.exc_bytes) { return fail(ALPGPU_ERR_INVALID, "blob: stream offsets do not ascend with the vector index"); }
+	// the range's stream extents (offsets ascend with the vector index: checked chunk by chunk below), as the one window of the whole range
+	const alpgpu::BlobWindow whole = alpgpu::blob_chunk_window(blob_vec, n, h.packed_bytes, h.exc_bytes, v_begin, v_end, nr, 0);
+	if (!whole.ok) { return fail(ALPGPU_ERR_INVALID, "blob: stream offsets do not ascend with the vector index"); }
+	const uint64_t P0 = whole.w[0], P1 = whole.w[1], E0 = whole.w[2], E1 = whole.w[3];
 	HostPipe P;
 	P.bind(ctx);
 	alpgpu_column col;
@@ -441,19 +436,9 @@ int decompress_host_range(alpgpu_ctx* ctx, const void* h_blob, const alpgpu_blob
 	} joiner {workers};
 	// the byte ranges a chunk's decode will find in HBM: from its first vector's offsets to the next chunk's (the streams are exclusive
 	// scans in vector order); every record of the chunk is checked against them
-	struct Window {
-		uint64_t w[4];
-		bool     ok;
-	};
-	auto window_of = [&](uint64_t c) {
-		const uint64_t v0 = v_begin + c * chunk, v1 = v_end - v0 < chunk ? v_end : v0 + chunk;
-		Window W;
-		W.w[0] = desc_at(v0).packed_off, W.w[2] = desc_at(v0).exc_off;
-		W.w[1] = v1 < n ? desc_at(v1).packed_off : h.packed_bytes;
-		W.w[3] = v1 < n ? desc_at(v1).exc_off : h.exc_bytes;
-		W.ok   = P0 <= W.w[0] && W.w[0] <= W.w[1] && W.w[1] <= P1 && E0 <= W.w[2] && W.w[2] <= W.w[3] && W.w[3] <= E1;
-		return W;
-	};
+	// (the rule: blob_check.hpp, blob_chunk_window)
+	using Window   = alpgpu::BlobWindow;
+	auto window_of = [&](uint64_t c) { return alpgpu::blob_chunk_window(blob_vec, n, h.packed_bytes, h.exc_bytes, v_begin, v_end, chunk, c); };
 	for (unsigned w = 0; w < n_workers; ++w) {
 		workers.emplace_back([&, w]() {
 			for (uint64_t c = w; c < n_chunks; c += n_workers) {

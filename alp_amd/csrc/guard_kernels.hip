@@ -5,6 +5,7 @@
 // from alpgpu_encode_* are well-formed by construction and blobs are validated on the host (api_container.hip: validate_blob_vectors); this kernel
 // is the same set of checks for descriptors that reached HBM some other way.  One thread per vector.
 #include "alp_device.hpp"
+#include "blob_check.hpp"
 #include "decode_policy.hpp"
 #include "launch.hpp"
 
@@ -17,18 +18,9 @@ __global__ __launch_bounds__(256) void k_validate_column(const alpgpu_vector_des
 	if (v >= n_vectors) { return; }
 	const alpgpu_vector_desc    d  = descs[v];
 	const alpgpu_rowgroup_state rg = rgs[v / kRowgroup];
-	const uint32_t vbits = 8u * value_bytes;
-	const uint32_t max_e = value_bytes == 8 ? 18u : 10u;
-	const bool     alp = d.scheme == ALPGPU_SCHEME_ALP, rd = d.scheme == ALPGPU_SCHEME_ALP_RD;
-	bool           ok  = (alp || rd) && rg.scheme == d.scheme;
-	const uint64_t psz = 128ull * (d.bw + (rd ? d.lbw : 0));
-	const uint64_t esz = ((alp ? value_bytes + 2ull : 4ull) * d.exc_cnt + 7ull) & ~7ull;
-	ok = ok && d.bw <= vbits && d.exc_cnt <= 1024 && (!alp || (d.e <= max_e && d.f <= d.e)) &&
-	     (!rd || (d.lbw >= 1 && d.lbw <= 3 && d.bw <= vbits - 1 && d.bw == rg.rd_rbw && d.lbw == rg.rd_lbw));
-	ok = ok && (d.packed_off & 127ull) == 0 && (d.exc_off & 7ull) == 0 && d.packed_off <= packed_capacity && psz <= packed_capacity - d.packed_off &&
-	     d.exc_off <= exc_capacity && esz <= exc_capacity - d.exc_off;
+	bool ok = blob_check_descriptor(d, rg, value_bytes, packed_capacity, exc_capacity) == kBlobOk; // the rule the host validator takes (blob_check.hpp)
 	if (ok && d.exc_cnt) { // only now is the record known to lie inside the stream
-		const uint16_t* pos = reinterpret_cast<const uint16_t*>(excs + d.exc_off + static_cast<uint64_t>(alp ? value_bytes : 2u) * d.exc_cnt);
+		const uint16_t* pos = reinterpret_cast<const uint16_t*>(excs + d.exc_off + blob_exc_value_bytes(d, value_bytes) * d.exc_cnt);
 		uint32_t        any = 0;
 		for (uint32_t j = 0; j < d.exc_cnt; ++j) { any |= pos[j]; }
 		ok = any < 1024;

@@ -1471,7 +1471,25 @@ typedef struct alpgpu_blob_header {
 uint64_t alpgpu_blob_size(uint64_t n_vectors, uint64_t packed_bytes, uint64_t exc_bytes);
 int      alpgpu_column_to_blob(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_t n_values, void* h_blob, uint64_t capacity,
                                uint64_t* written);
-/* validates the blob (sizes, every descriptor's extents) and copies it into the caller-allocated column buffers */
+/* validates the blob and copies it into the caller-allocated column buffers.  Nothing is copied, and no kernel runs, before the whole blob has passed.
+ * The header must satisfy, in this order (ALPGPU_ERR_INVALID otherwise):
+ *   size >= 64;  magic "ALPGPU1\0", version 1, header_bytes 64;  reserved names the entry point's value type (0 or 8: double, 4: float);
+ *   n_rowgroups == ceil(n_vectors / 100);  n_values lies in the last vector: (n_vectors - 1) * 1024 < n_values <= n_vectors * 1024, and 0 for no vectors;
+ *   packed_bytes <= 2^56 and exc_bytes <= 2^56;
+ *   64 + 32 * n_rowgroups + 32 * n_vectors + packed_bytes rounded up to 8 + exc_bytes rounded up to 8 <= size (bytes behind that are ignored).
+ * These are statements about integers: the validator evaluates them so that no field value can make one of its expressions wrap (n_vectors is bounded
+ * by size / 32 before anything is multiplied), so no field value can make it read outside [h_blob, h_blob + size).
+ * Then every descriptor, in vector order; the first that fails ends the call:
+ *   scheme is ALP or ALP_RD and equals its rowgroup's;
+ *   ALP: bw <= 64 (float: 32), e <= 18 (float: 10), f <= e.  ALP_RD: bw <= 63 (float: 31), 1 <= lbw <= 3, bw and lbw equal the rowgroup's rd_rbw and
+ *   rd_lbw.  exc_cnt <= 1024.  Fields documented as unused for the scheme (an ALP vector's lbw; an ALP_RD vector's e, f and base) may hold anything:
+ *   no kernel reads them for that scheme;
+ *   packed_off is a multiple of 128, exc_off of 8, and both records lie inside their streams: packed_off + 128 * bw (ALP_RD: + 128 * lbw) <= packed_bytes,
+ *   exc_off + the record's size (exc_cnt values of 8 / 4 bytes, ALP_RD: 2 bytes, then exc_cnt 2-byte positions, rounded up to 8) <= exc_bytes.  A record
+ *   of no bytes may sit at the stream's end.  Records may overlap and lie in any order here (alpgpu_decompress_host_* also wants every record inside
+ *   its chunk's stream range, which offsets that ascend with the vector index give);
+ *   every exception position is < 1024.
+ * The same rules, from the same function, are what alpgpu_column_validate holds a device column to (alp_amd/csrc/blob_check.hpp). */
 int      alpgpu_column_from_blob(alpgpu_ctx* ctx, const void* h_blob, uint64_t size, alpgpu_column* col, uint64_t* n_values);
 
 /* ---- vector primitives on batches (fixed strides; the reference's per-vector API, n at a time) ------
