@@ -291,6 +291,129 @@ def test_column_longer_than_one_fused_launch(ctx, dtype):
     assert int(psz.sum()) == pb and int(esz.sum()) == eb
 
 
+# ---- stream offsets of 2^32 and above: the smallest columns whose packed or exception stream crosses ---------------------------------------------------
+TWO32 = 1 << 32
+
+
+def _uniform(n_vectors, dtype, seed):
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    return torch.rand(n_vectors * 1024, dtype=torch.float64 if dtype == "f64" else torch.float32, device="cuda", generator=g)
+
+
+def _check_column_past_two_to_the_32(ctx, col, x, stream, ordered, expect_rowgroups, what):
+    """a column whose `stream` ("packed" / "exc") passes 2^32: no overflow, the round trip, a gather around the first record at or above 2^32, where the records lie, and
+    the seam vector's rowgroup with its two neighbours against expect_rowgroups(first vector, host values) -> the (rg, vec, packed, exc) layout.compact gives"""
+    from alp_amd import capi
+    n, dtype = col.n_vectors, col.dtype
+    W, it = (8, torch.int64) if dtype == "f64" else (4, torch.int32)
+    pb, eb, ov = ctx.column_totals(col)
+    assert ov == 0, "overflow flag"
+    assert (pb if stream == "packed" else eb) > TWO32, f"{what}: the {stream} stream stays below 2^32 ({pb}, {eb})"
+    out = ctx.decode(col)
+    ctx.synchronize()
+    assert torch.equal(out.view(it), x.view(it)), f"{what}: decode(encode(x)) differs from the input bits"
+    del out
+    vec = col.vectors.cpu().numpy().view(capi.VECTOR_DTYPE)[:n]
+    psz, esz = layout.record_sizes(vec["scheme"], vec["bw"], vec["lbw"], vec["exc_cnt"], W)
+    off, sz = (vec["packed_off"], psz) if stream == "packed" else (vec["exc_off"], esz)
+    off = off.astype(np.int64)
+    above = np.nonzero((off >= TWO32) & (sz > 0))[0]
+    assert above.size and (off[sz > 0] < TWO32).any(), "records on both sides of 2^32"
+    seam = int(above[np.argmin(off[above])])  # the vector of the first record at or above 2^32
+    print(f"{what}: pb = {pb}, eb = {eb}; the first {stream} record at or above 2^32 is vector {seam}'s, at {int(off[seam]):#x}; {above.size} records lie above")
+    idx = torch.arange((seam - 2) * 1024, (seam + 2) * 1024, dtype=torch.int64, device="cuda")
+    assert torch.equal(ctx.gather(col, idx).view(it), x[idx].view(it)), f"{what}: gather of the 4096 values around vector {seam}"
+    if ordered:  # the offsets are the exclusive scan of the record sizes, in vector order
+        assert np.array_equal(vec["packed_off"], np.concatenate([[0], np.cumsum(psz)[:-1]]).astype(np.uint64))
+        assert np.array_equal(vec["exc_off"], np.concatenate([[0], np.cumsum(esz)[:-1]]).astype(np.uint64))
+        assert int(psz.sum()) == pb and int(esz.sum()) == eb
+    else:
+        _assert_records_tile_the_streams(vec, pb, eb, W)
+    # the seam vector's rowgroup and its two neighbours: states, descriptors but for the two offsets, packed bytes and exception bytes, read through the descriptors' offsets
+    r0 = seam // 100 - 1
+    assert r0 >= 0 and (r0 + 3) * 100 <= n
+    v0, v1 = r0 * 100, (r0 + 3) * 100
+    w_rg, w_vec, w_packed, w_exc = expect_rowgroups(v0, x[v0 * 1024:v1 * 1024].cpu().numpy())
+    rg = col.rowgroups.cpu().numpy().view(capi.ROWGROUP_DTYPE)[r0:r0 + 3]
+    assert np.array_equal(rg.view(np.uint8), w_rg.view(np.uint8)), f"{what}: rowgroup states {r0}..{r0 + 2}"
+    for k in ("base", "bw", "e", "f", "lbw", "exc_cnt", "scheme"):
+        assert np.array_equal(vec[k][v0:v1], w_vec[k]), f"{what}: {k} of vectors {v0}..{v1 - 1}"
+    for v in range(v0, v1):
+        a, b, size = int(vec["packed_off"][v]), int(w_vec["packed_off"][v - v0]), int(psz[v])
+        assert np.array_equal(col.packed[a:a + size].cpu().numpy(), w_packed[b:b + size]), f"{what}: packed bytes of vector {v} at {a:#x}"
+        a, b, size = int(vec["exc_off"][v]), int(w_vec["exc_off"][v - v0]), int(esz[v])
+        assert np.array_equal(col.exc[a:a + size].cpu().numpy(), w_exc[b:b + size]), f"{what}: exception bytes of vector {v} at {a:#x}"
+    return pb, eb, seam
+
+
+@pytest.mark.parametrize("route", ["single_pass", "two_pass", "unordered"])
+def test_packed_stream_past_two_to_the_32(ctx, oracle, route):
+    """625 000 vectors of uniform doubles (torch.rand: multiples of 2^-53): ALP_RD at 55 bits, 7040 B per vector, so the packed stream passes 2^32 at vector
+    610 081 — base + (31-bit field) * 128 in every launch, the chain through d_totals[4..5], the unordered form's atomics.  (530 000 vectors, the count first
+    planned from 8.3 KB per vector, end at 3.73 GB.)"""
+    from alp_amd import capi
+    n = 625_000
+    x = _uniform(n, "f64", 21)
+    option = {"single_pass": None, "two_pass": capi.OPT_ENCODE_TWO_PASS, "unordered": capi.OPT_ENCODE_UNORDERED}[route]
+    col = capi.DeviceColumn(n)
+    try:
+        if option is not None:
+            ctx.set_option(option, 1)
+        ctx.encode(x, col)
+        ctx.synchronize()
+    finally:
+        if option is not None:
+            ctx.set_option(option, 0)
+    _check_column_past_two_to_the_32(ctx, col, x, "packed", route != "unordered", lambda v0, values: layout.compact(oracle.encode_column(values)), f"f64 {route}")
+
+
+def test_float_packed_stream_past_two_to_the_32(ctx):
+    """1 310 000 vectors of uniform floats (torch.rand: multiples of 2^-24), the default route: ALP_RD at 26 bits, about 3327 B per vector, so the packed stream
+    passes 2^32 near vector 1 291 000, in the second of two chained launches.  (1 040 000 vectors, the count first planned, end at 3.46 GB.)"""
+    from alp_amd import capi
+    from oracle.pyoracle import OracleF32
+    of32 = OracleF32()
+    n = 1_310_000
+    x = _uniform(n, "f32", 22)
+    col = capi.DeviceColumn(n, dtype="f32")
+    ctx.encode(x, col)
+    ctx.synchronize()
+    _check_column_past_two_to_the_32(ctx, col, x, "packed", True, lambda v0, values: layout.compact(of32.encode_column(values), 4), "f32 single_pass")
+
+
+def test_exception_stream_past_two_to_the_32(ctx, oracle):
+    """425 000 vectors of the same uniform doubles under caller-supplied ALP states with (e, f) = (0, 0), as gpu_encode(states=...) supplies them: no value of (0, 1)
+    is an integer, so every vector has 1024 exceptions, 10 240 B of exception record, and the exception stream passes 2^32 near vector 419 431"""
+    from alp_amd import capi
+    n = 425_000
+    x = _uniform(n, "f64", 21)
+    assert bool((x != 0).all())
+    states = np.zeros(n // 100, capi.ROWGROUP_DTYPE)
+    states["scheme"], states["k"] = capi.SCHEME_ALP, 1  # combos[0] = (e, f) = (0, 0)
+    col = capi.DeviceColumn(n)
+    col.rowgroups[: states.size * 32] = torch.from_numpy(states.view(np.uint8).reshape(-1)).cuda()
+    ctx.encode_vectors(x, col)
+    ctx.synchronize()
+
+    def expect(v0, values):
+        """the oracle's vector encode under that state: encode_simdized with (e, f) = (0, 0), then the frame of reference"""
+        m = values.size // 1024
+        o = dict(scheme=np.full(m, capi.SCHEME_ALP, np.uint8), e=np.zeros(m, np.uint8), f=np.zeros(m, np.uint8), bw=np.zeros(m, np.uint8), lbw=np.zeros(m, np.uint8),
+                 base=np.zeros(m, np.int64), exc_cnt=np.zeros(m, np.uint16), packed=np.zeros((m, 1024), np.int64), packed_left=np.zeros((m, 1024), np.uint16),
+                 exc=np.zeros((m, 1024), np.float64), pos=np.zeros((m, 1024), np.uint16), dict=np.zeros((m // 100, 8), np.uint16), dict_size=np.zeros(m // 100, np.uint8),
+                 k=np.ones(m // 100, np.uint8), combos=np.zeros((m // 100, 10), np.int32))
+        for i in range(m):
+            enc, o["exc"][i], o["pos"][i], o["exc_cnt"][i] = oracle.encode_simdized(values[1024 * i:1024 * i + 1024], 0, 0)
+            o["bw"][i], o["base"][i] = oracle.analyze_ffor(enc)
+            o["packed"][i] = oracle.ffor_u64(enc, int(o["bw"][i]), int(o["base"][i])).view(np.int64)
+        assert (o["exc_cnt"] == 1024).all()
+        return layout.compact(o)
+
+    pb, eb, seam = _check_column_past_two_to_the_32(ctx, col, x, "exc", True, expect, "f64 forced states")
+    assert eb == 10240 * n and seam == -(-TWO32 // 10240)
+
+
 @pytest.mark.parametrize("n_vectors", [4, 5, 252, 255, 256, 257, 260, 511, 512, 513, 16383, 16384, 16385, 16388])
 def test_look_back_block_boundaries(ctx, oracle, n_vectors):
     """column lengths around the look-back's block (64 tiles = 256 vectors) and tile (4 vectors) boundaries: offsets and
