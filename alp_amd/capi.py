@@ -211,6 +211,11 @@ BUCKET_EDGES_MAX = 1023  # ALPGPU_BUCKET_EDGES_MAX: n_edges + 1 buckets <= KEYED
 for _t in ("f64", "f32"):  # keyed MIN / MAX beyond KEYED_KEYS_MAX keys: the table in device memory
     _sig("alpgpu_decode_keyed_minmax_many_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp)
     _sig("alpgpu_debug_decode_keyed_minmax_many_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.POINTER(KeyedTuning), _vp)
+KEYED_EXACT_VECTORS_MAX = 1 << 21  # ALPGPU_KEYED_EXACT_VECTORS_MAX: 2^31 rows, what a limb of the exact sums' table holds
+_sig("alpgpu_keyed_exact_sum_table_bytes", _u64, C.c_uint32)
+for _t in ("f64", "f32"):  # the exact keyed SUM: (ctx, val, key, mask, zones, keys, n_keys, sums, counts, table, accumulate)
+    _sig("alpgpu_decode_keyed_exact_sum_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _int)
+    _sig("alpgpu_debug_decode_keyed_exact_sum_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _int, C.POINTER(KeyedTuning), _vp)
 _sig("alpgpu_bucket_sum_scratch_bytes", _u64, _u64, C.c_uint32)
 for _t in ("f64", "f32"):  # bucketed aggregation: the key column's buckets by sorted edges; (ctx, val, key, mask, zones, edges, n_edges, right, ...)
     _sig("alpgpu_decode_bucket_sum_" + _t, _int, _vp, C.POINTER(CColumn), C.POINTER(CColumn), _vp, _vp, _vp, C.c_uint32, _int, _vp, _vp, _vp)
@@ -1428,6 +1433,58 @@ class Context:
         of the SORTED keys (torch.sort on the device: NaNs last, where they match nothing).  counts=False keeps no counts at all, which is the
         cheaper call where distinct() has already counted.  Nothing is synchronised (alpgpu_decode_keyed_minmax_many_f64 / _f32)."""
         return self._keyed_minmax(self.keyed_minmax_many_into, KEYED_MANY_KEYS_MAX, val, key, keys, mask, zones, counts, sorted=False)  # (always sorts)
+
+    # ---- exact keyed SUM (include/alpgpu.h: alpgpu_decode_keyed_exact_sum_*) ---------------------------------------------
+    def keyed_sum_exact_table(self, n_keys: int):
+        """a table for keyed_sum_exact_into with this many keys (alpgpu_keyed_exact_sum_table_bytes; torch allocations are at least 16-byte
+        aligned).  Its contents are irrelevant before a call without accumulate; calls with accumulate add to it."""
+        n_keys = int(n_keys)
+        if not 1 <= n_keys <= KEYED_MANY_KEYS_MAX:
+            raise ValueError("n_keys must be in 1 .. %d" % KEYED_MANY_KEYS_MAX)
+        return torch.empty(lib.alpgpu_keyed_exact_sum_table_bytes(n_keys), dtype=torch.uint8, device=self._dev)
+
+    def keyed_sum_exact_into(self, val: "DeviceColumn", key: "DeviceColumn", keys, sums_out, counts_out=None, mask=None, zones=None, table=None, accumulate: bool = False,
+                             tuning=None, trace=None):
+        """the raw form of alpgpu_decode_keyed_exact_sum_f64 / _f32: keyed_minmax_many_into's columns, keys (SORTED, on the device, 1 ..
+        KEYED_MANY_KEYS_MAX long), match, counts, bitmap and zones; sums_out (float64 for both precisions, exactly len(keys)) takes, per key, the
+        CORRECTLY ROUNDED real sum of val over its selected rows: a NaN if a NaN or both infinities are among them, an infinity if it is, +-inf
+        where the sum rounds beyond the largest double, +0.0 for no row; the same bytes on every grid, device and row order.  table
+        (keyed_sum_exact_table(len(keys)); None: a new one) holds the sums as integers.  accumulate: the table and counts_out are added to and
+        not zeroed first, and sums_out is written from the table as it then stands, so calls over shards, ranges of a bitmap or further columns
+        extend the sums exactly; it needs the table of the earlier call.  A table takes at most 2^31 rows in all; one call at most
+        KEYED_EXACT_VECTORS_MAX vectors.  tuning: {"grid"}, trace: an int64 device tensor of 6 words that is ADDED to (keyed_sum_into's four,
+        the steps summed in registers, the steps sent lane by lane); either sends the call through the debug entry (the same bytes).  Nothing
+        is synchronised or read back; with a table given nothing is allocated either, so the call can be captured into a graph."""
+        self._check_pair(val, key)
+        n_keys = self._check_list(keys, "keys", val, 1, KEYED_MANY_KEYS_MAX)
+        if val.n_vectors > KEYED_EXACT_VECTORS_MAX:
+            raise ValueError("one call takes at most %d vectors" % KEYED_EXACT_VECTORS_MAX)
+        self._check_shape(sums_out, torch.float64, "sums_out", (n_keys,), "[len(keys)]")
+        if counts_out is not None:
+            self._check_shape(counts_out, torch.int64, "counts_out", (n_keys + 1,), "[len(keys) + 1]")
+        self._check_mask_zones(mask, zones, key)
+        self._check_trace(trace, 6)  # (6 words where the family's other traces have 4)
+        if accumulate and table is None:
+            raise ValueError("accumulate adds to a table: pass the one of the earlier call")
+        table = self._scratch(table, lib.alpgpu_keyed_exact_sum_table_bytes(n_keys), "keyed_sum_exact_table(len(keys))")
+        args = [C.byref(val.c), C.byref(key.c), _ptr(mask), _ptr(zones), _vp(keys.data_ptr()), n_keys, _vp(sums_out.data_ptr()), _ptr(counts_out), _vp(table.data_ptr()),
+                1 if accumulate else 0]
+        self._call_tuned("decode_keyed_exact_sum", val.dtype, args, tuning, trace, KeyedTuning, ("grid",))
+
+    def keyed_sum_exact(self, val: "DeviceColumn", key: "DeviceColumn", keys, mask=None, zones=None, counts: bool = True, sorted: bool = False):
+        """SUM(val), COUNT(*) GROUP BY key for up to KEYED_MANY_KEYS_MAX keys in one pass over the two columns, every sum correctly rounded:
+        (float64[K] sums, int64[K] counts or None with counts=False, unmatched), in the order of the SORTED keys.  keys: keyed_sum's forms,
+        brought into order by torch.sort on the device unless sorted.  Double and float columns; the sums are float64 for both.  To extend
+        sums over further calls use keyed_sum_exact_into with a table and accumulate.  Nothing is synchronised
+        (alpgpu_decode_keyed_exact_sum_f64 / _f32)."""
+        self._check_pair(val, key)
+        lst = self._list_to_device(keys, "keys", val, 1, KEYED_MANY_KEYS_MAX, sorted=sorted)
+        if val.n_vectors > KEYED_EXACT_VECTORS_MAX:
+            raise ValueError("one call takes at most %d vectors" % KEYED_EXACT_VECTORS_MAX)
+        sums = torch.empty(lst.numel(), dtype=torch.float64, device=self._dev)
+        cnt = torch.empty(lst.numel() + 1, dtype=torch.int64, device=self._dev) if counts else None
+        self.keyed_sum_exact_into(val, key, lst, sums, counts_out=cnt, mask=mask, zones=zones)
+        return sums, (cnt[:-1] if counts else None), (cnt[-1] if counts else None)
 
     # ---- bucketed aggregation (include/alpgpu.h: alpgpu_decode_bucket_sum_* / alpgpu_decode_bucket_minmax_*) -----------
     def bucket_sum_scratch(self, n_vectors: int, n_edges: int):

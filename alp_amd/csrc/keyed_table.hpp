@@ -1,6 +1,7 @@
 // keyed_table.hpp — what the aggregations over a value column decoded beside a key column share: keyed SUM (keyed_kernels.hip), keyed MIN / MAX
-// (keyed_minmax_kernels.hip), keyed MIN / MAX for many keys (keyed_minmax_many_kernels.hip) and bucketed SUM and MIN / MAX (bucket_kernels.hip).  Only
-// those four files include this header.  It holds the LEAF pieces of the two kinds of table (the sum table: a private table per wavefront fed by
+// (keyed_minmax_kernels.hip), keyed MIN / MAX for many keys (keyed_minmax_many_kernels.hip), bucketed SUM and MIN / MAX (bucket_kernels.hip) and the
+// exact keyed SUM (keyed_sum_exact_kernels.hip: of this header's own pieces it uses the trace's classes alone, and through it the headers included
+// below).  Only those five files include this header.  It holds the LEAF pieces of the two kinds of table (the sum table: a private table per wavefront fed by
 // keyed_step; the record table: one table per workgroup fed by kmm_step), the trace's classes, the tiers and the declarations of the two kernels that
 // bucket_kernels.hip launches from keyed_kernels.hip.
 //

@@ -234,6 +234,15 @@ int launch_keyed_minmax(hipStream_t stream, const alpgpu_column* val, const alpg
 int launch_keyed_minmax_many(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const void* d_zones, const void* d_keys,
                              uint32_t n_keys, void* d_out, uint64_t* d_counts, int value_bytes, int n_cus, const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
 
+// keyed_sum_exact_kernels.hip: the correctly rounded SUM and the COUNT per key for n_keys in 1 .. ALPGPU_KEYED_MANY_KEYS_MAX: launch_keyed_minmax_many's
+// arguments with d_sums (n_keys doubles for both precisions) in place of the records, d_table (keyed_sum_exact_table_bytes(n_keys) bytes, 16-byte
+// aligned: 66 limbs of int64 and a word of flags per key) and accumulate (0: a kernel zeroes the table and the counts first).  n_vectors may be 0.
+// The zero kernel, one launch of persistent workgroups, two per CU, and the finish kernel that rounds every entry into d_sums.
+uint64_t keyed_sum_exact_table_bytes(uint32_t n_keys);
+int launch_keyed_sum_exact(hipStream_t stream, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const void* d_zones, const void* d_keys,
+                           uint32_t n_keys, double* d_sums, uint64_t* d_counts, void* d_table, int accumulate, int value_bytes, int n_cus, const alpgpu_keyed_tuning* tuning,
+                           uint64_t* d_trace);
+
 // bucket_kernels.hip: SUM, the record {min, max} and the COUNT per bucket of the key column by n_edges (0 .. ALPGPU_BUCKET_EDGES_MAX) sorted edges:
 // launch_keyed_sum's / launch_keyed_minmax's arguments with d_edges (nullable with n_edges == 0) and `right` in place of the keys, n_edges + 1 sums or
 // records, d_counts n_edges + 2 words, d_scratch 64 bytes of header and S rows of n_edges + 1 doubles; value_bytes 8 or 4 for both.

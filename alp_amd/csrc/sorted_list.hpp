@@ -1,9 +1,9 @@
 // sorted_list.hpp — a sorted list staged in LDS and searched there, the one home of it: lds_bound, the branch-free, wave-uniform bound over LDS
 // words that k_in_list (in_list_kernels.hip), k_join_probe (join_kernels.hip), k_histogram (histogram_kernels.hip: its edges), k_keyed_sum
 // (keyed_kernels.hip: its keys), k_keyed_minmax (keyed_minmax_kernels.hip: its keys) and k_bucket_sum / k_bucket_minmax (bucket_kernels.hip: their edges) share, and, for the first two and k_keyed_minmax_many
-// (keyed_minmax_many_kernels.hip), the workgroup shape, the record that says what was staged (InArgs; k_join_probe and k_keyed_minmax_many leave
+// (keyed_minmax_many_kernels.hip) and k_keyed_sum_exact (keyed_sum_exact_kernels.hip), the workgroup shape, the record that says what was staged (InArgs; k_join_probe, k_keyed_minmax_many and k_keyed_sum_exact leave
 // the bitmap fields zero), the staging loop, in_list_search with its pivot tier, the zone bounds and the fetch for the equality test.  Only those
-// seven files include this header, the last four through keyed_table.hpp.
+// eight files include this header, the last five through keyed_table.hpp.
 #pragma once
 #include "launch.hpp"
 #include "register_decode.hpp"

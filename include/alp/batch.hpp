@@ -918,6 +918,50 @@ struct column {
 		out.unmatched = counts.back();
 		return out;
 	}
+	// Exact keyed SUM (include/alpgpu.h, "exact keyed SUM": alpgpu_decode_keyed_exact_sum_*): sum_by_key's arguments, key handling and result for up
+	// to ALPGPU_KEYED_MANY_KEYS_MAX = 2^20 keys and for double AND float columns, every sum the correctly rounded real sum of its rows (a double for
+	// both precisions): a NaN if a NaN or both infinities are among them, +-inf where it rounds beyond DBL_MAX, +0.0 for a key without rows.  The sums
+	// do not depend on the order of the rows, the grid or the device.  At most ALPGPU_KEYED_EXACT_VECTORS_MAX vectors per column.
+	static keyed_result sum_by_key_exact(const uint8_t* blob_val, size_t size_val, const uint8_t* blob_key, size_t size_key, const std::vector<uint64_t>* mask,
+	                                     const std::vector<zone>* zones, const PT* keys, size_t n_keys) {
+		const std::string who = "alp::gpu::column::sum_by_key_exact";
+		if (!keys || n_keys == 0 || n_keys > ALPGPU_KEYED_MANY_KEYS_MAX) { throw std::runtime_error(who + ": 1 .. ALPGPU_KEYED_MANY_KEYS_MAX keys"); }
+		uploaded_column val(blob_val, size_val, who.c_str()), key(blob_key, size_key, who.c_str());
+		const uint64_t  nv = val.col.n_vectors;
+		if (key.col.n_vectors != nv) { throw std::runtime_error(who + ": the columns differ in length"); }
+		if (nv > ALPGPU_KEYED_EXACT_VECTORS_MAX) { throw std::runtime_error(who + ": at most ALPGPU_KEYED_EXACT_VECTORS_MAX vectors"); }
+		if (mask && mask->size() != 16 * nv) { throw std::runtime_error(who + ": the mask must hold 16 words per vector"); }
+		if (zones && zones->size() != nv) { throw std::runtime_error(who + ": one record per vector"); }
+		keyed_result out;
+		out.keys.assign(keys, keys + n_keys);
+		std::sort(out.keys.begin(), out.keys.end(), [](PT a, PT b) { return b != b ? a == a : a < b; }); // ascending by <, NaNs last
+		out.sums.assign(n_keys, 0.0);
+		out.counts.assign(n_keys, 0);
+		if (nv == 0) { return out; }
+		const uint32_t nk       = static_cast<uint32_t>(n_keys);
+		uint64_t*      d_mask   = mask ? static_cast<uint64_t*>(val.get(mask->size() * sizeof(uint64_t))) : nullptr;
+		zone*          d_zones  = zones ? static_cast<zone*>(val.get(nv * sizeof(zone))) : nullptr;
+		PT*            d_keys   = static_cast<PT*>(val.get(n_keys * sizeof(PT)));
+		double*        d_sums   = static_cast<double*>(val.get(n_keys * sizeof(double)));
+		uint64_t*      d_counts = static_cast<uint64_t*>(val.get((n_keys + 1) * sizeof(uint64_t)));
+		void*          d_table  = val.get(alpgpu_keyed_exact_sum_table_bytes(nk));
+		if (mask) { check(alpgpu_memcpy_h2d(context(), d_mask, mask->data(), mask->size() * sizeof(uint64_t)), "alpgpu_memcpy_h2d"); }
+		if (zones) { check(alpgpu_memcpy_h2d(context(), d_zones, zones->data(), nv * sizeof(zone)), "alpgpu_memcpy_h2d"); }
+		check(alpgpu_memcpy_h2d(context(), d_keys, out.keys.data(), n_keys * sizeof(PT)), "alpgpu_memcpy_h2d");
+		if constexpr (sizeof(PT) == 8) {
+			check(alpgpu_decode_keyed_exact_sum_f64(context(), &val.col, &key.col, d_mask, d_zones, reinterpret_cast<const double*>(d_keys), nk, d_sums, d_counts, d_table, 0),
+			      "alpgpu_decode_keyed_exact_sum_f64");
+		} else {
+			check(alpgpu_decode_keyed_exact_sum_f32(context(), &val.col, &key.col, d_mask, d_zones, reinterpret_cast<const float*>(d_keys), nk, d_sums, d_counts, d_table, 0),
+			      "alpgpu_decode_keyed_exact_sum_f32");
+		}
+		std::vector<uint64_t> counts(n_keys + 1);
+		check(alpgpu_memcpy_d2h(context(), out.sums.data(), d_sums, n_keys * sizeof(double)), "alpgpu_memcpy_d2h");
+		check(alpgpu_memcpy_d2h(context(), counts.data(), d_counts, counts.size() * sizeof(uint64_t)), "alpgpu_memcpy_d2h");
+		out.counts.assign(counts.begin(), counts.end() - 1);
+		out.unmatched = counts.back();
+		return out;
+	}
 	// Keyed MIN / MAX (include/alpgpu.h, "keyed MIN / MAX"): the record {min, max} and the COUNT of this column (blob val) per key, with sum_by_key's
 	// arguments and key handling, for double and float columns (alpgpu_decode_keyed_minmax_*).  keys, records and counts come back in the order of
 	// the sorted keys.  A record ignores NaN values (they are counted), orders -0.0 below +0.0 and is {+inf, -inf} for a key without a number and

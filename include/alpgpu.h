@@ -1204,8 +1204,8 @@ int alpgpu_debug_distinct_f32(alpgpu_ctx* ctx, const alpgpu_column* col, uint64_
  * The call runs on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no state kept; none of what
  *   the context remembers about columns (the decode plans) is read or written; safe inside a stream capture.  No floating-point atomics; integer
  *   atomics for the counts and the ticket only; no workgroup waits for another.
- * Not built: more than 1024 keys per call, range groups (alpgpu_decode_group_sum_*), multi-column keys, keys not known in advance
- *   (alpgpu_distinct_* first).
+ * Not built: more than 1024 keys per call (in this order; alpgpu_decode_keyed_exact_sum_* takes up to 2^20 keys and float columns, under its own
+ *   contract), range groups (alpgpu_decode_group_sum_*), multi-column keys, keys not known in advance (alpgpu_distinct_* first).
  * TRUST: as for alpgpu_select_range_* (descriptors followed as found; exception positions ascend within a vector). */
 #define ALPGPU_KEYED_KEYS_MAX    1024u
 #define ALPGPU_KEYED_STRIPES_MAX 4096u
@@ -1329,7 +1329,8 @@ int alpgpu_debug_decode_keyed_minmax_f32(alpgpu_ctx* ctx, const alpgpu_column* v
  * The call runs on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no state kept; safe inside a
  *   stream capture (the keys and the bitmap are read at replay).  No workgroup waits for another.
  * The debug entry takes alpgpu_keyed_tuning (grid) and adds to the four trace words of alpgpu_debug_decode_keyed_sum_*; no tuning changes a byte.
- * Not built: more than 2^20 keys per call, a keyed SUM beyond 1024 keys, range groups (alpgpu_decode_group_minmax_*), multi-column keys, keys not
+ * Not built: more than 2^20 keys per call, a keyed SUM beyond 1024 keys in alpgpu_decode_keyed_sum_*'s striped order (the route beyond is
+ *   alpgpu_decode_keyed_exact_sum_*, below: another, stronger contract), range groups (alpgpu_decode_group_minmax_*), multi-column keys, keys not
  *   known in advance (alpgpu_distinct_* first).
  * TRUST: as for alpgpu_select_range_*. */
 #define ALPGPU_KEYED_MANY_KEYS_MAX (1u << 20) /* == ALPGPU_DISTINCT_MAX */
@@ -1343,6 +1344,78 @@ int alpgpu_debug_decode_keyed_minmax_many_f64(alpgpu_ctx* ctx, const alpgpu_colu
 int alpgpu_debug_decode_keyed_minmax_many_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f32* d_key_zones,
                                               const float* d_keys, uint32_t n_keys, alpgpu_zone_f32* d_out, uint64_t* d_counts, const alpgpu_keyed_tuning* tuning,
                                               uint64_t* d_trace);
+
+/* ---- exact keyed SUM --------------------------------------------------------------------------------------------------------------------------------
+ * SELECT key, SUM(x), COUNT(*) ... WHERE ... GROUP BY key for up to 2^20 discrete keys known in advance, in ONE pass that decodes both columns in
+ * registers, each sum the CORRECTLY ROUNDED real sum of its rows.  Built for double and float columns (the first keyed SUM a float column gets).
+ * alpgpu_decode_keyed_sum_* stops at 1024 keys because its sums are floating-point sums in a documented order; an exact sum needs no order.
+ *   alpgpu_decode_keyed_exact_sum_*   val, key (val == key allowed), d_mask, d_key_zones, d_keys and n_keys (1 .. ALPGPU_KEYED_MANY_KEYS_MAX) are
+ *                               alpgpu_decode_keyed_minmax_many_*'s, word for word, and so is the match: row r belongs to key i if i is the FIRST
+ *                               position with d_keys[i] == k_r; -0.0 matches +0.0; a NaN k_r matches nothing and a NaN in d_keys is never matched;
+ *                               later duplicates in d_keys receive nothing.  The zone-record rules are the same too: a record narrows its vector's
+ *                               search; a record that admits no key means rows without a key, neither column read; min == max on a key vector
+ *                               that is ALP without exceptions settles the key of every selected row without the key vector's packed words.
+ *                               Truthful records change no byte.  Records that do not contain the truth, or keys that are not sorted, give
+ *                               unspecified sums and counts; the sum of the n_keys + 1 counts is still the number of selected rows, and nothing
+ *                               is read outside d_keys[0 .. n_keys) or the columns nor written outside the outputs and the table: every probe
+ *                               index is clamped.
+ *                               d_sums: n_keys doubles, 8-byte aligned, for both precisions (a float x_r is widened to double, exactly).
+ *                               d_sums[i] is, over the selected rows of key i:
+ *                                 a NaN (0x7FF8000000000000) if one of them is a NaN, or if +inf and -inf both occur;
+ *                                 +inf / -inf if that infinity occurs;
+ *                                 otherwise the real number sum of the x_r, rounded ONCE to the nearest double, ties to even: +-inf where that
+ *                                 lies beyond DBL_MAX, exact where it is subnormal, +0.0 where it is zero (never -0.0, as in
+ *                                 alpgpu_decode_keyed_sum_*; a key without rows and every later duplicate get +0.0).
+ *                               There is no intermediate overflow and no cancellation error: DBL_MAX + DBL_MAX - DBL_MAX is DBL_MAX and
+ *                               1e300 + 1 - 1e300 is 1.  The sums are a function of the inputs alone: the same bytes on every grid, device,
+ *                               row order and sharding.
+ *                               d_counts (may be NULL): n_keys + 1 words of 8 bytes, alpgpu_decode_keyed_minmax_many_*'s: d_counts[i] counts
+ *                               every selected row of key i, the last word the selected rows without a key.  With NULL no count is kept.
+ *                               d_table: alpgpu_keyed_exact_sum_table_bytes(n_keys) bytes of device memory owned by the caller, 16-byte aligned,
+ *                               layout private (per key 66 limbs of int64, limb j of weight 2^(32 j - 1074), and a word of flags: NaN, +inf,
+ *                               -inf seen).  Every value is added to its key's limbs as an integer, by integer atomics; the call ends with a
+ *                               kernel that rounds every entry into d_sums.
+ *                               accumulate == 0: a kernel zeroes the table and d_counts first (not a memset node: DESIGN.md, "Histograms").
+ *                               accumulate != 0: the table is kept and added to, as alpgpu_histogram_*'s accumulate adds into its counts, and
+ *                               d_counts, if given, is added to as well; d_sums is written from the table at the end of every call.  A second
+ *                               call with accumulate on a shard of the columns, a range of a bitmap or another value column therefore extends
+ *                               the sums exactly: partial tables add without error, and the result is that of one call over all the rows (the
+ *                               same n_keys and keys; the table must come from a call with accumulate == 0 or be all zero bytes).
+ *                               The bound.  A limb takes at most 2^32 - 1 per row, so it holds 2^31 rows.  One call refuses more than
+ *                               ALPGPU_KEYED_EXACT_VECTORS_MAX = 2^21 vectors (2^31 rows); across accumulated calls the 2^31 rows per table are
+ *                               the CALLER's bound: breaking it gives wrong sums and nothing else.
+ *                               Cost: the zero kernel (536 bytes per key, the whole rounded up to 16), one launch of persistent workgroups sized to the device that stage
+ *                               the keys as alpgpu_decode_keyed_minmax_many_* does, and the rounding kernel.  A step of 64 rows that agree on
+ *                               their key and lie within 2^64 of each other is summed in registers and costs at most 5 integer atomics and one
+ *                               for the count; any other row costs up to 3 integer atomics and one for its count.  No floating-point atomics,
+ *                               no compare-and-swap loop, no workgroup waits for another.
+ *                               n_vectors == 0: neither column is read; the table is zeroed (accumulate == 0) or kept and d_sums written from it.
+ *                               ALPGPU_ERR_INVALID before anything is enqueued: a NULL ctx, val, key, d_keys, d_sums or d_table; n_keys outside
+ *                               1 .. ALPGPU_KEYED_MANY_KEYS_MAX; columns that differ in n_vectors; n_vectors > ALPGPU_KEYED_EXACT_VECTORS_MAX;
+ *                               d_sums, d_counts, d_mask or d_trace not 8-byte aligned; d_table not 16-byte aligned; d_key_zones not aligned to
+ *                               its records, d_keys not aligned to its elements; with n_vectors > 0, a column without descriptors.
+ *   alpgpu_keyed_exact_sum_table_bytes   536 * n_keys rounded up to a multiple of 16 (544 for one key), monotone; UINT64_MAX for n_keys outside 1 .. ALPGPU_KEYED_MANY_KEYS_MAX; host only.
+ * The call runs on the context's stream and on that stream only: asynchronous, no host synchronisation, no allocation, no state kept; none of what
+ *   the context remembers about columns is read or written; safe inside a stream capture (the keys, the bitmap and the table are read at replay).
+ * The debug entry takes alpgpu_keyed_tuning (grid) and adds to SIX trace words: the four of alpgpu_debug_decode_keyed_sum_*, then
+ *   [4] the steps of 64 rows summed in registers, [5] the steps sent to the table lane by lane.  No tuning changes a byte.
+ * The name is keyed_exact_sum and not keyed_sum_exact: the entry points whose names hold "keyed_sum" are alpgpu_decode_keyed_sum_*'s family, the striped
+ *   order, and are counted as such (tests/test_capi_refusals_cpu.py); the Python and C++ wrappers are keyed_sum_exact / sum_by_key_exact.
+ * Not built: a table in LDS for few keys (up to 1024 keys alpgpu_decode_keyed_sum_f64 keeps its tables there), more than 2^20 keys per call,
+ *   multi-column keys, keys not known in advance (alpgpu_distinct_* first).
+ * TRUST: as for alpgpu_select_range_*. */
+#define ALPGPU_KEYED_EXACT_VECTORS_MAX (1u << 21)
+uint64_t alpgpu_keyed_exact_sum_table_bytes(uint32_t n_keys);
+int alpgpu_decode_keyed_exact_sum_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
+                                      const double* d_keys, uint32_t n_keys, double* d_sums, uint64_t* d_counts, void* d_table, int accumulate);
+int alpgpu_decode_keyed_exact_sum_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f32* d_key_zones,
+                                      const float* d_keys, uint32_t n_keys, double* d_sums, uint64_t* d_counts, void* d_table, int accumulate);
+int alpgpu_debug_decode_keyed_exact_sum_f64(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f64* d_key_zones,
+                                            const double* d_keys, uint32_t n_keys, double* d_sums, uint64_t* d_counts, void* d_table, int accumulate,
+                                            const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
+int alpgpu_debug_decode_keyed_exact_sum_f32(alpgpu_ctx* ctx, const alpgpu_column* val, const alpgpu_column* key, const uint64_t* d_mask, const alpgpu_zone_f32* d_key_zones,
+                                            const float* d_keys, uint32_t n_keys, double* d_sums, uint64_t* d_counts, void* d_table, int accumulate,
+                                            const alpgpu_keyed_tuning* tuning, uint64_t* d_trace);
 
 /* ---- bucketed aggregation -------------------------------------------------------------------------------------------------------------------------
  * SELECT width_bucket(key, edges), SUM(x) / MIN(x) / MAX(x), COUNT(*) ... WHERE ... GROUP BY 1: resampling a column into bins of a second column
